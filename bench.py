@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark: Mrays/s of the HIP BVH traversal (BASELINE.json), renderer frame rates beside it.
 
-  python bench.py --gpus N --steps K --warmup W [--weak]
+  python bench.py --gpus N --steps K --warmup W [--weak] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Step  = one closest-hit traversal pass over one 1 048 576-ray batch resident in HBM (config[1] of BASELINE.json: <scene>.bvh +
@@ -30,6 +30,10 @@ roofline = ONE bound, stated once: VALU issue.  achieved = VALU wa
 render = `extra.render`: BASELINE configs 4 and 5 through the renderer ABI -- Cornell 1920 x 1080, 64 spp, path length 4 and the config-5
         scene at 3840 x 2160, 256 spp, path length 8 (one GPU: the whole frame; N GPUs: interleaved 16-row tiles + one film gather to
         rank 0), streaming and megakernel mappings, Msamples/s = spp * w * h / frame seconds / 1e6 (driver.cpp:300).
+dump  = --dump-outputs DIR: after the timed steps, the Hit1 records the timed path produced in its last step (primary and random set;
+        N > 1: rank 0's, strong = the gathered whole set) as DIR/<set>_<field>.npy, tri_id in float64 (exact), t / u / v in float32.
+        The inputs are seeded, so two builds given the same arguments can be compared array for array.  Above 64 MB in all, a fixed
+        seeded sample of the rays is written, with its indices in DIR/<set>_ray_index.npy.
 Code  = this file holds the contract (arguments, ranks, the JSON line); benchlib/ holds the sections: timing.py (the timed region),
         traversal.py (partitions, side measurements, CPU baseline), render.py (renderer section), profiles.py (profiles, rooflines).
 """
@@ -39,10 +43,16 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
+# The inputs (scene, BVH, ray sets: seeded, the same wherever they are generated) are made on first use in data/.  A checkout this user
+# cannot write to gets them in a directory of its own under the system's temporary directory; RODENT_DATA_DIR, when set, decides.  Set
+# before anything imports rodent_amd.scenes, which reads it once.
+if "RODENT_DATA_DIR" not in os.environ and not os.access(ROOT / "data" if (ROOT / "data").exists() else ROOT, os.W_OK):
+    os.environ["RODENT_DATA_DIR"] = str(Path(tempfile.gettempdir()) / f"rodent_amd-data-{os.getuid()}")
 
 # noqa: E402,F401
 from benchlib.profiles import (HBM_PEAK_GBPS, binding_bounds, current_profile, kernel_counters, latest_json, measured_traffic,
@@ -57,6 +67,7 @@ PREDICTED_SCALING = {"strong_1Mi_primary_contiguous_ranges": {"2": 1.27, "4": 1.
     "strong_1Mi_random": {"2": 1.33, "4": 1.72, "8": 2.05},
                      "cfg5_frame_interleaved_16_row_tiles": {"2": 1.99, "4": 3.99, "8": 7.94}, "weak": "1 Mi rays per GPU: ~N",
                      "source": "profiles/r06_range_costs.txt, profiles/r05_range_costs.txt, profiles/r04_band_costs.txt"}
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse_args():
@@ -79,7 +90,32 @@ def parse_args():
                         "first, ~80 s)")
     ap.add_argument("--render-spp5", type=int, default=256, help="samples per pixel of the config-5 frame (BASELINE: 256)")
     ap.add_argument("--only", choices=("primary", "random"), default=None, help="profiling aid: time only one ray set")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hit records of the last timed step to DIR/<set>_<field>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir, sets):
+    """--dump-outputs: {set name: Hit1 array} -> DIR/<set>_{tri_id,t,u,v}.npy (tri_id as float64: exact for every int32).  When the
+    whole arrays exceed DUMP_LIMIT_BYTES, the same seeded sample of rays is written every run and its indices beside it."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    per_ray = 8 + 3 * 4
+    total = sum(len(h) for h in sets.values())
+    sample = total * per_ray > DUMP_LIMIT_BYTES
+    for name, hits in sets.items():
+        if sample:
+            count = len(hits) * (DUMP_LIMIT_BYTES - (64 << 10)) // (total * (per_ray + 8))      # 64 KiB left for the .npy headers
+            idx = np.sort(np.random.default_rng(0).choice(len(hits), count, replace=False))
+            np.save(d / f"{name}_ray_index.npy", idx.astype(np.float64))
+            hits = hits[idx]
+        np.save(d / f"{name}_tri_id.npy", hits["tri_id"].astype(np.float64))
+        for field in ("t", "u", "v"):
+            np.save(d / f"{name}_{field}.npy", hits[field].astype(np.float32))
 
 
 def init_ranks(args):
@@ -137,9 +173,10 @@ def main():
     part, scaling, scaling_extra = timed_partitions(b)
     prim, rnd, n = part["prim"], part["rnd"], len(part["prim"])
     (k_mean, k_med, k_min), (kr_mean, kr_med, kr_min) = part["k"], part["kr"]
-    side = side_measurements(b, part)
+    # the hit records of the last timed step, read before the side measurements launch into the same buffers
     hits = abi.from_device(part["hits_dev"], F.HIT1)[:n]
     hits_rnd = abi.from_device(part["hits_rnd_dev"], F.HIT1)[:len(rnd)]
+    side = side_measurements(b, part)
     scene_rows = scene_matrix_rows(b)
     # renderer (BASELINE configs 4 / 5): after the traversal's timed regions, own timed frames
     render = render_section(args, torch, dist, rank, world, dev) if b.info and not args.no_render and width == 2 else None
@@ -147,6 +184,9 @@ def main():
         if dist is not None:
             dist.barrier(); dist.destroy_process_group()
         return
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"primary": part.get("hits_all", hits), "random": part.get("hits_rnd_all", hits_rnd)})
 
     # ---- rank 0: the JSON line -----------------------------------------------------------------
     kname = abi.kernel_name(width, variant)

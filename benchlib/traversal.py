@@ -111,6 +111,7 @@ def timed_partitions(b: Bench):
                   "random_Mrays_s": round(strong["value_rnd"], 3), "rays_per_gpu_per_step": len(strong["prim"]),
                   "kernel_ms_per_rank[primary,random]": strong["kernel_ms_per_rank"],
                   "what": "ONE 1 Mi-ray set in contiguous ranges (SURVEY 8e), Hit1 gather to rank 0 after the timed region"}
+    strong["hits_all"], strong["hits_rnd_all"] = full, full_rnd       # rank 0: what the caller of the strong partition receives
     main_part, scaling = (weak_part, "weak") if args.weak and not args.strong else (strong, "strong")
     return main_part, scaling, {"strong_scaling": strong_rec, "weak_scaling": weak, "strong_scaling_check": check}
 

@@ -13,6 +13,10 @@ import os
 from pathlib import Path
 
 import numpy as np
+# torch before the library, always: torch's bundled HIP runtime (torch/lib/libamdhip64.so) carries the soname the library links
+# (libamdhip64.so.7), so once torch is loaded the library binds to that same runtime.  Loaded the other way round, the library pulls in
+# the system ROCm runtime and torch then maps its own beside it: two HIP runtimes on one device (torch sees no GPU, or launches abort).
+import torch  # noqa: F401
 
 from . import formats as F
 

@@ -192,9 +192,11 @@ def build_oracle(force: bool = False) -> Path:
 
 
 def build_reference_tools(force: bool = False):
-    """oracle/_ref: the reference's own C++ pieces that compile here (optional)."""
+    """oracle/_ref: the reference's own C++ pieces that compile here (optional: skipped where the reference checkout is absent or not
+    readable by the user who builds)."""
     mk = ORACLE / "Makefile.ref"
-    if mk.exists() and Path("/root/reference").exists():
+    ref = "/root/reference"
+    if mk.exists() and os.path.isdir(ref) and os.access(ref, os.R_OK | os.X_OK):
         _run(["make", "-s", "-f", mk, "-C", ORACLE])
 
 

@@ -49,7 +49,8 @@ ap.add_argument("--steal", default="",
     "iterations")
 a = ap.parse_args()
 
-so = Path("/tmp/model_packet.so")
+so = ROOT / "build" / "model_packet.so"             # beside the other build products (git-ignored)
+so.parent.mkdir(parents=True, exist_ok=True)
 src = ROOT / "scripts/model_packet.c"
 if not so.exists() or so.stat().st_mtime < max(src.stat().st_mtime, (ROOT / "oracle/traversal_oracle.c").stat().st_mtime):
     subprocess.run(["gcc", "-O2", "-std=c11", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-shared", str(src), "-lm", "-o",
