@@ -73,6 +73,13 @@ struct RodentSceneDesc {           /* HOST pointers; copied to HBM by rodent_hip
 
 void    rodent_hip_scene_create(int32_t dev, const struct RodentSceneDesc* desc);   /* replaces the device's current scene */
 void    rodent_hip_scene_destroy(int32_t dev);
+/* rodent_hip_scene_create with a hierarchy built on the device (rodent_build.h: LBVH, leaves of at most max_leaf = 1 ... 8
+ * triangles, 2 = the host builder's threshold) from the vertices and indices it uploads: desc->nodes and desc->tris must be NULL and
+ * num_nodes / num_bvh_tris 0.  Everything the library derives from a hierarchy (the per-scene mapping rules, the LDS images) is derived
+ * from the built one; the hierarchy is deterministic, so is everything after it. */
+void    rodent_hip_scene_create_device_bvh(int32_t dev, const struct RodentSceneDesc* desc, int32_t max_leaf);
+/* The current scene's hierarchy on device `dev`: DEVICE pointers (owned by the scene) and counts -- for tests and tools. */
+void    rodent_hip_scene_bvh(int32_t dev, const struct Node2** nodes, const struct Tri1** tris, int32_t* num_nodes, int32_t* num_tris);
 void    rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len);   /* defaults 4 / 64 (converter.cpp:1007-1012) */
 /* 0 = streaming wavefront loop (src/render/mapping_gpu.impala:308-369), 1 = persistent-threads megakernel
  * (mapping_gpu.impala:371-474; the reference selects it at configure time with the converter target

@@ -40,6 +40,7 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "rodent_hip_kernel_name", "rodent_hip_version", "rodent_hip_source_digest", "rodent_hip_is_lab_build", "rodent_hip_phased_min_rays",
         "rodent_hip_top_min_rays", "rodent_hip_ray_kind_hint", "rodent_hip_ray_grid", "rodent_hip_schedule_history",
         "rodent_hip_read_stats", "rodent_hip_read_trace", "rodent_hip_debug_set_perm",
+    "rodent_hip_build_scratch_bytes", "rodent_hip_build_bvh2_tri1", "rodent_hip_build_bvh2_tri1_sync",
 ]
 BLOCK_OF_WIDTH = {2: F.BVH2_TRI1, 4: F.BVH4_TRI4, 8: F.BVH8_TRI4}
 
@@ -79,6 +80,12 @@ def lib():
         l.rodent_hip_read_trace.restype = None; l.rodent_hip_read_trace.argtypes = [i32, C.c_void_p]
         l.rodent_hip_debug_set_perm.restype = None; l.rodent_hip_debug_set_perm.argtypes = [i32, C.c_void_p]
         l.rodent_hip_read_stats.restype = None; l.rodent_hip_read_stats.argtypes = [i32, C.POINTER(C.c_uint64)]
+        # device BVH builder (include/rodent_build.h)
+        l.rodent_hip_build_scratch_bytes.restype = C.c_int64; l.rodent_hip_build_scratch_bytes.argtypes = [i32]
+        l.rodent_hip_build_bvh2_tri1.restype = i32
+        l.rodent_hip_build_bvh2_tri1.argtypes = [i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+        l.rodent_hip_build_bvh2_tri1_sync.restype = i32
+        l.rodent_hip_build_bvh2_tri1_sync.argtypes = [i32, vp, i32, vp, i32, i32, vp, vp, C.POINTER(i32)]
         _lib = l
     return _lib
 
@@ -134,6 +141,21 @@ class DeviceBvh:
         self.num_nodes, self.num_tris = len(nodes), len(tris)
         self.nodes = to_device(nodes, dev)
         self.tris = to_device(tris, dev)
+
+    @classmethod
+    def from_tensors(cls, width, nodes, tris, num_nodes, num_tris, dev=0):
+        """A BVH that is already on the device: `nodes` and `tris` are CUDA tensors (any dtype) holding at least num_nodes / num_tris
+        records of the layout; they are used as they are, not copied."""
+        assert width in (2, 4, 8)
+        node_dt, tri_dt = {2: (F.NODE2, F.TRI1), 4: (F.NODE4, F.TRI4), 8: (F.NODE8, F.TRI4)}[width]
+        for t, count, dt in ((nodes, num_nodes, node_dt), (tris, num_tris, tri_dt)):
+            if not t.is_cuda or t.numel() * t.element_size() < count * dt.itemsize or not t.is_contiguous():
+                raise ValueError("DeviceBvh.from_tensors: a contiguous CUDA tensor with room for every record is needed")
+        self = cls.__new__(cls)
+        self.width, self.dev = width, dev
+        self.num_nodes, self.num_tris = int(num_nodes), int(num_tris)
+        self.nodes, self.tris = nodes, tris
+        return self
 
     @classmethod
     def load(cls, path, width, dev=0):

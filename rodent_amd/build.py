@@ -40,7 +40,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 HOST_FLAGS = ["-O2", "-std=c++17", "-Wall", "-fPIC", f"-I{ROOT / 'include'}"]
 ORACLE_FLAGS = ["-O2", "-std=c11", "-Wall", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-mfma"]
 
-HIP_SOURCES = ["traversal.hip", "render.hip", "services.hip"]
+HIP_SOURCES = ["traversal.hip", "render.hip", "services.hip", "bvh_build.hip"]
 # Per-source options.  render.hip: the AMDGPU backend's "max-ilp" instruction scheduling strategy -- the renderer's traversal kernels are
 # compiled under an 8-waves-per-SIMD register budget, under which the default strategy serialises their loads; measured on one MI355X
 # (profiles/r04_flags_experiment.txt): config 5's frame +3.0 %, config 4 (megakernel) +1.1 %.  Scheduling only: the arithmetic is untouched

@@ -27,6 +27,7 @@
 #include <mutex>
 #include <vector>
 
+#include "rodent_build.h"
 #include "rodent_render.h"
 #include "shading.h"
 #include "traversal_device.h"
@@ -1410,7 +1411,7 @@ __global__ __launch_bounds__(kBinBlock) void k_scatter(PrimaryStream p, PrimaryS
 // ---------------------------------------------------------------------------------------------
 struct DevScene {
     bool loaded = false;
-    int num_nodes = 0;
+    int num_nodes = 0, num_bvh_tris = 0;
     // k_trace_refill's addressing of nodes and triangles from one base (rodent_hip_scene_create); 0 = not possible for this scene
     unsigned tri_delta = 0;
     SceneDev dev{};
@@ -2052,7 +2053,14 @@ void rodent_hip_scene_destroy(int32_t dev) {
     r.scene = DevScene();
 }
 
-void rodent_hip_scene_create(int32_t dev, const RodentSceneDesc* d) {
+} // extern "C"
+
+namespace {
+
+// rodent_hip_scene_create and rodent_hip_scene_create_device_bvh: max_leaf = 0 uploads the caller's hierarchy (desc->nodes / tris),
+// max_leaf > 0 builds one on the device from the vertices and indices just uploaded (bvh_build.hip) and takes a host copy of it; from
+// there on both are the same code: checks, LDS images, per-scene rules.
+void scene_create(int32_t dev, const RodentSceneDesc* d, int32_t max_leaf) {
     RenderDevice& r = rdev(dev);
     rodent_hip_scene_destroy(dev);
     HIP_CHECK(hipSetDevice(dev));
@@ -2061,15 +2069,42 @@ void rodent_hip_scene_create(int32_t dev, const RodentSceneDesc* d) {
     s.dev.normals = upload(s, d->normals, 4 * (size_t)d->num_vertices);
     s.dev.face_normals = upload(s, d->face_normals, 4 * (size_t)d->num_tris);
     s.dev.indices = upload(s, d->indices, 4 * (size_t)d->num_tris);
+    RodentSceneDesc built_desc;                 // d with the device-built hierarchy (host copy) in place of the caller's
+    std::vector<Node2> built_nodes;
+    std::vector<Tri1> built_tris;
     {   // nodes and triangles in ONE allocation: k_trace_refill addresses both from one base with 32-bit offsets (joint_fetch_off)
-        const size_t node_bytes = sizeof(Node2) * (size_t)d->num_nodes, tri_bytes = sizeof(Tri1) * (size_t)d->num_bvh_tris;
+        // (a device-built hierarchy: room for the builder's max(1, n - 1) nodes, then the triangles)
+        const size_t node_bytes = sizeof(Node2) * (size_t)(max_leaf > 0 ? std::max(1, d->num_tris - 1) : d->num_nodes);
+        const size_t tri_bytes = sizeof(Tri1) * (size_t)(max_leaf > 0 ? d->num_tris : d->num_bvh_tris);
         char* bvh = nullptr;
         HIP_CHECK(hipMalloc(&bvh, std::max<size_t>(node_bytes + tri_bytes, 16)));
         s.allocs.push_back(bvh);
-        if (node_bytes) HIP_CHECK(hipMemcpy(bvh, d->nodes, node_bytes, hipMemcpyHostToDevice));
-        if (tri_bytes) HIP_CHECK(hipMemcpy(bvh + node_bytes, d->tris, tri_bytes, hipMemcpyHostToDevice));
         s.dev.nodes = reinterpret_cast<const Node2*>(bvh);
         s.dev.tris = reinterpret_cast<const Tri1*>(bvh + node_bytes);
+        if (max_leaf > 0) {
+            const int64_t scratch_bytes = rodent_hip_build_scratch_bytes(d->num_tris);
+            char* scratch = nullptr;
+            int32_t info[RODENT_BUILD_INFO_WORDS];
+            HIP_CHECK(hipMalloc(&scratch, (size_t)std::max<int64_t>(scratch_bytes, 0) + sizeof info));
+            int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + std::max<int64_t>(scratch_bytes, 0));
+            const int32_t rc = rodent_hip_build_bvh2_tri1(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, max_leaf,
+                reinterpret_cast<Node2*>(bvh), reinterpret_cast<Tri1*>(bvh + node_bytes), scratch, info_dev, nullptr);
+            if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: device BVH build refused (%d)\n", rc); abort(); }
+            HIP_CHECK(hipMemcpy(info, info_dev, sizeof info, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipFree(scratch));
+            if (info[2]) { fprintf(stderr, "rodent_hip: invalid scene: device BVH build flagged the mesh (%d)\n", info[2]); abort(); }
+            built_nodes.resize(info[0]);
+            built_tris.resize(d->num_tris);
+            HIP_CHECK(hipMemcpy(built_nodes.data(), bvh, sizeof(Node2) * built_nodes.size(), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(built_tris.data(), bvh + node_bytes, tri_bytes, hipMemcpyDeviceToHost));
+            built_desc = *d;
+            built_desc.nodes = built_nodes.data(); built_desc.num_nodes = info[0];
+            built_desc.tris = built_tris.data(); built_desc.num_bvh_tris = d->num_tris;
+            d = &built_desc;
+        } else {
+            if (node_bytes) HIP_CHECK(hipMemcpy(bvh, d->nodes, node_bytes, hipMemcpyHostToDevice));
+            if (tri_bytes) HIP_CHECK(hipMemcpy(bvh + node_bytes, d->tris, tri_bytes, hipMemcpyHostToDevice));
+        }
         // tri_delta: bytes from the record a node id of 0 would have to triangle 0; 0 = not addressable this way (offsets beyond 32 bits,
         // or an index beyond the 24-bit multiply)
         const unsigned long long delta = sizeof(Node2) + node_bytes, end = delta + tri_bytes;
@@ -2168,10 +2203,34 @@ void rodent_hip_scene_create(int32_t dev, const RodentSceneDesc* d) {
         }
     }
     s.num_nodes = d->num_nodes;
+    s.num_bvh_tris = d->num_bvh_tris;
     s.loaded = true;
     r.mapping = resolve_mapping(r);
     r.trace_persistent = resolve_trace(r);
     resolve_refill(r);
+}
+
+} // namespace
+
+extern "C" {
+
+void rodent_hip_scene_create(int32_t dev, const RodentSceneDesc* d) { scene_create(dev, d, 0); }
+
+void rodent_hip_scene_create_device_bvh(int32_t dev, const RodentSceneDesc* d, int32_t max_leaf) {
+    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF || d->num_tris < 1 || d->num_tris > RODENT_BUILD_MAX_TRIS
+        || d->num_vertices < 1 || d->nodes || d->tris || d->num_nodes || d->num_bvh_tris) {
+        fprintf(stderr, "rodent_hip: rodent_hip_scene_create_device_bvh: invalid arguments (max_leaf 1 ... 8, 1 ... 2^25 triangles, "
+                        "no hierarchy in the description)\n");
+        abort();
+    }
+    scene_create(dev, d, max_leaf);
+}
+
+void rodent_hip_scene_bvh(int32_t dev, const Node2** nodes, const Tri1** tris, int32_t* num_nodes, int32_t* num_tris) {
+    RenderDevice& r = rdev(dev);
+    if (!r.scene.loaded) { fprintf(stderr, "rodent_hip: no scene loaded on device %d (call rodent_hip_scene_create)\n", dev); abort(); }
+    *nodes = r.scene.dev.nodes; *tris = r.scene.dev.tris;
+    *num_nodes = r.scene.num_nodes; *num_tris = r.scene.num_bvh_tris;
 }
 
 void rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len) {

@@ -56,7 +56,7 @@ RodentSceneDesc SceneData::desc() const {
     return d;
 }
 
-bool build_scene_from_obj(const std::string& obj_path, SceneData& scene, const BuildParams* bvh_params) {
+bool build_scene_from_obj(const std::string& obj_path, SceneData& scene, const BuildParams* bvh_params, bool with_bvh) {
     TriMesh mesh;
     if (!load_obj(obj_path, mesh)) return false;
     std::unordered_map<std::string, Material> lib;
@@ -142,6 +142,7 @@ bool build_scene_from_obj(const std::string& obj_path, SceneData& scene, const B
         scene.lights.push_back(L);
     }
 
+    if (!with_bvh) return true;
     // BVH2/Tri1 with the material id as geometry id
     const std::vector<Triangle> tris = mesh.triangles();
     std::vector<uint32_t> geom(nt);

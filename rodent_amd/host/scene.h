@@ -38,8 +38,9 @@ struct SceneData {
 };
 
 struct BuildParams;
-// bvh: builder parameters other than the defaults (arity is always 2)
-bool build_scene_from_obj(const std::string& obj_path, SceneData& scene, const BuildParams* bvh = nullptr);
+// bvh: builder parameters other than the defaults (arity is always 2); with_bvh = false: no host hierarchy (nodes / tris stay empty,
+// for rodent_hip_scene_create_device_bvh)
+bool build_scene_from_obj(const std::string& obj_path, SceneData& scene, const BuildParams* bvh = nullptr, bool with_bvh = true);
 bool save_scene(const std::string& path, const SceneData& scene);   // ".rscene" binary
 // validates counts against the file size and every index (validate_scene)
 bool load_scene(const std::string& path, SceneData& scene);

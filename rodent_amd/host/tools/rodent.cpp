@@ -14,6 +14,8 @@
 //                       ncclSend / ncclRecv, host/multi_gpu.h) brings the bands to the first device's film
 //   --target t          amdgpu-streaming or amdgpu-megakernel (default: chosen per scene) (converter.cpp:30-35,1032-1037)
 //   --sort / --no-sort  streaming target: sort hit rays by material before shading (the reference's loop) / shade in stream order (default)
+//   --gpu-bvh           build the hierarchy on the GPU (rodent_hip_scene_create_device_bvh: LBVH, include/rodent_build.h) instead of
+//                       the host SBVH (.obj input) or the file's (.rscene input); --max-leaf n: its largest leaf (1 ... 8, default 2)
 // Without --bench the reference opens an SDL window and renders until it is closed; this build is
 // headless (DISABLE_GUI, driver.cpp:236-242), so --bench or -o is required.
 #include <algorithm>
@@ -25,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "rodent_build.h"
 #include "../multi_gpu.h"
 #include "../png_write.h"
 #include "../scene.h"
@@ -45,6 +48,8 @@ static void usage() {
               << "   --target t          amdgpu-streaming or amdgpu-megakernel (default: chosen per scene)\n"
               << "   --sort              Sort rays by material before shading (streaming target; default: stream order)\n"
               << "   --no-sort           Do not sort rays by material before shading\n"
+              << "   --gpu-bvh           Builds the BVH on the GPU (LBVH) instead of the host SBVH or the scene file's BVH\n"
+              << "   --max-leaf n        With --gpu-bvh: at most n triangles per leaf (1 ... 8, default 2)\n"
               << "   --width  pixels     Sets the viewport horizontal dimension (in pixels)\n"
               << "   --height pixels     Sets the viewport vertical dimension (in pixels)\n"
               << "   --eye    x y z      Sets the position of the camera\n"
@@ -63,7 +68,8 @@ int main(int argc, char** argv) {
     float fov = 60.0f;
     V3 eye(0.0f), dir(0.0f, 0.0f, 1.0f), up(0.0f, 1.0f, 0.0f);
     int spp = 0, max_path_len = -1, dev = 0, mapping = -1, ngpu = 1;
-    bool bands = false, check = false;
+    bool bands = false, check = false, gpu_bvh = false;
+    int max_leaf = 2;
     int sort = -1;                                                        // -1: the library's default
 
     for (int i = 1; i < argc; ++i) {
@@ -91,6 +97,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--check")) check = true;
         else if (!strcmp(argv[i], "--no-sort")) sort = 0;
         else if (!strcmp(argv[i], "--sort")) sort = 1;
+        else if (!strcmp(argv[i], "--gpu-bvh")) gpu_bvh = true;
+        else if (!strcmp(argv[i], "--max-leaf")) { need(1); max_leaf = strtol(argv[++i], nullptr, 10); }
         else if (!strcmp(argv[i], "--target")) {
             need(1); ++i;
             if (!strcmp(argv[i], "amdgpu-streaming") || !strcmp(argv[i], "amdgpu")) mapping = 0;
@@ -106,7 +114,9 @@ int main(int argc, char** argv) {
 
     SceneData scene;
     const bool is_obj = scene_file.size() > 4 && scene_file.substr(scene_file.size() - 4) == ".obj";
-    if (is_obj ? !build_scene_from_obj(scene_file, scene) : !load_scene(scene_file, scene)) fail("Cannot load scene '" + scene_file + "'");
+    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) fail("Invalid --max-leaf (1 ... 8)");
+    if (is_obj ? !build_scene_from_obj(scene_file, scene, nullptr, !gpu_bvh) : !load_scene(scene_file, scene))
+        fail("Cannot load scene '" + scene_file + "'");
     if (scene.lights.empty()) fail("The scene has no light source");
     if (spp <= 0) spp = scene.default_spp;
     if (max_path_len < 0) max_path_len = scene.default_max_path_len;
@@ -122,13 +132,15 @@ int main(int argc, char** argv) {
         std::string err;
         if (!group.init(dev, ngpu, &err)) fail("No such GPU device(s): " + err);
     }
-    const RodentSceneDesc desc = scene.desc();
+    RodentSceneDesc desc = scene.desc();
+    if (gpu_bvh) { desc.nodes = nullptr; desc.tris = nullptr; desc.num_nodes = desc.num_bvh_tris = 0; }
     setup_interface(width, height);
     // (the first device last: it stays the current one of render() / get_spp())
     for (int r = ngpu - 1; r >= 0; r--) {
         const int d = group.device(r);
         rodent_hip_set_device(d);
-        rodent_hip_scene_create(d, &desc);
+        if (gpu_bvh) rodent_hip_scene_create_device_bvh(d, &desc, max_leaf);
+        else rodent_hip_scene_create(d, &desc);
         rodent_hip_render_config(d, spp, max_path_len);
         if (mapping >= 0) rodent_hip_render_mapping(d, mapping);
         if (sort >= 0) rodent_hip_render_sort(d, sort);

@@ -28,7 +28,8 @@ class SceneDesc(C.Structure):
                [(n, vp) for n in ("texcoords", "textures", "texels")] + [("num_textures", i32), ("num_texels", C.c_uint32)]
 
 
-RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_destroy", "rodent_hip_render_config", "rodent_hip_render_mapping",
+RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_bvh", "rodent_hip_scene_destroy",
+    "rodent_hip_render_config", "rodent_hip_render_mapping",
     "rodent_hip_render_capacity", "rodent_hip_render_sort", "rodent_hip_render_hit_records", "rodent_hip_render_overlap",
     "rodent_hip_render_fused_sort", "rodent_hip_render_fused_compact", "rodent_hip_render_mapping_in_effect", "rodent_hip_render_defaults",
     "rodent_hip_render_lds_image", "rodent_hip_render_mega_joint", "rodent_hip_render_trace_persistent", "rodent_hip_render_trace_refill",
@@ -53,6 +54,10 @@ def lib():
     if not _ready:
         l.rodent_hip_scene_create.argtypes = [i32, C.POINTER(SceneDesc)]; l.rodent_hip_scene_create.restype = None
         l.rodent_hip_scene_destroy.argtypes = [i32]; l.rodent_hip_scene_destroy.restype = None
+        l.rodent_hip_scene_create_device_bvh.argtypes = [i32, C.POINTER(SceneDesc), i32]
+        l.rodent_hip_scene_create_device_bvh.restype = None
+        l.rodent_hip_scene_bvh.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
+        l.rodent_hip_scene_bvh.restype = None
         l.rodent_hip_render_config.argtypes = [i32, i32, i32]; l.rodent_hip_render_config.restype = None
         l.rodent_hip_render_mapping.argtypes = [i32, i32]; l.rodent_hip_render_mapping.restype = None
         l.rodent_hip_render_capacity.argtypes = [i32, i32]; l.rodent_hip_render_capacity.restype = None
@@ -103,8 +108,9 @@ class Renderer:
 
     def __init__(self, scene, width, height, spp=4, max_path_len=64, dev=0, mapping="streaming", capacity=0, sort=None, overlap=None,
         fused_sort=None, lds_image=None,
-                 trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None):
-        """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says."""
+                 trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None):
+        """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says.
+        gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh)."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("rodent_amd: no GPU visible (the renderer has no CPU fallback)")
@@ -118,7 +124,12 @@ class Renderer:
                              len(scene.texels))
         l.rodent_hip_set_device(dev)
         l.rodent_hip_render_defaults(dev)                    # options of an earlier Renderer in this process do not leak into this one
-        l.rodent_hip_scene_create(dev, C.byref(desc))
+        if gpu_bvh:
+            desc.nodes = desc.tris = None
+            desc.num_nodes = desc.num_bvh_tris = 0
+            l.rodent_hip_scene_create_device_bvh(dev, C.byref(desc), int(gpu_bvh))
+        else:
+            l.rodent_hip_scene_create(dev, C.byref(desc))
         l.rodent_hip_render_config(dev, spp, max_path_len)
         l.rodent_hip_render_mapping(dev, self.MAPPINGS[mapping])
         l.rodent_hip_render_capacity(dev, capacity)          # rays per stream, 0 = default (32 Mi)
@@ -188,6 +199,19 @@ class Renderer:
         buf = (C.c_uint64 * 4)()
         lib().rodent_hip_render_counters(self.dev, buf)
         return {"primary_rays": buf[0], "shadow_rays": buf[1], "iterations": buf[2], "generated": buf[3]}
+
+    def scene_bvh(self):
+        """Host copies (nodes NODE2, tris TRI1) of the hierarchy the scene traces (rodent_hip_scene_bvh)."""
+        import torch
+        nodes, tris, nn, nt = vp(), vp(), i32(), i32()
+        lib().rodent_hip_scene_bvh(self.dev, C.byref(nodes), C.byref(tris), C.byref(nn), C.byref(nt))
+        out = []
+        for ptr, count, dt in ((nodes, nn.value, abi.F.NODE2), (tris, nt.value, abi.F.TRI1)):
+            t = torch.empty(max(count, 1) * dt.itemsize, dtype=torch.uint8, device=f"cuda:{self.dev}")
+            torch.cuda.synchronize(self.dev)
+            C.cdll.LoadLibrary("libamdhip64.so").hipMemcpy(C.c_void_p(t.data_ptr()), ptr, C.c_size_t(count * dt.itemsize), 3)
+            out.append(t.cpu().numpy()[: count * dt.itemsize].view(dt).copy())
+        return tuple(out)
 
     def close(self):
         lib().rodent_hip_scene_destroy(self.dev)

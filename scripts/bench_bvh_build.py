@@ -1,0 +1,117 @@
+"""Device BVH builder (rodent_amd.gpubuild, csrc/bvh_build.hip) against the host SBVH: build time, trace rate, tree quality.
+
+For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> converter -> .rscene):
+  * GPU build: device-event time of rodent_hip_build_bvh2_tri1 (median of --builds builds after 3 warm-ups), Mtriangles/s;
+  * host SBVH: wall time of `converter` on the OBJ (it parses the OBJ too: an upper bound of the builder's own time);
+  * traversal: Mrays/s of 1 Mi camera rays and 1 Mi random segments through hip_traverse_bvh2_tri1_async, default variant, closest
+    hit, on both trees (median of 10 launches after 2 warm-ups);
+  * quality: oracle steps (inner nodes + triangles) per ray on every 16th ray of both sets, and the SAH cost (tests/lbvh_model.py).
+
+    python scripts/bench_bvh_build.py [--scenes atrium gallery crown plant] [--builds 20] [-o profiles/gpu_bvh_build.txt]
+"""
+from __future__ import annotations
+
+import argparse
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+import torch  # noqa: E402
+
+from rodent_amd import abi, build, formats as F, gpubuild, raygen, scene as S, scenes  # noqa: E402
+
+
+def event_ms(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return float(np.median(times))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", nargs="+", default=["atrium", "gallery", "crown", "plant"])
+    ap.add_argument("--builds", type=int, default=20)
+    ap.add_argument("-o", "--output", default=str(ROOT / "profiles" / "gpu_bvh_build.txt"))
+    a = ap.parse_args()
+    from oracle import binding as O
+    import lbvh_model as L
+    build.build_all()
+    lines = [f"# scripts/bench_bvh_build.py on {torch.cuda.get_device_name(0)}; builds: median of {a.builds} after 3 warm-ups, "
+             "device events; traversal: default BVH2 variant, closest hit, median of 10 launches; steps: oracle, every 16th ray"]
+    hdr = (f"{'scene':>8} {'tris':>9} | {'gpu ms':>7} {'Mtri/s':>7} {'nodes':>8} {'depth':>5} | {'sbvh s':>6} {'nodes':>8} | "
+           f"{'prim Mr/s gpu':>13} {'sbvh':>6} | {'rand Mr/s gpu':>13} {'sbvh':>6} | {'steps prim gpu':>14} {'sbvh':>6} | "
+           f"{'steps rand gpu':>14} {'sbvh':>6} | {'SAH gpu':>7} {'sbvh':>6}")
+    lines.append(hdr)
+    print(hdr, flush=True)
+    out_dir = scenes.DATA
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name in a.scenes:
+        obj = scenes.scene_obj(name)
+        rs = out_dir / f"{name.replace('/', '-')}.rscene"
+        t0 = time.perf_counter()
+        subprocess.run([str(build.BIN_DIR / "converter"), str(obj), "-o", str(rs)], check=True, stdout=subprocess.DEVNULL)
+        host_s = time.perf_counter() - t0
+        sc = S.Scene(rs)
+        n = sc.num_tris
+        v = torch.from_numpy(sc.vertices).cuda()
+        ix = torch.from_numpy(sc.indices).cuda()
+        bvh = gpubuild.build_bvh2(v, ix, 2)
+        stream = torch.cuda.current_stream()
+        info = torch.empty(4, dtype=torch.int32, device="cuda")
+        import ctypes as C
+
+        def one_build():
+            rc = abi.lib().rodent_hip_build_bvh2_tri1(0, v.data_ptr(), len(sc.vertices), ix.data_ptr(), n, 2, bvh.nodes.data_ptr(),
+                                                      bvh.tris.data_ptr(), bvh.scratch.data_ptr(), info.data_ptr(),
+                                                      C.c_void_p(stream.cuda_stream))
+            assert rc == 0
+        build_ms = event_ms(one_build, 3, a.builds)
+        assert info.cpu().numpy().tolist() == bvh.info.tolist()
+        nodes, tris = gpubuild.download(bvh)
+        sbvh = abi.DeviceBvh(2, sc.nodes, sc.tris, 0)
+        kind = name.split("/")[0]
+        eye, d, up, fov = scenes.CAMERAS[kind]
+        lo, hi = sc.vertices[:, :3].min(0), sc.vertices[:, :3].max(0)
+        ray_sets = {"primary": raygen.primary_rays(eye, d, up, fov, 1024, 1024, 0.0, scenes.PRIMARY_TMAX),
+                    "random": raygen.random_rays(lo, hi, 1 << 20, 42, 0.0, scenes.RANDOM_TMAX)}
+        rate, steps = {}, {}
+        for rk, rays in ray_sets.items():
+            rays_dev = abi.to_device(rays)
+            hits = torch.empty(len(rays) * 16, dtype=torch.uint8, device="cuda")
+            for tk, tree in (("gpu", bvh), ("sbvh", sbvh)):
+                ms = event_ms(lambda: abi.traverse_async(tree, rays_dev, hits, len(rays)), 2, 10)
+                abi.check_errors()
+                rate[rk, tk] = len(rays) / ms / 1e3
+            sub = rays[::16]
+            steps[rk, "gpu"] = O.ray_steps(nodes, tris, sub).sum(1).mean()
+            steps[rk, "sbvh"] = O.ray_steps(sc.nodes, sc.tris, sub).sum(1).mean()
+        row = (f"{name:>8} {n:>9} | {build_ms:>7.3f} {n / build_ms / 1e3:>7.0f} {bvh.num_nodes:>8} {bvh.depth:>5} | {host_s:>6.1f} "
+               f"{len(sc.nodes):>8} | {rate['primary', 'gpu']:>13.0f} {rate['primary', 'sbvh']:>6.0f} | {rate['random', 'gpu']:>13.0f} "
+               f"{rate['random', 'sbvh']:>6.0f} | {steps['primary', 'gpu']:>14.1f} {steps['primary', 'sbvh']:>6.1f} | "
+               f"{steps['random', 'gpu']:>14.1f} {steps['random', 'sbvh']:>6.1f} | {L.sah_cost(nodes, tris):>7.1f} "
+               f"{L.sah_cost(sc.nodes, sc.tris):>6.1f}")
+        lines.append(row)
+        print(row, flush=True)
+        del bvh, sbvh, v, ix
+        torch.cuda.empty_cache()
+    Path(a.output).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.output).write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
