@@ -28,7 +28,8 @@ extern "C" {
 
 #define RODENT_BUILD_MAX_TRIS    (1 << 25)
 #define RODENT_BUILD_MAX_LEAF    8
-#define RODENT_BUILD_INFO_WORDS  4      /* info: [0] Node2 count, [1] depth, [2] error flags (below), [3] 0 */
+#define RODENT_BUILD_INFO_WORDS  4      /* info: [0] Node2 count, [1] depth, [2] error flags (below), [3] 0 (optimising builder:
+                                           topologies rejected by the depth rule) */
 
 /* error flags in info[2] (found on the device; the hierarchy is then undefined, but nothing is read out of bounds) */
 #define RODENT_BUILD_BAD_INDEX   1      /* a vertex index outside [0, num_vertices): that vertex is read as the origin */
@@ -43,6 +44,8 @@ extern "C" {
 #define RODENT_BUILD_ERR_DEVICE        -5   /* no such device */
 #define RODENT_BUILD_ERR_LAUNCH        -6   /* the HIP runtime refused a launch / an allocation (sync form) */
 #define RODENT_BUILD_ERR_INPUT         -7   /* sync form only: the device raised an error flag (info[2]) */
+#define RODENT_BUILD_ERR_PASSES        -8   /* RodentBuildOptions.treelet_passes outside [0, 3] */
+#define RODENT_BUILD_ERR_COST          -9   /* RodentBuildOptions.node_cost / tri_cost not in (0, 1e6] */
 
 /* Bytes of device scratch rodent_hip_build_bvh2_tri1 needs for num_tris triangles (-1 outside [1, 2^25]); any 256-byte aligned
  * buffer of that size, its contents are ignored. */
@@ -62,6 +65,58 @@ int32_t rodent_hip_build_bvh2_tri1(int32_t dev, const float* vertices, int32_t n
  * `info` (host, may be NULL) and returns RODENT_BUILD_ERR_INPUT when the device raised a flag. */
 int32_t rodent_hip_build_bvh2_tri1_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
                                         int32_t num_tris, int32_t max_leaf, struct Node2* nodes, struct Tri1* tris, int32_t* info);
+
+/* ---- the optimising builder: treelet restructuring + SAH leaf collapse ------------------------------------------------------
+ *
+ * After the LBVH's Karras tree (single-triangle leaves), `treelet_passes` passes of treelet restructuring (Karras & Aila, "Fast
+ * Parallel Construction of High-Quality Bounding Volume Hierarchies", HPG 2013) and a surface-area (SAH) leaf collapse.  The output
+ * is a pure function of (vertices, indices, num_vertices, num_tris, options), byte for byte; tests/trbvh_model.py restates every stage.
+ *
+ * Costs, all fp32 in this order (A = half the surface area of a box, (dx * dy + dy * dz) + dz * dx; N = triangles under a node):
+ *   C(triangle) = (tri_cost * A) * 1;   inner = node_cost * A + (C(left) + C(right));   leaf = (tri_cost * A) * N
+ *   C(node) = leaf when N <= max_leaf and leaf <= inner, else inner: such a node is COLLAPSED.
+ * Passes: pass k (0-based) visits the nodes bottom-up and restructures the treelet of every node with at least gamma_k = 7 << k
+ *   triangles (7, 14, 28):
+ *   - growth: the treelet's leaves start as the node's two children; five times, the leaf of largest A that is an inner node (ties:
+ *     the lowest slot) is replaced by its left child and its right child takes the next slot: 7 leaves, 6 inner nodes.
+ *   - DP over the 127 non-empty subsets S of the 7 leaves by size: the best split of S is the first P, among the subsets of S that
+ *     hold S's lowest leaf (S itself excluded) in increasing bit order, of least C(P) + C(S \ P); C(S) as above, with that sum.
+ *   - depth rule: with d(n) the inner nodes above n at the start of the pass, the new topology is taken only when its height
+ *     (Node2 levels, single-triangle leaves, computed from the slots' stored heights) is at most 56 - d(n); otherwise the treelet
+ *     stays as it is and only the node's height and cost are refitted from its current children, so every stored height is true
+ *     when an ancestor reads it.  A pass never lengthens the path above a node it visits, so by induction every tree has at most
+ *     56 levels (the LBVH's Karras tree has at most 55), and
+ *     the collapse only shortens it.  info[3] counts the rejected topologies over all passes.
+ *   - the new inner nodes, in pre-order (the part holding the lowest leaf first), take the node's own id, then the ids of the
+ *     expanded nodes in expansion order; the node keeps its id, so the links above it stay valid.
+ * Collapse and emission: a node is a leaf when it is collapsed and no ancestor is; the root too (then the single-leaf form above).
+ *   Node2 records in depth-first pre-order, child 0 first (root 0, an inner child 0 at index + 1); Tri1 records in the leaves'
+ *   left-to-right order; prim_id and the end-of-leaf bit as above.  info[0] and info[1] as above; max_leaf is an upper bound on a
+ *   leaf, not a threshold.  treelet_passes = 0 gives exactly the bytes of rodent_hip_build_bvh2_tri1 with the same max_leaf. */
+#define RODENT_BUILD_MAX_TREELET_PASSES  3
+#define RODENT_BUILD_DEFAULT_NODE_COST   1.2f    /* Karras & Aila's C_i */
+#define RODENT_BUILD_DEFAULT_TRI_COST    1.0f    /* Karras & Aila's C_t */
+
+struct RodentBuildOptions {
+    int32_t max_leaf;          /* 1 ... 8: the largest leaf */
+    int32_t treelet_passes;    /* 0 ... 3: 0 = the LBVH of rodent_hip_build_bvh2_tri1 */
+    float node_cost, tri_cost; /* SAH cost of a node visit and of a triangle test, in (0, 1e6] (defaults above) */
+};
+
+/* Bytes of device scratch rodent_hip_build_bvh2_tri1_opt needs (-1 for num_tris outside [1, 2^25] or invalid options). */
+int64_t rodent_hip_build_opt_scratch_bytes(int32_t num_tris, const struct RodentBuildOptions* opt);
+
+/* rodent_hip_build_bvh2_tri1 with options: the same arguments, buffers and node buffer size (max(1, num_tris - 1) Node2), scratch of
+ * rodent_hip_build_opt_scratch_bytes.  Invalid options (NULL: RODENT_BUILD_ERR_NULL, RODENT_BUILD_ERR_MAX_LEAF / _PASSES / _COST)
+ * are refused before anything is enqueued. */
+int32_t rodent_hip_build_bvh2_tri1_opt(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                       int32_t num_tris, const struct RodentBuildOptions* opt, struct Node2* nodes, struct Tri1* tris,
+                                       void* scratch, int32_t* info_dev, void* stream);
+
+/* Synchronous form, as rodent_hip_build_bvh2_tri1_sync. */
+int32_t rodent_hip_build_bvh2_tri1_opt_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                            int32_t num_tris, const struct RodentBuildOptions* opt, struct Node2* nodes,
+                                            struct Tri1* tris, int32_t* info);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,10 @@ void    rodent_hip_scene_destroy(int32_t dev);
  * num_nodes / num_bvh_tris 0.  Everything the library derives from a hierarchy (the per-scene mapping rules, the LDS images) is derived
  * from the built one; the hierarchy is deterministic, so is everything after it. */
 void    rodent_hip_scene_create_device_bvh(int32_t dev, const struct RodentSceneDesc* desc, int32_t max_leaf);
+/* The same with the options of the optimising builder (rodent_build.h: RodentBuildOptions; treelet_passes = 0 is the call above
+ * with opt->max_leaf).  Invalid options abort, as invalid arguments above do. */
+struct RodentBuildOptions;
+void    rodent_hip_scene_create_device_bvh_opt(int32_t dev, const struct RodentSceneDesc* desc, const struct RodentBuildOptions* opt);
 /* The current scene's hierarchy on device `dev`: DEVICE pointers (owned by the scene) and counts -- for tests and tools. */
 void    rodent_hip_scene_bvh(int32_t dev, const struct Node2** nodes, const struct Tri1** tris, int32_t* num_nodes, int32_t* num_tris);
 void    rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len);   /* defaults 4 / 64 (converter.cpp:1007-1012) */

@@ -41,10 +41,16 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
         "rodent_hip_top_min_rays", "rodent_hip_ray_kind_hint", "rodent_hip_ray_grid", "rodent_hip_schedule_history",
         "rodent_hip_read_stats", "rodent_hip_read_trace", "rodent_hip_debug_set_perm",
     "rodent_hip_build_scratch_bytes", "rodent_hip_build_bvh2_tri1", "rodent_hip_build_bvh2_tri1_sync",
+    "rodent_hip_build_opt_scratch_bytes", "rodent_hip_build_bvh2_tri1_opt", "rodent_hip_build_bvh2_tri1_opt_sync",
 ]
 BLOCK_OF_WIDTH = {2: F.BVH2_TRI1, 4: F.BVH4_TRI4, 8: F.BVH8_TRI4}
 
 _lib = None
+
+
+class BuildOptions(C.Structure):
+    """struct RodentBuildOptions (include/rodent_build.h)."""
+    _fields_ = [("max_leaf", C.c_int32), ("treelet_passes", C.c_int32), ("node_cost", C.c_float), ("tri_cost", C.c_float)]
 
 
 class MissingExtension(RuntimeError):
@@ -86,6 +92,12 @@ def lib():
         l.rodent_hip_build_bvh2_tri1.argtypes = [i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
         l.rodent_hip_build_bvh2_tri1_sync.restype = i32
         l.rodent_hip_build_bvh2_tri1_sync.argtypes = [i32, vp, i32, vp, i32, i32, vp, vp, C.POINTER(i32)]
+        opt = C.POINTER(BuildOptions)
+        l.rodent_hip_build_opt_scratch_bytes.restype = C.c_int64; l.rodent_hip_build_opt_scratch_bytes.argtypes = [i32, opt]
+        l.rodent_hip_build_bvh2_tri1_opt.restype = i32
+        l.rodent_hip_build_bvh2_tri1_opt.argtypes = [i32, vp, i32, vp, i32, opt, vp, vp, vp, vp, vp]
+        l.rodent_hip_build_bvh2_tri1_opt_sync.restype = i32
+        l.rodent_hip_build_bvh2_tri1_opt_sync.argtypes = [i32, vp, i32, vp, i32, opt, vp, vp, C.POINTER(i32)]
         _lib = l
     return _lib
 

@@ -2057,10 +2057,10 @@ void rodent_hip_scene_destroy(int32_t dev) {
 
 namespace {
 
-// rodent_hip_scene_create and rodent_hip_scene_create_device_bvh: max_leaf = 0 uploads the caller's hierarchy (desc->nodes / tris),
-// max_leaf > 0 builds one on the device from the vertices and indices just uploaded (bvh_build.hip) and takes a host copy of it; from
+// rodent_hip_scene_create and rodent_hip_scene_create_device_bvh(_opt): build = NULL uploads the caller's hierarchy (desc->nodes /
+// tris), build options build one on the device from the vertices and indices just uploaded (bvh_build.hip) and takes a host copy of it; from
 // there on both are the same code: checks, LDS images, per-scene rules.
-void scene_create(int32_t dev, const RodentSceneDesc* d, int32_t max_leaf) {
+void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* build) {
     RenderDevice& r = rdev(dev);
     rodent_hip_scene_destroy(dev);
     HIP_CHECK(hipSetDevice(dev));
@@ -2074,20 +2074,20 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, int32_t max_leaf) {
     std::vector<Tri1> built_tris;
     {   // nodes and triangles in ONE allocation: k_trace_refill addresses both from one base with 32-bit offsets (joint_fetch_off)
         // (a device-built hierarchy: room for the builder's max(1, n - 1) nodes, then the triangles)
-        const size_t node_bytes = sizeof(Node2) * (size_t)(max_leaf > 0 ? std::max(1, d->num_tris - 1) : d->num_nodes);
-        const size_t tri_bytes = sizeof(Tri1) * (size_t)(max_leaf > 0 ? d->num_tris : d->num_bvh_tris);
+        const size_t node_bytes = sizeof(Node2) * (size_t)(build ? std::max(1, d->num_tris - 1) : d->num_nodes);
+        const size_t tri_bytes = sizeof(Tri1) * (size_t)(build ? d->num_tris : d->num_bvh_tris);
         char* bvh = nullptr;
         HIP_CHECK(hipMalloc(&bvh, std::max<size_t>(node_bytes + tri_bytes, 16)));
         s.allocs.push_back(bvh);
         s.dev.nodes = reinterpret_cast<const Node2*>(bvh);
         s.dev.tris = reinterpret_cast<const Tri1*>(bvh + node_bytes);
-        if (max_leaf > 0) {
-            const int64_t scratch_bytes = rodent_hip_build_scratch_bytes(d->num_tris);
+        if (build) {
+            const int64_t scratch_bytes = rodent_hip_build_opt_scratch_bytes(d->num_tris, build);
             char* scratch = nullptr;
             int32_t info[RODENT_BUILD_INFO_WORDS];
             HIP_CHECK(hipMalloc(&scratch, (size_t)std::max<int64_t>(scratch_bytes, 0) + sizeof info));
             int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + std::max<int64_t>(scratch_bytes, 0));
-            const int32_t rc = rodent_hip_build_bvh2_tri1(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, max_leaf,
+            const int32_t rc = rodent_hip_build_bvh2_tri1_opt(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build,
                 reinterpret_cast<Node2*>(bvh), reinterpret_cast<Tri1*>(bvh + node_bytes), scratch, info_dev, nullptr);
             if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: device BVH build refused (%d)\n", rc); abort(); }
             HIP_CHECK(hipMemcpy(info, info_dev, sizeof info, hipMemcpyDeviceToHost));
@@ -2214,16 +2214,22 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, int32_t max_leaf) {
 
 extern "C" {
 
-void rodent_hip_scene_create(int32_t dev, const RodentSceneDesc* d) { scene_create(dev, d, 0); }
+void rodent_hip_scene_create(int32_t dev, const RodentSceneDesc* d) { scene_create(dev, d, nullptr); }
 
 void rodent_hip_scene_create_device_bvh(int32_t dev, const RodentSceneDesc* d, int32_t max_leaf) {
-    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF || d->num_tris < 1 || d->num_tris > RODENT_BUILD_MAX_TRIS
+    const RodentBuildOptions opt{max_leaf, 0, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
+    rodent_hip_scene_create_device_bvh_opt(dev, d, &opt);
+}
+
+void rodent_hip_scene_create_device_bvh_opt(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* opt) {
+    if (!opt || rodent_hip_build_opt_scratch_bytes(1, opt) < 0 || d->num_tris < 1 || d->num_tris > RODENT_BUILD_MAX_TRIS
         || d->num_vertices < 1 || d->nodes || d->tris || d->num_nodes || d->num_bvh_tris) {
-        fprintf(stderr, "rodent_hip: rodent_hip_scene_create_device_bvh: invalid arguments (max_leaf 1 ... 8, 1 ... 2^25 triangles, "
+        fprintf(stderr, "rodent_hip: rodent_hip_scene_create_device_bvh: invalid arguments (max_leaf 1 ... 8, treelet passes 0 ... 3, "
+                        "costs in (0, 1e6], 1 ... 2^25 triangles, "
                         "no hierarchy in the description)\n");
         abort();
     }
-    scene_create(dev, d, max_leaf);
+    scene_create(dev, d, opt);
 }
 
 void rodent_hip_scene_bvh(int32_t dev, const Node2** nodes, const Tri1** tris, int32_t* num_nodes, int32_t* num_tris) {

@@ -16,6 +16,8 @@
 //   --sort / --no-sort  streaming target: sort hit rays by material before shading (the reference's loop) / shade in stream order (default)
 //   --gpu-bvh           build the hierarchy on the GPU (rodent_hip_scene_create_device_bvh: LBVH, include/rodent_build.h) instead of
 //                       the host SBVH (.obj input) or the file's (.rscene input); --max-leaf n: its largest leaf (1 ... 8, default 2)
+//   --treelet-passes n  with --gpu-bvh: n = 1 ... 3 passes of treelet restructuring and an SAH leaf collapse (rodent_build.h,
+//                       rodent_hip_scene_create_device_bvh_opt); 0 (the default) = the LBVH as it is
 // Without --bench the reference opens an SDL window and renders until it is closed; this build is
 // headless (DISABLE_GUI, driver.cpp:236-242), so --bench or -o is required.
 #include <algorithm>
@@ -50,6 +52,7 @@ static void usage() {
               << "   --no-sort           Do not sort rays by material before shading\n"
               << "   --gpu-bvh           Builds the BVH on the GPU (LBVH) instead of the host SBVH or the scene file's BVH\n"
               << "   --max-leaf n        With --gpu-bvh: at most n triangles per leaf (1 ... 8, default 2)\n"
+              << "   --treelet-passes n  With --gpu-bvh: n passes (0 ... 3, default 0) of treelet restructuring + SAH leaf collapse\n"
               << "   --width  pixels     Sets the viewport horizontal dimension (in pixels)\n"
               << "   --height pixels     Sets the viewport vertical dimension (in pixels)\n"
               << "   --eye    x y z      Sets the position of the camera\n"
@@ -69,7 +72,8 @@ int main(int argc, char** argv) {
     V3 eye(0.0f), dir(0.0f, 0.0f, 1.0f), up(0.0f, 1.0f, 0.0f);
     int spp = 0, max_path_len = -1, dev = 0, mapping = -1, ngpu = 1;
     bool bands = false, check = false, gpu_bvh = false;
-    int max_leaf = 2;
+    int max_leaf = 2, treelet_passes = 0;
+    bool treelet_given = false;
     int sort = -1;                                                        // -1: the library's default
 
     for (int i = 1; i < argc; ++i) {
@@ -99,6 +103,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--sort")) sort = 1;
         else if (!strcmp(argv[i], "--gpu-bvh")) gpu_bvh = true;
         else if (!strcmp(argv[i], "--max-leaf")) { need(1); max_leaf = strtol(argv[++i], nullptr, 10); }
+        else if (!strcmp(argv[i], "--treelet-passes")) { need(1); treelet_passes = strtol(argv[++i], nullptr, 10); treelet_given = true; }
         else if (!strcmp(argv[i], "--target")) {
             need(1); ++i;
             if (!strcmp(argv[i], "amdgpu-streaming") || !strcmp(argv[i], "amdgpu")) mapping = 0;
@@ -115,6 +120,8 @@ int main(int argc, char** argv) {
     SceneData scene;
     const bool is_obj = scene_file.size() > 4 && scene_file.substr(scene_file.size() - 4) == ".obj";
     if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) fail("Invalid --max-leaf (1 ... 8)");
+    if (treelet_passes < 0 || treelet_passes > RODENT_BUILD_MAX_TREELET_PASSES) fail("Invalid --treelet-passes (0 ... 3)");
+    if (treelet_given && !gpu_bvh) fail("--treelet-passes needs --gpu-bvh");
     if (is_obj ? !build_scene_from_obj(scene_file, scene, nullptr, !gpu_bvh) : !load_scene(scene_file, scene))
         fail("Cannot load scene '" + scene_file + "'");
     if (scene.lights.empty()) fail("The scene has no light source");
@@ -139,7 +146,10 @@ int main(int argc, char** argv) {
     for (int r = ngpu - 1; r >= 0; r--) {
         const int d = group.device(r);
         rodent_hip_set_device(d);
-        if (gpu_bvh) rodent_hip_scene_create_device_bvh(d, &desc, max_leaf);
+        if (gpu_bvh) {
+            const RodentBuildOptions opt{max_leaf, treelet_passes, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
+            rodent_hip_scene_create_device_bvh_opt(d, &desc, &opt);
+        }
         else rodent_hip_scene_create(d, &desc);
         rodent_hip_render_config(d, spp, max_path_len);
         if (mapping >= 0) rodent_hip_render_mapping(d, mapping);

@@ -28,7 +28,8 @@ class SceneDesc(C.Structure):
                [(n, vp) for n in ("texcoords", "textures", "texels")] + [("num_textures", i32), ("num_texels", C.c_uint32)]
 
 
-RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_bvh", "rodent_hip_scene_destroy",
+RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_create_device_bvh_opt",
+    "rodent_hip_scene_bvh", "rodent_hip_scene_destroy",
     "rodent_hip_render_config", "rodent_hip_render_mapping",
     "rodent_hip_render_capacity", "rodent_hip_render_sort", "rodent_hip_render_hit_records", "rodent_hip_render_overlap",
     "rodent_hip_render_fused_sort", "rodent_hip_render_fused_compact", "rodent_hip_render_mapping_in_effect", "rodent_hip_render_defaults",
@@ -56,6 +57,8 @@ def lib():
         l.rodent_hip_scene_destroy.argtypes = [i32]; l.rodent_hip_scene_destroy.restype = None
         l.rodent_hip_scene_create_device_bvh.argtypes = [i32, C.POINTER(SceneDesc), i32]
         l.rodent_hip_scene_create_device_bvh.restype = None
+        l.rodent_hip_scene_create_device_bvh_opt.argtypes = [i32, C.POINTER(SceneDesc), C.POINTER(abi.BuildOptions)]
+        l.rodent_hip_scene_create_device_bvh_opt.restype = None
         l.rodent_hip_scene_bvh.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
         l.rodent_hip_scene_bvh.restype = None
         l.rodent_hip_render_config.argtypes = [i32, i32, i32]; l.rodent_hip_render_config.restype = None
@@ -108,9 +111,13 @@ class Renderer:
 
     def __init__(self, scene, width, height, spp=4, max_path_len=64, dev=0, mapping="streaming", capacity=0, sort=None, overlap=None,
         fused_sort=None, lds_image=None,
-                 trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None):
+                 trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None,
+                 gpu_bvh_passes=0):
         """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says.
-        gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh)."""
+        gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh);
+        gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it (rodent_hip_scene_create_device_bvh_opt)."""
+        if gpu_bvh_passes and not gpu_bvh:
+            raise ValueError("gpu_bvh_passes needs gpu_bvh (the treelet passes act on the device-built hierarchy)")
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("rodent_amd: no GPU visible (the renderer has no CPU fallback)")
@@ -127,7 +134,12 @@ class Renderer:
         if gpu_bvh:
             desc.nodes = desc.tris = None
             desc.num_nodes = desc.num_bvh_tris = 0
-            l.rodent_hip_scene_create_device_bvh(dev, C.byref(desc), int(gpu_bvh))
+            if gpu_bvh_passes:
+                from . import gpubuild
+                opt = gpubuild.options(int(gpu_bvh), int(gpu_bvh_passes))
+                l.rodent_hip_scene_create_device_bvh_opt(dev, C.byref(desc), C.byref(opt))
+            else:
+                l.rodent_hip_scene_create_device_bvh(dev, C.byref(desc), int(gpu_bvh))
         else:
             l.rodent_hip_scene_create(dev, C.byref(desc))
         l.rodent_hip_render_config(dev, spp, max_path_len)

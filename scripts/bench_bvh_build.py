@@ -6,12 +6,16 @@ For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> conve
   * traversal: Mrays/s of 1 Mi camera rays and 1 Mi random segments through hip_traverse_bvh2_tri1_async, default variant, closest
     hit, on both trees (median of 10 launches after 2 warm-ups);
   * quality: oracle steps (inner nodes + triangles) per ray on every 16th ray of both sets, and the SAH cost (tests/lbvh_model.py).
+  * with --treelet-passes N > 0, the same for the optimised build (rodent_hip_build_bvh2_tri1_opt: N treelet passes + SAH leaf
+    collapse, default costs) in the "opt" columns.
 
     python scripts/bench_bvh_build.py [--scenes atrium gallery crown plant] [--builds 20] [-o profiles/gpu_bvh_build.txt]
+    python scripts/bench_bvh_build.py --treelet-passes 3 -o profiles/gpu_bvh_build_opt.txt
 """
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import subprocess
 import sys
 import time
@@ -42,10 +46,24 @@ def event_ms(fn, warmup, reps):
     return float(np.median(times))
 
 
+def tree_depth(nodes):
+    """Node2 levels of a BVH2, level by level; every inner child index must be in range and referenced once."""
+    child = nodes["child"].astype(np.int64)
+    inner = child[child > 0] - 1
+    assert (inner < len(nodes)).all() and len(np.unique(inner)) == len(inner) == len(nodes) - 1
+    depth, frontier = 0, np.array([0])
+    while len(frontier) and depth <= 64:
+        depth += 1
+        c = child[frontier].reshape(-1)
+        frontier = c[c > 0] - 1
+    return depth
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", nargs="+", default=["atrium", "gallery", "crown", "plant"])
     ap.add_argument("--builds", type=int, default=20)
+    ap.add_argument("--treelet-passes", type=int, default=0, help="also measure the optimised build with N passes (1 ... 3)")
     ap.add_argument("-o", "--output", default=str(ROOT / "profiles" / "gpu_bvh_build.txt"))
     a = ap.parse_args()
     from oracle import binding as O
@@ -56,6 +74,11 @@ def main():
     hdr = (f"{'scene':>8} {'tris':>9} | {'gpu ms':>7} {'Mtri/s':>7} {'nodes':>8} {'depth':>5} | {'sbvh s':>6} {'nodes':>8} | "
            f"{'prim Mr/s gpu':>13} {'sbvh':>6} | {'rand Mr/s gpu':>13} {'sbvh':>6} | {'steps prim gpu':>14} {'sbvh':>6} | "
            f"{'steps rand gpu':>14} {'sbvh':>6} | {'SAH gpu':>7} {'sbvh':>6}")
+    P = a.treelet_passes
+    if P:
+        lines[0] += f"; opt: {P} treelet passes + SAH leaf collapse, max_leaf 2"
+        hdr += (f" || {'opt ms':>7} {'nodes':>8} {'depth':>5} {'rej':>4} | {'prim Mr/s':>9} {'rand Mr/s':>9} | {'steps prim':>10} "
+                f"{'rand':>6} | {'SAH':>6}")
     lines.append(hdr)
     print(hdr, flush=True)
     out_dir = scenes.DATA
@@ -73,7 +96,6 @@ def main():
         bvh = gpubuild.build_bvh2(v, ix, 2)
         stream = torch.cuda.current_stream()
         info = torch.empty(4, dtype=torch.int32, device="cuda")
-        import ctypes as C
 
         def one_build():
             rc = abi.lib().rodent_hip_build_bvh2_tri1(0, v.data_ptr(), len(sc.vertices), ix.data_ptr(), n, 2, bvh.nodes.data_ptr(),
@@ -89,22 +111,43 @@ def main():
         lo, hi = sc.vertices[:, :3].min(0), sc.vertices[:, :3].max(0)
         ray_sets = {"primary": raygen.primary_rays(eye, d, up, fov, 1024, 1024, 0.0, scenes.PRIMARY_TMAX),
                     "random": raygen.random_rays(lo, hi, 1 << 20, 42, 0.0, scenes.RANDOM_TMAX)}
+        trees = {"gpu": bvh, "sbvh": sbvh}
+        host = {"gpu": (nodes, tris), "sbvh": (sc.nodes, sc.tris)}
+        if P:
+            opt = gpubuild.build_bvh2(v, ix, 2, treelet_passes=P)
+            copt = gpubuild.options(2, P)
+
+            def one_opt_build():
+                rc = abi.lib().rodent_hip_build_bvh2_tri1_opt(0, v.data_ptr(), len(sc.vertices), ix.data_ptr(), n, C.byref(copt),
+                                                              opt.nodes.data_ptr(), opt.tris.data_ptr(), opt.scratch.data_ptr(),
+                                                              info.data_ptr(), C.c_void_p(stream.cuda_stream))
+                assert rc == 0
+            opt_ms = event_ms(one_opt_build, 3, a.builds)
+            assert info.cpu().numpy().tolist() == opt.info.tolist()
+            host["opt"] = gpubuild.download(opt)
+            assert tree_depth(host["opt"][0]) == opt.depth <= 56        # checked before anything traces it
+            trees["opt"] = opt
         rate, steps = {}, {}
         for rk, rays in ray_sets.items():
             rays_dev = abi.to_device(rays)
             hits = torch.empty(len(rays) * 16, dtype=torch.uint8, device="cuda")
-            for tk, tree in (("gpu", bvh), ("sbvh", sbvh)):
+            for tk, tree in trees.items():
                 ms = event_ms(lambda: abi.traverse_async(tree, rays_dev, hits, len(rays)), 2, 10)
                 abi.check_errors()
                 rate[rk, tk] = len(rays) / ms / 1e3
             sub = rays[::16]
-            steps[rk, "gpu"] = O.ray_steps(nodes, tris, sub).sum(1).mean()
-            steps[rk, "sbvh"] = O.ray_steps(sc.nodes, sc.tris, sub).sum(1).mean()
+            for tk, (hn, ht) in host.items():
+                steps[rk, tk] = O.ray_steps(hn, ht, sub).sum(1).mean()
         row = (f"{name:>8} {n:>9} | {build_ms:>7.3f} {n / build_ms / 1e3:>7.0f} {bvh.num_nodes:>8} {bvh.depth:>5} | {host_s:>6.1f} "
                f"{len(sc.nodes):>8} | {rate['primary', 'gpu']:>13.0f} {rate['primary', 'sbvh']:>6.0f} | {rate['random', 'gpu']:>13.0f} "
                f"{rate['random', 'sbvh']:>6.0f} | {steps['primary', 'gpu']:>14.1f} {steps['primary', 'sbvh']:>6.1f} | "
                f"{steps['random', 'gpu']:>14.1f} {steps['random', 'sbvh']:>6.1f} | {L.sah_cost(nodes, tris):>7.1f} "
                f"{L.sah_cost(sc.nodes, sc.tris):>6.1f}")
+        if P:
+            row += (f" || {opt_ms:>7.3f} {opt.num_nodes:>8} {opt.depth:>5} {int(opt.info[3]):>4} | {rate['primary', 'opt']:>9.0f} "
+                    f"{rate['random', 'opt']:>9.0f} | {steps['primary', 'opt']:>10.1f} {steps['random', 'opt']:>6.1f} | "
+                    f"{L.sah_cost(*host['opt']):>6.1f}")
+            del opt, trees
         lines.append(row)
         print(row, flush=True)
         del bvh, sbvh, v, ix
