@@ -118,6 +118,72 @@ int32_t rodent_hip_build_bvh2_tri1_opt_sync(int32_t dev, const float* vertices, 
                                             int32_t num_tris, const struct RodentBuildOptions* opt, struct Node2* nodes,
                                             struct Tri1* tris, int32_t* info);
 
+/* ---- triangle pre-splitting (Karras & Aila, HPG 2013, section 5) ----------------------------------------------------------------
+ *
+ * Before the Morton codes, the triangles whose boxes waste the most area are cut along planes of a grid into several REFERENCES,
+ * each with a tighter box; the stages above (the LBVH for treelet_passes = 0, the optimising builder otherwise) then run over the
+ * n' references instead of the n triangles.  A Tri1 record holds the whole triangle and its id, so a triangle may appear in several
+ * leaves (or twice in one).  The output is a pure function of (vertices, indices, num_vertices, num_tris, options, split options),
+ * byte for byte; tests/split_model.py restates every stage.  All arithmetic is fp32 in the order written (only + - * and correctly
+ * rounded division and square root), integer sums, exact min / max.  Vertex coordinates are taken as x + 0 (no -0).
+ *
+ * Frame: the union of the triangle boxes, lo_a ... hi_a per axis; step_a = (hi_a - lo_a) * 0x1p-10f when that is finite and > 0,
+ *   otherwise the axis has no planes.  Plane c (1 ... 1023) of axis a lies at lo_a + (float)c * step_a; its level is ctz(c) (9 the
+ *   coarsest).  The plane of a box: the coarsest plane lying strictly inside the box on its axis (lo < plane < hi), ties to x, y, z.
+ * Priority of triangle t (box b, n = (v1 - v0) x (v2 - v0) component by component, x = ey * fz - ez * fy, and so on):
+ *   excess = max(0, A(b) - 0.5f * ((|nx| + |ny|) + |nz|)),  p = sqrt(2^L * excess), L the level of b's plane; p = 0 when b has no
+ *   plane, when the triangle raised an error flag, and when p is not finite (Karras & Aila's exponent 1/3 becomes a square root).
+ * Allotment, B = min(floor(budget * n) (exact product), 2^25 - n) extra references:
+ *   pmax = max p;  w = (uint32)floorf(__fdiv_rn(p, pmax) * 65536.0f) (0 when pmax = 0);  W = sum of w (uint64);
+ *   s = min(max_pieces - 1, (w * B) / W) in 64-bit integers (0 when W = 0): the triangle may become s + 1 pieces, sum s <= B.
+ * Cutting (triangles with s > 0; a piece is a box and a count k of splits it still holds; the first piece is the triangle's box, k = s):
+ *   loop: k = 0, or the piece's box has no plane -> the piece is final (its k splits are "not made", counted in info[6]);
+ *   otherwise cut at the plane (axis a, position x): each vertex goes to the side(s) it lies on (v_a <= x left, v_a >= x right); each
+ *   edge v_i -> v_{i+1 mod 3} with its ends strictly on opposite sides adds, to both sides, the point of axis-a coordinate x and, on
+ *   each other axis b, the interval [max(y - g, min(p_b, q_b)), min(y + g, max(p_b, q_b))], with t = __fdiv_rn(x - p_a, q_a - p_a),
+ *   y = p_b + t * (q_b - p_b) and the margin g = max(max(|p_b|, |q_b|) * 0x1p-19f, 0x1p-126f), which exceeds the rounding error of
+ *   y (about 12 ulps of max(|p_b|, |q_b|)); a side's box, the box of its points, is then intersected with the piece's box and
+ *   clamped to its half space.  When one side's box is empty the piece takes the other side's box and keeps its k (the plane then
+ *   lies on its border, so this ends); when both are, the piece is final with its k not made.  Otherwise the left side gets
+ *   kl = (int)min(max(floorf(__fdiv_rn((float)(k - 1) * el, el + er) + 0.5f), 0), k - 1) splits (a NaN quotient gives 0), the right
+ *   side k - 1 - kl; el, er are the sides' longest extents.  Pieces are final in depth-first order, left side first.
+ * References: every triangle's pieces in that order, triangles in id order (an exclusive scan).  An uncut triangle's box is its
+ *   triangle box and its Morton point the vertex sum (v0 + v1) + v2; a piece's point is (lo + hi) * 1.5f per axis (the same 3x scale).
+ *   The stages above then run over the references: the Morton frame is the bounds of the references' points, the sort orders
+ *   (code, reference index), leaf boxes are the references' boxes and Tri1 records their triangles.  n' <= 2^25, so the depth bounds
+ *   above (55 for the LBVH, 56 with treelets) hold.  budget = 0 or max_pieces = 1: the bytes of rodent_hip_build_bvh2_tri1_opt. */
+#define RODENT_BUILD_SPLIT_INFO_WORDS  8   /* [0] Node2 count [1] depth [2] flags [3] rejected topologies
+                                              [4] Tri1 count (references) [5] triangles split [6] splits allotted but not made [7] 0 */
+#define RODENT_BUILD_MAX_PIECES        64
+#define RODENT_BUILD_MAX_SPLIT_BUDGET  4.0f
+#define RODENT_BUILD_ERR_SPLIT        -10  /* RodentSplitOptions out of range */
+
+struct RodentSplitOptions {
+    float   budget;      /* [0, 4]: extra references as a fraction of num_tris; 0 = no splitting */
+    int32_t max_pieces;  /* 1 ... 64: the most references one triangle may become */
+};
+
+/* The most references the split builder can make: num_tris + min(B, num_tris * (max_pieces - 1)) (-1 on invalid arguments).  The
+ * node buffer holds max(1, max_refs - 1) Node2, the triangle buffer max_refs Tri1. */
+int64_t rodent_hip_build_split_max_refs(int32_t num_tris, const struct RodentSplitOptions* split);
+
+/* Bytes of device scratch rodent_hip_build_bvh2_tri1_split needs (-1 on invalid arguments). */
+int64_t rodent_hip_build_split_scratch_bytes(int32_t num_tris, const struct RodentBuildOptions* opt,
+                                             const struct RodentSplitOptions* split);
+
+/* rodent_hip_build_bvh2_tri1_opt over pre-split references: the same arguments plus `split`; nodes: max(1, max_refs - 1) Node2,
+ * tris: max_refs Tri1, info_dev: RODENT_BUILD_SPLIT_INFO_WORDS ints (info[4] = the Tri1 count).  Asynchronous like the others:
+ * nothing is allocated, nothing waits for the device.  Invalid split options: RODENT_BUILD_ERR_SPLIT before anything is enqueued. */
+int32_t rodent_hip_build_bvh2_tri1_split(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                         int32_t num_tris, const struct RodentBuildOptions* opt, const struct RodentSplitOptions* split,
+                                         struct Node2* nodes, struct Tri1* tris, void* scratch, int32_t* info_dev, void* stream);
+
+/* Synchronous form, as rodent_hip_build_bvh2_tri1_opt_sync; `info` receives RODENT_BUILD_SPLIT_INFO_WORDS words. */
+int32_t rodent_hip_build_bvh2_tri1_split_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                              int32_t num_tris, const struct RodentBuildOptions* opt,
+                                              const struct RodentSplitOptions* split, struct Node2* nodes, struct Tri1* tris,
+                                              int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,11 @@ void    rodent_hip_scene_create_device_bvh(int32_t dev, const struct RodentScene
  * with opt->max_leaf).  Invalid options abort, as invalid arguments above do. */
 struct RodentBuildOptions;
 void    rodent_hip_scene_create_device_bvh_opt(int32_t dev, const struct RodentSceneDesc* desc, const struct RodentBuildOptions* opt);
+/* The same over pre-split triangle references (rodent_build.h: RodentSplitOptions); the scene's BVH triangle count is the reference
+ * count the builder reports.  Invalid options abort. */
+struct RodentSplitOptions;
+void    rodent_hip_scene_create_device_bvh_split(int32_t dev, const struct RodentSceneDesc* desc, const struct RodentBuildOptions* opt,
+                                                 const struct RodentSplitOptions* split);
 /* The current scene's hierarchy on device `dev`: DEVICE pointers (owned by the scene) and counts -- for tests and tools. */
 void    rodent_hip_scene_bvh(int32_t dev, const struct Node2** nodes, const struct Tri1** tris, int32_t* num_nodes, int32_t* num_tris);
 void    rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len);   /* defaults 4 / 64 (converter.cpp:1007-1012) */

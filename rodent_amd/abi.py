@@ -42,6 +42,8 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
         "rodent_hip_read_stats", "rodent_hip_read_trace", "rodent_hip_debug_set_perm",
     "rodent_hip_build_scratch_bytes", "rodent_hip_build_bvh2_tri1", "rodent_hip_build_bvh2_tri1_sync",
     "rodent_hip_build_opt_scratch_bytes", "rodent_hip_build_bvh2_tri1_opt", "rodent_hip_build_bvh2_tri1_opt_sync",
+    "rodent_hip_build_split_max_refs", "rodent_hip_build_split_scratch_bytes", "rodent_hip_build_bvh2_tri1_split",
+    "rodent_hip_build_bvh2_tri1_split_sync",
 ]
 BLOCK_OF_WIDTH = {2: F.BVH2_TRI1, 4: F.BVH4_TRI4, 8: F.BVH8_TRI4}
 
@@ -51,6 +53,11 @@ _lib = None
 class BuildOptions(C.Structure):
     """struct RodentBuildOptions (include/rodent_build.h)."""
     _fields_ = [("max_leaf", C.c_int32), ("treelet_passes", C.c_int32), ("node_cost", C.c_float), ("tri_cost", C.c_float)]
+
+
+class SplitOptions(C.Structure):
+    """struct RodentSplitOptions (include/rodent_build.h)."""
+    _fields_ = [("budget", C.c_float), ("max_pieces", C.c_int32)]
 
 
 class MissingExtension(RuntimeError):
@@ -98,6 +105,14 @@ def lib():
         l.rodent_hip_build_bvh2_tri1_opt.argtypes = [i32, vp, i32, vp, i32, opt, vp, vp, vp, vp, vp]
         l.rodent_hip_build_bvh2_tri1_opt_sync.restype = i32
         l.rodent_hip_build_bvh2_tri1_opt_sync.argtypes = [i32, vp, i32, vp, i32, opt, vp, vp, C.POINTER(i32)]
+        spl = C.POINTER(SplitOptions)
+        l.rodent_hip_build_split_max_refs.restype = C.c_int64; l.rodent_hip_build_split_max_refs.argtypes = [i32, spl]
+        l.rodent_hip_build_split_scratch_bytes.restype = C.c_int64
+        l.rodent_hip_build_split_scratch_bytes.argtypes = [i32, opt, spl]
+        l.rodent_hip_build_bvh2_tri1_split.restype = i32
+        l.rodent_hip_build_bvh2_tri1_split.argtypes = [i32, vp, i32, vp, i32, opt, spl, vp, vp, vp, vp, vp]
+        l.rodent_hip_build_bvh2_tri1_split_sync.restype = i32
+        l.rodent_hip_build_bvh2_tri1_split_sync.argtypes = [i32, vp, i32, vp, i32, opt, spl, vp, vp, C.POINTER(i32)]
         _lib = l
     return _lib
 

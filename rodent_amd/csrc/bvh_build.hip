@@ -22,6 +22,10 @@
 //                    climb again; each node of at least gamma triangles gets its 7-leaf treelet restructured by its wave
 //   k_fit            again: the SAH leaf collapse decisions and emitted-node counts of the final tree
 //   k_emit_opt_nodes / k_emit_opt_tris   Node2 in depth-first pre-order, Tri1 in left-to-right leaf order (O(depth) walks)
+//
+// The splitting entry (rodent_hip_build_bvh2_tri1_split; CPU model: tests/split_model.py) puts the pre-splitting stages of section 9
+// in front and runs the stages above over the n' references they make.  n' is known on the device only: those stages get grids sized
+// for max_refs and read n' (`nref`) from info[4]; without `nref` they behave exactly as before.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -96,8 +100,8 @@ __device__ __forceinline__ float canon(float x) { return x + 0.0f; }
 
 // The vertex triple of triangle t, each index checked before its vertex is read: an index outside [0, num_vertices) reads as the
 // origin and raises kBuildBadIndex (when `info` is given), a non-finite coordinate raises kBuildNonFinite.
-__device__ __forceinline__ void load_triangle(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices, int t,
-                                              float3 v[3], int* geom, int* info) {
+__device__ __forceinline__ int load_triangle(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices, int t,
+                                             float3 v[3], int* geom, int* info) {
     const int4 ix = indices[t];
     const int id[3] = {ix.x, ix.y, ix.z};
     int flags = 0;
@@ -113,6 +117,7 @@ __device__ __forceinline__ void load_triangle(const float4* __restrict__ vertice
     }
     *geom = ix.w;
     if (info && flags) atomicOr(&info[kInfoFlags], flags);
+    return flags;
 }
 
 // ---- 1. centroids and their bounds ----------------------------------------------------------------------------------------------
@@ -175,7 +180,8 @@ __device__ __forceinline__ uint32_t spread10(uint32_t x) {    // bit k -> bit 3k
 }
 
 __global__ __launch_bounds__(kBlock) void k_morton(const float4* __restrict__ cent, int n, const float* __restrict__ frame,
-                                                   uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+                                                   uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, const int* nref) {
+    if (nref) n = *nref;
     const int t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= n) return;
     const float4 c = cent[t];
@@ -190,7 +196,9 @@ __global__ __launch_bounds__(kBlock) void k_morton(const float4* __restrict__ ce
 }
 
 // ---- 3. stable LSD radix sort, 8 bits per pass ------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_radix_hist(const uint32_t* __restrict__ keys, int n, int shift, uint32_t* __restrict__ hist) {
+__global__ __launch_bounds__(kBlock) void k_radix_hist(const uint32_t* __restrict__ keys, int n, int shift, uint32_t* __restrict__ hist,
+                                                       const int* nref) {
+    if (nref) n = *nref;                               // tiles past n' count nothing: their digits scan to the same places
     __shared__ uint32_t h[256];
     h[threadIdx.x] = 0;
     __syncthreads();
@@ -226,7 +234,8 @@ __global__ __launch_bounds__(1024) void k_scan(uint32_t* a, int count, int* tota
 // order, 256 keys at a time), so the pass is stable.
 __global__ __launch_bounds__(kBlock) void k_radix_scatter(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
                                                           uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
-                                                          const uint32_t* __restrict__ hist, int n, int shift) {
+                                                          const uint32_t* __restrict__ hist, int n, int shift, const int* nref) {
+    if (nref) n = *nref;
     __shared__ uint32_t running[256];
     __shared__ uint32_t wcount[kBlock / 64][256];
     const int tid = threadIdx.x, w = tid >> 6;
@@ -262,16 +271,22 @@ __global__ __launch_bounds__(kBlock) void k_radix_scatter(const uint32_t* __rest
 // ---- 4. leaves: Tri1 records and boxes in sorted order ----------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_leaves(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices,
                                                    const uint32_t* __restrict__ order, int n, Tri1* __restrict__ tris,
-                                                   float* __restrict__ leafbox) {
+                                                   float* __restrict__ leafbox, const int* nref, const int* __restrict__ reftri,
+                                                   const float* __restrict__ refbox) {
+    if (nref) n = *nref;
     const int p = blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
-    const int t = (int)order[p];
+    const int r = (int)order[p], t = reftri ? reftri[r] : r;      // the split entry sorts references: triangle and box through them
     float3 v[3]; int geom;
     load_triangle(vertices, nv, indices, t, v, &geom, nullptr);
     float4* out = reinterpret_cast<float4*>(tris + p);
     out[0] = make_float4(v[0].x, v[0].y, v[0].z, 0.0f);
     out[1] = make_float4(v[0].x - v[1].x, v[0].y - v[1].y, v[0].z - v[1].z, __int_as_float(geom));
     out[2] = make_float4(v[2].x - v[0].x, v[2].y - v[0].y, v[2].z - v[0].z, __int_as_float(t));
+    if (refbox) {
+        for (int k = 0; k < 6; k++) leafbox[6 * (size_t)p + k] = refbox[6 * (size_t)r + k];
+        return;
+    }
     const float c[3][3] = {{v[0].x, v[1].x, v[2].x}, {v[0].y, v[1].y, v[2].y}, {v[0].z, v[1].z, v[2].z}};
     for (int a = 0; a < 3; a++) {
         leafbox[6 * (size_t)p + 2 * a] = fminf(fminf(canon(c[a][0]), canon(c[a][1])), canon(c[a][2]));
@@ -290,7 +305,9 @@ __device__ __forceinline__ int delta(const uint32_t* __restrict__ codes, int n, 
 
 __global__ __launch_bounds__(kBlock) void k_karras(const uint32_t* __restrict__ codes, int n, int max_leaf, int* __restrict__ first,
                                                    int* __restrict__ last, int* __restrict__ split, int* __restrict__ parent,
-                                                   int* __restrict__ leaf_parent, uint32_t* __restrict__ blockcount) {
+                                                   int* __restrict__ leaf_parent, uint32_t* __restrict__ blockcount,
+                                                   const int* nref) {
+    if (nref) n = *nref;                               // blocks past n' - 1 keep nothing: their counts are 0
     const int m = n - 1, i = blockIdx.x * kBlock + threadIdx.x;
     bool kept = false;
     if (i < m) {
@@ -319,7 +336,9 @@ __global__ __launch_bounds__(kBlock) void k_karras(const uint32_t* __restrict__ 
 }
 
 __global__ __launch_bounds__(kBlock) void k_renumber(const int* __restrict__ first, const int* __restrict__ last, int m, int max_leaf,
-                                                     const uint32_t* __restrict__ blockoff, int* __restrict__ newidx) {
+                                                     const uint32_t* __restrict__ blockoff, int* __restrict__ newidx,
+                                                     const int* nref) {
+    if (nref) m = *nref - 1;
     __shared__ uint32_t wave_total[kBlock / 64];
     const int i = blockIdx.x * kBlock + threadIdx.x, w = threadIdx.x >> 6;
     const bool kept = i < m && last[i] - first[i] + 1 > max_leaf;
@@ -339,9 +358,10 @@ __global__ __launch_bounds__(kBlock) void k_renumber(const int* __restrict__ fir
 __global__ __launch_bounds__(kBlock) void k_bottom_up(int n, int max_leaf, const int* __restrict__ first, const int* __restrict__ last,
                                                       const int* __restrict__ split, const int* __restrict__ parent,
                                                       const int* __restrict__ leaf_parent, const float* __restrict__ leafbox,
-                                                      float* box, int* height, uint32_t* arrivals, int* info) {
+                                                      float* box, int* height, uint32_t* arrivals, int* info, const int* nref) {
+    if (nref) n = *nref;
     const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p >= n) return;
+    if (p >= n || n < 2) return;
     int node = leaf_parent[p];
     while (node >= 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -369,7 +389,8 @@ __device__ __forceinline__ void put_bounds(float* dst, const float* b) { for (in
 __global__ __launch_bounds__(kBlock) void k_emit(int m, const int* __restrict__ first, const int* __restrict__ last,
                                                  const int* __restrict__ split, const int* __restrict__ newidx,
                                                  const float* __restrict__ leafbox, const float* __restrict__ box,
-                                                 Node2* __restrict__ nodes, Tri1* __restrict__ tris) {
+                                                 Node2* __restrict__ nodes, Tri1* __restrict__ tris, const int* nref) {
+    if (nref) m = *nref - 1;                           // n' <= max_leaf: no node is kept, nothing is written
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= m || newidx[i] < 0) return;
     const int g = split[i];
@@ -394,9 +415,11 @@ __global__ __launch_bounds__(kBlock) void k_emit(int m, const int* __restrict__ 
     out[3] = make_float4(__int_as_float(child[0]), __int_as_float(child[1]), 0.0f, 0.0f);
 }
 
-// n <= max_leaf: one root whose child 0 is the whole leaf; the empty slot as the host writer leaves it (+inf, -inf)
+// n <= max_leaf: one root whose child 0 is the whole leaf; the empty slot as the host writer leaves it (+inf, -inf).  With `nref`
+// (the split entry: n' on the device) it writes only when n' <= limit.
 __global__ void k_emit_root(int n, const float* __restrict__ leafbox, const float* __restrict__ box, Node2* __restrict__ nodes,
-                            Tri1* __restrict__ tris, int* info) {
+                            Tri1* __restrict__ tris, int* info, const int* nref, int limit) {
+    if (nref) { n = *nref; if (n > limit) return; }
     const float* b = n == 1 ? leafbox : box;
     Node2 nd;
     for (int k = 0; k < 6; k++) nd.bounds[k] = b[k];
@@ -426,7 +449,14 @@ struct Opt {
     int *left, *right, *parent, *leaf_parent, *count, *height, *emitted, *depth;
     float *box, *cost;
     const float* leafbox;
+    const int* nref;                                     // the split entry: n' references, on the device (grids sized for max_refs)
 };
+
+// n and m from the device count when there is one; false when there is no inner node (then every optimising stage is a no-op)
+__device__ __forceinline__ bool resolve(Opt& o) {
+    if (o.nref) { o.n = *o.nref; o.m = o.n - 1; }
+    return o.m > 0;
+}
 
 __device__ __forceinline__ float half_area(const float* b) {
     const float dx = b[1] - b[0], dy = b[3] - b[2], dz = b[5] - b[4];
@@ -448,7 +478,9 @@ __device__ __forceinline__ void set_parent(const Opt& o, int id, int p) {
 __device__ __forceinline__ bool valid_id(const Opt& o, int id) { return (unsigned)id < (unsigned)(o.m + o.n); }
 
 __global__ __launch_bounds__(kBlock) void k_explicit(int m, const int* __restrict__ first, const int* __restrict__ last,
-                                                     const int* __restrict__ split, int* __restrict__ left, int* __restrict__ right) {
+                                                     const int* __restrict__ split, int* __restrict__ left, int* __restrict__ right,
+                                                     const int* nref) {
+    if (nref) m = *nref - 1;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= m) return;
     const int g = split[i];
@@ -468,6 +500,7 @@ __device__ __forceinline__ bool refit(const Opt& o, int node, int l, int r, floa
 
 // Box, count, height, cost and emitted-node count of every inner node, bottom-up with the hand-off of k_bottom_up.
 __global__ __launch_bounds__(kBlock) void k_fit(Opt o, uint32_t* arrivals) {
+    if (!resolve(o)) return;
     const int p = blockIdx.x * kBlock + threadIdx.x;
     if (p >= o.n) return;
     int node = o.leaf_parent[p];
@@ -492,6 +525,7 @@ __global__ __launch_bounds__(kBlock) void k_fit(Opt o, uint32_t* arrivals) {
 
 // d(n): inner nodes above n (the root's is 0), at the start of a pass.
 __global__ __launch_bounds__(kBlock) void k_depth(Opt o) {
+    if (!resolve(o)) return;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= o.m) return;
     int d = 0, c = i;
@@ -666,6 +700,7 @@ __device__ void treelet(const Opt& o, int root, int* info, TreeletLds& t) {
 // wave handles a node: a node is reached once its two subtrees are final, and a treelet writes nodes of its own subtree only.
 __global__ __launch_bounds__(64) void k_treelet(Opt o, int gamma, uint32_t* arrivals, int* info) {
     __shared__ TreeletLds t;
+    if (!resolve(o)) return;                             // uniform over the block
     const int p = blockIdx.x * 64 + threadIdx.x;
     int node = p < o.n ? o.leaf_parent[p] : -1;
     bool active = node >= 0;
@@ -690,6 +725,7 @@ __global__ __launch_bounds__(64) void k_treelet(Opt o, int gamma, uint32_t* arri
 // Node2 records in depth-first pre-order: a node is emitted when it is inner, not collapsed and has no collapsed ancestor; its index
 // and first triangle come from a walk to the root (a right child adds its left sibling's emitted count + 1 and triangle count).
 __global__ __launch_bounds__(kBlock) void k_emit_opt_nodes(Opt o, Node2* __restrict__ nodes, int* info) {
+    if (!resolve(o)) return;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= o.m) return;
     if (o.emitted[i] == 0) {
@@ -734,7 +770,8 @@ __global__ __launch_bounds__(kBlock) void k_emit_opt_nodes(Opt o, Node2* __restr
 // triangle (or of the triangle itself).
 __global__ __launch_bounds__(kBlock) void k_emit_opt_tris(Opt o, const float4* __restrict__ vertices, int nv,
                                                           const int4* __restrict__ indices, const uint32_t* __restrict__ order,
-                                                          Tri1* __restrict__ tris) {
+                                                          Tri1* __restrict__ tris, const int* __restrict__ reftri) {
+    if (!resolve(o)) return;
     const int p = blockIdx.x * kBlock + threadIdx.x;
     if (p >= o.n) return;
     int c = o.m + p, top = c, off = 0, within = 0;
@@ -748,13 +785,351 @@ __global__ __launch_bounds__(kBlock) void k_emit_opt_tris(Opt o, const float4* _
     }
     if (c != 0 || off < 0 || off >= o.n) return;
     const bool last = within == node_count(o, top) - 1;
-    const int t = (int)order[p];
+    const int t = reftri ? reftri[order[p]] : (int)order[p];
     float3 v[3]; int geom;
     load_triangle(vertices, nv, indices, t, v, &geom, nullptr);
     float4* out = reinterpret_cast<float4*>(tris + off);
     out[0] = make_float4(v[0].x, v[0].y, v[0].z, 0.0f);
     out[1] = make_float4(v[0].x - v[1].x, v[0].y - v[1].y, v[0].z - v[1].z, __int_as_float(geom));
     out[2] = make_float4(v[2].x - v[0].x, v[2].y - v[0].y, v[2].z - v[0].z, __int_as_float((int)((uint32_t)t | (last ? kLastInLeaf : 0u))));
+}
+
+// ---- 9. triangle pre-splitting (Karras & Aila 2013, section 5; the rules in include/rodent_build.h) -----------------------------
+// Per triangle: k_split_boxes (box, frame partials, flags), k_split_frame, k_priority (p and its max), k_weights (w and W), k_allot
+// (s and the block totals of s + 1), a scan, k_split (the pieces, in the triangle's slot range), a scan of the pieces made (n' in
+// info[4]), k_refs (the references in order, their Morton points and point bounds).  Then launch_tree and the tails over n'.
+constexpr int kSplitSteps = 4096;   // a cut loop takes at most 2 * 63 + 1 cuts and emits plus 3 * 1023 one-sided cuts (each removes a plane)
+enum { kInfoRefs = 4, kInfoSplit = 5, kInfoUnmade = 6 };
+
+struct SplitScratch {
+    float* tbox;                  // per triangle: its box (canonical zeros)
+    float* prio;                  // per triangle: p
+    uint32_t *w, *s, *start, *made;
+    uint32_t *blocktot, *blockmade;   // per block of kBlock triangles: sum of s + 1 / of the pieces made, scanned in place
+    float* kpartial;              // per block: bounds of the references' Morton points
+    float* sframe;                // lo[3], step[3]
+    uint32_t* pmax;               // the bits of max p (p >= 0: integer order is float order); followed by W (uint64)
+    unsigned long long* wsum;
+    float* pbox;                  // per slot: a piece's box (the front of a triangle's range) or a pending piece (the back)
+    int* pk;                      // per slot: a pending piece's splits
+    float* refbox;                // per reference: its box
+    int* reftri;                  // per reference: its triangle
+    size_t bytes;
+};
+
+SplitScratch carve_split(char* base, int n, int max_refs) {
+    SplitScratch q{};
+    size_t off = 0;
+    const auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~size_t(255); return p; };
+    const size_t N = (size_t)n, R = (size_t)max_refs, NB = (N + kBlock - 1) / kBlock;
+    q.tbox = (float*)take(4 * 6 * N); q.prio = (float*)take(4 * N);
+    q.w = (uint32_t*)take(4 * N); q.s = (uint32_t*)take(4 * N); q.start = (uint32_t*)take(4 * N); q.made = (uint32_t*)take(4 * N);
+    q.blocktot = (uint32_t*)take(4 * NB); q.blockmade = (uint32_t*)take(4 * NB);
+    q.kpartial = (float*)take(4 * 6 * NB);
+    q.sframe = (float*)take(4 * 8);
+    q.pmax = (uint32_t*)take(16); q.wsum = q.pmax ? (unsigned long long*)(q.pmax + 2) : nullptr;
+    q.pbox = (float*)take(4 * 6 * R); q.pk = (int*)take(4 * R);
+    q.refbox = (float*)take(4 * 6 * R); q.reftri = (int*)take(4 * R);
+    q.bytes = off;
+    return q;
+}
+
+// Block-wide min / max of per-thread bounds into out[6] (lo_x lo_y lo_z hi_x hi_y hi_z: the layout of k_centroids' partials).
+__device__ void block_bounds(float lo[3], float hi[3], float* out) {
+    __shared__ float red[6][kBlock];
+    for (int a = 0; a < 3; a++) { red[a][threadIdx.x] = lo[a]; red[3 + a][threadIdx.x] = hi[a]; }
+    __syncthreads();
+    for (int w = kBlock / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int a = 0; a < 3; a++) {
+                red[a][threadIdx.x] = fminf(red[a][threadIdx.x], red[a][threadIdx.x + w]);
+                red[3 + a][threadIdx.x] = fmaxf(red[3 + a][threadIdx.x], red[3 + a][threadIdx.x + w]);
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) out[threadIdx.x] = red[threadIdx.x][0];
+}
+
+// Exclusive scan of v over the block (every thread takes part; once per kernel), the block's total in *total.
+__device__ uint32_t block_scan(uint32_t v, uint32_t* total) {
+    __shared__ uint32_t wsum[kBlock / 64];
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    uint32_t x = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (int k = 0; k < kBlock / 64; k++) { before += k < w ? wsum[k] : 0u; all += wsum[k]; }
+    *total = all;
+    return before + x - v;
+}
+
+// Canonical vertices of triangle t (x + 0: no -0), as rows V[vertex][axis]; returns the error flags.
+__device__ __forceinline__ int load_canon(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices, int t,
+                                          float V[3][3], int* info) {
+    float3 v[3]; int geom;
+    const int flags = load_triangle(vertices, nv, indices, t, v, &geom, info);
+    for (int k = 0; k < 3; k++) { V[k][0] = canon(v[k].x); V[k][1] = canon(v[k].y); V[k][2] = canon(v[k].z); }
+    return flags;
+}
+
+__global__ __launch_bounds__(kBlock) void k_split_boxes(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices,
+                                                        int n, float* __restrict__ tbox, float* __restrict__ partial, int* info) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int t = blockIdx.x * kBlock + threadIdx.x; t < n; t += gridDim.x * kBlock) {
+        float V[3][3];
+        load_canon(vertices, nv, indices, t, V, info);
+        for (int a = 0; a < 3; a++) {
+            const float l = fminf(fminf(V[0][a], V[1][a]), V[2][a]), h = fmaxf(fmaxf(V[0][a], V[1][a]), V[2][a]);
+            tbox[6 * (size_t)t + 2 * a] = l; tbox[6 * (size_t)t + 2 * a + 1] = h;
+            lo[a] = fminf(lo[a], l); hi[a] = fmaxf(hi[a], h);
+        }
+    }
+    block_bounds(lo, hi, partial + 6 * blockIdx.x);
+}
+
+__global__ __launch_bounds__(kBlock) void k_split_frame(const float* __restrict__ partial, int blocks, float* __restrict__ sframe) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int b = threadIdx.x; b < blocks; b += kBlock)
+        for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], partial[6 * b + a]); hi[a] = fmaxf(hi[a], partial[6 * b + 3 + a]); }
+    __shared__ float out[6];
+    block_bounds(lo, hi, out);
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        const float step = (out[3 + a] - out[a]) * 0x1p-10f;
+        sframe[a] = out[a];
+        sframe[3 + a] = (step > 0.0f && isfinite(step)) ? step : 0.0f;     // 0: the axis has no planes
+    }
+}
+
+// The plane of box b: the coarsest grid plane strictly inside it, ties to x, y, z.  Returns its level (-1: none), *axis and *x.
+// Per axis two binary searches over the monotone positions lo + (float)c * step give the planes strictly inside, c in [cmin, cmax];
+// the coarsest of them keeps the bits above the highest bit where cmin - 1 and cmax differ.
+__device__ __forceinline__ int find_plane(const float* __restrict__ sframe, const float b[6], int* axis, float* x) {
+    int best = -1;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float lo = sframe[a], step = sframe[3 + a];
+        if (!(step > 0.0f)) continue;
+        int c0 = 1, h0 = 1024, c1 = 1, h1 = 1024;        // first c with pos > b_lo, first c with pos >= b_hi (1024: none)
+        for (int it = 0; it < 10; it++) {
+            const int m0 = (c0 + h0) >> 1, m1 = (c1 + h1) >> 1;
+            if (c0 < h0) { if (lo + (float)m0 * step > b[2 * a]) h0 = m0; else c0 = m0 + 1; }
+            if (c1 < h1) { if (lo + (float)m1 * step >= b[2 * a + 1]) h1 = m1; else c1 = m1 + 1; }
+        }
+        const int cmin = c0, cmax = c1 - 1;
+        if (cmin > cmax) continue;
+        const int level = 31 - __clz((cmin - 1) ^ cmax), c = (cmax >> level) << level;
+        if (level > best) { best = level; *axis = a; *x = lo + (float)c * step; }
+    }
+    return best;
+}
+
+__device__ __forceinline__ float pick(const float v[3], int a) { return a == 0 ? v[0] : (a == 1 ? v[1] : v[2]); }
+
+// The SBVH reference split of the triangle V's piece B at plane (axis, x) into boxes L and R (empty: lo > hi on some axis).  Fully
+// unrolled, the axis selected by compares: no runtime-indexed private array.
+__device__ __forceinline__ void cut(const float V[3][3], const float B[6], int axis, float x, float L[6], float R[6]) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) { L[k] = (k & 1) ? -INFINITY : INFINITY; R[k] = L[k]; }
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const float* P = V[i];
+        const float* Q = V[(i + 1) % 3];
+        const float pa = pick(P, axis), qa = pick(Q, axis);
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            if (pa <= x) { L[2 * b] = fminf(L[2 * b], P[b]); L[2 * b + 1] = fmaxf(L[2 * b + 1], P[b]); }
+            if (pa >= x) { R[2 * b] = fminf(R[2 * b], P[b]); R[2 * b + 1] = fmaxf(R[2 * b + 1], P[b]); }
+        }
+        if ((pa < x && qa > x) || (pa > x && qa < x)) {
+            const float t = __fdiv_rn(x - pa, qa - pa);
+#pragma unroll
+            for (int b = 0; b < 3; b++) {
+                float lo = x, hi = x;
+                if (b != axis) {
+                    const float y = P[b] + t * (Q[b] - P[b]);
+                    const float g = fmaxf(fmaxf(fabsf(P[b]), fabsf(Q[b])) * 0x1p-19f, 0x1p-126f);
+                    lo = fmaxf(y - g, fminf(P[b], Q[b]));
+                    hi = fminf(y + g, fmaxf(P[b], Q[b]));
+                }
+                L[2 * b] = fminf(L[2 * b], lo); L[2 * b + 1] = fmaxf(L[2 * b + 1], hi);
+                R[2 * b] = fminf(R[2 * b], lo); R[2 * b + 1] = fmaxf(R[2 * b + 1], hi);
+            }
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < 3; b++) {
+        L[2 * b] = fmaxf(L[2 * b], B[2 * b]); L[2 * b + 1] = fminf(L[2 * b + 1], B[2 * b + 1]);
+        R[2 * b] = fmaxf(R[2 * b], B[2 * b]); R[2 * b + 1] = fminf(R[2 * b + 1], B[2 * b + 1]);
+        if (b == axis) { L[2 * b + 1] = fminf(L[2 * b + 1], x); R[2 * b] = fmaxf(R[2 * b], x); }
+    }
+}
+
+__device__ __forceinline__ bool box_empty(const float b[6]) { return b[0] > b[1] || b[2] > b[3] || b[4] > b[5]; }
+__device__ __forceinline__ float longest(const float b[6]) { return fmaxf(fmaxf(b[1] - b[0], b[3] - b[2]), b[5] - b[4]); }
+
+__global__ __launch_bounds__(kBlock) void k_priority(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices,
+                                                     int n, const float* __restrict__ tbox, const float* __restrict__ sframe,
+                                                     float* __restrict__ prio, uint32_t* pmax) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    float p = 0.0f;
+    if (t < n) {
+        float V[3][3];
+        if (!load_canon(vertices, nv, indices, t, V, nullptr)) {
+            float b[6];
+            for (int k = 0; k < 6; k++) b[k] = tbox[6 * (size_t)t + k];
+            int axis; float x;
+            const int level = find_plane(sframe, b, &axis, &x);
+            if (level >= 0) {
+                const float ex = V[1][0] - V[0][0], ey = V[1][1] - V[0][1], ez = V[1][2] - V[0][2];
+                const float fx = V[2][0] - V[0][0], fy = V[2][1] - V[0][1], fz = V[2][2] - V[0][2];
+                const float nx = ey * fz - ez * fy, ny = ez * fx - ex * fz, nz = ex * fy - ey * fx;
+                const float excess = fmaxf(0.0f, half_area(b) - 0.5f * ((fabsf(nx) + fabsf(ny)) + fabsf(nz)));
+                p = __fsqrt_rn((float)(1 << level) * excess);
+                if (!isfinite(p)) p = 0.0f;
+            }
+        }
+        prio[t] = p;
+    }
+    float m = p;
+    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
+    if (lane_id() == 0) atomicMax(pmax, __float_as_uint(m));
+}
+
+__global__ __launch_bounds__(kBlock) void k_weights(const float* __restrict__ prio, int n, const uint32_t* __restrict__ pmax,
+                                                    uint32_t* __restrict__ w, unsigned long long* wsum) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    const float top = __uint_as_float(*pmax);
+    uint32_t wt = 0;
+    if (t < n) {
+        if (top > 0.0f) wt = (uint32_t)floorf(__fdiv_rn(prio[t], top) * 65536.0f);
+        w[t] = wt;
+    }
+    uint32_t sum = wt;                                   // at most 64 * 65536 per wave
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+    if (lane_id() == 0 && sum) atomicAdd(wsum, (unsigned long long)sum);
+}
+
+__global__ __launch_bounds__(kBlock) void k_allot(const uint32_t* __restrict__ w, int n, long long budget, int max_pieces,
+                                                  const unsigned long long* __restrict__ wsum, uint32_t* __restrict__ s,
+                                                  uint32_t* __restrict__ blocktot, int* info) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    const unsigned long long W = *wsum;
+    uint32_t st = 0;
+    if (t < n) {
+        if (W) st = (uint32_t)std::min((unsigned long long)(max_pieces - 1), ((unsigned long long)w[t] * (unsigned long long)budget) / W);
+        s[t] = st;
+    }
+    const uint64_t split = __ballot(st > 0);
+    if (lane_id() == 0 && split) atomicAdd(&info[kInfoSplit], (int)__popcll(split));
+    uint32_t total;
+    block_scan(t < n ? st + 1 : 0u, &total);
+    if (threadIdx.x == 0) blocktot[blockIdx.x] = total;
+}
+
+// One thread per triangle cuts it into at most s + 1 pieces inside its slot range [start, start + s]: final pieces from the front,
+// pending ones (box + splits) on a stack growing down from the back.  Every pending piece ends as at least one final piece and every
+// cut spends a split, so (final pieces) + (pending pieces) <= s + 1: the two ends never meet.
+__global__ __launch_bounds__(kBlock) void k_split(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices, int n,
+                                                  const float* __restrict__ tbox, const float* __restrict__ sframe,
+                                                  const uint32_t* __restrict__ s, const uint32_t* __restrict__ blockoff,
+                                                  float* __restrict__ pbox, int* __restrict__ pk, uint32_t* __restrict__ start,
+                                                  uint32_t* __restrict__ made, uint32_t* __restrict__ blockmade, int* info) {
+    __shared__ uint32_t block_made;
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    const int st = t < n ? (int)s[t] : 0;
+    uint32_t total;
+    const uint32_t first = blockoff[blockIdx.x] + block_scan(t < n ? (uint32_t)st + 1 : 0u, &total);
+    if (threadIdx.x == 0) block_made = 0;
+    __syncthreads();
+    int out = 1;
+    if (t < n && st > 0) {
+        float V[3][3], cb[6];
+        load_canon(vertices, nv, indices, t, V, nullptr);
+        for (int k = 0; k < 6; k++) cb[k] = tbox[6 * (size_t)t + k];
+        int k = st, sp = 0, unmade = 0;
+        out = 0;
+        for (int step = 0; step < kSplitSteps; step++) {
+            int axis = 0; float x = 0.0f;
+            bool final = k == 0 || find_plane(sframe, cb, &axis, &x) < 0;
+            if (!final) {
+                float L[6], R[6];
+                cut(V, cb, axis, x, L, R);
+                const bool le = box_empty(L), re = box_empty(R);
+                if (le && re) {
+                    final = true;
+                } else if (le || re) {                   // the piece lies on one side: it takes that side's box and keeps its splits
+                    for (int j = 0; j < 6; j++) cb[j] = le ? R[j] : L[j];
+                    continue;
+                } else {
+                    const float el = longest(L), er = longest(R);
+                    const float q = __fdiv_rn((float)(k - 1) * el, el + er);
+                    const int kl = (int)fminf(fmaxf(floorf(q + 0.5f), 0.0f), (float)(k - 1));
+                    const size_t slot = first + (size_t)(st - sp);
+                    for (int j = 0; j < 6; j++) pbox[6 * slot + j] = R[j];
+                    pk[slot] = k - 1 - kl;
+                    sp++;
+                    for (int j = 0; j < 6; j++) cb[j] = L[j];
+                    k = kl;
+                    continue;
+                }
+            }
+            unmade += k;
+            const size_t slot = first + (size_t)out;
+            for (int j = 0; j < 6; j++) pbox[6 * slot + j] = canon(cb[j]);
+            out++;
+            if (sp == 0) break;
+            sp--;
+            const size_t top = first + (size_t)(st - sp);
+            for (int j = 0; j < 6; j++) cb[j] = pbox[6 * top + j];
+            k = pk[top];
+        }
+        if (unmade) atomicAdd(&info[kInfoUnmade], unmade);
+    }
+    if (t < n) { start[t] = first; made[t] = (uint32_t)out; atomicAdd(&block_made, (uint32_t)out); }
+    __syncthreads();
+    if (threadIdx.x == 0) blockmade[blockIdx.x] = block_made;
+}
+
+// References in order: per triangle its pieces (or, uncut, its box and vertex sum), their Morton points and the block's point bounds.
+__global__ __launch_bounds__(kBlock) void k_refs(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices, int n,
+                                                 const float* __restrict__ tbox, const uint32_t* __restrict__ s,
+                                                 const uint32_t* __restrict__ start, const uint32_t* __restrict__ made,
+                                                 const uint32_t* __restrict__ blockoff, const float* __restrict__ pbox,
+                                                 float* __restrict__ refbox, int* __restrict__ reftri, float4* __restrict__ cent,
+                                                 float* __restrict__ kpartial) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t total;
+    const uint32_t dst = blockoff[blockIdx.x] + block_scan(t < n ? made[t] : 0u, &total);
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (t < n) {
+        if (s[t] == 0) {
+            float3 v[3]; int geom;
+            load_triangle(vertices, nv, indices, t, v, &geom, nullptr);
+            const float c[3] = {(v[0].x + v[1].x) + v[2].x, (v[0].y + v[1].y) + v[2].y, (v[0].z + v[1].z) + v[2].z};
+            for (int k = 0; k < 6; k++) refbox[6 * (size_t)dst + k] = tbox[6 * (size_t)t + k];
+            reftri[dst] = t;
+            cent[dst] = make_float4(c[0], c[1], c[2], 0.0f);
+            for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], c[a]); hi[a] = fmaxf(hi[a], c[a]); }
+        } else {
+            const uint32_t count = made[t];
+            for (uint32_t j = 0; j < count; j++) {
+                const float* b = pbox + 6 * ((size_t)start[t] + j);
+                float c[3];
+                for (int a = 0; a < 3; a++) c[a] = (b[2 * a] + b[2 * a + 1]) * 1.5f;
+                for (int k = 0; k < 6; k++) refbox[6 * ((size_t)dst + j) + k] = b[k];
+                reftri[dst + j] = t;
+                cent[dst + j] = make_float4(c[0], c[1], c[2], 0.0f);
+                for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], c[a]); hi[a] = fmaxf(hi[a], c[a]); }
+            }
+        }
+    }
+    block_bounds(lo, hi, kpartial + 6 * blockIdx.x);
 }
 
 inline int blocks_for(long long items) { return (int)((items + kBlock - 1) / kBlock); }
@@ -771,8 +1146,29 @@ int32_t check_args(int32_t dev, const float* vertices, int32_t num_vertices, con
     return RODENT_BUILD_OK;
 }
 
-// The stages both entries share: info and arrival counters zeroed, centroids, Morton codes, the sort, the sorted leaves and (n > 1)
-// the Karras hierarchy.
+// Morton codes (from s.cent and s.frame), the sort, the sorted leaves and (n > 1) the Karras hierarchy.  With `nref` (the split
+// entry) the grids are sized for n = max_refs and every kernel runs over the n' = *nref references (reftri / refbox: their
+// triangles and boxes).
+void launch_tree(const Scratch& s, const float4* v4, int nv, const int4* i4, int n, int max_leaf, Tri1* tris, const int* nref,
+                 const int* reftri, const float* refbox, hipStream_t stream) {
+    const int m = n - 1;
+    hipLaunchKernelGGL(k_morton, dim3(blocks_for(n)), dim3(kBlock), 0, stream, s.cent, n, s.frame, s.keys[0], s.vals[0], nref);
+    const int tiles = radix_tiles(n);
+    for (int pass = 0; pass < 4; pass++) {                       // 30 key bits: 8 + 8 + 8 + 6; four passes end in buffer 0
+        const int in = pass & 1, shift = 8 * pass;
+        hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(kBlock), 0, stream, s.keys[in], n, shift, s.hist, nref);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.hist, 256 * tiles, (int*)nullptr);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(kBlock), 0, stream, s.keys[in], s.vals[in], s.keys[in ^ 1],
+                           s.vals[in ^ 1], s.hist, n, shift, nref);
+    }
+    hipLaunchKernelGGL(k_leaves, dim3(blocks_for(n)), dim3(kBlock), 0, stream, v4, nv, i4, s.vals[0], n, tris, s.leafbox, nref,
+                       reftri, refbox);
+    if (m > 0)
+        hipLaunchKernelGGL(k_karras, dim3(blocks_for(m)), dim3(kBlock), 0, stream, s.keys[0], n, max_leaf, s.first, s.last, s.split,
+                           s.parent, s.leaf_parent, s.blockcount, nref);
+}
+
+// The stages both entries share: info and arrival counters zeroed, centroids, then launch_tree.
 bool launch_front(const Scratch& s, const float4* v4, int nv, const int4* i4, int n, int max_leaf, Tri1* tris, int32_t* info_dev,
                   hipStream_t stream) {
     const int m = n - 1;
@@ -781,19 +1177,7 @@ bool launch_front(const Scratch& s, const float4* v4, int nv, const int4* i4, in
     const int cblocks = std::min(kBoundsBlocks, blocks_for(n));
     hipLaunchKernelGGL(k_centroids, dim3(cblocks), dim3(kBlock), 0, stream, v4, nv, i4, n, s.cent, s.partial, info_dev);
     hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, s.partial, cblocks, s.frame);
-    hipLaunchKernelGGL(k_morton, dim3(blocks_for(n)), dim3(kBlock), 0, stream, s.cent, n, s.frame, s.keys[0], s.vals[0]);
-    const int tiles = radix_tiles(n);
-    for (int pass = 0; pass < 4; pass++) {                       // 30 key bits: 8 + 8 + 8 + 6; four passes end in buffer 0
-        const int in = pass & 1, shift = 8 * pass;
-        hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(kBlock), 0, stream, s.keys[in], n, shift, s.hist);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.hist, 256 * tiles, (int*)nullptr);
-        hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(kBlock), 0, stream, s.keys[in], s.vals[in], s.keys[in ^ 1],
-                           s.vals[in ^ 1], s.hist, n, shift);
-    }
-    hipLaunchKernelGGL(k_leaves, dim3(blocks_for(n)), dim3(kBlock), 0, stream, v4, nv, i4, s.vals[0], n, tris, s.leafbox);
-    if (m > 0)
-        hipLaunchKernelGGL(k_karras, dim3(blocks_for(m)), dim3(kBlock), 0, stream, s.keys[0], n, max_leaf, s.first, s.last, s.split,
-                           s.parent, s.leaf_parent, s.blockcount);
+    launch_tree(s, v4, nv, i4, n, max_leaf, tris, nullptr, nullptr, nullptr, stream);
     return true;
 }
 
@@ -804,6 +1188,22 @@ int32_t check_options(const RodentBuildOptions* opt) {
     if (!(opt->node_cost > 0.0f && opt->node_cost <= 1e6f) || !(opt->tri_cost > 0.0f && opt->tri_cost <= 1e6f))
         return RODENT_BUILD_ERR_COST;
     return RODENT_BUILD_OK;
+}
+
+int32_t check_split(const RodentSplitOptions* split) {
+    if (!split) return RODENT_BUILD_ERR_NULL;
+    if (!(split->budget >= 0.0f && split->budget <= RODENT_BUILD_MAX_SPLIT_BUDGET)) return RODENT_BUILD_ERR_SPLIT;   // NaN too
+    if (split->max_pieces < 1 || split->max_pieces > RODENT_BUILD_MAX_PIECES) return RODENT_BUILD_ERR_SPLIT;
+    return RODENT_BUILD_OK;
+}
+
+// B = min(floor(budget * n), 2^25 - n): the product of a float and an int below 2^25 is exact in double
+long long split_budget(int n, const RodentSplitOptions* split) {
+    return std::min((long long)std::floor((double)split->budget * (double)n), (long long)kMaxTris - n);
+}
+
+long long split_max_refs(int n, const RodentSplitOptions* split) {
+    return n + std::min(split_budget(n, split), (long long)n * (split->max_pieces - 1));
 }
 
 } // namespace
@@ -829,15 +1229,17 @@ int32_t rodent_hip_build_bvh2_tri1(int32_t dev, const float* vertices, int32_t n
     if (m > 0) {
         const int kblocks = blocks_for(m);
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.blockcount, kblocks, info_dev + kInfoNodes);
-        hipLaunchKernelGGL(k_renumber, dim3(kblocks), dim3(kBlock), 0, stream, s.first, s.last, m, max_leaf, s.blockcount, s.newidx);
+        hipLaunchKernelGGL(k_renumber, dim3(kblocks), dim3(kBlock), 0, stream, s.first, s.last, m, max_leaf, s.blockcount, s.newidx,
+                           (const int*)nullptr);
         hipLaunchKernelGGL(k_bottom_up, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, max_leaf, s.first, s.last, s.split, s.parent,
-                           s.leaf_parent, s.leafbox, s.box, s.height, s.arrivals, info_dev);
+                           s.leaf_parent, s.leafbox, s.box, s.height, s.arrivals, info_dev, (const int*)nullptr);
     }
     if (n > max_leaf)
         hipLaunchKernelGGL(k_emit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.newidx, s.leafbox,
-                           s.box, nodes, tris);
+                           s.box, nodes, tris, (const int*)nullptr);
     else
-        hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, n, s.leafbox, s.box, nodes, tris, info_dev);
+        hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, n, s.leafbox, s.box, nodes, tris, info_dev, (const int*)nullptr,
+                           0);
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
 
@@ -889,7 +1291,8 @@ int32_t rodent_hip_build_bvh2_tri1_opt(int32_t dev, const float* vertices, int32
     o.n = n; o.m = m; o.max_leaf = opt->max_leaf; o.node_cost = opt->node_cost; o.tri_cost = opt->tri_cost;
     o.left = s.left; o.right = s.right; o.parent = s.parent; o.leaf_parent = s.leaf_parent; o.count = s.count; o.height = s.height;
     o.emitted = s.emitted; o.depth = s.depth; o.box = s.box; o.cost = s.cost; o.leafbox = s.leafbox;
-    hipLaunchKernelGGL(k_explicit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.left, s.right);
+    hipLaunchKernelGGL(k_explicit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.left, s.right,
+                       (const int*)nullptr);
     hipLaunchKernelGGL(k_fit, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, s.arrivals);
     for (int pass = 0; pass < opt->treelet_passes; pass++) {
         hipLaunchKernelGGL(k_depth, dim3(blocks_for(m)), dim3(kBlock), 0, stream, o);
@@ -899,7 +1302,8 @@ int32_t rodent_hip_build_bvh2_tri1_opt(int32_t dev, const float* vertices, int32
     if (hipMemsetAsync(s.arrivals, 0, 4 * (size_t)m, stream) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
     hipLaunchKernelGGL(k_fit, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, s.arrivals);
     hipLaunchKernelGGL(k_emit_opt_nodes, dim3(blocks_for(m)), dim3(kBlock), 0, stream, o, nodes, info_dev);
-    hipLaunchKernelGGL(k_emit_opt_tris, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, v4, num_vertices, i4, s.vals[0], tris);
+    hipLaunchKernelGGL(k_emit_opt_tris, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, v4, num_vertices, i4, s.vals[0], tris,
+                       (const int*)nullptr);
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
 
@@ -923,6 +1327,119 @@ int32_t rodent_hip_build_bvh2_tri1_opt_sync(int32_t dev, const float* vertices, 
         rc = RODENT_BUILD_ERR_LAUNCH;
     (void)hipFree(scratch);
     if (info) for (int k = 0; k < RODENT_BUILD_INFO_WORDS; k++) info[k] = words[k];
+    if (rc == RODENT_BUILD_OK && words[kInfoFlags]) rc = RODENT_BUILD_ERR_INPUT;
+    return rc;
+}
+
+int64_t rodent_hip_build_split_max_refs(int32_t num_tris, const struct RodentSplitOptions* split) {
+    if (num_tris < 1 || num_tris > kMaxTris || check_split(split) != RODENT_BUILD_OK) return -1;
+    return split_max_refs(num_tris, split);
+}
+
+int64_t rodent_hip_build_split_scratch_bytes(int32_t num_tris, const struct RodentBuildOptions* opt,
+                                             const struct RodentSplitOptions* split) {
+    if (num_tris < 1 || num_tris > kMaxTris || check_options(opt) != RODENT_BUILD_OK || check_split(split) != RODENT_BUILD_OK) return -1;
+    const int refs = (int)split_max_refs(num_tris, split);
+    return (int64_t)(carve(nullptr, refs, opt->treelet_passes > 0).bytes + carve_split(nullptr, num_tris, refs).bytes);
+}
+
+int32_t rodent_hip_build_bvh2_tri1_split(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                         int32_t num_tris, const struct RodentBuildOptions* opt, const struct RodentSplitOptions* split,
+                                         struct Node2* nodes, struct Tri1* tris, void* scratch, int32_t* info_dev, void* stream_) {
+    int32_t rc = check_options(opt);
+    if (rc == RODENT_BUILD_OK) rc = check_split(split);
+    if (rc == RODENT_BUILD_OK)
+        rc = check_args(dev, vertices, num_vertices, indices, num_tris, opt->max_leaf, nodes, tris, scratch, info_dev);
+    if (rc != RODENT_BUILD_OK) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int n = num_tris, R = (int)split_max_refs(n, split), max_leaf = opt->max_leaf;
+    const bool optimise = opt->treelet_passes > 0;
+    const Scratch s = carve(static_cast<char*>(scratch), R, optimise);
+    const SplitScratch q = carve_split(static_cast<char*>(scratch) + s.bytes, n, R);
+    const float4* v4 = reinterpret_cast<const float4*>(vertices);
+    const int4* i4 = reinterpret_cast<const int4*>(indices);
+    const int* nref = info_dev + kInfoRefs;             // n', written by the second scan; every later stage reads it
+    if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_SPLIT_INFO_WORDS, stream) != hipSuccess
+        || (R > 1 && hipMemsetAsync(s.arrivals, 0, 4 * (size_t)(R - 1), stream) != hipSuccess)
+        || hipMemsetAsync(q.pmax, 0, 16, stream) != hipSuccess)
+        return RODENT_BUILD_ERR_LAUNCH;
+    const int nb = blocks_for(n), cblocks = std::min(kBoundsBlocks, nb);
+    hipLaunchKernelGGL(k_split_boxes, dim3(cblocks), dim3(kBlock), 0, stream, v4, num_vertices, i4, n, q.tbox, s.partial, info_dev);
+    hipLaunchKernelGGL(k_split_frame, dim3(1), dim3(kBlock), 0, stream, s.partial, cblocks, q.sframe);
+    hipLaunchKernelGGL(k_priority, dim3(nb), dim3(kBlock), 0, stream, v4, num_vertices, i4, n, q.tbox, q.sframe, q.prio, q.pmax);
+    hipLaunchKernelGGL(k_weights, dim3(nb), dim3(kBlock), 0, stream, q.prio, n, q.pmax, q.w, q.wsum);
+    hipLaunchKernelGGL(k_allot, dim3(nb), dim3(kBlock), 0, stream, q.w, n, split_budget(n, split), split->max_pieces, q.wsum, q.s,
+                       q.blocktot, info_dev);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, q.blocktot, nb, (int*)nullptr);
+    hipLaunchKernelGGL(k_split, dim3(nb), dim3(kBlock), 0, stream, v4, num_vertices, i4, n, q.tbox, q.sframe, q.s, q.blocktot, q.pbox,
+                       q.pk, q.start, q.made, q.blockmade, info_dev);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, q.blockmade, nb, info_dev + kInfoRefs);
+    hipLaunchKernelGGL(k_refs, dim3(nb), dim3(kBlock), 0, stream, v4, num_vertices, i4, n, q.tbox, q.s, q.start, q.made, q.blockmade,
+                       q.pbox, q.refbox, q.reftri, s.cent, q.kpartial);
+    hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, q.kpartial, nb, s.frame);
+    launch_tree(s, v4, num_vertices, i4, R, max_leaf, tris, nref, q.reftri, q.refbox, stream);
+    const int M = R - 1;
+    if (!optimise) {
+        if (M > 0) {
+            const int kblocks = blocks_for(M);
+            hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.blockcount, kblocks, info_dev + kInfoNodes);
+            hipLaunchKernelGGL(k_renumber, dim3(kblocks), dim3(kBlock), 0, stream, s.first, s.last, M, max_leaf, s.blockcount, s.newidx,
+                               nref);
+            hipLaunchKernelGGL(k_bottom_up, dim3(blocks_for(R)), dim3(kBlock), 0, stream, R, max_leaf, s.first, s.last, s.split,
+                               s.parent, s.leaf_parent, s.leafbox, s.box, s.height, s.arrivals, info_dev, nref);
+            hipLaunchKernelGGL(k_emit, dim3(kblocks), dim3(kBlock), 0, stream, M, s.first, s.last, s.split, s.newidx, s.leafbox, s.box,
+                               nodes, tris, nref);
+        }
+        hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, R, s.leafbox, s.box, nodes, tris, info_dev, nref, max_leaf);
+    } else {
+        if (M > 0) {
+            Opt o{};
+            o.n = R; o.m = M; o.max_leaf = max_leaf; o.node_cost = opt->node_cost; o.tri_cost = opt->tri_cost;
+            o.left = s.left; o.right = s.right; o.parent = s.parent; o.leaf_parent = s.leaf_parent; o.count = s.count;
+            o.height = s.height; o.emitted = s.emitted; o.depth = s.depth; o.box = s.box; o.cost = s.cost; o.leafbox = s.leafbox;
+            o.nref = nref;
+            hipLaunchKernelGGL(k_explicit, dim3(blocks_for(M)), dim3(kBlock), 0, stream, M, s.first, s.last, s.split, s.left, s.right,
+                               nref);
+            hipLaunchKernelGGL(k_fit, dim3(blocks_for(R)), dim3(kBlock), 0, stream, o, s.arrivals);
+            for (int pass = 0; pass < opt->treelet_passes; pass++) {
+                hipLaunchKernelGGL(k_depth, dim3(blocks_for(M)), dim3(kBlock), 0, stream, o);
+                if (hipMemsetAsync(s.arrivals, 0, 4 * (size_t)M, stream) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
+                hipLaunchKernelGGL(k_treelet, dim3((R + 63) / 64), dim3(64), 0, stream, o, kTreelet << pass, s.arrivals, info_dev);
+            }
+            if (hipMemsetAsync(s.arrivals, 0, 4 * (size_t)M, stream) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
+            hipLaunchKernelGGL(k_fit, dim3(blocks_for(R)), dim3(kBlock), 0, stream, o, s.arrivals);
+            hipLaunchKernelGGL(k_emit_opt_nodes, dim3(blocks_for(M)), dim3(kBlock), 0, stream, o, nodes, info_dev);
+            hipLaunchKernelGGL(k_emit_opt_tris, dim3(blocks_for(R)), dim3(kBlock), 0, stream, o, v4, num_vertices, i4, s.vals[0], tris,
+                               (const int*)q.reftri);
+        }
+        // one reference (one triangle, not cut): the single-leaf form, as the optimising entry's LBVH fallback writes it
+        hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, R, s.leafbox, s.box, nodes, tris, info_dev, nref, 1);
+    }
+    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
+int32_t rodent_hip_build_bvh2_tri1_split_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                              int32_t num_tris, const struct RodentBuildOptions* opt,
+                                              const struct RodentSplitOptions* split, struct Node2* nodes, struct Tri1* tris,
+                                              int32_t* info) {
+    int32_t rc = check_options(opt);
+    if (rc == RODENT_BUILD_OK) rc = check_split(split);
+    if (rc != RODENT_BUILD_OK) return rc;
+    const int64_t bytes = rodent_hip_build_split_scratch_bytes(num_tris, opt, split);
+    if (bytes < 0) return RODENT_BUILD_ERR_NUM_TRIS;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || dev < 0 || dev >= count || hipSetDevice(dev) != hipSuccess)
+        return RODENT_BUILD_ERR_DEVICE;
+    void* scratch = nullptr;
+    if (hipMalloc(&scratch, (size_t)bytes + 4 * RODENT_BUILD_SPLIT_INFO_WORDS) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
+    int32_t* info_dev = reinterpret_cast<int32_t*>(static_cast<char*>(scratch) + bytes);
+    rc = rodent_hip_build_bvh2_tri1_split(dev, vertices, num_vertices, indices, num_tris, opt, split, nodes, tris, scratch, info_dev,
+                                          nullptr);
+    int32_t words[RODENT_BUILD_SPLIT_INFO_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rc == RODENT_BUILD_OK && hipMemcpy(words, info_dev, sizeof words, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = RODENT_BUILD_ERR_LAUNCH;
+    (void)hipFree(scratch);
+    if (info) for (int k = 0; k < RODENT_BUILD_SPLIT_INFO_WORDS; k++) info[k] = words[k];
     if (rc == RODENT_BUILD_OK && words[kInfoFlags]) rc = RODENT_BUILD_ERR_INPUT;
     return rc;
 }

@@ -2057,10 +2057,11 @@ void rodent_hip_scene_destroy(int32_t dev) {
 
 namespace {
 
-// rodent_hip_scene_create and rodent_hip_scene_create_device_bvh(_opt): build = NULL uploads the caller's hierarchy (desc->nodes /
-// tris), build options build one on the device from the vertices and indices just uploaded (bvh_build.hip) and takes a host copy of it; from
-// there on both are the same code: checks, LDS images, per-scene rules.
-void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* build) {
+// rodent_hip_scene_create and rodent_hip_scene_create_device_bvh(_opt / _split): build = NULL uploads the caller's hierarchy
+// (desc->nodes / tris), build options build one on the device from the vertices and indices just uploaded (bvh_build.hip; with
+// `split`, over pre-split references) and takes a host copy of it; from there on both are the same code: checks, LDS images, per-scene
+// rules.
+void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* build, const RodentSplitOptions* split = nullptr) {
     RenderDevice& r = rdev(dev);
     rodent_hip_scene_destroy(dev);
     HIP_CHECK(hipSetDevice(dev));
@@ -2073,33 +2074,41 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOption
     std::vector<Node2> built_nodes;
     std::vector<Tri1> built_tris;
     {   // nodes and triangles in ONE allocation: k_trace_refill addresses both from one base with 32-bit offsets (joint_fetch_off)
-        // (a device-built hierarchy: room for the builder's max(1, n - 1) nodes, then the triangles)
-        const size_t node_bytes = sizeof(Node2) * (size_t)(build ? std::max(1, d->num_tris - 1) : d->num_nodes);
-        const size_t tri_bytes = sizeof(Tri1) * (size_t)(build ? d->num_tris : d->num_bvh_tris);
+        // (a device-built hierarchy: room for the builder's max(1, refs - 1) nodes, then its refs triangles; refs = n unsplit)
+        const int32_t refs = split ? (int32_t)rodent_hip_build_split_max_refs(d->num_tris, split) : d->num_tris;
+        const size_t node_bytes = sizeof(Node2) * (size_t)(build ? std::max(1, refs - 1) : d->num_nodes);
+        const size_t tri_bytes = sizeof(Tri1) * (size_t)(build ? refs : d->num_bvh_tris);
         char* bvh = nullptr;
         HIP_CHECK(hipMalloc(&bvh, std::max<size_t>(node_bytes + tri_bytes, 16)));
         s.allocs.push_back(bvh);
         s.dev.nodes = reinterpret_cast<const Node2*>(bvh);
         s.dev.tris = reinterpret_cast<const Tri1*>(bvh + node_bytes);
         if (build) {
-            const int64_t scratch_bytes = rodent_hip_build_opt_scratch_bytes(d->num_tris, build);
+            const int64_t scratch_bytes = split ? rodent_hip_build_split_scratch_bytes(d->num_tris, build, split)
+                                                : rodent_hip_build_opt_scratch_bytes(d->num_tris, build);
             char* scratch = nullptr;
-            int32_t info[RODENT_BUILD_INFO_WORDS];
-            HIP_CHECK(hipMalloc(&scratch, (size_t)std::max<int64_t>(scratch_bytes, 0) + sizeof info));
+            int32_t info[RODENT_BUILD_SPLIT_INFO_WORDS] = {0, 0, 0, 0, d->num_tris, 0, 0, 0};
+            const size_t info_bytes = 4 * (size_t)(split ? RODENT_BUILD_SPLIT_INFO_WORDS : RODENT_BUILD_INFO_WORDS);
+            HIP_CHECK(hipMalloc(&scratch, (size_t)std::max<int64_t>(scratch_bytes, 0) + info_bytes));
             int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + std::max<int64_t>(scratch_bytes, 0));
-            const int32_t rc = rodent_hip_build_bvh2_tri1_opt(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build,
-                reinterpret_cast<Node2*>(bvh), reinterpret_cast<Tri1*>(bvh + node_bytes), scratch, info_dev, nullptr);
+            Node2* out_nodes = reinterpret_cast<Node2*>(bvh);
+            Tri1* out_tris = reinterpret_cast<Tri1*>(bvh + node_bytes);
+            const int32_t rc = split
+                ? rodent_hip_build_bvh2_tri1_split(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build, split,
+                                                   out_nodes, out_tris, scratch, info_dev, nullptr)
+                : rodent_hip_build_bvh2_tri1_opt(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build, out_nodes,
+                                                 out_tris, scratch, info_dev, nullptr);
             if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: device BVH build refused (%d)\n", rc); abort(); }
-            HIP_CHECK(hipMemcpy(info, info_dev, sizeof info, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(info, info_dev, info_bytes, hipMemcpyDeviceToHost));
             HIP_CHECK(hipFree(scratch));
             if (info[2]) { fprintf(stderr, "rodent_hip: invalid scene: device BVH build flagged the mesh (%d)\n", info[2]); abort(); }
             built_nodes.resize(info[0]);
-            built_tris.resize(d->num_tris);
+            built_tris.resize(info[4]);                  // the references (= num_tris unsplit)
             HIP_CHECK(hipMemcpy(built_nodes.data(), bvh, sizeof(Node2) * built_nodes.size(), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(built_tris.data(), bvh + node_bytes, tri_bytes, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(built_tris.data(), bvh + node_bytes, sizeof(Tri1) * built_tris.size(), hipMemcpyDeviceToHost));
             built_desc = *d;
             built_desc.nodes = built_nodes.data(); built_desc.num_nodes = info[0];
-            built_desc.tris = built_tris.data(); built_desc.num_bvh_tris = d->num_tris;
+            built_desc.tris = built_tris.data(); built_desc.num_bvh_tris = info[4];
             d = &built_desc;
         } else {
             if (node_bytes) HIP_CHECK(hipMemcpy(bvh, d->nodes, node_bytes, hipMemcpyHostToDevice));
@@ -2230,6 +2239,18 @@ void rodent_hip_scene_create_device_bvh_opt(int32_t dev, const RodentSceneDesc* 
         abort();
     }
     scene_create(dev, d, opt);
+}
+
+void rodent_hip_scene_create_device_bvh_split(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* opt,
+                                              const RodentSplitOptions* split) {
+    if (!opt || !split || rodent_hip_build_split_scratch_bytes(1, opt, split) < 0 || d->num_tris < 1
+        || d->num_tris > RODENT_BUILD_MAX_TRIS || d->num_vertices < 1 || d->nodes || d->tris || d->num_nodes || d->num_bvh_tris) {
+        fprintf(stderr, "rodent_hip: rodent_hip_scene_create_device_bvh_split: invalid arguments (max_leaf 1 ... 8, treelet passes "
+                        "0 ... 3, costs in (0, 1e6], split budget 0 ... 4, max_pieces 1 ... 64, 1 ... 2^25 triangles, "
+                        "no hierarchy in the description)\n");
+        abort();
+    }
+    scene_create(dev, d, opt, split);
 }
 
 void rodent_hip_scene_bvh(int32_t dev, const Node2** nodes, const Tri1** tris, int32_t* num_nodes, int32_t* num_tris) {

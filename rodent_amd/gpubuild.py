@@ -2,11 +2,12 @@
 
     bvh = build_bvh2(vertices, indices)            # numpy arrays or CUDA tensors, (n, 3) or (n, 4)
     bvh = build_bvh2(vertices, indices, treelet_passes=2)   # + treelet restructuring and an SAH leaf collapse
+    bvh = build_bvh2(vertices, indices, treelet_passes=3, split_budget=1.0)   # + triangle pre-splitting (bvh.num_tris references)
     hits = abi.traverse(bvh, rays)
 
 The result is a pure function of the inputs, byte for byte.  As a tool:
 
-    python -m rodent_amd.gpubuild scene.rscene -o out.bvh [--max-leaf N] [--treelet-passes N]
+    python -m rodent_amd.gpubuild scene.rscene -o out.bvh [--max-leaf N] [--treelet-passes N] [--split-budget F [--max-pieces K]]
 
 writes a .bvh holding the BVH2_TRI1 block of the scene's mesh (bench_traversal reads it).
 """
@@ -25,9 +26,13 @@ MAX_LEAF = 8
 MAX_TREELET_PASSES = 3
 NODE_COST, TRI_COST = 1.2, 1.0         # RODENT_BUILD_DEFAULT_NODE_COST / _TRI_COST
 INFO_WORDS = 4
+SPLIT_INFO_WORDS = 8                   # + [4] Tri1 count (references) [5] triangles split [6] splits allotted but not made [7] 0
+MAX_PIECES, MAX_SPLIT_BUDGET = 64, 4.0
 BAD_INDEX, NON_FINITE = 1, 2
+ERR_SPLIT = -10
 _ERRORS = {-1: "num_tris outside [1, 2^25]", -2: "max_leaf outside [1, 8]", -3: "no vertices", -4: "NULL pointer",
-           -5: "no such device", -6: "launch failed", -8: "treelet_passes outside [0, 3]", -9: "node_cost / tri_cost outside (0, 1e6]"}
+           -5: "no such device", -6: "launch failed", -8: "treelet_passes outside [0, 3]", -9: "node_cost / tri_cost outside (0, 1e6]",
+           ERR_SPLIT: "split budget outside [0, 4] or max_pieces outside [1, 64]"}
 
 
 class BuildError(RuntimeError):
@@ -57,8 +62,18 @@ def options(max_leaf=2, treelet_passes=0, node_cost=NODE_COST, tri_cost=TRI_COST
     return opt
 
 
+def split_options(budget=0.0, max_pieces=MAX_PIECES) -> abi.SplitOptions:
+    """A checked RodentSplitOptions; raises BuildError on values the library would refuse."""
+    sp = abi.SplitOptions(float(budget), int(max_pieces))
+    if not 0.0 <= sp.budget <= MAX_SPLIT_BUDGET:
+        raise BuildError(f"split budget = {budget}: outside [0, 4]")
+    if not 1 <= max_pieces <= MAX_PIECES:
+        raise BuildError(f"max_pieces = {max_pieces}: outside [1, 64]")
+    return sp
+
+
 def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, out=None, treelet_passes=0, node_cost=NODE_COST,
-               tri_cost=TRI_COST) -> abi.DeviceBvh:
+               tri_cost=TRI_COST, split_budget=0.0, max_pieces=None) -> abi.DeviceBvh:
     """Builds the BVH2 / Tri1 hierarchy of the triangles `indices` (v0 v1 v2 [geometry id]; 3 columns: geometry id 0) over
     `vertices` (x y z [w]) on device `dev`, on `stream` (torch stream, None = the current one).  Returns an abi.DeviceBvh whose
     `depth` and `info` are set.  Raises BuildError on invalid arguments and on the device's error flags (an index outside the
@@ -67,7 +82,10 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
     scratch / out: reuse the scratch tensor / the node and triangle tensors of an earlier result (rebuild in place); they must be
     large enough.
     treelet_passes = 1 ... 3: restructure the LBVH's treelets and collapse its leaves by SAH cost (node_cost, tri_cost; max_leaf is
-    then the largest leaf allowed, not a threshold); info[3] counts the topologies the depth rule rejected.  0: the LBVH as it is."""
+    then the largest leaf allowed, not a threshold); info[3] counts the topologies the depth rule rejected.  0: the LBVH as it is.
+    split_budget > 0 or max_pieces given: pre-split the triangles first (rodent_hip_build_bvh2_tri1_split; up to split_budget * n
+    extra references, at most max_pieces (default 64) per triangle); bvh.num_tris is then the reference count info[4], and info has
+    8 words."""
     if not torch.cuda.is_available():
         raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
     v = _columns4(vertices, torch.float32, dev)
@@ -76,27 +94,38 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
     if not 1 <= n <= MAX_TRIS:
         raise BuildError(f"num_tris = {n}: outside [1, 2^25]")
     opt = options(max_leaf, treelet_passes, node_cost, tri_cost)
+    splitting = bool(split_budget) or max_pieces is not None
+    sp = split_options(split_budget, MAX_PIECES if max_pieces is None else max_pieces) if splitting else None
     if stream is None:
         stream = torch.cuda.current_stream(dev)
     l = abi.lib()
-    need = l.rodent_hip_build_opt_scratch_bytes(n, C.byref(opt))
+    if splitting:
+        need = l.rodent_hip_build_split_scratch_bytes(n, C.byref(opt), C.byref(sp))
+        refs = l.rodent_hip_build_split_max_refs(n, C.byref(sp))
+    else:
+        need, refs = l.rodent_hip_build_opt_scratch_bytes(n, C.byref(opt)), n
     cuda = f"cuda:{dev}"
     if scratch is None or scratch.numel() * scratch.element_size() < need:
         scratch = torch.empty(need, dtype=torch.uint8, device=cuda)
     if out is None:
-        nodes = torch.empty(max(1, n - 1) * F.NODE2.itemsize, dtype=torch.uint8, device=cuda)
-        tris = torch.empty(n * F.TRI1.itemsize, dtype=torch.uint8, device=cuda)
+        nodes = torch.empty(max(1, refs - 1) * F.NODE2.itemsize, dtype=torch.uint8, device=cuda)
+        tris = torch.empty(refs * F.TRI1.itemsize, dtype=torch.uint8, device=cuda)
     else:
         nodes, tris = out.nodes, out.tris
-        if (nodes.numel() * nodes.element_size() < max(1, n - 1) * F.NODE2.itemsize
-                or tris.numel() * tris.element_size() < n * F.TRI1.itemsize):
+        if (nodes.numel() * nodes.element_size() < max(1, refs - 1) * F.NODE2.itemsize
+                or tris.numel() * tris.element_size() < refs * F.TRI1.itemsize):
             raise ValueError("build_bvh2: the buffers of `out` are too small for this mesh")
-    info = torch.empty(INFO_WORDS, dtype=torch.int32, device=cuda)
+    info = torch.empty(SPLIT_INFO_WORDS if splitting else INFO_WORDS, dtype=torch.int32, device=cuda)
     # the caller's tensors may come from another stream: make this one wait for the inputs
     stream.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(stream):
-        entry = "rodent_hip_build_bvh2_tri1_opt" if treelet_passes else "rodent_hip_build_bvh2_tri1"
-        if treelet_passes:
+        entry = ("rodent_hip_build_bvh2_tri1_split" if splitting else
+                 "rodent_hip_build_bvh2_tri1_opt" if treelet_passes else "rodent_hip_build_bvh2_tri1")
+        if splitting:
+            rc = l.rodent_hip_build_bvh2_tri1_split(dev, v.data_ptr(), nv, ix.data_ptr(), n, C.byref(opt), C.byref(sp),
+                                                    nodes.data_ptr(), tris.data_ptr(), scratch.data_ptr(), info.data_ptr(),
+                                                    C.c_void_p(stream.cuda_stream))
+        elif treelet_passes:
             rc = l.rodent_hip_build_bvh2_tri1_opt(dev, v.data_ptr(), nv, ix.data_ptr(), n, C.byref(opt), nodes.data_ptr(),
                                                   tris.data_ptr(), scratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
         else:
@@ -111,7 +140,7 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
         what = [s for bit, s in ((BAD_INDEX, "vertex index outside the vertex array"), (NON_FINITE, "non-finite vertex coordinate"))
                 if words[2] & bit]
         raise BuildError(f"{entry}: " + ", ".join(what))
-    bvh = abi.DeviceBvh.from_tensors(2, nodes, tris, int(words[0]), n, dev)
+    bvh = abi.DeviceBvh.from_tensors(2, nodes, tris, int(words[0]), int(words[4]) if splitting else n, dev)
     bvh.depth, bvh.info, bvh.scratch = int(words[1]), words.copy(), scratch
     return bvh
 
@@ -131,10 +160,14 @@ def main(argv=None):
     ap.add_argument("--max-leaf", type=int, default=2, help="largest leaf (1 ... 8, default 2)")
     ap.add_argument("--treelet-passes", type=int, default=0,
                     help="treelet restructuring passes + SAH leaf collapse (0 ... 3, default 0: the LBVH as it is)")
+    ap.add_argument("--split-budget", type=float, default=0.0,
+                    help="pre-split triangles into up to this fraction of extra references (0 ... 4, default 0: no splitting)")
+    ap.add_argument("--max-pieces", type=int, default=None, help="the most references one triangle may become (1 ... 64, default 64)")
     ap.add_argument("--dev", type=int, default=0)
     a = ap.parse_args(argv)
     sc = Scene(a.scene)
-    bvh = build_bvh2(sc.vertices, sc.indices, a.max_leaf, a.dev, treelet_passes=a.treelet_passes)
+    bvh = build_bvh2(sc.vertices, sc.indices, a.max_leaf, a.dev, treelet_passes=a.treelet_passes, split_budget=a.split_budget,
+                     max_pieces=a.max_pieces)
     nodes, tris = download(bvh)
     F.write_bvh(a.output, [(F.BVH2_TRI1, nodes, tris)])
     print(f"{a.output}: {len(tris)} triangles, {len(nodes)} nodes, depth {bvh.depth}")

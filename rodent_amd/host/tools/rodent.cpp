@@ -18,6 +18,8 @@
 //                       the host SBVH (.obj input) or the file's (.rscene input); --max-leaf n: its largest leaf (1 ... 8, default 2)
 //   --treelet-passes n  with --gpu-bvh: n = 1 ... 3 passes of treelet restructuring and an SAH leaf collapse (rodent_build.h,
 //                       rodent_hip_scene_create_device_bvh_opt); 0 (the default) = the LBVH as it is
+//   --split-budget f    with --gpu-bvh: pre-split triangles into up to f * n extra references (0 ... 4, default 0; rodent_build.h,
+//                       rodent_hip_scene_create_device_bvh_split); --max-pieces k: at most k references per triangle (1 ... 64, default 64)
 // Without --bench the reference opens an SDL window and renders until it is closed; this build is
 // headless (DISABLE_GUI, driver.cpp:236-242), so --bench or -o is required.
 #include <algorithm>
@@ -53,6 +55,8 @@ static void usage() {
               << "   --gpu-bvh           Builds the BVH on the GPU (LBVH) instead of the host SBVH or the scene file's BVH\n"
               << "   --max-leaf n        With --gpu-bvh: at most n triangles per leaf (1 ... 8, default 2)\n"
               << "   --treelet-passes n  With --gpu-bvh: n passes (0 ... 3, default 0) of treelet restructuring + SAH leaf collapse\n"
+              << "   --split-budget f    With --gpu-bvh: pre-split triangles into up to f * n extra references (0 ... 4, default 0)\n"
+              << "   --max-pieces k      With --split-budget: at most k references per triangle (1 ... 64, default 64)\n"
               << "   --width  pixels     Sets the viewport horizontal dimension (in pixels)\n"
               << "   --height pixels     Sets the viewport vertical dimension (in pixels)\n"
               << "   --eye    x y z      Sets the position of the camera\n"
@@ -74,6 +78,9 @@ int main(int argc, char** argv) {
     bool bands = false, check = false, gpu_bvh = false;
     int max_leaf = 2, treelet_passes = 0;
     bool treelet_given = false;
+    float split_budget = 0.0f;
+    int max_pieces = RODENT_BUILD_MAX_PIECES;
+    bool split_given = false, pieces_given = false;
     int sort = -1;                                                        // -1: the library's default
 
     for (int i = 1; i < argc; ++i) {
@@ -104,6 +111,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--gpu-bvh")) gpu_bvh = true;
         else if (!strcmp(argv[i], "--max-leaf")) { need(1); max_leaf = strtol(argv[++i], nullptr, 10); }
         else if (!strcmp(argv[i], "--treelet-passes")) { need(1); treelet_passes = strtol(argv[++i], nullptr, 10); treelet_given = true; }
+        else if (!strcmp(argv[i], "--split-budget")) { need(1); split_budget = strtof(argv[++i], nullptr); split_given = true; }
+        else if (!strcmp(argv[i], "--max-pieces")) { need(1); max_pieces = strtol(argv[++i], nullptr, 10); pieces_given = true; }
         else if (!strcmp(argv[i], "--target")) {
             need(1); ++i;
             if (!strcmp(argv[i], "amdgpu-streaming") || !strcmp(argv[i], "amdgpu")) mapping = 0;
@@ -122,6 +131,10 @@ int main(int argc, char** argv) {
     if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) fail("Invalid --max-leaf (1 ... 8)");
     if (treelet_passes < 0 || treelet_passes > RODENT_BUILD_MAX_TREELET_PASSES) fail("Invalid --treelet-passes (0 ... 3)");
     if (treelet_given && !gpu_bvh) fail("--treelet-passes needs --gpu-bvh");
+    if (!(split_budget >= 0.0f && split_budget <= RODENT_BUILD_MAX_SPLIT_BUDGET)) fail("Invalid --split-budget (0 ... 4)");
+    if (max_pieces < 1 || max_pieces > RODENT_BUILD_MAX_PIECES) fail("Invalid --max-pieces (1 ... 64)");
+    if (split_given && !gpu_bvh) fail("--split-budget needs --gpu-bvh");
+    if (pieces_given && !split_given) fail("--max-pieces needs --split-budget");
     if (is_obj ? !build_scene_from_obj(scene_file, scene, nullptr, !gpu_bvh) : !load_scene(scene_file, scene))
         fail("Cannot load scene '" + scene_file + "'");
     if (scene.lights.empty()) fail("The scene has no light source");
@@ -148,7 +161,9 @@ int main(int argc, char** argv) {
         rodent_hip_set_device(d);
         if (gpu_bvh) {
             const RodentBuildOptions opt{max_leaf, treelet_passes, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
-            rodent_hip_scene_create_device_bvh_opt(d, &desc, &opt);
+            const RodentSplitOptions split{split_budget, max_pieces};
+            if (split_given) rodent_hip_scene_create_device_bvh_split(d, &desc, &opt, &split);
+            else rodent_hip_scene_create_device_bvh_opt(d, &desc, &opt);
         }
         else rodent_hip_scene_create(d, &desc);
         rodent_hip_render_config(d, spp, max_path_len);

@@ -29,6 +29,7 @@ class SceneDesc(C.Structure):
 
 
 RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_create_device_bvh_opt",
+                  "rodent_hip_scene_create_device_bvh_split",
     "rodent_hip_scene_bvh", "rodent_hip_scene_destroy",
     "rodent_hip_render_config", "rodent_hip_render_mapping",
     "rodent_hip_render_capacity", "rodent_hip_render_sort", "rodent_hip_render_hit_records", "rodent_hip_render_overlap",
@@ -59,6 +60,9 @@ def lib():
         l.rodent_hip_scene_create_device_bvh.restype = None
         l.rodent_hip_scene_create_device_bvh_opt.argtypes = [i32, C.POINTER(SceneDesc), C.POINTER(abi.BuildOptions)]
         l.rodent_hip_scene_create_device_bvh_opt.restype = None
+        l.rodent_hip_scene_create_device_bvh_split.argtypes = [i32, C.POINTER(SceneDesc), C.POINTER(abi.BuildOptions),
+                                                               C.POINTER(abi.SplitOptions)]
+        l.rodent_hip_scene_create_device_bvh_split.restype = None
         l.rodent_hip_scene_bvh.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
         l.rodent_hip_scene_bvh.restype = None
         l.rodent_hip_render_config.argtypes = [i32, i32, i32]; l.rodent_hip_render_config.restype = None
@@ -112,12 +116,16 @@ class Renderer:
     def __init__(self, scene, width, height, spp=4, max_path_len=64, dev=0, mapping="streaming", capacity=0, sort=None, overlap=None,
         fused_sort=None, lds_image=None,
                  trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None,
-                 gpu_bvh_passes=0):
+                 gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64):
         """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says.
         gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh);
-        gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it (rodent_hip_scene_create_device_bvh_opt)."""
+        gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it (rodent_hip_scene_create_device_bvh_opt).
+        gpu_bvh_split = (0, 4]: pre-split the triangles into up to that fraction of extra references, at most gpu_bvh_max_pieces per
+        triangle (rodent_hip_scene_create_device_bvh_split)."""
         if gpu_bvh_passes and not gpu_bvh:
             raise ValueError("gpu_bvh_passes needs gpu_bvh (the treelet passes act on the device-built hierarchy)")
+        if gpu_bvh_split and not gpu_bvh:
+            raise ValueError("gpu_bvh_split needs gpu_bvh (the split references feed the device-built hierarchy)")
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("rodent_amd: no GPU visible (the renderer has no CPU fallback)")
@@ -134,7 +142,12 @@ class Renderer:
         if gpu_bvh:
             desc.nodes = desc.tris = None
             desc.num_nodes = desc.num_bvh_tris = 0
-            if gpu_bvh_passes:
+            if gpu_bvh_split:
+                from . import gpubuild
+                opt = gpubuild.options(int(gpu_bvh), int(gpu_bvh_passes))
+                sp = gpubuild.split_options(float(gpu_bvh_split), int(gpu_bvh_max_pieces))
+                l.rodent_hip_scene_create_device_bvh_split(dev, C.byref(desc), C.byref(opt), C.byref(sp))
+            elif gpu_bvh_passes:
                 from . import gpubuild
                 opt = gpubuild.options(int(gpu_bvh), int(gpu_bvh_passes))
                 l.rodent_hip_scene_create_device_bvh_opt(dev, C.byref(desc), C.byref(opt))

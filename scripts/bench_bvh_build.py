@@ -9,8 +9,13 @@ For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> conve
   * with --treelet-passes N > 0, the same for the optimised build (rodent_hip_build_bvh2_tri1_opt: N treelet passes + SAH leaf
     collapse, default costs) in the "opt" columns.
 
+  * with --split-budget F [F ...] (and --treelet-passes N), the same for pre-split builds (rodent_hip_build_bvh2_tri1_split: budget F,
+    --max-pieces K, N passes) in the "split F" columns: build ms, split ms (split build - unsplit build with the same passes),
+    references, triangles split, leaves holding one triangle twice ("dup").
+
     python scripts/bench_bvh_build.py [--scenes atrium gallery crown plant] [--builds 20] [-o profiles/gpu_bvh_build.txt]
     python scripts/bench_bvh_build.py --treelet-passes 3 -o profiles/gpu_bvh_build_opt.txt
+    python scripts/bench_bvh_build.py --treelet-passes 3 --split-budget 0.25 1 -o profiles/gpu_bvh_build_split.txt
 """
 from __future__ import annotations
 
@@ -64,6 +69,8 @@ def main():
     ap.add_argument("--scenes", nargs="+", default=["atrium", "gallery", "crown", "plant"])
     ap.add_argument("--builds", type=int, default=20)
     ap.add_argument("--treelet-passes", type=int, default=0, help="also measure the optimised build with N passes (1 ... 3)")
+    ap.add_argument("--split-budget", type=float, nargs="*", default=[], help="also measure pre-split builds with these budgets")
+    ap.add_argument("--max-pieces", type=int, default=64)
     ap.add_argument("-o", "--output", default=str(ROOT / "profiles" / "gpu_bvh_build.txt"))
     a = ap.parse_args()
     from oracle import binding as O
@@ -79,6 +86,11 @@ def main():
         lines[0] += f"; opt: {P} treelet passes + SAH leaf collapse, max_leaf 2"
         hdr += (f" || {'opt ms':>7} {'nodes':>8} {'depth':>5} {'rej':>4} | {'prim Mr/s':>9} {'rand Mr/s':>9} | {'steps prim':>10} "
                 f"{'rand':>6} | {'SAH':>6}")
+    for B in a.split_budget:
+        hdr += (f" || {'split ' + str(B):>10} {'split ms':>8} {'refs':>8} {'split':>7} {'dup':>6} {'depth':>5} | {'prim Mr/s':>9} "
+                f"{'rand Mr/s':>9} | {'steps prim':>10} {'rand':>6} | {'SAH':>6}")
+    if a.split_budget:
+        lines[0] += f"; split: max_pieces {a.max_pieces}, {P} treelet passes, max_leaf 2"
     lines.append(hdr)
     print(hdr, flush=True)
     out_dir = scenes.DATA
@@ -127,6 +139,27 @@ def main():
             host["opt"] = gpubuild.download(opt)
             assert tree_depth(host["opt"][0]) == opt.depth <= 56        # checked before anything traces it
             trees["opt"] = opt
+        split_ms, split_info = {}, {}
+        base_ms = opt_ms if P else build_ms
+        for B in a.split_budget:
+            sb = gpubuild.build_bvh2(v, ix, 2, treelet_passes=P, split_budget=B, max_pieces=a.max_pieces)
+            copt, csp = gpubuild.options(2, P), gpubuild.split_options(B, a.max_pieces)
+            sinfo = torch.empty(8, dtype=torch.int32, device="cuda")
+
+            def one_split_build():
+                rc = abi.lib().rodent_hip_build_bvh2_tri1_split(0, v.data_ptr(), len(sc.vertices), ix.data_ptr(), n, C.byref(copt),
+                                                                C.byref(csp), sb.nodes.data_ptr(), sb.tris.data_ptr(),
+                                                                sb.scratch.data_ptr(), sinfo.data_ptr(), C.c_void_p(stream.cuda_stream))
+                assert rc == 0
+            split_ms[B] = event_ms(one_split_build, 3, a.builds)
+            assert sinfo.cpu().numpy().tolist() == sb.info.tolist()
+            host[B] = gpubuild.download(sb)
+            assert tree_depth(host[B][0]) == sb.depth <= 56          # checked before anything traces it
+            ht = host[B][1]
+            leaf = np.concatenate([[0], np.cumsum(ht["prim_id"][:-1] < 0)])
+            pairs = np.unique(np.stack([leaf, ht["prim_id"] & 0x7FFFFFFF], 1), axis=0, return_counts=True)
+            split_info[B] = (sb.num_tris, int(sb.info[5]), len(np.unique(pairs[0][pairs[1] > 1][:, 0])), sb.depth)
+            trees[B] = sb
         rate, steps = {}, {}
         for rk, rays in ray_sets.items():
             rays_dev = abi.to_device(rays)
@@ -147,7 +180,12 @@ def main():
             row += (f" || {opt_ms:>7.3f} {opt.num_nodes:>8} {opt.depth:>5} {int(opt.info[3]):>4} | {rate['primary', 'opt']:>9.0f} "
                     f"{rate['random', 'opt']:>9.0f} | {steps['primary', 'opt']:>10.1f} {steps['random', 'opt']:>6.1f} | "
                     f"{L.sah_cost(*host['opt']):>6.1f}")
-            del opt, trees
+        for B in a.split_budget:
+            refs, nsplit, dup, depth = split_info[B]
+            row += (f" || {split_ms[B]:>10.3f} {split_ms[B] - base_ms:>8.3f} {refs:>8} {nsplit:>7} {dup:>6} {depth:>5} | "
+                    f"{rate['primary', B]:>9.0f} {rate['random', B]:>9.0f} | {steps['primary', B]:>10.1f} {steps['random', B]:>6.1f} | "
+                    f"{L.sah_cost(*host[B]):>6.1f}")
+        trees.clear()
         lines.append(row)
         print(row, flush=True)
         del bvh, sbvh, v, ix
