@@ -1,31 +1,35 @@
-// bvh_build.hip -- linear BVH builder on the device (LBVH: Morton codes + Karras 2012 hierarchy) writing BVH2 / Tri1 in the layout
-// of include/rodent_traversal.h.  C ABI: include/rodent_build.h.  CPU model of every stage, byte for byte: tests/lbvh_model.py.
+// bvh_build.hip -- BVH builder on the device writing BVH2 / Tri1 in the layout of include/rodent_traversal.h: a linear BVH (Morton
+// codes + Karras 2012 hierarchy), optionally restructured by treelets with an SAH leaf collapse, optionally over pre-split triangles.
+// C ABI: include/rodent_build.h.  CPU models of every stage, byte for byte: tests/lbvh_model.py, tests/trbvh_model.py (treelets),
+// tests/split_model.py (pre-splitting).
 //
-// Stages, all on the caller's stream, nothing allocated, no host synchronisation:
+// One pipeline (launch_build), all on the caller's stream, nothing allocated, no host synchronisation.  The three entry points only
+// choose its options: rodent_hip_build_bvh2_tri1 the LBVH, _opt treelet_passes (0, or one triangle: the LBVH), _split the split front.
+// Front, one of:
 //   k_centroids      per triangle: indices checked before any vertex load, centroid sum s = (v0 + v1) + v2, per-block min / max
 //   k_bounds         one block: the centroid bounds and per-axis scale = 1024 / extent (0 for an empty or non-finite extent)
+// or (split) the pre-splitting stages of section 9, k_split_boxes ... k_refs, which make the n' references, then k_bounds over
+// their Morton points.
+// Tree (launch_tree):
 //   k_morton         30-bit Morton code: cell = (uint)min(max((s - lo) * scale, 0), 1023) per axis, x in the highest bit of a triple
 //   k_radix_*        stable LSD radix sort of (code, triangle id), 4 passes of 8 bits: order = by code, then by triangle id
 //   k_leaves         Tri1 records in sorted order + the sorted triangles' boxes
 //   k_karras         the n - 1 internal nodes (Karras 2012, delta ties broken by the sorted position), parent links, kept-node counts
+// Tail, the LBVH's (treelet_passes = 0, launch_lbvh_tail):
 //   k_renumber       kept internal nodes (more than max_leaf triangles) numbered by an exclusive scan in Karras order
 //   k_bottom_up      boxes and heights, per-node arrival counters (first arriver leaves, the second goes on; no waiting)
 //   k_emit / k_emit_root   Node2 records, end-of-leaf bits
-// Every value is a function of the inputs alone: min / max are exact and do not depend on the order they are taken in, the sort is
-// stable, and arrival order decides only WHICH thread computes a node, never what it computes.
-//
-// The optimising entry (rodent_hip_build_bvh2_tri1_opt, treelet_passes > 0) shares the stages up to k_karras, then (CPU model of
-// every stage, byte for byte: tests/trbvh_model.py):
+// or the optimising one (treelet_passes > 0, launch_opt_tail):
 //   k_explicit       the Karras tree as an explicit binary tree: left / right child ids (leaves: m + sorted position), parents
 //   k_fit            bottom-up: box, triangle count, height, SAH cost, emitted-node count per inner node (arrival counters)
 //   per pass k:      k_depth (every node's depth, a walk up the parent links), then k_treelet with gamma = 7 << k: the bottom-up
 //                    climb again; each node of at least gamma triangles gets its 7-leaf treelet restructured by its wave
 //   k_fit            again: the SAH leaf collapse decisions and emitted-node counts of the final tree
 //   k_emit_opt_nodes / k_emit_opt_tris   Node2 in depth-first pre-order, Tri1 in left-to-right leaf order (O(depth) walks)
-//
-// The splitting entry (rodent_hip_build_bvh2_tri1_split; CPU model: tests/split_model.py) puts the pre-splitting stages of section 9
-// in front and runs the stages above over the n' references they make.  n' is known on the device only: those stages get grids sized
-// for max_refs and read n' (`nref`) from info[4]; without `nref` they behave exactly as before.
+// Split, n' is known on the device only: the tree and tail stages get grids sized for max_refs and read n' (`nref`) from info[4];
+// without `nref` the host sizes them for the n triangles.
+// Every value is a function of the inputs alone: min / max are exact and do not depend on the order they are taken in, the sort is
+// stable, and arrival order decides only WHICH thread computes a node, never what it computes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1134,51 +1138,18 @@ __global__ __launch_bounds__(kBlock) void k_refs(const float4* __restrict__ vert
 
 inline int blocks_for(long long items) { return (int)((items + kBlock - 1) / kBlock); }
 
+bool set_device(int32_t dev) {
+    int count = 0;
+    return hipGetDeviceCount(&count) == hipSuccess && dev >= 0 && dev < count && hipSetDevice(dev) == hipSuccess;
+}
+
 int32_t check_args(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris, int32_t max_leaf,
                    const void* nodes, const void* tris, const void* scratch, const int32_t* info_dev) {
     if (num_tris < 1 || num_tris > kMaxTris) return RODENT_BUILD_ERR_NUM_TRIS;
     if (max_leaf < 1 || max_leaf > 8) return RODENT_BUILD_ERR_MAX_LEAF;
     if (num_vertices < 1) return RODENT_BUILD_ERR_NUM_VERTICES;
     if (!vertices || !indices || !nodes || !tris || !scratch || !info_dev) return RODENT_BUILD_ERR_NULL;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || dev < 0 || dev >= count) return RODENT_BUILD_ERR_DEVICE;
-    if (hipSetDevice(dev) != hipSuccess) return RODENT_BUILD_ERR_DEVICE;
-    return RODENT_BUILD_OK;
-}
-
-// Morton codes (from s.cent and s.frame), the sort, the sorted leaves and (n > 1) the Karras hierarchy.  With `nref` (the split
-// entry) the grids are sized for n = max_refs and every kernel runs over the n' = *nref references (reftri / refbox: their
-// triangles and boxes).
-void launch_tree(const Scratch& s, const float4* v4, int nv, const int4* i4, int n, int max_leaf, Tri1* tris, const int* nref,
-                 const int* reftri, const float* refbox, hipStream_t stream) {
-    const int m = n - 1;
-    hipLaunchKernelGGL(k_morton, dim3(blocks_for(n)), dim3(kBlock), 0, stream, s.cent, n, s.frame, s.keys[0], s.vals[0], nref);
-    const int tiles = radix_tiles(n);
-    for (int pass = 0; pass < 4; pass++) {                       // 30 key bits: 8 + 8 + 8 + 6; four passes end in buffer 0
-        const int in = pass & 1, shift = 8 * pass;
-        hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(kBlock), 0, stream, s.keys[in], n, shift, s.hist, nref);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.hist, 256 * tiles, (int*)nullptr);
-        hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(kBlock), 0, stream, s.keys[in], s.vals[in], s.keys[in ^ 1],
-                           s.vals[in ^ 1], s.hist, n, shift, nref);
-    }
-    hipLaunchKernelGGL(k_leaves, dim3(blocks_for(n)), dim3(kBlock), 0, stream, v4, nv, i4, s.vals[0], n, tris, s.leafbox, nref,
-                       reftri, refbox);
-    if (m > 0)
-        hipLaunchKernelGGL(k_karras, dim3(blocks_for(m)), dim3(kBlock), 0, stream, s.keys[0], n, max_leaf, s.first, s.last, s.split,
-                           s.parent, s.leaf_parent, s.blockcount, nref);
-}
-
-// The stages both entries share: info and arrival counters zeroed, centroids, then launch_tree.
-bool launch_front(const Scratch& s, const float4* v4, int nv, const int4* i4, int n, int max_leaf, Tri1* tris, int32_t* info_dev,
-                  hipStream_t stream) {
-    const int m = n - 1;
-    if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess) return false;
-    if (m > 0 && hipMemsetAsync(s.arrivals, 0, 4 * (size_t)m, stream) != hipSuccess) return false;
-    const int cblocks = std::min(kBoundsBlocks, blocks_for(n));
-    hipLaunchKernelGGL(k_centroids, dim3(cblocks), dim3(kBlock), 0, stream, v4, nv, i4, n, s.cent, s.partial, info_dev);
-    hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, s.partial, cblocks, s.frame);
-    launch_tree(s, v4, nv, i4, n, max_leaf, tris, nullptr, nullptr, nullptr, stream);
-    return true;
+    return set_device(dev) ? RODENT_BUILD_OK : RODENT_BUILD_ERR_DEVICE;
 }
 
 int32_t check_options(const RodentBuildOptions* opt) {
@@ -1206,6 +1177,139 @@ long long split_max_refs(int n, const RodentSplitOptions* split) {
     return n + std::min(split_budget(n, split), (long long)n * (split->max_pieces - 1));
 }
 
+// Morton codes (from s.cent and s.frame), the sort, the sorted leaves and (n > 1) the Karras hierarchy.  With `nref` (split) the
+// grids are sized for n = max_refs and every kernel runs over the n' = *nref references (reftri / refbox: their triangles and boxes).
+void launch_tree(const Scratch& s, const float4* v4, int nv, const int4* i4, int n, int max_leaf, Tri1* tris, const int* nref,
+                 const int* reftri, const float* refbox, hipStream_t stream) {
+    const int m = n - 1;
+    hipLaunchKernelGGL(k_morton, dim3(blocks_for(n)), dim3(kBlock), 0, stream, s.cent, n, s.frame, s.keys[0], s.vals[0], nref);
+    const int tiles = radix_tiles(n);
+    for (int pass = 0; pass < 4; pass++) {                       // 30 key bits: 8 + 8 + 8 + 6; four passes end in buffer 0
+        const int in = pass & 1, shift = 8 * pass;
+        hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(kBlock), 0, stream, s.keys[in], n, shift, s.hist, nref);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.hist, 256 * tiles, (int*)nullptr);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(kBlock), 0, stream, s.keys[in], s.vals[in], s.keys[in ^ 1],
+                           s.vals[in ^ 1], s.hist, n, shift, nref);
+    }
+    hipLaunchKernelGGL(k_leaves, dim3(blocks_for(n)), dim3(kBlock), 0, stream, v4, nv, i4, s.vals[0], n, tris, s.leafbox, nref,
+                       reftri, refbox);
+    if (m > 0)
+        hipLaunchKernelGGL(k_karras, dim3(blocks_for(m)), dim3(kBlock), 0, stream, s.keys[0], n, max_leaf, s.first, s.last, s.split,
+                           s.parent, s.leaf_parent, s.blockcount, nref);
+}
+
+// The LBVH tail: renumbering, boxes and heights, Node2 records.  Without `nref` the host knows n and launches either k_emit or the
+// single-leaf root; with it both are launched and each writes only when n' calls for it.
+void launch_lbvh_tail(const Scratch& s, int n, int max_leaf, Node2* nodes, Tri1* tris, int32_t* info_dev, const int* nref,
+                      hipStream_t stream) {
+    const int m = n - 1;
+    if (m > 0) {
+        const int kblocks = blocks_for(m);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.blockcount, kblocks, info_dev + kInfoNodes);
+        hipLaunchKernelGGL(k_renumber, dim3(kblocks), dim3(kBlock), 0, stream, s.first, s.last, m, max_leaf, s.blockcount, s.newidx,
+                           nref);
+        hipLaunchKernelGGL(k_bottom_up, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, max_leaf, s.first, s.last, s.split, s.parent,
+                           s.leaf_parent, s.leafbox, s.box, s.height, s.arrivals, info_dev, nref);
+    }
+    if (nref ? m > 0 : n > max_leaf)
+        hipLaunchKernelGGL(k_emit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.newidx, s.leafbox,
+                           s.box, nodes, tris, nref);
+    if (nref || n <= max_leaf)
+        hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, n, s.leafbox, s.box, nodes, tris, info_dev, nref, max_leaf);
+}
+
+// The optimising tail: the explicit tree, k_fit, the treelet passes, k_fit again, pre-order emission.  Without `nref` it is only
+// reached with n > 1; with it the single-leaf root follows, written when n' = 1.  False when a memset is refused.
+bool launch_opt_tail(const Scratch& s, int n, const RodentBuildOptions& opt, const float4* v4, int nv, const int4* i4, Node2* nodes,
+                     Tri1* tris, int32_t* info_dev, const int* nref, const int* reftri, hipStream_t stream) {
+    const int m = n - 1;
+    if (m > 0) {
+        Opt o{};
+        o.n = n; o.m = m; o.max_leaf = opt.max_leaf; o.node_cost = opt.node_cost; o.tri_cost = opt.tri_cost;
+        o.left = s.left; o.right = s.right; o.parent = s.parent; o.leaf_parent = s.leaf_parent; o.count = s.count; o.height = s.height;
+        o.emitted = s.emitted; o.depth = s.depth; o.box = s.box; o.cost = s.cost; o.leafbox = s.leafbox; o.nref = nref;
+        hipLaunchKernelGGL(k_explicit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.left, s.right,
+                           nref);
+        hipLaunchKernelGGL(k_fit, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, s.arrivals);
+        for (int pass = 0; pass < opt.treelet_passes; pass++) {
+            hipLaunchKernelGGL(k_depth, dim3(blocks_for(m)), dim3(kBlock), 0, stream, o);
+            if (hipMemsetAsync(s.arrivals, 0, 4 * (size_t)m, stream) != hipSuccess) return false;
+            hipLaunchKernelGGL(k_treelet, dim3((n + 63) / 64), dim3(64), 0, stream, o, kTreelet << pass, s.arrivals, info_dev);
+        }
+        if (hipMemsetAsync(s.arrivals, 0, 4 * (size_t)m, stream) != hipSuccess) return false;
+        hipLaunchKernelGGL(k_fit, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, s.arrivals);
+        hipLaunchKernelGGL(k_emit_opt_nodes, dim3(blocks_for(m)), dim3(kBlock), 0, stream, o, nodes, info_dev);
+        hipLaunchKernelGGL(k_emit_opt_tris, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, v4, nv, i4, s.vals[0], tris, reftri);
+    }
+    // one reference (one triangle, not cut): the single-leaf form, as the LBVH writes it for one triangle
+    if (nref) hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, n, s.leafbox, s.box, nodes, tris, info_dev, nref, 1);
+    return true;
+}
+
+// Every entry after its argument checks: info words and arrival counters zeroed, the front (centroids, or with `split` the
+// pre-splitting stages of section 9), launch_tree, then the LBVH tail (treelet_passes = 0) or the optimising one.  Without `split`
+// the stages run over the n triangles; with it over the n' references, on grids sized for max_refs.
+int32_t launch_build(const float* vertices, int nv, const int32_t* indices, int n, const RodentBuildOptions& opt,
+                     const RodentSplitOptions* split, Node2* nodes, Tri1* tris, void* scratch, int32_t* info_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int R = split ? (int)split_max_refs(n, split) : n, M = R - 1;
+    const bool optimise = opt.treelet_passes > 0;
+    const Scratch s = carve(static_cast<char*>(scratch), R, optimise);
+    const SplitScratch q = split ? carve_split(static_cast<char*>(scratch) + s.bytes, n, R) : SplitScratch{};
+    const float4* v4 = reinterpret_cast<const float4*>(vertices);
+    const int4* i4 = reinterpret_cast<const int4*>(indices);
+    const int* nref = split ? info_dev + kInfoRefs : nullptr;     // n', written by the second scan; every later stage reads it
+    // an unsplit caller's info buffer may hold only RODENT_BUILD_INFO_WORDS words
+    const size_t info_bytes = 4 * (size_t)(split ? RODENT_BUILD_SPLIT_INFO_WORDS : RODENT_BUILD_INFO_WORDS);
+    if (hipMemsetAsync(info_dev, 0, info_bytes, stream) != hipSuccess
+        || (M > 0 && hipMemsetAsync(s.arrivals, 0, 4 * (size_t)M, stream) != hipSuccess)
+        || (split && hipMemsetAsync(q.pmax, 0, 16, stream) != hipSuccess))
+        return RODENT_BUILD_ERR_LAUNCH;
+    const int nb = blocks_for(n), cblocks = std::min(kBoundsBlocks, nb);
+    if (!split) {
+        hipLaunchKernelGGL(k_centroids, dim3(cblocks), dim3(kBlock), 0, stream, v4, nv, i4, n, s.cent, s.partial, info_dev);
+        hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, s.partial, cblocks, s.frame);
+    } else {
+        hipLaunchKernelGGL(k_split_boxes, dim3(cblocks), dim3(kBlock), 0, stream, v4, nv, i4, n, q.tbox, s.partial, info_dev);
+        hipLaunchKernelGGL(k_split_frame, dim3(1), dim3(kBlock), 0, stream, s.partial, cblocks, q.sframe);
+        hipLaunchKernelGGL(k_priority, dim3(nb), dim3(kBlock), 0, stream, v4, nv, i4, n, q.tbox, q.sframe, q.prio, q.pmax);
+        hipLaunchKernelGGL(k_weights, dim3(nb), dim3(kBlock), 0, stream, q.prio, n, q.pmax, q.w, q.wsum);
+        hipLaunchKernelGGL(k_allot, dim3(nb), dim3(kBlock), 0, stream, q.w, n, split_budget(n, split), split->max_pieces, q.wsum, q.s,
+                           q.blocktot, info_dev);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, q.blocktot, nb, (int*)nullptr);
+        hipLaunchKernelGGL(k_split, dim3(nb), dim3(kBlock), 0, stream, v4, nv, i4, n, q.tbox, q.sframe, q.s, q.blocktot, q.pbox, q.pk,
+                           q.start, q.made, q.blockmade, info_dev);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, q.blockmade, nb, info_dev + kInfoRefs);
+        hipLaunchKernelGGL(k_refs, dim3(nb), dim3(kBlock), 0, stream, v4, nv, i4, n, q.tbox, q.s, q.start, q.made, q.blockmade, q.pbox,
+                           q.refbox, q.reftri, s.cent, q.kpartial);
+        hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, q.kpartial, nb, s.frame);
+    }
+    launch_tree(s, v4, nv, i4, R, opt.max_leaf, tris, nref, q.reftri, q.refbox, stream);
+    if (!optimise)
+        launch_lbvh_tail(s, R, opt.max_leaf, nodes, tris, info_dev, nref, stream);
+    else if (!launch_opt_tail(s, R, opt, v4, nv, i4, nodes, tris, info_dev, nref, q.reftri, stream))
+        return RODENT_BUILD_ERR_LAUNCH;
+    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
+// The sync forms after their own checks: scratch and `words` info words in one allocation, the entry (`build(scratch, info_dev)`) on
+// the null stream, the info words copied to `info`; RODENT_BUILD_ERR_INPUT when the device raised a flag.
+template <class Build>
+int32_t build_sync(int32_t dev, int64_t scratch_bytes, int words, int32_t* info, Build build) {
+    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
+    void* scratch = nullptr;
+    if (hipMalloc(&scratch, (size_t)scratch_bytes + 4 * words) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
+    int32_t* info_dev = reinterpret_cast<int32_t*>(static_cast<char*>(scratch) + scratch_bytes);
+    int32_t rc = build(scratch, info_dev);
+    int32_t host[RODENT_BUILD_SPLIT_INFO_WORDS] = {};
+    if (rc == RODENT_BUILD_OK && hipMemcpy(host, info_dev, 4 * (size_t)words, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = RODENT_BUILD_ERR_LAUNCH;
+    (void)hipFree(scratch);
+    if (info) std::copy(host, host + words, info);
+    if (rc == RODENT_BUILD_OK && host[kInfoFlags]) rc = RODENT_BUILD_ERR_INPUT;
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -1217,30 +1321,11 @@ int64_t rodent_hip_build_scratch_bytes(int32_t num_tris) {
 
 int32_t rodent_hip_build_bvh2_tri1(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
                                    int32_t max_leaf, struct Node2* nodes, struct Tri1* tris, void* scratch, int32_t* info_dev,
-                                   void* stream_) {
+                                   void* stream) {
     const int32_t rc = check_args(dev, vertices, num_vertices, indices, num_tris, max_leaf, nodes, tris, scratch, info_dev);
     if (rc != RODENT_BUILD_OK) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int n = num_tris, m = n - 1;
-    const Scratch s = carve(static_cast<char*>(scratch), n);
-    const float4* v4 = reinterpret_cast<const float4*>(vertices);
-    const int4* i4 = reinterpret_cast<const int4*>(indices);
-    if (!launch_front(s, v4, num_vertices, i4, n, max_leaf, tris, info_dev, stream)) return RODENT_BUILD_ERR_LAUNCH;
-    if (m > 0) {
-        const int kblocks = blocks_for(m);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.blockcount, kblocks, info_dev + kInfoNodes);
-        hipLaunchKernelGGL(k_renumber, dim3(kblocks), dim3(kBlock), 0, stream, s.first, s.last, m, max_leaf, s.blockcount, s.newidx,
-                           (const int*)nullptr);
-        hipLaunchKernelGGL(k_bottom_up, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, max_leaf, s.first, s.last, s.split, s.parent,
-                           s.leaf_parent, s.leafbox, s.box, s.height, s.arrivals, info_dev, (const int*)nullptr);
-    }
-    if (n > max_leaf)
-        hipLaunchKernelGGL(k_emit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.newidx, s.leafbox,
-                           s.box, nodes, tris, (const int*)nullptr);
-    else
-        hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, n, s.leafbox, s.box, nodes, tris, info_dev, (const int*)nullptr,
-                           0);
-    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+    const RodentBuildOptions opt{max_leaf, 0, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
+    return launch_build(vertices, num_vertices, indices, num_tris, opt, nullptr, nodes, tris, scratch, info_dev, stream);
 }
 
 int32_t rodent_hip_build_bvh2_tri1_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
@@ -1248,21 +1333,10 @@ int32_t rodent_hip_build_bvh2_tri1_sync(int32_t dev, const float* vertices, int3
     const int64_t bytes = rodent_hip_build_scratch_bytes(num_tris);
     if (bytes < 0) return RODENT_BUILD_ERR_NUM_TRIS;
     if (max_leaf < 1 || max_leaf > 8) return RODENT_BUILD_ERR_MAX_LEAF;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || dev < 0 || dev >= count || hipSetDevice(dev) != hipSuccess)
-        return RODENT_BUILD_ERR_DEVICE;
-    void* scratch = nullptr;
-    if (hipMalloc(&scratch, (size_t)bytes + 4 * RODENT_BUILD_INFO_WORDS) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
-    int32_t* info_dev = reinterpret_cast<int32_t*>(static_cast<char*>(scratch) + bytes);
-    int32_t rc = rodent_hip_build_bvh2_tri1(dev, vertices, num_vertices, indices, num_tris, max_leaf, nodes, tris, scratch, info_dev,
-                                            nullptr);
-    int32_t words[RODENT_BUILD_INFO_WORDS] = {0, 0, 0, 0};
-    if (rc == RODENT_BUILD_OK && hipMemcpy(words, info_dev, sizeof words, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = RODENT_BUILD_ERR_LAUNCH;
-    (void)hipFree(scratch);
-    if (info) for (int k = 0; k < RODENT_BUILD_INFO_WORDS; k++) info[k] = words[k];
-    if (rc == RODENT_BUILD_OK && words[kInfoFlags]) rc = RODENT_BUILD_ERR_INPUT;
-    return rc;
+    return build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
+        return rodent_hip_build_bvh2_tri1(dev, vertices, num_vertices, indices, num_tris, max_leaf, nodes, tris, scratch, info_dev,
+                                          nullptr);
+    });
 }
 
 int64_t rodent_hip_build_opt_scratch_bytes(int32_t num_tris, const struct RodentBuildOptions* opt) {
@@ -1272,63 +1346,27 @@ int64_t rodent_hip_build_opt_scratch_bytes(int32_t num_tris, const struct Rodent
 
 int32_t rodent_hip_build_bvh2_tri1_opt(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
                                        int32_t num_tris, const struct RodentBuildOptions* opt, struct Node2* nodes, struct Tri1* tris,
-                                       void* scratch, int32_t* info_dev, void* stream_) {
-    const int32_t orc = check_options(opt);
-    if (orc != RODENT_BUILD_OK) return orc;
-    // no passes, or one triangle (nothing to restructure or collapse): the LBVH entry, byte for byte
-    if (opt->treelet_passes == 0 || num_tris == 1)
-        return rodent_hip_build_bvh2_tri1(dev, vertices, num_vertices, indices, num_tris, opt->max_leaf, nodes, tris, scratch, info_dev,
-                                          stream_);
-    const int32_t rc = check_args(dev, vertices, num_vertices, indices, num_tris, opt->max_leaf, nodes, tris, scratch, info_dev);
+                                       void* scratch, int32_t* info_dev, void* stream) {
+    int32_t rc = check_options(opt);
+    if (rc == RODENT_BUILD_OK)
+        rc = check_args(dev, vertices, num_vertices, indices, num_tris, opt->max_leaf, nodes, tris, scratch, info_dev);
     if (rc != RODENT_BUILD_OK) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int n = num_tris, m = n - 1;
-    const Scratch s = carve(static_cast<char*>(scratch), n, true);
-    const float4* v4 = reinterpret_cast<const float4*>(vertices);
-    const int4* i4 = reinterpret_cast<const int4*>(indices);
-    if (!launch_front(s, v4, num_vertices, i4, n, opt->max_leaf, tris, info_dev, stream)) return RODENT_BUILD_ERR_LAUNCH;
-    Opt o{};
-    o.n = n; o.m = m; o.max_leaf = opt->max_leaf; o.node_cost = opt->node_cost; o.tri_cost = opt->tri_cost;
-    o.left = s.left; o.right = s.right; o.parent = s.parent; o.leaf_parent = s.leaf_parent; o.count = s.count; o.height = s.height;
-    o.emitted = s.emitted; o.depth = s.depth; o.box = s.box; o.cost = s.cost; o.leafbox = s.leafbox;
-    hipLaunchKernelGGL(k_explicit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.left, s.right,
-                       (const int*)nullptr);
-    hipLaunchKernelGGL(k_fit, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, s.arrivals);
-    for (int pass = 0; pass < opt->treelet_passes; pass++) {
-        hipLaunchKernelGGL(k_depth, dim3(blocks_for(m)), dim3(kBlock), 0, stream, o);
-        if (hipMemsetAsync(s.arrivals, 0, 4 * (size_t)m, stream) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
-        hipLaunchKernelGGL(k_treelet, dim3((n + 63) / 64), dim3(64), 0, stream, o, kTreelet << pass, s.arrivals, info_dev);
-    }
-    if (hipMemsetAsync(s.arrivals, 0, 4 * (size_t)m, stream) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
-    hipLaunchKernelGGL(k_fit, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, s.arrivals);
-    hipLaunchKernelGGL(k_emit_opt_nodes, dim3(blocks_for(m)), dim3(kBlock), 0, stream, o, nodes, info_dev);
-    hipLaunchKernelGGL(k_emit_opt_tris, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, v4, num_vertices, i4, s.vals[0], tris,
-                       (const int*)nullptr);
-    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+    RodentBuildOptions o = *opt;
+    if (num_tris == 1) o.treelet_passes = 0;          // nothing to restructure or collapse: the LBVH, byte for byte
+    return launch_build(vertices, num_vertices, indices, num_tris, o, nullptr, nodes, tris, scratch, info_dev, stream);
 }
 
 int32_t rodent_hip_build_bvh2_tri1_opt_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
                                             int32_t num_tris, const struct RodentBuildOptions* opt, struct Node2* nodes,
                                             struct Tri1* tris, int32_t* info) {
-    const int32_t orc = check_options(opt);
-    if (orc != RODENT_BUILD_OK) return orc;
+    const int32_t rc = check_options(opt);
+    if (rc != RODENT_BUILD_OK) return rc;
     const int64_t bytes = rodent_hip_build_opt_scratch_bytes(num_tris, opt);
     if (bytes < 0) return RODENT_BUILD_ERR_NUM_TRIS;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || dev < 0 || dev >= count || hipSetDevice(dev) != hipSuccess)
-        return RODENT_BUILD_ERR_DEVICE;
-    void* scratch = nullptr;
-    if (hipMalloc(&scratch, (size_t)bytes + 4 * RODENT_BUILD_INFO_WORDS) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
-    int32_t* info_dev = reinterpret_cast<int32_t*>(static_cast<char*>(scratch) + bytes);
-    int32_t rc = rodent_hip_build_bvh2_tri1_opt(dev, vertices, num_vertices, indices, num_tris, opt, nodes, tris, scratch, info_dev,
-                                                nullptr);
-    int32_t words[RODENT_BUILD_INFO_WORDS] = {0, 0, 0, 0};
-    if (rc == RODENT_BUILD_OK && hipMemcpy(words, info_dev, sizeof words, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = RODENT_BUILD_ERR_LAUNCH;
-    (void)hipFree(scratch);
-    if (info) for (int k = 0; k < RODENT_BUILD_INFO_WORDS; k++) info[k] = words[k];
-    if (rc == RODENT_BUILD_OK && words[kInfoFlags]) rc = RODENT_BUILD_ERR_INPUT;
-    return rc;
+    return build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
+        return rodent_hip_build_bvh2_tri1_opt(dev, vertices, num_vertices, indices, num_tris, opt, nodes, tris, scratch, info_dev,
+                                              nullptr);
+    });
 }
 
 int64_t rodent_hip_build_split_max_refs(int32_t num_tris, const struct RodentSplitOptions* split) {
@@ -1345,77 +1383,13 @@ int64_t rodent_hip_build_split_scratch_bytes(int32_t num_tris, const struct Rode
 
 int32_t rodent_hip_build_bvh2_tri1_split(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
                                          int32_t num_tris, const struct RodentBuildOptions* opt, const struct RodentSplitOptions* split,
-                                         struct Node2* nodes, struct Tri1* tris, void* scratch, int32_t* info_dev, void* stream_) {
+                                         struct Node2* nodes, struct Tri1* tris, void* scratch, int32_t* info_dev, void* stream) {
     int32_t rc = check_options(opt);
     if (rc == RODENT_BUILD_OK) rc = check_split(split);
     if (rc == RODENT_BUILD_OK)
         rc = check_args(dev, vertices, num_vertices, indices, num_tris, opt->max_leaf, nodes, tris, scratch, info_dev);
     if (rc != RODENT_BUILD_OK) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int n = num_tris, R = (int)split_max_refs(n, split), max_leaf = opt->max_leaf;
-    const bool optimise = opt->treelet_passes > 0;
-    const Scratch s = carve(static_cast<char*>(scratch), R, optimise);
-    const SplitScratch q = carve_split(static_cast<char*>(scratch) + s.bytes, n, R);
-    const float4* v4 = reinterpret_cast<const float4*>(vertices);
-    const int4* i4 = reinterpret_cast<const int4*>(indices);
-    const int* nref = info_dev + kInfoRefs;             // n', written by the second scan; every later stage reads it
-    if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_SPLIT_INFO_WORDS, stream) != hipSuccess
-        || (R > 1 && hipMemsetAsync(s.arrivals, 0, 4 * (size_t)(R - 1), stream) != hipSuccess)
-        || hipMemsetAsync(q.pmax, 0, 16, stream) != hipSuccess)
-        return RODENT_BUILD_ERR_LAUNCH;
-    const int nb = blocks_for(n), cblocks = std::min(kBoundsBlocks, nb);
-    hipLaunchKernelGGL(k_split_boxes, dim3(cblocks), dim3(kBlock), 0, stream, v4, num_vertices, i4, n, q.tbox, s.partial, info_dev);
-    hipLaunchKernelGGL(k_split_frame, dim3(1), dim3(kBlock), 0, stream, s.partial, cblocks, q.sframe);
-    hipLaunchKernelGGL(k_priority, dim3(nb), dim3(kBlock), 0, stream, v4, num_vertices, i4, n, q.tbox, q.sframe, q.prio, q.pmax);
-    hipLaunchKernelGGL(k_weights, dim3(nb), dim3(kBlock), 0, stream, q.prio, n, q.pmax, q.w, q.wsum);
-    hipLaunchKernelGGL(k_allot, dim3(nb), dim3(kBlock), 0, stream, q.w, n, split_budget(n, split), split->max_pieces, q.wsum, q.s,
-                       q.blocktot, info_dev);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, q.blocktot, nb, (int*)nullptr);
-    hipLaunchKernelGGL(k_split, dim3(nb), dim3(kBlock), 0, stream, v4, num_vertices, i4, n, q.tbox, q.sframe, q.s, q.blocktot, q.pbox,
-                       q.pk, q.start, q.made, q.blockmade, info_dev);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, q.blockmade, nb, info_dev + kInfoRefs);
-    hipLaunchKernelGGL(k_refs, dim3(nb), dim3(kBlock), 0, stream, v4, num_vertices, i4, n, q.tbox, q.s, q.start, q.made, q.blockmade,
-                       q.pbox, q.refbox, q.reftri, s.cent, q.kpartial);
-    hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, q.kpartial, nb, s.frame);
-    launch_tree(s, v4, num_vertices, i4, R, max_leaf, tris, nref, q.reftri, q.refbox, stream);
-    const int M = R - 1;
-    if (!optimise) {
-        if (M > 0) {
-            const int kblocks = blocks_for(M);
-            hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.blockcount, kblocks, info_dev + kInfoNodes);
-            hipLaunchKernelGGL(k_renumber, dim3(kblocks), dim3(kBlock), 0, stream, s.first, s.last, M, max_leaf, s.blockcount, s.newidx,
-                               nref);
-            hipLaunchKernelGGL(k_bottom_up, dim3(blocks_for(R)), dim3(kBlock), 0, stream, R, max_leaf, s.first, s.last, s.split,
-                               s.parent, s.leaf_parent, s.leafbox, s.box, s.height, s.arrivals, info_dev, nref);
-            hipLaunchKernelGGL(k_emit, dim3(kblocks), dim3(kBlock), 0, stream, M, s.first, s.last, s.split, s.newidx, s.leafbox, s.box,
-                               nodes, tris, nref);
-        }
-        hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, R, s.leafbox, s.box, nodes, tris, info_dev, nref, max_leaf);
-    } else {
-        if (M > 0) {
-            Opt o{};
-            o.n = R; o.m = M; o.max_leaf = max_leaf; o.node_cost = opt->node_cost; o.tri_cost = opt->tri_cost;
-            o.left = s.left; o.right = s.right; o.parent = s.parent; o.leaf_parent = s.leaf_parent; o.count = s.count;
-            o.height = s.height; o.emitted = s.emitted; o.depth = s.depth; o.box = s.box; o.cost = s.cost; o.leafbox = s.leafbox;
-            o.nref = nref;
-            hipLaunchKernelGGL(k_explicit, dim3(blocks_for(M)), dim3(kBlock), 0, stream, M, s.first, s.last, s.split, s.left, s.right,
-                               nref);
-            hipLaunchKernelGGL(k_fit, dim3(blocks_for(R)), dim3(kBlock), 0, stream, o, s.arrivals);
-            for (int pass = 0; pass < opt->treelet_passes; pass++) {
-                hipLaunchKernelGGL(k_depth, dim3(blocks_for(M)), dim3(kBlock), 0, stream, o);
-                if (hipMemsetAsync(s.arrivals, 0, 4 * (size_t)M, stream) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
-                hipLaunchKernelGGL(k_treelet, dim3((R + 63) / 64), dim3(64), 0, stream, o, kTreelet << pass, s.arrivals, info_dev);
-            }
-            if (hipMemsetAsync(s.arrivals, 0, 4 * (size_t)M, stream) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
-            hipLaunchKernelGGL(k_fit, dim3(blocks_for(R)), dim3(kBlock), 0, stream, o, s.arrivals);
-            hipLaunchKernelGGL(k_emit_opt_nodes, dim3(blocks_for(M)), dim3(kBlock), 0, stream, o, nodes, info_dev);
-            hipLaunchKernelGGL(k_emit_opt_tris, dim3(blocks_for(R)), dim3(kBlock), 0, stream, o, v4, num_vertices, i4, s.vals[0], tris,
-                               (const int*)q.reftri);
-        }
-        // one reference (one triangle, not cut): the single-leaf form, as the optimising entry's LBVH fallback writes it
-        hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, R, s.leafbox, s.box, nodes, tris, info_dev, nref, 1);
-    }
-    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+    return launch_build(vertices, num_vertices, indices, num_tris, *opt, split, nodes, tris, scratch, info_dev, stream);
 }
 
 int32_t rodent_hip_build_bvh2_tri1_split_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
@@ -1427,21 +1401,10 @@ int32_t rodent_hip_build_bvh2_tri1_split_sync(int32_t dev, const float* vertices
     if (rc != RODENT_BUILD_OK) return rc;
     const int64_t bytes = rodent_hip_build_split_scratch_bytes(num_tris, opt, split);
     if (bytes < 0) return RODENT_BUILD_ERR_NUM_TRIS;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || dev < 0 || dev >= count || hipSetDevice(dev) != hipSuccess)
-        return RODENT_BUILD_ERR_DEVICE;
-    void* scratch = nullptr;
-    if (hipMalloc(&scratch, (size_t)bytes + 4 * RODENT_BUILD_SPLIT_INFO_WORDS) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
-    int32_t* info_dev = reinterpret_cast<int32_t*>(static_cast<char*>(scratch) + bytes);
-    rc = rodent_hip_build_bvh2_tri1_split(dev, vertices, num_vertices, indices, num_tris, opt, split, nodes, tris, scratch, info_dev,
-                                          nullptr);
-    int32_t words[RODENT_BUILD_SPLIT_INFO_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (rc == RODENT_BUILD_OK && hipMemcpy(words, info_dev, sizeof words, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = RODENT_BUILD_ERR_LAUNCH;
-    (void)hipFree(scratch);
-    if (info) for (int k = 0; k < RODENT_BUILD_SPLIT_INFO_WORDS; k++) info[k] = words[k];
-    if (rc == RODENT_BUILD_OK && words[kInfoFlags]) rc = RODENT_BUILD_ERR_INPUT;
-    return rc;
+    return build_sync(dev, bytes, RODENT_BUILD_SPLIT_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
+        return rodent_hip_build_bvh2_tri1_split(dev, vertices, num_vertices, indices, num_tris, opt, split, nodes, tris, scratch,
+                                                info_dev, nullptr);
+    });
 }
 
 } // extern "C"

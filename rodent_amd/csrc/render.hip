@@ -2074,8 +2074,15 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOption
     std::vector<Node2> built_nodes;
     std::vector<Tri1> built_tris;
     {   // nodes and triangles in ONE allocation: k_trace_refill addresses both from one base with 32-bit offsets (joint_fetch_off)
-        // (a device-built hierarchy: room for the builder's max(1, refs - 1) nodes, then its refs triangles; refs = n unsplit)
-        const int32_t refs = split ? (int32_t)rodent_hip_build_split_max_refs(d->num_tris, split) : d->num_tris;
+        // (a device-built hierarchy: room for the builder's max(1, refs - 1) nodes, then its refs triangles; the builder's scratch and
+        // info words.  Unsplit: refs = n, 4 info words, info[4] keeps n)
+        int32_t refs = d->num_tris, info_words = RODENT_BUILD_INFO_WORDS;
+        int64_t scratch_bytes = build ? rodent_hip_build_opt_scratch_bytes(d->num_tris, build) : 0;
+        if (split) {
+            refs = (int32_t)rodent_hip_build_split_max_refs(d->num_tris, split);
+            scratch_bytes = rodent_hip_build_split_scratch_bytes(d->num_tris, build, split);
+            info_words = RODENT_BUILD_SPLIT_INFO_WORDS;
+        }
         const size_t node_bytes = sizeof(Node2) * (size_t)(build ? std::max(1, refs - 1) : d->num_nodes);
         const size_t tri_bytes = sizeof(Tri1) * (size_t)(build ? refs : d->num_bvh_tris);
         char* bvh = nullptr;
@@ -2084,11 +2091,9 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOption
         s.dev.nodes = reinterpret_cast<const Node2*>(bvh);
         s.dev.tris = reinterpret_cast<const Tri1*>(bvh + node_bytes);
         if (build) {
-            const int64_t scratch_bytes = split ? rodent_hip_build_split_scratch_bytes(d->num_tris, build, split)
-                                                : rodent_hip_build_opt_scratch_bytes(d->num_tris, build);
             char* scratch = nullptr;
             int32_t info[RODENT_BUILD_SPLIT_INFO_WORDS] = {0, 0, 0, 0, d->num_tris, 0, 0, 0};
-            const size_t info_bytes = 4 * (size_t)(split ? RODENT_BUILD_SPLIT_INFO_WORDS : RODENT_BUILD_INFO_WORDS);
+            const size_t info_bytes = 4 * (size_t)info_words;
             HIP_CHECK(hipMalloc(&scratch, (size_t)std::max<int64_t>(scratch_bytes, 0) + info_bytes));
             int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + std::max<int64_t>(scratch_bytes, 0));
             Node2* out_nodes = reinterpret_cast<Node2*>(bvh);

@@ -99,10 +99,14 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
     if stream is None:
         stream = torch.cuda.current_stream(dev)
     l = abi.lib()
+    # the entry and its option arguments, its scratch bytes, the Tri1 records it may write, its info words
     if splitting:
-        need = l.rodent_hip_build_split_scratch_bytes(n, C.byref(opt), C.byref(sp))
-        refs = l.rodent_hip_build_split_max_refs(n, C.byref(sp))
+        entry, args, info_words = "rodent_hip_build_bvh2_tri1_split", (C.byref(opt), C.byref(sp)), SPLIT_INFO_WORDS
+        need, refs = l.rodent_hip_build_split_scratch_bytes(n, *args), l.rodent_hip_build_split_max_refs(n, C.byref(sp))
     else:
+        entry, args = (("rodent_hip_build_bvh2_tri1_opt", (C.byref(opt),)) if treelet_passes else
+                       ("rodent_hip_build_bvh2_tri1", (int(max_leaf),)))
+        info_words = INFO_WORDS
         need, refs = l.rodent_hip_build_opt_scratch_bytes(n, C.byref(opt)), n
     cuda = f"cuda:{dev}"
     if scratch is None or scratch.numel() * scratch.element_size() < need:
@@ -115,22 +119,12 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
         if (nodes.numel() * nodes.element_size() < max(1, refs - 1) * F.NODE2.itemsize
                 or tris.numel() * tris.element_size() < refs * F.TRI1.itemsize):
             raise ValueError("build_bvh2: the buffers of `out` are too small for this mesh")
-    info = torch.empty(SPLIT_INFO_WORDS if splitting else INFO_WORDS, dtype=torch.int32, device=cuda)
+    info = torch.empty(info_words, dtype=torch.int32, device=cuda)
     # the caller's tensors may come from another stream: make this one wait for the inputs
     stream.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(stream):
-        entry = ("rodent_hip_build_bvh2_tri1_split" if splitting else
-                 "rodent_hip_build_bvh2_tri1_opt" if treelet_passes else "rodent_hip_build_bvh2_tri1")
-        if splitting:
-            rc = l.rodent_hip_build_bvh2_tri1_split(dev, v.data_ptr(), nv, ix.data_ptr(), n, C.byref(opt), C.byref(sp),
-                                                    nodes.data_ptr(), tris.data_ptr(), scratch.data_ptr(), info.data_ptr(),
-                                                    C.c_void_p(stream.cuda_stream))
-        elif treelet_passes:
-            rc = l.rodent_hip_build_bvh2_tri1_opt(dev, v.data_ptr(), nv, ix.data_ptr(), n, C.byref(opt), nodes.data_ptr(),
-                                                  tris.data_ptr(), scratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
-        else:
-            rc = l.rodent_hip_build_bvh2_tri1(dev, v.data_ptr(), nv, ix.data_ptr(), n, int(max_leaf), nodes.data_ptr(),
-                                              tris.data_ptr(), scratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
+        rc = getattr(l, entry)(dev, v.data_ptr(), nv, ix.data_ptr(), n, *args, nodes.data_ptr(), tris.data_ptr(), scratch.data_ptr(),
+                               info.data_ptr(), C.c_void_p(stream.cuda_stream))
         if rc != 0:
             raise BuildError(f"{entry}: {_ERRORS.get(rc, rc)}")
         for t in (v, ix, scratch, info):

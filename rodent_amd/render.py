@@ -118,8 +118,8 @@ class Renderer:
                  trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None,
                  gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64):
         """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says.
-        gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh);
-        gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it (rodent_hip_scene_create_device_bvh_opt).
+        gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh_opt);
+        gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it.
         gpu_bvh_split = (0, 4]: pre-split the triangles into up to that fraction of extra references, at most gpu_bvh_max_pieces per
         triangle (rodent_hip_scene_create_device_bvh_split)."""
         if gpu_bvh_passes and not gpu_bvh:
@@ -140,19 +140,15 @@ class Renderer:
         l.rodent_hip_set_device(dev)
         l.rodent_hip_render_defaults(dev)                    # options of an earlier Renderer in this process do not leak into this one
         if gpu_bvh:
+            from . import gpubuild
             desc.nodes = desc.tris = None
             desc.num_nodes = desc.num_bvh_tris = 0
+            opt = gpubuild.options(int(gpu_bvh), int(gpu_bvh_passes))
             if gpu_bvh_split:
-                from . import gpubuild
-                opt = gpubuild.options(int(gpu_bvh), int(gpu_bvh_passes))
                 sp = gpubuild.split_options(float(gpu_bvh_split), int(gpu_bvh_max_pieces))
                 l.rodent_hip_scene_create_device_bvh_split(dev, C.byref(desc), C.byref(opt), C.byref(sp))
-            elif gpu_bvh_passes:
-                from . import gpubuild
-                opt = gpubuild.options(int(gpu_bvh), int(gpu_bvh_passes))
-                l.rodent_hip_scene_create_device_bvh_opt(dev, C.byref(desc), C.byref(opt))
             else:
-                l.rodent_hip_scene_create_device_bvh(dev, C.byref(desc), int(gpu_bvh))
+                l.rodent_hip_scene_create_device_bvh_opt(dev, C.byref(desc), C.byref(opt))
         else:
             l.rodent_hip_scene_create(dev, C.byref(desc))
         l.rodent_hip_render_config(dev, spp, max_path_len)

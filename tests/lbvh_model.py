@@ -2,7 +2,8 @@
 
 It predicts the builder's output bytes: the same fp32 operations in the same order (numpy float32 arithmetic is correctly rounded,
 like the kernels under -ffp-contract=off), the same stable order, the same Karras search.  Vectorised: Karras' searches run on all
-nodes at once, the bottom-up pass level by level.
+nodes at once, the bottom-up pass level by level.  sort_references and emit work over references, so tests/trbvh_model.py and
+tests/split_model.py share them; an unsplit build's references are its triangles (triangle_references).
 """
 from __future__ import annotations
 
@@ -48,17 +49,57 @@ def load_triangles(vertices, indices):
     return v.astype(F32), indices[:, 3].copy(), flags
 
 
-def morton_codes(v):
-    """30-bit codes from the centroid sums s = (v0 + v1) + v2 over their bounds (fmin / fmax ignore NaN like fminf / fmaxf)."""
+def boxes_of(V):
+    """Boxes (lo_x hi_x lo_y hi_y lo_z hi_z) of triangles V [n, 3 vertices, 3 axes]."""
+    b = np.empty((len(V), 6), F32)
+    b[:, 0::2] = np.fmin(np.fmin(V[:, 0], V[:, 1]), V[:, 2])
+    b[:, 1::2] = np.fmax(np.fmax(V[:, 0], V[:, 1]), V[:, 2])
+    return b
+
+
+def morton_codes(points):
+    """30-bit codes of Morton points over their bounds (k_bounds + k_morton; fmin / fmax ignore NaN like fminf / fmaxf)."""
     with np.errstate(all="ignore"):
-        s = (v[:, 0] + v[:, 1]) + v[:, 2]
-        lo = np.fmin.reduce(s, axis=0)
-        hi = np.fmax.reduce(s, axis=0)
+        lo = np.fmin.reduce(points, axis=0)
+        hi = np.fmax.reduce(points, axis=0)
         extent = hi - lo
         scale = np.where((extent > 0) & np.isfinite(extent), F32(1024) / np.where(extent > 0, extent, F32(1)), F32(0)).astype(F32)
-        q = (s - lo) * scale
+        q = (points - lo) * scale
         cell = np.fmin(np.fmax(q, F32(0)), F32(1023)).astype(np.uint32)
     return (_spread10(cell[:, 0]) << np.uint32(2)) | (_spread10(cell[:, 1]) << np.uint32(1)) | _spread10(cell[:, 2])
+
+
+def triangle_references(v):
+    """An unsplit build's references (reftri, refbox, points): triangle t is reference t, its box that of its corners x + 0 (-0 ->
+    +0, as canon() in the kernel), its Morton point the centroid sum s = (v0 + v1) + v2."""
+    with np.errstate(all="ignore"):
+        return np.arange(len(v)), boxes_of(v + F32(0)), (v[:, 0] + v[:, 1]) + v[:, 2]
+
+
+def sort_references(v, geom, reftri, refbox, points):
+    """Morton codes, the sort and the leaves (k_morton ... k_leaves) over references: (codes, leaf boxes, Tri1 records without the
+    end-of-leaf bits, prim ids) in (code, reference index) order, the stable radix sort's order."""
+    codes = morton_codes(points)
+    order = np.lexsort((np.arange(len(codes)), codes))
+    tri = reftri[order]
+    sv = v[tri]
+    tris = np.zeros(len(tri), F.TRI1)
+    with np.errstate(all="ignore"):
+        tris["v0"] = sv[:, 0]
+        tris["e1"] = sv[:, 0] - sv[:, 1]
+        tris["e2"] = sv[:, 2] - sv[:, 0]
+    tris["geom_id"] = geom[tri]
+    return codes[order], refbox[order], tris, tri.astype(np.int64)
+
+
+def single_leaf(box):
+    """The one-node tree: child 0 the whole leaf, the empty slot as the host writer leaves it (+inf, -inf)."""
+    nodes = np.zeros(1, F.NODE2)
+    nodes[0]["bounds"][:6] = box
+    nodes[0]["bounds"][6::2] = np.inf
+    nodes[0]["bounds"][7::2] = -np.inf
+    nodes[0]["child"] = [~0, 0]
+    return nodes
 
 
 def _delta(codes, i, j):
@@ -101,38 +142,16 @@ def karras(codes):
     return np.minimum(i, j), np.maximum(i, j), split
 
 
-def build(vertices, indices, max_leaf=2):
-    """Returns (nodes NODE2, tris TRI1, info int32[4]) as the device builder writes them."""
-    assert 1 <= max_leaf <= 8
-    v, geom, flags = load_triangles(vertices, indices)
-    n = len(v)
-    assert 1 <= n <= 1 << 25
-    codes = morton_codes(v)
-    order = np.lexsort((np.arange(n), codes))                  # by code, then by triangle id: the stable radix sort's order
-    codes = codes[order]
-    sv = v[order]
-    tris = np.zeros(n, F.TRI1)
-    with np.errstate(all="ignore"):
-        tris["v0"] = sv[:, 0]
-        tris["e1"] = sv[:, 0] - sv[:, 1]
-        tris["e2"] = sv[:, 2] - sv[:, 0]
-        c = sv + F32(0)                                         # -0 -> +0, as canon() in the kernel
-    tris["geom_id"] = geom[order]
-    prim = order.astype(np.int64)
-    leafbox = np.empty((n, 6), F32)
-    leafbox[:, 0::2] = np.fmin(np.fmin(c[:, 0], c[:, 1]), c[:, 2])
-    leafbox[:, 1::2] = np.fmax(np.fmax(c[:, 0], c[:, 1]), c[:, 2])
+def emit(codes, leafbox, tris, prim, max_leaf):
+    """The hierarchy and its emission (k_karras ... k_emit / k_emit_root) over sorted references (sort_references): (nodes NODE2,
+    tris TRI1, info int32[4] without the error flags)."""
+    n = len(codes)
+    tris = tris.copy()
     info = np.zeros(4, np.int32)
-    info[2] = flags
     last_in_leaf = np.zeros(n, bool)
     if n <= max_leaf:
-        box = leafbox[0] if n == 1 else np.concatenate([np.fmin.reduce(leafbox[:, 0::2], 0)[:, None],
-                                                         np.fmax.reduce(leafbox[:, 1::2], 0)[:, None]], 1).reshape(-1)
-        nodes = np.zeros(1, F.NODE2)
-        nodes[0]["bounds"][:6] = box
-        nodes[0]["bounds"][6::2] = np.inf
-        nodes[0]["bounds"][7::2] = -np.inf
-        nodes[0]["child"] = [~0, 0]
+        nodes = single_leaf(leafbox[0] if n == 1 else np.concatenate([np.fmin.reduce(leafbox[:, 0::2], 0)[:, None],
+                                                                      np.fmax.reduce(leafbox[:, 1::2], 0)[:, None]], 1).reshape(-1))
         last_in_leaf[n - 1] = True
         info[0], info[1] = 1, 1
     else:
@@ -181,6 +200,16 @@ def build(vertices, indices, max_leaf=2):
             nodes["child"][newidx[ks], k] = np.where(inner, newidx[np.where(sg, 0, c_)] + 1, ~lo_k)
             last_in_leaf[hi_k[~inner]] = True
     tris["prim_id"] = (prim | np.where(last_in_leaf, 1 << 31, 0)).astype(np.uint32).view(np.int32)
+    return nodes, tris, info
+
+
+def build(vertices, indices, max_leaf=2):
+    """Returns (nodes NODE2, tris TRI1, info int32[4]) as the device builder writes them."""
+    assert 1 <= max_leaf <= 8
+    v, geom, flags = load_triangles(vertices, indices)
+    assert 1 <= len(v) <= 1 << 25
+    nodes, tris, info = emit(*sort_references(v, geom, *triangle_references(v)), max_leaf)
+    info[2] = flags
     return nodes, tris, info
 
 

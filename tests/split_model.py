@@ -1,6 +1,6 @@
 """CPU model of the device builder's triangle pre-splitting (rodent_hip_build_bvh2_tri1_split, csrc/bvh_build.hip), stage for stage,
-in numpy: frame, priority, allotment, the recursive cut, compaction and Morton points, then the existing stages of
-tests/lbvh_model.py (Karras) and tests/trbvh_model.py (Tree) over the references, with the emission restated for references.
+in numpy: frame, priority, allotment, the recursive cut, compaction and Morton points, then the stages of tests/lbvh_model.py
+(sort_references, emit) or, with treelet passes, tests/trbvh_model.py (emit) over the references.
 It predicts the output bytes: the same fp32 operations in the same order, the rules of include/rodent_build.h.
 
 The cut runs in lock-step over all split triangles, one step of each triangle's loop per iteration, as the device's threads do.
@@ -11,7 +11,6 @@ import numpy as np
 
 import lbvh_model as L
 import trbvh_model as T
-from rodent_amd import formats as F
 
 F32 = np.float32
 MAX_REFS = 1 << 25
@@ -27,14 +26,6 @@ def triangle_flags(vertices, indices):
     ok = (idx >= 0) & (idx < len(vertices))
     fin = np.isfinite(vertices[np.where(ok, idx, 0), :3]).all(-1)
     return ~(ok & fin).all(1)
-
-
-def boxes_of(V):
-    """Boxes (lo_x hi_x lo_y hi_y lo_z hi_z) of triangles V [n, 3 vertices, 3 axes]."""
-    b = np.empty((len(V), 6), F32)
-    b[:, 0::2] = np.fmin(np.fmin(V[:, 0], V[:, 1]), V[:, 2])
-    b[:, 1::2] = np.fmax(np.fmax(V[:, 0], V[:, 1]), V[:, 2])
-    return b
 
 
 def split_frame(tbox):
@@ -222,7 +213,7 @@ def references(vertices, indices, budget, max_pieces):
     n = len(v)
     with np.errstate(all="ignore"):
         V = (v + F32(0)).astype(F32)
-    tbox = boxes_of(V)
+    tbox = L.boxes_of(V)
     frame = split_frame(tbox)
     flagged = triangle_flags(vertices, indices)
     p = priority(V, tbox, flagged, frame)
@@ -250,134 +241,6 @@ def references(vertices, indices, budget, max_pieces):
     return v, geom, flags, reftri, refbox, points, stats
 
 
-def morton_of_points(s):
-    """30-bit codes of Morton points over their bounds (k_bounds + k_morton)."""
-    with np.errstate(all="ignore"):
-        lo = np.fmin.reduce(s, axis=0)
-        hi = np.fmax.reduce(s, axis=0)
-        extent = hi - lo
-        scale = np.where((extent > 0) & np.isfinite(extent), F32(1024) / np.where(extent > 0, extent, F32(1)), F32(0)).astype(F32)
-        q = (s - lo) * scale
-        cell = np.fmin(np.fmax(q, F32(0)), F32(1023)).astype(np.uint32)
-    return (L._spread10(cell[:, 0]) << np.uint32(2)) | (L._spread10(cell[:, 1]) << np.uint32(1)) | L._spread10(cell[:, 2])
-
-
-def _single_leaf(leafbox, n, tris, prim):
-    nodes = np.zeros(1, F.NODE2)
-    nodes[0]["bounds"][:6] = leafbox[0] if n == 1 else np.concatenate(
-        [np.fmin.reduce(leafbox[:, 0::2], 0)[:, None], np.fmax.reduce(leafbox[:, 1::2], 0)[:, None]], 1).reshape(-1)
-    nodes[0]["bounds"][6::2] = np.inf
-    nodes[0]["bounds"][7::2] = -np.inf
-    nodes[0]["child"] = [~0, 0]
-    last = np.zeros(n, bool)
-    last[n - 1] = True
-    tris["prim_id"] = (prim | np.where(last, 1 << 31, 0)).astype(np.uint32).view(np.int32)
-    return nodes, tris
-
-
-def _emit_lbvh(codes, leafbox, srt, prim, max_leaf, info):
-    """lbvh_model.build's hierarchy and emission over sorted references."""
-    n = len(codes)
-    tris = srt.copy()
-    if n <= max_leaf:
-        info[0], info[1] = 1, 1
-        return _single_leaf(leafbox, n, tris, prim)
-    first, last, split = L.karras(codes)
-    m = n - 1
-    kept = last - first + 1 > max_leaf
-    newidx = np.where(kept, np.cumsum(kept) - 1, -1)
-    single = [first == split, last == split + 1]
-    child_ids = [split, split + 1]
-    level = np.full(m, -1, np.int64)
-    level[0] = 0
-    frontier = np.array([0])
-    while len(frontier):
-        nxt = []
-        for k in range(2):
-            inner = frontier[~single[k][frontier]]
-            level[child_ids[k][inner]] = level[inner] + 1
-            nxt.append(child_ids[k][inner])
-        frontier = np.concatenate(nxt)
-    box = np.zeros((m, 6), F32)
-    height = np.zeros(m, np.int64)
-    for lv in range(level.max(), -1, -1):
-        at = np.nonzero(level == lv)[0]
-        cb, ch = [], []
-        for k in range(2):
-            c_ = child_ids[k][at]
-            sg = single[k][at]
-            cb.append(np.where(sg[:, None], leafbox[c_], box[np.where(sg, 0, c_)]))
-            ch.append(np.where(sg, 0, height[np.where(sg, 0, c_)]))
-        box[at, 0::2] = np.fmin(cb[0][:, 0::2], cb[1][:, 0::2])
-        box[at, 1::2] = np.fmax(cb[0][:, 1::2], cb[1][:, 1::2])
-        height[at] = np.where(kept[at], 1 + np.maximum(ch[0], ch[1]), 0)
-    info[0], info[1] = int(kept.sum()), int(height[0])
-    ks = np.nonzero(kept)[0]
-    nodes = np.zeros(len(ks), F.NODE2)
-    last_in_leaf = np.zeros(n, bool)
-    for k in range(2):
-        c_ = child_ids[k][ks]
-        sg = single[k][ks]
-        cb = np.where(sg[:, None], leafbox[c_], box[np.where(sg, 0, c_)])
-        inner = ~sg & kept[np.where(sg, 0, c_)]
-        lo_k = first[ks] if k == 0 else split[ks] + 1
-        hi_k = split[ks] if k == 0 else last[ks]
-        nodes["bounds"][newidx[ks], 6 * k: 6 * k + 6] = cb
-        nodes["child"][newidx[ks], k] = np.where(inner, newidx[np.where(sg, 0, c_)] + 1, ~lo_k)
-        last_in_leaf[hi_k[~inner]] = True
-    tris["prim_id"] = (prim | np.where(last_in_leaf, 1 << 31, 0)).astype(np.uint32).view(np.int32)
-    return nodes, tris
-
-
-def _emit_opt(codes, leafbox, srt, prim, max_leaf, passes, node_cost, tri_cost, info):
-    """trbvh_model.build's optimisation and emission over sorted references."""
-    n = len(codes)
-    first, last, split = L.karras(codes)
-    t = T.Tree(first, last, split, leafbox, max_leaf, node_cost, tri_cost)
-    with np.errstate(all="ignore"):
-        t.fit()
-        for k in range(passes):
-            t.treelet_pass(T.gamma(k))
-        t.fit()
-    m = t.m
-    idx = np.zeros(m + n, np.int64)
-    off = np.zeros(m + n, np.int64)
-    level = np.zeros(m + n, np.int64)
-    top = np.full(m + n, -1, np.int64)
-    levels, _ = t.levels()
-    for at in levels:
-        top[at] = np.where(top[at] >= 0, top[at], np.where(t.emitted[at] == 0, at, -1))
-        l, r = t.left[at], t.right[at]
-        idx[l], idx[r] = idx[at] + 1, idx[at] + 1 + t.emitted[l]
-        off[l], off[r] = off[at], off[at] + t.count[l]
-        level[l], level[r] = level[at] + 1, level[at] + 1
-        top[l], top[r] = top[at], top[at]
-    leaves = np.arange(m, m + n)
-    top[leaves] = np.where(top[leaves] >= 0, top[leaves], leaves)
-    info[3] = t.rejected
-    tris = np.zeros(n, F.TRI1)
-    pos = off[leaves]
-    last_in_leaf = pos == off[top[leaves]] + t.count[top[leaves]] - 1
-    tris[pos] = srt
-    tris["prim_id"][pos] = (prim | np.where(last_in_leaf, 1 << 31, 0)).astype(np.uint32).view(np.int32)
-    if t.emitted[0] == 0:
-        nodes = np.zeros(1, F.NODE2)
-        nodes[0]["bounds"][:6] = t.box[0]
-        nodes[0]["bounds"][6::2] = np.inf
-        nodes[0]["bounds"][7::2] = -np.inf
-        nodes[0]["child"] = [~0, 0]
-        info[0], info[1] = 1, 1
-        return nodes, tris
-    emit = np.nonzero((t.emitted[:m] > 0) & (top[:m] < 0))[0]
-    nodes = np.zeros(int(t.emitted[0]), F.NODE2)
-    for k, ch in enumerate((t.left[emit], t.right[emit])):
-        nodes["bounds"][idx[emit], 6 * k: 6 * k + 6] = t.box[ch]
-        inner = (ch < m) & (t.emitted[ch] > 0)
-        nodes["child"][idx[emit], k] = np.where(inner, idx[ch] + 1, ~off[ch])
-    info[0], info[1] = len(nodes), int(level[emit].max()) + 1
-    return nodes, tris
-
-
 def build(vertices, indices, max_leaf=2, passes=0, budget=0.0, max_pieces=MAX_PIECES, node_cost=T.NODE_COST, tri_cost=T.TRI_COST,
           stats=None):
     """Returns (nodes NODE2, tris TRI1, info int32[8]) as rodent_hip_build_bvh2_tri1_split writes them.  `stats`: a dict that
@@ -386,29 +249,11 @@ def build(vertices, indices, max_leaf=2, passes=0, budget=0.0, max_pieces=MAX_PI
     v, geom, flags, reftri, refbox, points, st = references(vertices, indices, budget, max_pieces)
     if stats is not None:
         stats.update(st, reftri=reftri, refbox=refbox)
-    n = len(reftri)
-    codes = morton_of_points(points)
-    order = np.lexsort((np.arange(n), codes))
-    codes = codes[order]
-    tri = reftri[order]
-    sv = v[tri]
-    srt = np.zeros(n, F.TRI1)
-    with np.errstate(all="ignore"):
-        srt["v0"] = sv[:, 0]
-        srt["e1"] = sv[:, 0] - sv[:, 1]
-        srt["e2"] = sv[:, 2] - sv[:, 0]
-    srt["geom_id"] = geom[tri]
-    prim = tri.astype(np.int64)
-    leafbox = refbox[order]
+    refs = L.sort_references(v, geom, reftri, refbox, points)
+    nodes, tris, head = T.emit(*refs, max_leaf, passes, node_cost, tri_cost) if passes else L.emit(*refs, max_leaf)
     info = np.zeros(INFO_WORDS, np.int32)
-    info[2], info[4], info[5], info[6] = flags, n, st["split"], st["unmade"]
-    if passes == 0:
-        nodes, tris = _emit_lbvh(codes, leafbox, srt, prim, max_leaf, info)
-    elif n == 1:
-        info[0], info[1] = 1, 1
-        nodes, tris = _single_leaf(leafbox, 1, srt.copy(), prim)
-    else:
-        nodes, tris = _emit_opt(codes, leafbox, srt, prim, max_leaf, passes, node_cost, tri_cost, info)
+    info[:4] = head
+    info[2], info[4], info[5], info[6] = flags, len(reftri), st["split"], st["unmade"]
     return nodes, tris, info
 
 

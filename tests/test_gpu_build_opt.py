@@ -22,30 +22,11 @@ import lbvh_model as L
 import trbvh_model as T
 from conftest import GOLDEN, ambiguous_mask
 from rodent_amd import scene as S
-from test_gpu_build import FILM_ATOL, FILM_RTOL, soup
+from test_gpu_build import FILM_ATOL, FILM_RTOL, atrium, cornell_scene, gb, soup  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 MAX_LEAVES = (1, 2, 4, 8)
 PASSES = (1, 2, 3)
-
-
-@pytest.fixture(scope="module")
-def gb(native_build):
-    import torch
-    from rodent_amd import gpubuild
-    assert torch.cuda.is_available(), "these tests need a GPU"
-    return gpubuild
-
-
-@pytest.fixture(scope="module")
-def cornell_scene(native_build, tmp_path_factory):
-    return S.convert(GOLDEN / "cornell_box.obj", tmp_path_factory.mktemp("scene") / "cornell.rscene")
-
-
-@pytest.fixture(scope="module")
-def atrium(native_build, tmp_path_factory):
-    from rodent_amd import scenes
-    return S.convert(scenes.scene_obj("atrium"), tmp_path_factory.mktemp("atrium") / "atrium.rscene")
 
 
 def checked(gb, bvh, num_tris, max_leaf):

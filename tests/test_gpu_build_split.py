@@ -21,30 +21,11 @@ import split_model as SM
 import trbvh_model as T
 from conftest import GOLDEN, ambiguous_mask
 from rodent_amd import scene as S
-from test_gpu_build import FILM_ATOL, FILM_RTOL, soup
+from test_gpu_build import FILM_ATOL, FILM_RTOL, atrium, cornell_scene, gb, soup  # noqa: F401 (fixtures)
 from test_split_model import slivers, sliver_soup_with_unmade_splits
 
 pytestmark = pytest.mark.gpu
 SPLITS = [(0.0, 64), (0.25, 64), (1.0, 2), (1.0, 64), (4.0, 1), (4.0, 2), (4.0, 64)]
-
-
-@pytest.fixture(scope="module")
-def gb(native_build):
-    import torch
-    from rodent_amd import gpubuild
-    assert torch.cuda.is_available(), "these tests need a GPU"
-    return gpubuild
-
-
-@pytest.fixture(scope="module")
-def cornell_scene(native_build, tmp_path_factory):
-    return S.convert(GOLDEN / "cornell_box.obj", tmp_path_factory.mktemp("scene") / "cornell.rscene")
-
-
-@pytest.fixture(scope="module")
-def atrium(native_build, tmp_path_factory):
-    from rodent_amd import scenes
-    return S.convert(scenes.scene_obj("atrium"), tmp_path_factory.mktemp("atrium") / "atrium.rscene")
 
 
 @pytest.fixture(scope="module")

@@ -196,30 +196,13 @@ class Tree:
         self.refit(R[~accept])
 
 
-def build(vertices, indices, max_leaf=2, passes=1, node_cost=NODE_COST, tri_cost=TRI_COST):
-    """Returns (nodes NODE2, tris TRI1, info int32[4]) as rodent_hip_build_bvh2_tri1_opt writes them; info[3] counts the treelet
-    topologies the depth rule rejected."""
-    assert 1 <= max_leaf <= 8 and 0 <= passes <= 3
-    if passes == 0:
-        return L.build(vertices, indices, max_leaf)
-    v, geom, flags = L.load_triangles(vertices, indices)
-    n = len(v)
+def emit(codes, leafbox, srt, prim, max_leaf, passes, node_cost=NODE_COST, tri_cost=TRI_COST):
+    """The treelet passes, the collapse and the pre-order emission (k_explicit ... k_emit_opt_tris) over sorted references
+    (lbvh_model.sort_references): (nodes NODE2, tris TRI1, info int32[4] without the error flags; info[3] counts the treelet
+    topologies the depth rule rejected).  One reference: the LBVH's single leaf."""
+    n = len(codes)
     if n == 1:
-        return L.build(vertices, indices, max_leaf)
-    codes = L.morton_codes(v)
-    order = np.lexsort((np.arange(n), codes))
-    codes = codes[order]
-    sv = v[order]
-    srt = np.zeros(n, F.TRI1)
-    with np.errstate(all="ignore"):
-        srt["v0"] = sv[:, 0]
-        srt["e1"] = sv[:, 0] - sv[:, 1]
-        srt["e2"] = sv[:, 2] - sv[:, 0]
-        c = sv + F32(0)
-    srt["geom_id"] = geom[order]
-    leafbox = np.empty((n, 6), F32)
-    leafbox[:, 0::2] = np.fmin(np.fmin(c[:, 0], c[:, 1]), c[:, 2])
-    leafbox[:, 1::2] = np.fmax(np.fmax(c[:, 0], c[:, 1]), c[:, 2])
+        return L.emit(codes, leafbox, srt, prim, max_leaf)
     first, last, split = L.karras(codes)
     t = Tree(first, last, split, leafbox, max_leaf, node_cost, tri_cost)
     with np.errstate(all="ignore"):
@@ -244,27 +227,34 @@ def build(vertices, indices, max_leaf=2, passes=1, node_cost=NODE_COST, tri_cost
     leaves = np.arange(m, m + n)
     top[leaves] = np.where(top[leaves] >= 0, top[leaves], leaves)
     info = np.zeros(4, np.int32)
-    info[2], info[3] = flags, t.rejected
+    info[3] = t.rejected
     tris = np.zeros(n, F.TRI1)
     pos = off[leaves]
     last_in_leaf = pos == off[top[leaves]] + t.count[top[leaves]] - 1
     tris[pos] = srt
-    tris["prim_id"][pos] = (order | np.where(last_in_leaf, 1 << 31, 0)).astype(np.uint32).view(np.int32)
+    tris["prim_id"][pos] = (prim | np.where(last_in_leaf, 1 << 31, 0)).astype(np.uint32).view(np.int32)
     if t.emitted[0] == 0:                                             # the root collapsed: the single-leaf form
-        nodes = np.zeros(1, F.NODE2)
-        nodes[0]["bounds"][:6] = t.box[0]
-        nodes[0]["bounds"][6::2] = np.inf
-        nodes[0]["bounds"][7::2] = -np.inf
-        nodes[0]["child"] = [~0, 0]
         info[0], info[1] = 1, 1
-        return nodes, tris, info
-    emit = np.nonzero((t.emitted[:m] > 0) & (top[:m] < 0))[0]
+        return L.single_leaf(t.box[0]), tris, info
+    kept = np.nonzero((t.emitted[:m] > 0) & (top[:m] < 0))[0]
     nodes = np.zeros(int(t.emitted[0]), F.NODE2)
-    for k, ch in enumerate((t.left[emit], t.right[emit])):
-        nodes["bounds"][idx[emit], 6 * k: 6 * k + 6] = t.box[ch]
+    for k, ch in enumerate((t.left[kept], t.right[kept])):
+        nodes["bounds"][idx[kept], 6 * k: 6 * k + 6] = t.box[ch]
         inner = (ch < m) & (t.emitted[ch] > 0)
-        nodes["child"][idx[emit], k] = np.where(inner, idx[ch] + 1, ~off[ch])
-    info[0], info[1] = len(nodes), int(level[emit].max()) + 1
+        nodes["child"][idx[kept], k] = np.where(inner, idx[ch] + 1, ~off[ch])
+    info[0], info[1] = len(nodes), int(level[kept].max()) + 1
+    return nodes, tris, info
+
+
+def build(vertices, indices, max_leaf=2, passes=1, node_cost=NODE_COST, tri_cost=TRI_COST):
+    """Returns (nodes NODE2, tris TRI1, info int32[4]) as rodent_hip_build_bvh2_tri1_opt writes them; info[3] counts the treelet
+    topologies the depth rule rejected."""
+    assert 1 <= max_leaf <= 8 and 0 <= passes <= 3
+    if passes == 0:
+        return L.build(vertices, indices, max_leaf)
+    v, geom, flags = L.load_triangles(vertices, indices)
+    nodes, tris, info = emit(*L.sort_references(v, geom, *L.triangle_references(v)), max_leaf, passes, node_cost, tri_cost)
+    info[2] = flags
     return nodes, tris, info
 
 
