@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""bench.py -- headline benchmark: Mrays/s of the HIP BVH traversal (BASELINE.json), renderer frame rates beside it.
+"""bench.py -- headline benchmark: Mrays/s of the HIP BVH traversal (BASELINE.json); --full adds renderer frame rates and the rest.
 
-  python bench.py --gpus N --steps K --warmup W [--weak] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--weak] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Step  = one closest-hit traversal pass over one 1 048 576-ray batch resident in HBM (config[1] of BASELINE.json: <scene>.bvh +
@@ -10,7 +10,8 @@ Scene = "sponza" if data/sponza.{bvh,-primary.rays,-random.rays} were supplied, 
         reference checkout lacks the Sponza blobs).
 value = rays traced by all ranks per second / 1e6, kernel passes only (rays, BVH and hit buffers resident in HBM; H2D / D2H excluded
         like bench_traversal.cpp:124-135).
-N > 1 = no data-path collective: the BVH is replicated, rays are independent units.  BOTH partitions are timed:
+N > 1 = no data-path collective: the BVH is replicated, rays are independent units.  --full times BOTH partitions (a plain run the one
+        `value` is quoted on):
         strong (`value`, "scaling": "strong" -- BASELINE's metric is ONE 1 Mi-ray dump at 1 / 2 / 4 / 8 GPUs): rank r
         traces the contiguous range ray_range(n, r, N) of the SAME set the N = 1 run traces; after the timed region one RCCL gather brings
         the Hit1 ranges to rank 0, which compares the assembled array with its own trace of the whole set (`extra.strong_scaling_check`);
@@ -34,6 +35,15 @@ dump  = --dump-outputs DIR: after the timed steps, the Hit1 records the timed pa
         N > 1: rank 0's, strong = the gathered whole set) as DIR/<set>_<field>.npy, tri_id in float64 (exact), t / u / v in float32.
         The inputs are seeded, so two builds given the same arguments can be compared array for array.  Above 64 MB in all, a fixed
         seeded sample of the rays is written, with its indices in DIR/<set>_ray_index.npy.
+plain = without --full a run does what `value` needs and no more: it makes its inputs, warms up, times the K steps of both ray sets (N > 1:
+        the partition `value` is quoted on), writes --dump-outputs and prints the line.  The atrium and its BVH are generated afresh in a
+        directory of the run's own, removed at exit, so that no run reads what an earlier one left behind; Sponza blobs supplied by hand
+        are read where they lie.
+full  = --full: everything else as well -- the per-launch spread of the timed kernels, the side measurements beside the headline
+        (mappings with state, "sorted" / "refill", 16 Mi / 8 Mi-ray launches, two streams), the scene x ray-class matrix, the renderer,
+        the oracle parity of every ray with the roofline, the CPU baselines; N > 1: both partitions and the strong one's check against a
+        single-GPU trace.  Its inputs are kept in data/ (RODENT_DATA_DIR) for later runs, as they always were: the other scene classes
+        take minutes to build.
 Code  = this file holds the contract (arguments, ranks, the JSON line); benchlib/ holds the sections: timing.py (the timed region),
         traversal.py (partitions, side measurements, CPU baseline), render.py (renderer section), profiles.py (profiles, rooflines).
 """
@@ -42,15 +52,16 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import shutil
 import sys
 import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
-# The inputs (scene, BVH, ray sets: seeded, the same wherever they are generated) are made on first use in data/.  A checkout this user
-# cannot write to gets them in a directory of its own under the system's temporary directory; RODENT_DATA_DIR, when set, decides.  Set
-# before anything imports rodent_amd.scenes, which reads it once.
+# The inputs (scene, BVH, ray sets: seeded, the same wherever they are generated) of a --full run are made on first use in data/ (a plain
+# run makes its own afresh: main()).  A checkout this user cannot write to gets them in a directory of its own under the system's temporary
+# directory; RODENT_DATA_DIR, when set, decides.  Set before anything imports rodent_amd.scenes, which reads it once.
 if "RODENT_DATA_DIR" not in os.environ and not os.access(ROOT / "data" if (ROOT / "data").exists() else ROOT, os.W_OK):
     os.environ["RODENT_DATA_DIR"] = str(Path(tempfile.gettempdir()) / f"rodent_amd-data-{os.getuid()}")
 
@@ -82,13 +93,16 @@ def parse_args():
     ap.add_argument("--strong", action="store_true",
                     help="accepted for compatibility: strong scaling (ONE 1 Mi-ray set in contiguous ranges, SURVEY 8e) is the default for "
                         "N > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline too: side measurements, scene matrix, renderer, oracle "
+                        "parity and roofline, CPU baselines, both partitions for N > 1 (the options below apply to it)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-        help="profiling aid: no oracle leg, no CPU baselines, no informational extras")
-    ap.add_argument("--no-render", action="store_true", help="skip the renderer section (extra.render)")
+        help="--full, profiling aid: no oracle leg, no CPU baselines, no informational extras")
+    ap.add_argument("--no-render", action="store_true", help="--full: skip the renderer section (extra.render)")
     ap.add_argument("--no-scenes", action="store_true",
-                    help="skip the scene x ray-class matrix (extra.scenes: the gallery / crown / plant classes are generated and built "
-                        "first, ~80 s)")
-    ap.add_argument("--render-spp5", type=int, default=256, help="samples per pixel of the config-5 frame (BASELINE: 256)")
+                    help="--full: skip the scene x ray-class matrix (extra.scenes: the gallery / crown / plant classes are generated and "
+                        "built first, ~80 s)")
+    ap.add_argument("--render-spp5", type=int, default=256, help="--full: samples per pixel of the config-5 frame (BASELINE: 256)")
     ap.add_argument("--only", choices=("primary", "random"), default=None, help="profiling aid: time only one ray set")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the hit records of the last timed step to DIR/<set>_<field>.npy (float32 / float64, at most 64 MB)")
@@ -116,6 +130,14 @@ def dump_outputs(out_dir, sets):
         np.save(d / f"{name}_tri_id.npy", hits["tri_id"].astype(np.float64))
         for field in ("t", "u", "v"):
             np.save(d / f"{name}_{field}.npy", hits[field].astype(np.float32))
+
+
+def fresh_inputs_dir(dist, rank):
+    """A plain run's own directory for the inputs it generates (rank 0 makes it, every rank gets its path; rank 0 removes it at exit)."""
+    path = [tempfile.mkdtemp(prefix="rodent_amd-bench-") if rank == 0 else None]
+    if dist is not None:
+        dist.broadcast_object_list(path, src=0)
+    return Path(path[0])
 
 
 def init_ranks(args):
@@ -152,10 +174,22 @@ def init_ranks(args):
 def main():
     args = parse_args()
     torch, dist, rank, dev, world = init_ranks(args)
+    from rodent_amd import scenes
+    scene = args.scene or scenes.default_scene()
+    inputs = None if args.full or scene == "sponza" else fresh_inputs_dir(dist, rank)
+    try:
+        if inputs is not None:
+            scenes.DATA = inputs
+        run(args, torch, dist, rank, dev, world, scene)
+    finally:
+        if inputs is not None and rank == 0:
+            shutil.rmtree(inputs, ignore_errors=True)
+
+
+def run(args, torch, dist, rank, dev, world, scene):
     from rodent_amd import abi, formats as F, scenes
 
     # ---- inputs (rank 0 builds the files, the others wait) ----------------------------------
-    scene = args.scene or scenes.default_scene()
     if rank == 0:
         scenes.scene_bvh(scene)
     if dist is not None:
@@ -164,7 +198,8 @@ def main():
     width = args.bvh_width
     variant = args.variant if args.variant >= 0 else int(os.environ.get(f"RODENT_HIP_BVH{width}_VARIANT", "0"))
     b = Bench(args=args, torch=torch, abi=abi, dist=dist, rank=rank, world=world, dev=dev, scene=scene, bvh_path=bvh_path, width=width,
-              variant=variant, bvh=abi.DeviceBvh.load(bvh_path, width, dev), info=not args.no_cpu_baseline and args.only is None,
+              variant=variant, bvh=abi.DeviceBvh.load(bvh_path, width, dev),
+              info=args.full and not args.no_cpu_baseline and args.only is None,
               steps={"primary": (args.steps, args.warmup) if args.only != "random" else (1, 0),
                      "random": (args.steps, args.warmup) if args.only != "primary" else (1, 0)})
     steps_p, steps_r = b.steps["primary"][0], b.steps["random"][0]
@@ -176,8 +211,9 @@ def main():
     # the hit records of the last timed step, read before the side measurements launch into the same buffers
     hits = abi.from_device(part["hits_dev"], F.HIT1)[:n]
     hits_rnd = abi.from_device(part["hits_rnd_dev"], F.HIT1)[:len(rnd)]
-    side = side_measurements(b, part)
-    scene_rows = scene_matrix_rows(b)
+    # --full: what rides along
+    side = side_measurements(b, part) if args.full else {}
+    scene_rows = scene_matrix_rows(b) if args.full else None
     # renderer (BASELINE configs 4 / 5): after the traversal's timed regions, own timed frames
     render = render_section(args, torch, dist, rank, world, dev) if b.info and not args.no_render and width == 2 else None
     if rank != 0:
@@ -205,21 +241,21 @@ def main():
                    "parallelism": f"replicated BVH x {world}" + (f", {sharding}" if world > 1 else ""), "world_size": world,
                    "collective_backend": backend},
         "extra": {"random_Mrays_s": round(part["value_rnd"], 3), "random_ms_per_step": round(1e3 * part["wall_r"] / steps_r, 5),
-                  # mean: HIP events around the whole timed region / steps; single_*: each launch between its own event pair in a second
-                  # pass (adds the dispatch latency)
-                  "primary_kernel_ms": {"mean": round(k_mean, 5), "single_launch_median": round(k_med, 5),
-                      "single_launch_min": round(k_min, 5)},
-                  "random_kernel_ms": {"mean": round(kr_mean, 5), "single_launch_median": round(kr_med, 5),
-                      "single_launch_min": round(kr_min, 5)},
+                  # mean: HIP events around the whole timed region / steps; single_* (--full): each launch between its own event pair
+                  # in a second pass (adds the dispatch latency)
+                  "primary_kernel_ms": {"mean": round(k_mean, 5)}, "random_kernel_ms": {"mean": round(kr_mean, 5)},
                   "kernel_ms_per_rank[primary,random]": part["kernel_ms_per_rank"],
                   "hit_counts[primary,random]": [int((hits["tri_id"] >= 0).sum()), int((hits_rnd["tri_id"] >= 0).sum())],
                   # the prebuilt .so against the sources lying next to it
                   "library": {"version": abi.lib().rodent_hip_version().decode(),
                       "source_digest": abi.lib().rodent_hip_source_digest().decode(),
-                              "built_from_these_sources": abi.built_from_these_sources()},
-                  "two_streams_Mrays_s_per_gpu": None, "primary_16Mi_rays_per_launch": None, "random_8Mi_rays_per_launch": None},
+                              "built_from_these_sources": abi.built_from_these_sources()}},
     }
     cfg, extra = out["config"], out["extra"]
+    if args.full:
+        extra["primary_kernel_ms"].update(single_launch_median=round(k_med, 5), single_launch_min=round(k_min, 5))
+        extra["random_kernel_ms"].update(single_launch_median=round(kr_med, 5), single_launch_min=round(kr_min, 5))
+        extra.update(two_streams_Mrays_s_per_gpu=None, primary_16Mi_rays_per_launch=None, random_8Mi_rays_per_launch=None)
     extra.update(side)
     extra.update(scaling_extra)
     if render is not None:
@@ -246,10 +282,10 @@ def main():
     if world > 1:
         cfg["predicted_scaling_x"] = PREDICTED_SCALING
         cfg["world_size_seen_by_the_collective_backend"] = dist.get_world_size()
-        strong_rec, weak = scaling_extra["strong_scaling"], scaling_extra["weak_scaling"]
-        # ONE 1 Mi-ray set over the N GPUs
-        cfg["strong_scaling_Mrays_s[primary,random]"] = [strong_rec["Mrays_s"], strong_rec["random_Mrays_s"]]
-        cfg["weak_scaling_Mrays_s[primary,random]"] = [weak["Mrays_s"], weak["random_Mrays_s"]]
+        # ONE 1 Mi-ray set over the N GPUs; 1 Mi rays per GPU (both with --full, else the one `value` is quoted on)
+        for key in ("strong_scaling", "weak_scaling"):
+            if key in scaling_extra:
+                cfg[f"{key}_Mrays_s[primary,random]"] = [scaling_extra[key]["Mrays_s"], scaling_extra[key]["random_Mrays_s"]]
     if side.get("primary_16Mi_rays_per_launch"):
         cfg["primary_16Mi_Mrays_s"] = side["primary_16Mi_rays_per_launch"].get("Mrays_s")
     if side.get("random_8Mi_rays_per_launch"):
@@ -259,11 +295,11 @@ def main():
         if "Msamples_s" in auto:
             cfg[cfg_name.split("_")[0] + "_Msamples_s"] = auto["Msamples_s"]
             cfg[cfg_name.split("_")[0] + "_mapping"] = entry.get("auto_mapping")
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["roofline"], extra["all_rays_bit_exact_vs_oracle"] = traversal_roofline(b, part, hits, hits_rnd, kname)
         cfg["hbm_measured_frac"] = out["roofline"]["hbm_measured_frac"]
         cfg["cache_served_bytes_over_hbm_peak"] = out["roofline"]["cache_served_bytes_over_hbm_peak"]
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], more, threads = cpu_baseline(b, prim, rnd, hits)
         extra.update(more)
         if render is not None:

@@ -30,7 +30,7 @@ class Bench:
     width: int
     variant: int
     bvh: object
-    info: bool            # the informational extras run (never in the profiling runs)
+    info: bool            # the informational extras run (--full only, never in the profiling runs)
     steps: dict = field(default_factory=dict)      # {"primary": (K, W), "random": (K, W)}
 
     @property
@@ -54,15 +54,18 @@ def ray_sets(b: Bench, sample, samples):
 
 
 def run_partition(b: Bench, prim, rnd):
-    """Times both sets on this rank's share; returns the per-partition record (times already max over ranks)."""
+    """Times both sets on this rank's share; returns the per-partition record (times already max over ranks).  The per-launch spread
+    (time_passes' second pass) is measured under --full only."""
     from rodent_amd import formats as F
     torch, abi, dev = b.torch, b.abi, b.dev
     (steps_p, warm_p), (steps_r, warm_r) = b.steps["primary"], b.steps["random"]
     pd, rd = abi.to_device(prim, dev), abi.to_device(rnd, dev)
     hp = torch.zeros(max(len(prim), 1) * F.HIT1.itemsize, dtype=torch.uint8, device=f"cuda:{dev}")
     hr = torch.zeros(max(len(rnd), 1) * F.HIT1.itemsize, dtype=torch.uint8, device=f"cuda:{dev}")
-    wall, k_mean, k_med, k_min = time_passes(abi, torch, b.bvh, pd, hp, len(prim), b.variant, steps_p, warm_p, b.dist)
-    wall_r, kr_mean, kr_med, kr_min = time_passes(abi, torch, b.bvh, rd, hr, len(rnd), b.variant, steps_r, warm_r, b.dist)
+    full = b.args.full
+    wall, k_mean, k_med, k_min = time_passes(abi, torch, b.bvh, pd, hp, len(prim), b.variant, steps_p, warm_p, b.dist, single_launches=full)
+    wall_r, kr_mean, kr_med, kr_min = time_passes(abi, torch, b.bvh, rd, hr, len(rnd), b.variant, steps_r, warm_r, b.dist,
+                                                  single_launches=full)
     abi.check_errors(dev)
     wall, wall_r = max_over_ranks(torch, b.dist, dev, [wall, wall_r])
     per_rank = gather_scalars(torch, b.dist, dev, [k_mean, kr_mean, float(len(prim)), float(len(rnd))])
@@ -75,7 +78,9 @@ def run_partition(b: Bench, prim, rnd):
 
 def timed_partitions(b: Bench):
     """The timed regions.  One rank: the whole 1 Mi-ray sets.  N ranks: the strong partition (ONE set in contiguous ranges -- `value` unless
-    --weak) and the weak one (1 Mi rays per rank).  Returns (the partition `value` is quoted on, "strong" | "weak", extras for N > 1)."""
+    --weak) and the weak one (1 Mi rays per rank).  Without --full only the partition `value` is quoted on is timed, and the strong one
+    skips its comparison with a single-GPU trace (its Hit1 gather runs for --dump-outputs alone).  Returns (the partition `value` is quoted
+    on, "strong" | "weak", extras for N > 1)."""
     from rodent_amd import formats as F, parallel
     abi, args = b.abi, b.args
     steps_p = b.steps["primary"][0]
@@ -83,37 +88,45 @@ def timed_partitions(b: Bench):
     if b.world == 1:
         # (N = 1 of the fixed 1 Mi-ray workload: the same set the N > 1 runs split)
         return run_partition(b, prim_all, rnd_all), "strong", {}
-    # strong: ONE ray set in contiguous ranges -- contiguous keeps coherent rays coherent
-    lo, hi = parallel.ray_range(len(prim_all), b.rank, b.world)
-    strong = run_partition(b, prim_all[lo:hi], rnd_all[lo:hi])
-    # after the timed region: ONE gather of the Hit1 ranges to rank 0 (16 B/ray: 16 MiB in total), compared there with a single-GPU
-    # trace of the whole set
-    full = parallel.gather_hits_device(strong["hits_dev"], len(prim_all), b.dist, b.dev)
-    full_rnd = parallel.gather_hits_device(strong["hits_rnd_dev"], len(rnd_all), b.dist, b.dev)
-    check = None
-    if b.rank == 0:
-        whole = abi.traverse(b.bvh, prim_all, variant=b.variant)
-        whole_rnd = abi.traverse(b.bvh, rnd_all, variant=b.variant)
-        check = {"primary_equal_to_single_gpu": bool(full.tobytes() == whole.tobytes()),
-                 "random_equal_to_single_gpu": bool(full_rnd.tobytes() == whole_rnd.tobytes())}
-    # weak: every rank its own 1 Mi rays (sub-pixel sample `rank` of `world`)
-    pw, rw = ray_sets(b, b.rank, b.world)
-    weak_part = run_partition(b, pw, rw)
-    counts = gather_scalars(b.torch, b.dist, b.dev, [float((abi.from_device(weak_part["hits_dev"], F.HIT1)["tri_id"] >= 0).sum()),
-                                                      float((abi.from_device(weak_part["hits_rnd_dev"], F.HIT1)["tri_id"] >= 0).sum())])
-    weak = {"Mrays_s": round(weak_part["value"], 3), "ms_per_step": round(1e3 * weak_part["wall"] / steps_p, 5),
+    scaling = "weak" if args.weak and not args.strong else "strong"
+    extras, strong, weak_part = {}, None, None
+    if args.full or scaling == "strong":
+        # strong: ONE ray set in contiguous ranges -- contiguous keeps coherent rays coherent
+        lo, hi = parallel.ray_range(len(prim_all), b.rank, b.world)
+        strong = run_partition(b, prim_all[lo:hi], rnd_all[lo:hi])
+        extras["strong_scaling"] = {
+            "Mrays_s": round(strong["value"], 3), "ms_per_step": round(1e3 * strong["wall"] / steps_p, 5),
+            "random_Mrays_s": round(strong["value_rnd"], 3), "rays_per_gpu_per_step": len(strong["prim"]),
+            "kernel_ms_per_rank[primary,random]": strong["kernel_ms_per_rank"],
+            "what": "ONE 1 Mi-ray set in contiguous ranges (SURVEY 8e), Hit1 gather to rank 0 after the timed region"}
+    if strong is not None and (args.full or args.dump_outputs):
+        # after the timed region: ONE gather of the Hit1 ranges to rank 0 (16 B/ray: 16 MiB in total), compared there (--full) with a
+        # single-GPU trace of the whole set
+        gathered = parallel.gather_hits_device(strong["hits_dev"], len(prim_all), b.dist, b.dev)
+        gathered_rnd = parallel.gather_hits_device(strong["hits_rnd_dev"], len(rnd_all), b.dist, b.dev)
+        strong["hits_all"], strong["hits_rnd_all"] = gathered, gathered_rnd      # rank 0: what the caller of the strong partition receives
+        if args.full:
+            check = None
+            if b.rank == 0:
+                whole = abi.traverse(b.bvh, prim_all, variant=b.variant)
+                whole_rnd = abi.traverse(b.bvh, rnd_all, variant=b.variant)
+                check = {"primary_equal_to_single_gpu": bool(gathered.tobytes() == whole.tobytes()),
+                         "random_equal_to_single_gpu": bool(gathered_rnd.tobytes() == whole_rnd.tobytes())}
+            extras["strong_scaling_check"] = check
+    if args.full or scaling == "weak":
+        # weak: every rank its own 1 Mi rays (sub-pixel sample `rank` of `world`)
+        pw, rw = ray_sets(b, b.rank, b.world)
+        weak_part = run_partition(b, pw, rw)
+        counts = gather_scalars(b.torch, b.dist, b.dev, [float((abi.from_device(weak_part["hits_dev"], F.HIT1)["tri_id"] >= 0).sum()),
+                                                          float((abi.from_device(weak_part["hits_rnd_dev"], F.HIT1)["tri_id"] >= 0).sum())])
+        extras["weak_scaling"] = {
+            "Mrays_s": round(weak_part["value"], 3), "ms_per_step": round(1e3 * weak_part["wall"] / steps_p, 5),
             "random_Mrays_s": round(weak_part["value_rnd"], 3), "rays_per_gpu_per_step": len(pw),
             "kernel_ms_per_rank[primary,random]": weak_part["kernel_ms_per_rank"],
             "hit_counts_per_rank[primary,random]": [[int(c[0]), int(c[1])] for c in counts],
             "what": "rank r traces sub-pixel sample r of N through the same 1024 x 1024 pixel grid (random: seed 42 + r): per-GPU work "
                 "fixed"}
-    strong_rec = {"Mrays_s": round(strong["value"], 3), "ms_per_step": round(1e3 * strong["wall"] / steps_p, 5),
-                  "random_Mrays_s": round(strong["value_rnd"], 3), "rays_per_gpu_per_step": len(strong["prim"]),
-                  "kernel_ms_per_rank[primary,random]": strong["kernel_ms_per_rank"],
-                  "what": "ONE 1 Mi-ray set in contiguous ranges (SURVEY 8e), Hit1 gather to rank 0 after the timed region"}
-    strong["hits_all"], strong["hits_rnd_all"] = full, full_rnd       # rank 0: what the caller of the strong partition receives
-    main_part, scaling = (weak_part, "weak") if args.weak and not args.strong else (strong, "strong")
-    return main_part, scaling, {"strong_scaling": strong_rec, "weak_scaling": weak, "strong_scaling_check": check}
+    return (weak_part if scaling == "weak" else strong), scaling, extras
 
 
 def side_measurements(b: Bench, part):

@@ -4,7 +4,7 @@
 # rocprofv3 --pmc pass (no tracing in the same run): which unit is busy while the kernel runs.
 TAG=${1:-r02}; VARIANT=${2:--1}; OUT=gpurun_out/profiles; mkdir -p $OUT; export TMPDIR=/tmp
 for SET in primary random; do
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --only $SET --variant $VARIANT"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --only $SET --variant $VARIANT"
 run() { name=$1; shift; timeout -k 5 150 rocprofv3 --pmc "$@" --output-format csv -d $OUT/${TAG}_pmc_${SET}_$name -o bench -- $B > $OUT/${TAG}_pmc_${SET}_$name.log 2>&1 || echo "pass $SET $name failed"; }
 run grbm GRBM_GUI_ACTIVE GRBM_TA_BUSY
 run ta1 TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum

@@ -4,7 +4,7 @@
 # HBM-traffic counters (FETCH_SIZE / WRITE_SIZE / TCC, one group per pass) for the primary-ray pass,
 # and kernel-trace stats of the renderer CLI (cfg4: Cornell 1920x1080, 64 spp, max path length 4).
 TAG=${1:-r01}; OUT=gpurun_out/profiles; mkdir -p $OUT; export TMPDIR=/tmp
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+B="python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline"
 run() { name=$1; shift; timeout -k 5 150 rocprofv3 "$@" > $OUT/${TAG}_$name.log 2>&1 || echo "pass $name failed"; }
 run trace --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -o bench -- $B
 run trace_primary --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace_primary -o bench -- $B --only primary

@@ -410,12 +410,12 @@ def test_bench_traversal_cli(gpu, native_build, oracle, cornell, tmp_path):
 
 
 def test_bench_py_contract(native_build):
-    """bench.py prints ONE JSON line with the contract's keys, the roofline and cpu_baseline objects, the binding bounds, and
+    """bench.py --full prints ONE JSON line with the contract's keys, the roofline and cpu_baseline objects, the binding bounds, and
     reports every ray of both sets bit-exact against the oracle (variant 0 = what the driver runs)."""
     import json, sys
     from conftest import ROOT
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1"], capture_output=True, text=True,
-        check=True, cwd=ROOT)
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--full"], capture_output=True,
+        text=True, check=True, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -474,9 +474,9 @@ def test_bench_py_contract(native_build):
 
 
 def test_bench_py_with_two_ranks(native_build):
-    """The N > 1 code path of bench.py -- strong partition as `value` (BASELINE's metric: ONE 1 Mi-ray set, contiguous ranges, Hit1 gather
-    to rank 0 after the timed region, assembled array equal to a single-GPU trace), weak partition beside it (1 Mi rays per GPU), config 5
-    as interleaved 16-row tiles with a film gather -- with two ranks.  On a box with one GPU the ranks share it and the collectives go
+    """The N > 1 code path of bench.py --full -- strong partition as `value` (BASELINE's metric: ONE 1 Mi-ray set, contiguous ranges, Hit1
+    gather to rank 0 after the timed region, assembled array equal to a single-GPU trace), weak partition beside it (1 Mi rays per GPU),
+    config 5 as interleaved 16-row tiles with a film gather -- with two ranks.  On a box with one GPU the ranks share it and the collectives go
     through gloo (RODENT_BENCH_SHARE_GPUS / _BACKEND); with two or more GPUs this is the driver's RCCL launch."""
     import json, os, sys
     import torch
@@ -484,8 +484,8 @@ def test_bench_py_with_two_ranks(native_build):
     env = dict(os.environ, MASTER_PORT="29541")
     if torch.cuda.device_count() < 2:
         env.update(RODENT_BENCH_BACKEND="gloo", RODENT_BENCH_SHARE_GPUS="1")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--render-spp5", "2"],
-        capture_output=True, text=True, cwd=ROOT, env=env)
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--render-spp5", "2",
+        "--full"], capture_output=True, text=True, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -505,6 +505,70 @@ def test_bench_py_with_two_ranks(native_build):
     assert c5["rows_per_gpu"] == 68 * 16 and "interleaved" in c5["partition"] and c5["auto"]["film_complete_on_root"] is True
     assert c5["auto"]["film_gather_ms"] > 0 and "cfg4_cornell_1920x1080_64spp_len4" not in e["render"]
     assert "cpu_baseline" not in d                                                          # rank 0, N = 1 only
+
+
+def _plain_bench(tmp, *extra_args, env=None):
+    """A plain bench.py run (no --full) with --dump-outputs: (its JSON line, {<set>_<field>: array})."""
+    import json, sys
+    from conftest import ROOT
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", tmp, *extra_args],
+        capture_output=True, text=True, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), {f.stem: np.load(f) for f in sorted(tmp.glob("*.npy"))}
+
+
+@pytest.fixture(scope="module")
+def plain_bench(native_build, tmp_path_factory):
+    """One plain single-GPU run, with what it left in the inputs directory (data/) and the temporary directory before and after."""
+    import tempfile
+    from pathlib import Path
+    from rodent_amd import scenes
+
+    def listing():
+        return ({f.name: f.stat().st_mtime_ns for f in scenes.DATA.iterdir()} if scenes.DATA.exists() else {},
+                {f.name for f in Path(tempfile.gettempdir()).glob("rodent_amd-bench-*")})
+    before = listing()
+    d, dumps = _plain_bench(tmp_path_factory.mktemp("plain"))
+    return d, dumps, before, listing()
+
+
+def test_bench_py_plain_run_is_lean(plain_bench):
+    """Without --full bench.py times the headline and nothing beside it: the contract's keys, no roofline, CPU baseline, renderer, scene
+    matrix, side measurements or per-launch spread; the dumped hit records of both 1 Mi-ray sets match the line's hit counts.  Its inputs
+    are generated in a directory of its own, removed at exit: data/ is neither read nor written."""
+    d, dumps, before, after = plain_bench
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype", "config"):
+        assert k in d, k
+    assert d["metric"] == d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 3
+    assert d["value"] > 1000 and abs(d["ms_per_step"] - (1 << 20) / d["value"] / 1e3) < 1e-3 * d["ms_per_step"]
+    e = d["extra"]
+    assert "roofline" not in d and "cpu_baseline" not in d
+    assert not {"render", "scenes", "random_sorted", "random_refill", "random_8Mi_rays_per_launch", "two_streams_Mrays_s_per_gpu",
+                "all_rays_bit_exact_vs_oracle"} & set(e)
+    assert e["primary_kernel_ms"].keys() == e["random_kernel_ms"].keys() == {"mean"}
+    assert e["library"]["built_from_these_sources"] is True
+    for s, count in zip(("primary", "random"), e["hit_counts[primary,random]"]):
+        assert dumps[f"{s}_tri_id"].shape == dumps[f"{s}_t"].shape == (1 << 20,) and int((dumps[f"{s}_tri_id"] >= 0).sum()) == count
+    assert before == after
+
+
+def test_bench_py_plain_run_with_two_ranks(plain_bench, tmp_path):
+    """Without --full the N > 1 path times the strong partition alone (no weak partition, no single-GPU check) and dumps the gathered
+    whole set: array for array what the single-GPU run dumped."""
+    import os
+    import torch
+    d1, dumps1, _, _ = plain_bench
+    env = dict(os.environ, MASTER_PORT="29543")
+    if torch.cuda.device_count() < 2:
+        env.update(RODENT_BENCH_BACKEND="gloo", RODENT_BENCH_SHARE_GPUS="1")
+    d, dumps = _plain_bench(tmp_path, "--gpus", "2", env=env)
+    assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["rays_per_gpu_per_step"] == (1 << 19) and d["value"] > 1000
+    e = d["extra"]
+    assert e["strong_scaling"]["Mrays_s"] == d["value"] and "weak_scaling" not in e and "strong_scaling_check" not in e
+    assert "render" not in e and "roofline" not in d
+    assert dumps.keys() == dumps1.keys() and all(np.array_equal(dumps[k], dumps1[k]) for k in dumps)
 
 
 def test_stack_overflow_is_reported_not_silent(gpu, oracle):
