@@ -87,10 +87,10 @@ __global__ __launch_bounds__(kWave * WAVES) void k_wide8_coop(const char* __rest
 template <bool ANY, int N, int STACK> void L_wide8_coop(WIDE_LAUNCH_ARGS) {
     static_assert(N == 8, "Node8 only");
     if (!ANY) { L_wide_single<false, 8, 24, 32>(s, nodes, tris, rays, hits, n, stream); return; }
-    ensure_deep_list(s, n);
+    s.deep_list.ensure(n);
     constexpr int kWaves = 4, kRays = 8 * kWaves;
     hipLaunchKernelGGL((k_wide8_coop<STACK, kWaves>), dim3((n + kRays - 1) / kRays), dim3(kWave * kWaves), 0, stream, (const char*)nodes,
-        tris, rays, hits, n, s.ctl(), s.deep_list);
+        tris, rays, hits, n, s.ctl(), s.deep_list.ptr);
     hipLaunchKernelGGL((k_wide_finish<true, 8>), dim3(kFinishGroups), dim3(kWave), 0, stream, (const char*)nodes, tris, rays, hits,
-        s.ctl(), s.deep_list, s.deep_stack, (int*)nullptr);
+        s.ctl(), s.deep_list.ptr, s.deep_stack, (int*)nullptr);
 }

@@ -236,14 +236,14 @@ template <bool ANY, int LDS_N, int PEND, int TOPN, int WAVES, int REFILL, int DR
     bool STATS = false> void L_defer(LAUNCH_ARGS) {
     const int max_id = top_kernel_ids(nodes, n);
     if (max_id == 0) { L_single<ANY, 16, 32>(s, nodes, tris, rays, hits, n, stream); return; }
-    ensure_deep_list(s, n);
+    const int groups = persistent_groups(s, 32, WAVES);
+    s.deep_list.ensure(n);
     ensure_top_buffers(s);
-    const int groups = spill_checked(((s.num_cus * (32 / WAVES) + kStripes - 1) / kStripes) * kStripes, WAVES);
     ensure_spill(s, groups * WAVES);
     s.top_image_nodes = nullptr; s.order_rays = 0;
     hipLaunchKernelGGL((k_bvh2_top_defer<ANY, LDS_N, PEND, TOPN, WAVES, REFILL, DRAIN, MODE, STATS>), dim3(groups), dim3(kWave * WAVES), 0,
-        stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list,
-                       s.top_image, s.tickets, max_id, s.spill, g_ray_grid);
+        stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
+                       s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, g_ray_grid);
 }
 
 // -----------------------------------------------------------------------------------------------------------------------------------------
@@ -404,12 +404,12 @@ __global__ __launch_bounds__(kWave * WAVES) __attribute__((amdgpu_waves_per_eu(8
 template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL, int P> void L_turns(LAUNCH_ARGS) {
     const int max_id = top_kernel_ids(nodes, n);
     if (max_id == 0) { L_single<ANY, 16, 32>(s, nodes, tris, rays, hits, n, stream); return; }
-    ensure_deep_list(s, n);
+    const int groups = persistent_groups(s, 32, WAVES);
+    s.deep_list.ensure(n);
     ensure_top_buffers(s);
-    const int groups = spill_checked(((s.num_cus * (32 / WAVES) + kStripes - 1) / kStripes) * kStripes, WAVES);
     ensure_spill(s, groups * WAVES);
     s.top_image_nodes = nullptr; s.order_rays = 0;
     hipLaunchKernelGGL((k_bvh2_top_turns<ANY, LDS_N, TOPN, WAVES, REFILL, P>), dim3(groups), dim3(kWave * WAVES), 0, stream, nodes, tris,
         rays, hits,
-                       n, s.ctl(), s.deep_list, s.top_image, s.tickets, max_id, s.spill, g_ray_grid);
+                       n, s.ctl(), s.deep_list.ptr, s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, g_ray_grid);
 }

@@ -3,7 +3,7 @@
 // one-ray-per-lane mapping of the reference, the while-while family with its persistent / static-stride / instrumented
 // forms, and the per-step ballot scheduler.  All keep the reference's per-ray visit order and are bit-identical to the
 // default.  Included by traversal.hip inside its anonymous namespace, after Ctl, k_bvh2_finish, DeviceState,
-// LAUNCH_ARGS, ensure_deep_list and traversal_wide.h -- in the LAB build only (-DRODENT_HIP_LAB, librodent_hip_lab.so).
+// LAUNCH_ARGS and traversal_wide.h -- in the LAB build only (-DRODENT_HIP_LAB, librodent_hip_lab.so).
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
@@ -402,18 +402,18 @@ template <bool ANY, int LDS_N, int NE> void L_ww(LAUNCH_ARGS) {
 }
 template <bool ANY, int LDS_N, int NE, bool P, int RI, int CH, bool ST = false, int XCD = 0, bool TR = false,
     bool SC = false> void L_fast(LAUNCH_ARGS) {
-    ensure_deep_list(s, n);
+    s.deep_list.ensure(n);
     const int per_block = P ? CH : kWave;
     int grid = (n + per_block - 1) / per_block;
     if (P) grid = std::min(grid, s.num_cus * (SC ? static_waves_per_cu() : persistent_waves_per_cu()));
     if (needs_wide_offsets(nodes, tris))
         hipLaunchKernelGGL((k_bvh2_fast<ANY, LDS_N, NE, P, RI, CH, ST, XCD, TR, SC, true>), dim3(grid), dim3(kWave), 0, stream, nodes,
-            tris, rays, hits, n, s.ctl(), s.deep_list);
+            tris, rays, hits, n, s.ctl(), s.deep_list.ptr);
     else
         hipLaunchKernelGGL((k_bvh2_fast<ANY, LDS_N, NE, P, RI, CH, ST, XCD, TR, SC, false>), dim3(grid), dim3(kWave), 0, stream, nodes,
-            tris, rays, hits, n, s.ctl(), s.deep_list);
-    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list, s.deep_stack,
-        (int*)nullptr);
+            tris, rays, hits, n, s.ctl(), s.deep_list.ptr);
+    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list.ptr,
+        s.deep_stack, (int*)nullptr);
 }
 
 int coprime_stride(int count) {
@@ -426,16 +426,16 @@ int coprime_stride(int count) {
 
 template <bool ANY, int LDS_N, bool P, int RI, int CH, int TB, bool PERMUTE = false, bool ST = false,
     bool TR = false> void L_sched(LAUNCH_ARGS) {
-    ensure_deep_list(s, n);
+    s.deep_list.ensure(n);
     const int per_block = P ? CH : kWave;
     const int chunks = (n + per_block - 1) / per_block;
     int grid = chunks;
     if (P) grid = std::min(grid, s.num_cus * persistent_waves_per_cu());
     const ChunkPerm perm{chunks, PERMUTE ? coprime_stride(chunks) : 1};
     hipLaunchKernelGGL((k_bvh2_sched<ANY, LDS_N, P, RI, CH, TB, ST, TR>), dim3(grid), dim3(kWave), 0, stream, nodes, tris, rays, hits, n,
-        s.ctl(), s.deep_list, perm);
-    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list, s.deep_stack,
-        (int*)nullptr);
+        s.ctl(), s.deep_list.ptr, perm);
+    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list.ptr,
+        s.deep_stack, (int*)nullptr);
 }
 
 
@@ -551,22 +551,14 @@ __global__ void k_partner_reset(int* tickets) { const int s = threadIdx.x;
     for (int w = 1; w <= 8; w++) tickets[s * kCounterStride + w] = 0; }
 
 template <bool ANY, int LDS_N, int TOPN, int WAVES, int HOT_ITER, int HOT_LANES> void L_top_partner(LAUNCH_ARGS) {
-    ensure_deep_list(s, n);
-    if (!s.top_image || !s.tickets) {
-        std::lock_guard<std::mutex> lock(g_mutex);
-        if (!s.top_image) { HIP_CHECK(hipMalloc(&s.top_image, kMaxTopNodes * sizeof(Node2)));
-            HIP_CHECK(hipMemset(s.top_image, 0, kMaxTopNodes * sizeof(Node2))); }
-        if (!s.tickets) {
-            HIP_CHECK(hipMalloc(&s.tickets, sizeof(int) * kMaxPhases * kStripes * kCounterStride));
-            HIP_CHECK(hipMemset(s.tickets, 0, sizeof(int) * kMaxPhases * kStripes * kCounterStride));
-        }
-    }
+    const int groups = persistent_groups(s, 32, WAVES);
+    s.deep_list.ensure(n);
+    ensure_top_buffers(s);
     s.top_image_nodes = nullptr;
-    const int groups = ((s.num_cus * (32 / WAVES) + kStripes - 1) / kStripes) * kStripes;
     hipLaunchKernelGGL((k_bvh2_top_partner<ANY, LDS_N, TOPN, WAVES, HOT_ITER, HOT_LANES>), dim3(groups), dim3(kWave * WAVES), 0, stream,
-        nodes, tris, rays, hits, n, s.ctl(), s.deep_list,
-                       s.top_image, s.tickets, mapped_node_ids(nodes));
+        nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
+                       s.top_image.ptr, s.tickets.ptr, mapped_node_ids(nodes));
     hipLaunchKernelGGL((k_bvh2_top_finish<ANY>), dim3(kFinishGroups), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(),
-        s.deep_list, s.deep_stack, s.tickets, s.top_image, TOPN);
-    hipLaunchKernelGGL(k_partner_reset, dim3(1), dim3(kStripes), 0, stream, s.tickets);
+        s.deep_list.ptr, s.deep_stack, s.tickets.ptr, s.top_image.ptr, TOPN);
+    hipLaunchKernelGGL(k_partner_reset, dim3(1), dim3(kStripes), 0, stream, s.tickets.ptr);
 }

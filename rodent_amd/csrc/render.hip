@@ -27,19 +27,11 @@
 #include <mutex>
 #include <vector>
 
+#include "device_buffer.h"
 #include "rodent_build.h"
 #include "rodent_render.h"
 #include "shading.h"
 #include "traversal_device.h"
-
-#define HIP_CHECK(expr)                                                                        \
-    do {                                                                                       \
-        hipError_t err_ = (expr);                                                              \
-        if (err_ != hipSuccess) {                                                              \
-            fprintf(stderr, "rodent_hip: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(err_), __FILE__, __LINE__); \
-            abort();                                                                           \
-        }                                                                                      \
-    } while (0)
 
 namespace {
 
@@ -1441,7 +1433,7 @@ struct RenderDevice {
     // shadow rays); 0 = whole chunks (k_trace_persist)
     int trace_refill = 0, trace_refill_shadow = 0;
     int trace_refill_request[2] = {-1, -1};    // -1 = per scene (resolve_refill), else the caller's thresholds
-    int* tickets[2] = {nullptr, nullptr}; int num_cus = 0;
+    DeviceBuffer<int> tickets[2]; int num_cus = 0;
     // 1 = the stream traversal kernels stage the scene's top-of-tree image in LDS (2-wave workgroups); 0 = every node from memory
     int lds_image = 1;
     // 0 = rays are moved by the sort (copy_primary_ray), then shaded in place; 1 = the sort only computes the permutation and the shader
@@ -1454,23 +1446,23 @@ struct RenderDevice {
     // scan (deterministic stream order; measured slower); 0 = shade in place, then the separate compaction pass (mapping_gpu.impala:267-300
     // as it stands)
     int fused_compact = 2;
-    unsigned* scan = nullptr; int scan_cap = 0;    // per-block words of the shader's look-back scan (zero before every launch)
-    int* perm = nullptr; int perm_cap = 0;     // sorted position -> stream index
+    DeviceBuffer<unsigned> scan;               // per-block words of the shader's look-back scan (zero before every launch)
+    DeviceBuffer<int> perm;                    // sorted position -> stream index
     int mapping = 0;                           // in effect: 0 = streaming wavefront (mapping_gpu.impala:308-369), 1 = megakernel (:371-474)
     int mapping_request = -1;                  // -1 = chosen per scene (auto_mapping), 0 / 1 = the caller's choice
     float* film = nullptr; int film_w = 0, film_h = 0;
-    float* slab[3] = {nullptr, nullptr, nullptr}; int slab_cap[3] = {0, 0, 0};       // first primary, second primary, secondary
-    int* tmp = nullptr; int tmp_cap = 0;
+    DeviceBuffer<float> slab[3];                   // first primary, second primary, secondary
+    DeviceBuffer<int> tmp;
     // rays handed to k_trace_deep: [0] primary, [1] secondary (may run at the same time)
-    int* deep_list[2] = {nullptr, nullptr}; int deep_cap[2] = {0, 0};
-    int* deep_done[2] = {nullptr, nullptr};        // k_trace_deep's workgroup counters (zero between launches)
+    DeviceBuffer<int> deep_list[2];
+    DeviceBuffer<int> deep_done[2];                // k_trace_deep's workgroup counters (zero between launches)
     // out-of-window stack entries of the persistent traversal launches: one block per resident wave (stack_spill); [1]: the shadow pass on
     // the second stream
-    int* spill[2] = {nullptr, nullptr};
+    DeviceBuffer<int> spill[2];
     hipStream_t aux = nullptr;                     // shadow-ray traversal runs here, beside the compaction / next primary pass
     hipEvent_t ev_shade = nullptr, ev_sec = nullptr, ev_copy = nullptr;
     int overlap = 1;                               // 0: everything on the caller's stream
-    int* hist = nullptr; size_t hist_cap = 0;
+    DeviceBuffer<int> hist;
     int* ctl = nullptr;       // [0] primary size, [1] secondary size, [2] error flag, [8..] bin_total, bin_begin, bin_end (kMaxBins each)
     unsigned long long* counters = nullptr;    // [0] primary rays, [1] unused, [2] iterations, [3] generated, [4..67] shadow rays (striped)
     // rodent_hip_render_tiles: its sub-calls after the first ADD to the counters instead of starting them again
@@ -1545,18 +1537,9 @@ inline int round_cap(int size) { return (size & ~31) + 32; }                 // 
 
 // may_fail: an allocation the device has no room for returns nullptr (the slab is gone then) instead of aborting
 float* ensure_slab(RenderDevice& r, int which, int size, int multiplier, bool may_fail = false) {
-    const int cap = round_cap(size);
-    if (r.slab_cap[which] < cap) {
-        HIP_CHECK(hipSetDevice(r.dev));
-        if (r.slab[which]) HIP_CHECK(hipFree(r.slab[which]));
-        r.slab[which] = nullptr; r.slab_cap[which] = 0;
-        const hipError_t e = hipMalloc(&r.slab[which], sizeof(float) * (size_t)cap * multiplier);
-        if (e != hipSuccess && may_fail) { (void)hipGetLastError(); r.slab[which] = nullptr; return nullptr; }
-        HIP_CHECK(e);
-        HIP_CHECK(hipMemset(r.slab[which], 0, sizeof(float) * (size_t)cap * multiplier));
-        r.slab_cap[which] = cap;
-    }
-    return r.slab[which];
+    const size_t n = (size_t)round_cap(size) * multiplier;
+    if (r.slab[which].count < n) HIP_CHECK(hipSetDevice(r.dev));
+    return may_fail ? r.slab[which].try_ensure(n, 0) : r.slab[which].ensure(n, 0);
 }
 
 void carve_rays(RayStream& rays, float* ptr, size_t cap) {                    // interface.cpp:528-538
@@ -1579,15 +1562,9 @@ void carve_secondary(SecondaryStream& s, float* ptr, size_t cap) {           // 
 }
 
 void ensure_deep(RenderDevice& r, int which, int rays) {
-    if (r.deep_cap[which] < rays) {
-        HIP_CHECK(hipSetDevice(r.dev));
-        HIP_CHECK(hipDeviceSynchronize());
-        if (r.deep_list[which]) HIP_CHECK(hipFree(r.deep_list[which]));
-        HIP_CHECK(hipMalloc(&r.deep_list[which], sizeof(int) * (size_t)rays));
-        r.deep_cap[which] = rays;
-    }
-    if (!r.deep_done[which]) { HIP_CHECK(hipMalloc(&r.deep_done[which], sizeof(int) * 16));
-        HIP_CHECK(hipMemset(r.deep_done[which], 0, sizeof(int) * 16)); }
+    if (r.deep_list[which].count < (size_t)rays) HIP_CHECK(hipSetDevice(r.dev));
+    r.deep_list[which].ensure(rays);
+    r.deep_done[which].ensure(16, 0);
 }
 int persistent_grid(RenderDevice& r);
 int shadow_order() { static const int v = [] { const char* e = getenv("RODENT_HIP_SHADOW_ORDER");
@@ -1604,22 +1581,13 @@ int lazy_miss() { static const int v = [] { const char* e = getenv("RODENT_HIP_L
 // the spill blocks of a persistent launch on stream `which` (103 MB for the 8192 resident waves of this chip, allocated with the first such
 // launch)
 int* ensure_spill(RenderDevice& r, int which) {
-    if (!r.spill[which]) {
-        HIP_CHECK(hipSetDevice(r.dev));
-        HIP_CHECK(hipMalloc(&r.spill[which], sizeof(int) * (size_t)persistent_grid(r) * kPersistWaves * kSpillWaveInts));
-    }
-    return r.spill[which];
+    if (!r.spill[which].ptr) HIP_CHECK(hipSetDevice(r.dev));
+    return r.spill[which].ensure((size_t)persistent_grid(r) * kPersistWaves * kSpillWaveInts);
 }
 
 // Stream traversal launches: the main kernel, then the one-wave kernel for the rays it abandoned.
 // ctl words: [2] error flag, [3] primary deep count, [4] secondary deep count, [5] secondary stream size (copy for the aux stream)
-void ensure_tickets(RenderDevice& r) {
-    for (int k = 0; k < 2; k++)
-        if (!r.tickets[k]) {
-            HIP_CHECK(hipMalloc(&r.tickets[k], sizeof(int) * kTraceStripes * kTraceCounterStride));
-            HIP_CHECK(hipMemset(r.tickets[k], 0, sizeof(int) * kTraceStripes * kTraceCounterStride));
-        }
-}
+void ensure_tickets(RenderDevice& r) { for (auto& t : r.tickets) t.ensure(kTraceStripes * kTraceCounterStride, 0); }
 int persistent_grid(RenderDevice& r) {
     if (!r.num_cus) { hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, r.dev)); r.num_cus = prop.multiProcessorCount; }
     return ((r.num_cus * (32 / kPersistWaves) + kTraceStripes - 1) / kTraceStripes) * kTraceStripes;
@@ -1672,45 +1640,47 @@ void launch_trace_primary(RenderDevice& r, hipStream_t stream, const PrimaryStre
     ensure_deep(r, 0, n);
     int* tickets = nullptr;
     if (r.trace_persistent && n >= kPersistMinRays) {
-        ensure_tickets(r); tickets = r.tickets[0];
+        ensure_tickets(r); tickets = r.tickets[0].ptr;
         StreamSlab ps, none{nullptr, 0, 0};
         if (r.trace_refill > 0 && r.scene.tri_delta && coherent_from >= 0 && refill_indexable(n, 0) && stream_slab(p, ps))
             LAUNCH_TRACE_REFILL(dim3(persistent_grid(r)), dim3(kWave * kPersistWaves), 0, stream, r.scene.dev, ps, n, coherent_from, none,
                 (const int*)nullptr, 0, (float*)nullptr, 0.0f,
-                               r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0], r.deep_list[1], tickets, r.trace_refill,
+                               r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0].ptr, r.deep_list[1].ptr, tickets, r.trace_refill,
                                    r.trace_refill_shadow, ensure_spill(r, 0), r.ctl + 2);
         else hipLaunchKernelGGL(k_trace_persist<0>, dim3(persistent_grid(r)), dim3(kWave * kPersistWaves), 0, stream, r.scene.dev, p, n,
             SecondaryStream{}, (const int*)nullptr, 0, (float*)nullptr, 0.0f,
-                           r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0], r.deep_list[1], tickets, ensure_spill(r, 0), r.ctl + 2);
+                           r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0].ptr, r.deep_list[1].ptr, tickets, ensure_spill(r, 0),
+                               r.ctl + 2);
     } else if (r.lds_image) hipLaunchKernelGGL((k_trace_primary<kTraceWaves, kSceneTopNodes>),
         dim3((n + kTraceWaves * kWave - 1) / (kTraceWaves * kWave)), dim3(kTraceWaves * kWave), 0, stream, r.scene.dev, p,
-        (const int*)nullptr, n, r.ctl + 3, r.counters, r.deep_list[0]);
+        (const int*)nullptr, n, r.ctl + 3, r.counters, r.deep_list[0].ptr);
     else hipLaunchKernelGGL((k_trace_primary<1, 0>), dim3((n + kWave - 1) / kWave), dim3(kWave), 0, stream, r.scene.dev, p,
-        (const int*)nullptr, n, r.ctl + 3, r.counters, r.deep_list[0]);
+        (const int*)nullptr, n, r.ctl + 3, r.counters, r.deep_list[0].ptr);
     hipLaunchKernelGGL(k_trace_deep<false>, dim3(kDeepGroups), dim3(kWave), 0, stream, r.scene.dev, p, SecondaryStream{}, (float*)nullptr,
-        0.0f, r.ctl + 2, r.ctl + 3, r.deep_list[0], r.deep_done[0], tickets, r.ctl + 6);
+        0.0f, r.ctl + 2, r.ctl + 3, r.deep_list[0].ptr, r.deep_done[0].ptr, tickets, r.ctl + 6);
 }
 void launch_trace_secondary(RenderDevice& r, hipStream_t stream, const SecondaryStream& s, const int* size_ptr, int max_n, float inv_spp) {
     ensure_deep(r, 1, max_n);
     int* tickets = nullptr;
     if (r.trace_persistent && max_n >= kPersistMinRays) {
-        ensure_tickets(r); tickets = r.tickets[1];
+        ensure_tickets(r); tickets = r.tickets[1].ptr;
         StreamSlab ss, none{nullptr, 0, 0};
         if (r.trace_refill > 0 && r.scene.tri_delta && refill_indexable(0, max_n) && stream_slab(s, ss))
             LAUNCH_TRACE_REFILL(dim3(persistent_grid(r)), dim3(kWave * kPersistWaves), 0, stream, r.scene.dev, none, 0, 0, ss, size_ptr,
                 max_n, r.film, inv_spp,
-                               r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0], r.deep_list[1], tickets, r.trace_refill,
+                               r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0].ptr, r.deep_list[1].ptr, tickets, r.trace_refill,
                                    r.trace_refill_shadow, ensure_spill(r, 1), r.ctl + 2);
         else hipLaunchKernelGGL(k_trace_persist<1>, dim3(persistent_grid(r)), dim3(kWave * kPersistWaves), 0, stream, r.scene.dev,
             PrimaryStream{}, 0, s, size_ptr, max_n, r.film, inv_spp,
-                           r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0], r.deep_list[1], tickets, ensure_spill(r, 1), r.ctl + 2);
+                           r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0].ptr, r.deep_list[1].ptr, tickets, ensure_spill(r, 1),
+                               r.ctl + 2);
     } else if (r.lds_image) hipLaunchKernelGGL((k_trace_secondary<kTraceWaves, kSceneTopNodes>),
         dim3((max_n + kTraceWaves * kWave - 1) / (kTraceWaves * kWave)), dim3(kTraceWaves * kWave), 0, stream, r.scene.dev, s, size_ptr,
-        max_n, r.film, inv_spp, r.ctl + 4, r.counters, r.deep_list[1]);
+        max_n, r.film, inv_spp, r.ctl + 4, r.counters, r.deep_list[1].ptr);
     else hipLaunchKernelGGL((k_trace_secondary<1, 0>), dim3((max_n + kWave - 1) / kWave), dim3(kWave), 0, stream, r.scene.dev, s, size_ptr,
-        max_n, r.film, inv_spp, r.ctl + 4, r.counters, r.deep_list[1]);
+        max_n, r.film, inv_spp, r.ctl + 4, r.counters, r.deep_list[1].ptr);
     hipLaunchKernelGGL(k_trace_deep<true>, dim3(kDeepGroups), dim3(kWave), 0, stream, r.scene.dev, PrimaryStream{}, s, r.film, inv_spp,
-        r.ctl + 2, r.ctl + 4, r.deep_list[1], r.deep_done[1], tickets, (int*)nullptr);
+        r.ctl + 2, r.ctl + 4, r.deep_list[1].ptr, r.deep_done[1].ptr, tickets, (int*)nullptr);
 }
 
 // Joint form: the closest-hit pass over `p` (n rays) and the shadow pass over `s` (size *size_ptr, or max_n) in ONE persistent launch,
@@ -1723,23 +1693,16 @@ void launch_trace_joint(RenderDevice& r, hipStream_t stream, const PrimaryStream
     if (r.trace_refill > 0 && r.scene.tri_delta && refill_indexable(n, max_n) && stream_slab(p, ps) && stream_slab(s, ss))
         LAUNCH_TRACE_REFILL(dim3(persistent_grid(r)), dim3(kWave * kPersistWaves), 0, stream, r.scene.dev, ps, n, coherent_from, ss,
             size_ptr, max_n, r.film, inv_spp,
-                           r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0], r.deep_list[1], r.tickets[0], r.trace_refill,
+                           r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0].ptr, r.deep_list[1].ptr, r.tickets[0].ptr, r.trace_refill,
                                r.trace_refill_shadow, ensure_spill(r, 0), r.ctl + 2);
     else hipLaunchKernelGGL(k_trace_persist<2>, dim3(persistent_grid(r)), dim3(kWave * kPersistWaves), 0, stream, r.scene.dev, p, n, s,
         size_ptr, max_n, r.film, inv_spp,
-                       r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0], r.deep_list[1], r.tickets[0], ensure_spill(r, 0), r.ctl + 2);
+                       r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0].ptr, r.deep_list[1].ptr, r.tickets[0].ptr, ensure_spill(r, 0),
+                           r.ctl + 2);
     // (nothing is abandoned by the persistent kernels any more: the follow-up kernel is the launch's housekeeping -- ticket counters, the
     // shader's slot counter)
     hipLaunchKernelGGL(k_trace_deep<false>, dim3(1), dim3(kWave), 0, stream, r.scene.dev, p, SecondaryStream{}, (float*)nullptr, 0.0f,
-        r.ctl + 2, r.ctl + 3, r.deep_list[0], r.deep_done[0], r.tickets[0], r.ctl + 6);
-}
-
-void ensure_hist(RenderDevice& r, size_t ints) {
-    if (r.hist_cap < ints) {
-        if (r.hist) HIP_CHECK(hipFree(r.hist));
-        HIP_CHECK(hipMalloc(&r.hist, sizeof(int) * ints));
-        r.hist_cap = ints;
-    }
+        r.ctl + 2, r.ctl + 3, r.deep_list[0].ptr, r.deep_done[0].ptr, r.tickets[0].ptr, r.ctl + 6);
 }
 
 // two sets of bin arrays: set 0 = sort by geometry, set 1 = compaction (the compaction reads its input size from set 0)
@@ -1752,13 +1715,13 @@ void bin_stream(RenderDevice& r, int set, const PrimaryStream& p, const PrimaryS
     int num_bins,
                 int keep_hit, int drop_from_bin, hipStream_t stream, int copy_interval = 1, int* perm = nullptr) {
     const int blocks = std::max(1, (max_n + kBinBlock - 1) / kBinBlock);
-    ensure_hist(r, (size_t)num_bins * blocks);
+    int* const hist = r.hist.ensure((size_t)num_bins * blocks);
     const size_t lds = sizeof(int) * (kBinBlock / kWave) * num_bins;
     hipLaunchKernelGGL(k_bin_count, dim3(blocks), dim3(kBlock), sizeof(int) * num_bins, stream, p, size_ptr, max_n, mode, num_bins, blocks,
-        r.hist);
-    hipLaunchKernelGGL(k_bin_scan_blocks, dim3(num_bins), dim3(kBlock), 0, stream, r.hist, blocks, bin_total(r, set));
+        hist);
+    hipLaunchKernelGGL(k_bin_scan_blocks, dim3(num_bins), dim3(kBlock), 0, stream, hist, blocks, bin_total(r, set));
     hipLaunchKernelGGL(k_bin_scan_bins, dim3(1), dim3(1), 0, stream, bin_total(r, set), num_bins, bin_begin(r, set), bin_end(r, set));
-    hipLaunchKernelGGL(k_scatter, dim3(blocks), dim3(kBinBlock), lds, stream, p, q, size_ptr, max_n, mode, num_bins, blocks, r.hist,
+    hipLaunchKernelGGL(k_scatter, dim3(blocks), dim3(kBinBlock), lds, stream, p, q, size_ptr, max_n, mode, num_bins, blocks, hist,
         bin_begin(r, set), keep_hit, drop_from_bin, copy_interval, perm);
     HIP_CHECK(hipGetLastError());
 }
@@ -1849,30 +1812,20 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
         HIP_CHECK(hipEventCreateWithFlags(&r.ev_copy, hipEventDisableTiming));
     }
     ensure_deep(r, 0, kCapacity); ensure_deep(r, 1, kCapacity);       // before the loop: growing them synchronises the device
-    if (r.perm_cap < round_cap(kCapacity)) {
-        HIP_CHECK(hipDeviceSynchronize());
-        if (r.perm) HIP_CHECK(hipFree(r.perm));
-        HIP_CHECK(hipMalloc(&r.perm, sizeof(int) * (size_t)round_cap(kCapacity)));
-        r.perm_cap = round_cap(kCapacity);
-    }
+    r.perm.ensure(round_cap(kCapacity));
     const bool fused = r.fused_compact != 0;
     int* d_alive = r.ctl + 6;                            // fused compaction: the shader's last block leaves the new stream size here
-    if (fused && r.scan_cap < (kCapacity + kBlock - 1) / kBlock) {
-        HIP_CHECK(hipDeviceSynchronize());
-        if (r.scan) HIP_CHECK(hipFree(r.scan));
-        r.scan_cap = (kCapacity + kBlock - 1) / kBlock;
-        HIP_CHECK(hipMalloc(&r.scan, sizeof(unsigned) * (size_t)r.scan_cap));
-    }
+    if (fused) r.scan.ensure((kCapacity + kBlock - 1) / kBlock);
     // the shader, either in place (then the compaction pass follows) or compacting into the other stream itself
     const auto shade = [&](const PrimaryStream& from, const PrimaryStream& to, const int* perm, const int* size_ptr, int n_value,
         int unsorted, int blocks) {
         if (fused) {
-            if (r.fused_compact != 2) HIP_CHECK(hipMemsetAsync(r.scan, 0, sizeof(unsigned) * (size_t)blocks, stream));
+            if (r.fused_compact != 2) HIP_CHECK(hipMemsetAsync(r.scan.ptr, 0, sizeof(unsigned) * (size_t)blocks, stream));
             // (d_alive was zeroed by the primary pass's follow-up kernel, k_trace_deep<false>)
         }
         launch_k_shade(stream, blocks * kBlock, r.scene.dev, from, to, perm, sec, size_ptr, n_value, r.film, inv_spp, r.max_path_len,
             unsorted,
-                       fused ? (r.fused_compact == 2 ? kScanAtomic : r.scan) : (unsigned*)nullptr, d_alive);
+                       fused ? (r.fused_compact == 2 ? kScanAtomic : r.scan.ptr) : (unsigned*)nullptr, d_alive);
     };
     while (id < num_rays || size > 0) {
         // [0, survivors): what the last bounce left; behind them the rays generated now
@@ -1904,10 +1857,10 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
             if (r.fused_sort) {
                 // sort by geometry WITHOUT moving the rays: the binning kernels only compute the permutation, the shader gathers
                 // through it and writes the sorted, shaded stream (misses, bin G, are not in the permutation: dropped, :347-357)
-                bin_stream(r, 0, *primary, *other, nullptr, size, KEY_GEOM, G + 1, 1, G, stream, 0, r.perm);
+                bin_stream(r, 0, *primary, *other, nullptr, size, KEY_GEOM, G + 1, 1, G, stream, 0, r.perm.ptr);
                 // the previous shadow rays have been traced
                 if (overlap && iterations) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_sec, 0));
-                shade(*primary, *other, r.perm, d_valid, 0, 0, blocks);
+                shade(*primary, *other, r.perm.ptr, d_valid, 0, 0, blocks);
                 std::swap(primary, other);
             } else {
                 // misses (bin G) are dropped (:347-357); tmin / tmax stay behind
@@ -2339,9 +2292,8 @@ void rodent_gpu_get_secondary_stream(int32_t dev, SecondaryStream* s, int32_t si
     carve_secondary(*s, ensure_slab(r, 2, size, 13), round_cap(size)); }
 void rodent_gpu_get_tmp_buffer(int32_t dev, int32_t** buf, int32_t size) {
     RenderDevice& r = rdev(dev);
-    if (r.tmp_cap < round_cap(size)) { HIP_CHECK(hipSetDevice(dev)); if (r.tmp) HIP_CHECK(hipFree(r.tmp));
-        HIP_CHECK(hipMalloc(&r.tmp, sizeof(int) * round_cap(size))); r.tmp_cap = round_cap(size); }
-    *buf = r.tmp;
+    if (r.tmp.count < (size_t)round_cap(size)) HIP_CHECK(hipSetDevice(dev));
+    *buf = r.tmp.ensure(round_cap(size));
 }
 // Host stream slabs with the same carving (interface.cpp:367-373,621-629).  The library computes nothing on the CPU;
 // a host that stages rays itself (or the reference's CPU mapping) gets the layout it expects.

@@ -23,20 +23,12 @@
 #include <utility>
 #include <vector>
 
+#include "device_buffer.h"
 #include "rodent_render.h"
 #include "../host/buffer_io.h"
 #include "../host/image.h"
 
 namespace {
-
-#define HIP_CHECK(expr)                                                                        \
-    do {                                                                                       \
-        hipError_t err_ = (expr);                                                              \
-        if (err_ != hipSuccess) {                                                              \
-            fprintf(stderr, "rodent_hip: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(err_), __FILE__, __LINE__); \
-            abort();                                                                           \
-        }                                                                                      \
-    } while (0)
 
 [[noreturn]] void fail(const char* what, const char* file) { fprintf(stderr, "rodent_hip: %s '%s'\n", what, file); abort(); }
 

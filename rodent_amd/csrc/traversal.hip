@@ -41,18 +41,9 @@
 #include <utility>
 #include <vector>
 
+#include "device_buffer.h"
 #include "rodent_traversal.h"
 #include "traversal_device.h"
-
-#define HIP_CHECK(expr)                                                                       \
-    do {                                                                                      \
-        hipError_t err_ = (expr);                                                             \
-        if (err_ != hipSuccess) {                                                             \
-            fprintf(stderr, "rodent_hip: %s failed: %s (%s:%d)\n", #expr,                     \
-                    hipGetErrorString(err_), __FILE__, __LINE__);                             \
-            abort();                                                                          \
-        }                                                                                     \
-    } while (0)
 
 namespace {
 
@@ -749,26 +740,27 @@ __global__ __launch_bounds__(kSortThreads) void k_raysort_scatter(const unsigned
 // Host side
 // ---------------------------------------------------------------------------------------------
 constexpr int kHostPageInts = 64, kHostErr = 16;        // (the error word in a cache line of its own, away from the ray-kind words)
+// The buffers grow under `mutex`, and a launcher holds it from its first ensure to its last enqueue: another thread's launch on the same
+// context cannot free a block between the moment a launcher reads its pointer and the moment its kernel is enqueued.
 struct DeviceState {
     bool  init = false;
+    std::mutex mutex;                          // held by every launch on this context, see above
     int*  scratch = nullptr;    // [0] ray counter of the first persistent kernels, [16..] Ctl
     int   num_cus = 0;
-    int*  deep_list = nullptr;  // ray indices whose stack overflowed the LDS window
-    int   deep_cap = 0;
+    DeviceBuffer<int> deep_list;               // ray indices whose stack overflowed the LDS window
     int*  deep_stack = nullptr; // 64 x 64 ints: global-memory stack of k_bvh2_finish
-    unsigned long long* trace = nullptr;   // debug: 16384 x 4 words (instrumented variants)
-    int*  queue_mem[2] = {nullptr, nullptr};   // suspended-ray queues of the phased traversal (ping-pong), queue_cap slots each
-    int   queue_cap = 0;
-    int*  qcount = nullptr;                    // [phase][stripe] suspended-ray counters, 64 bytes apart
-    int*  sort_perm = nullptr; unsigned short* sort_keys = nullptr; int sort_cap = 0;     // "sorted" mapping: permutation and cell keys
-    int*  sort_totals = nullptr;               // [0, 512) cell counts (zero between launches), [512, 1024) cell cursors
-    int4* top_image = nullptr;                 // "top*" mappings: kMaxTopNodes x 64 bytes, rebuilt by every launch
+    DeviceBuffer<unsigned long long> trace;    // debug: 16384 x 4 words (instrumented variants)
+    DeviceBuffer<int> queue_mem[2];            // suspended-ray queues of the phased traversal (ping-pong), kQueueWords ints per slot
+    DeviceBuffer<int> qcount;                  // [phase][stripe] suspended-ray counters, 64 bytes apart
+    DeviceBuffer<int> sort_perm; DeviceBuffer<unsigned short> sort_keys;      // "sorted" mapping: permutation and cell keys
+    DeviceBuffer<int> sort_totals;             // [0, 512) cell counts (zero between launches), [512, 1024) cell cursors
+    DeviceBuffer<int4> top_image;              // "top*" mappings: kMaxTopNodes x 64 bytes, rebuilt by every launch
     const Node2* top_image_nodes = nullptr; int top_image_n = 0;
     // schedule history: wave iterations per chunk of the last launch, the order sorted from them
-    int*  chunk_cost = nullptr; int* chunk_order = nullptr;
+    DeviceBuffer<int> chunk_cost, chunk_order;
     int   order_rays = 0;                      // ray count of the launch chunk_order was sorted for (0: none)
     // per stripe: {chunks the last two launches both found in their expensive half, half the stripe's chunks}
-    int*  order_agree = nullptr;
+    DeviceBuffer<int> order_agree;
     // lab: caller-supplied ray permutation of the "top-userperm" mapping (rodent_hip_debug_set_perm)
     const int* debug_perm = nullptr;
     // pinned host memory the kernels store into: [0] / [1] ray-kind reports (host_kinds), [kHostErr] stack-overflow flag (Ctl::host_err)
@@ -779,9 +771,9 @@ struct DeviceState {
     // coherent / incoherent (pinned host memory the kernels store into); hint_* = the ray list the hint is about and the first launch that
     // traced it.
     int*  host_kinds = nullptr; int launch_id = 0; const void* hint_rays = nullptr; int hint_n = 0, hint_first_id = 0;
-    int*  tickets = nullptr;                   // persistent "top*p" mappings: chunk tickets per XCD (zero between launches)
-    // out-of-window stack entries: spill_slots wave blocks of kSpillWaveInts ints (stack_spill, traversal_device.h; ensure_spill)
-    int*  spill = nullptr; int spill_slots = 0;
+    DeviceBuffer<int> tickets;                 // persistent "top*p" mappings: chunk tickets per XCD (zero between launches)
+    // out-of-window stack entries: wave blocks of kSpillWaveInts ints (stack_spill, traversal_device.h; ensure_spill)
+    DeviceBuffer<int> spill;
     Ctl*  ctl() const { return reinterpret_cast<Ctl*>(scratch + 16); }
 };
 // One DeviceState per (device, stream): launches enqueued on different streams of a device may overlap, so each
@@ -842,54 +834,29 @@ DeviceState& device_state(int dev) {
 
 inline int blocks_for(int n) { return (n + kWave - 1) / kWave; }
 constexpr int kQueueWords = 4 + 16;             // per slot: ray, tmax, top, depth + a 16-entry stack window
+// the ints of a set of striped counters: the tickets and the suspended-ray counters (the size k_bvh2_finish clears)
+constexpr size_t kCounterInts = kMaxPhases * kStripes * kCounterStride;
 RayQueue ensure_queue(DeviceState& s, int which, int n) {
     // a stripe receives the survivors of at most ceil(blocks / kStripes) waves
-    const int stripe_cap = ((blocks_for(n) + kStripes - 1) / kStripes) * kWave, cap = stripe_cap * kStripes;
-    if (cap > s.queue_cap || !s.qcount) {
-        std::lock_guard<std::mutex> lock(g_mutex);
-        HIP_CHECK(hipDeviceSynchronize());
-        if (cap > s.queue_cap) {
-            for (int k = 0; k < 2; k++) {
-                if (s.queue_mem[k]) HIP_CHECK(hipFree(s.queue_mem[k]));
-                HIP_CHECK(hipMalloc(&s.queue_mem[k], sizeof(int) * (size_t)kQueueWords * cap));
-            }
-            s.queue_cap = cap;
-        }
-        if (!s.qcount) {
-            HIP_CHECK(hipMalloc(&s.qcount, sizeof(int) * kMaxPhases * kStripes * kCounterStride));
-            HIP_CHECK(hipMemset(s.qcount, 0, sizeof(int) * kMaxPhases * kStripes * kCounterStride));
-        }
-    }
-    int* m = s.queue_mem[which]; const size_t c = (size_t)s.queue_cap;
-    return RayQueue{m, reinterpret_cast<float*>(m + c), m + 2 * c, m + 3 * c, m + 4 * c, s.queue_cap, stripe_cap};
+    const int stripe_cap = ((blocks_for(n) + kStripes - 1) / kStripes) * kWave;
+    int* m = s.queue_mem[which].ensure((size_t)kQueueWords * stripe_cap * kStripes);
+    s.qcount.ensure(kCounterInts, 0);
+    const size_t c = s.queue_mem[which].count / kQueueWords;          // the slots allocated: the arrays' stride
+    return RayQueue{m, reinterpret_cast<float*>(m + c), m + 2 * c, m + 3 * c, m + 4 * c, (int)c, stripe_cap};
 }
 
-void ensure_sort_buffers(DeviceState& s, int n) {
-    if (n <= s.sort_cap && s.sort_totals) return;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    HIP_CHECK(hipDeviceSynchronize());
-    if (n > s.sort_cap) {
-        if (s.sort_perm) HIP_CHECK(hipFree(s.sort_perm));
-        if (s.sort_keys) HIP_CHECK(hipFree(s.sort_keys));
-        HIP_CHECK(hipMalloc(&s.sort_perm, sizeof(int) * (size_t)n));
-        HIP_CHECK(hipMalloc(&s.sort_keys, sizeof(unsigned short) * (size_t)n));
-        s.sort_cap = n;
-    }
-    if (!s.sort_totals) {
-        HIP_CHECK(hipMalloc(&s.sort_totals, sizeof(int) * 2 * kSortCells));
-        HIP_CHECK(hipMemset(s.sort_totals, 0, sizeof(int) * 2 * kSortCells));
-    }
-}
+void ensure_sort_buffers(DeviceState& s, int n) { s.sort_perm.ensure(n); s.sort_keys.ensure(n); s.sort_totals.ensure(2 * kSortCells, 0); }
 
-void ensure_deep_list(DeviceState& s, int n) {
-    if (n <= s.deep_cap) return;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    if (n <= s.deep_cap) return;
-    HIP_CHECK(hipDeviceSynchronize());
-    if (s.deep_list) HIP_CHECK(hipFree(s.deep_list));
-    HIP_CHECK(hipMalloc(&s.deep_list, sizeof(int) * (size_t)n));
-    s.deep_cap = n;
+// "top*" mappings: the top-of-tree image and the chunk tickets
+void ensure_top_buffers(DeviceState& s) {
+    s.top_image.ensure(kMaxTopNodes * sizeof(Node2) / sizeof(int4), 0); s.tickets.ensure(kCounterInts, 0); }
+// schedule history (rodent_hip_schedule_history): chunk costs and order per stripe, and the stripes' agreement words
+void ensure_history(DeviceState& s) {
+    s.chunk_cost.ensure(kStripes * kMaxStripeChunks); s.chunk_order.ensure(kStripes * kMaxStripeChunks);
+    s.order_agree.ensure(2 * kStripes, 0xFF);
 }
+// chunks of a launch's fullest stripe
+int stripe_chunks(int n) { return ((blocks_for(n) + 31) / 32 + kStripes - 1) / kStripes * 32; }
 
 // The blocks the traversal stacks spill into beyond their LDS windows: one per wave slot of a resident generation of the persistent kernels
 // (num_cus x 32 waves = 8192), which the one-chunk kernels' launches below rodent_hip_top_min_rays (6144 chunks; 9216 until round 4) fit as
@@ -899,22 +866,14 @@ void ensure_deep_list(DeviceState& s, int n) {
 // num_cus x 32 = 8 192 (100 MB).  Touched only by rays deeper than their window.
 constexpr int kSpillSlots = 9216;
 void ensure_spill(DeviceState& s, int slots) {
-    if (slots <= s.spill_slots) return;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    if (slots <= s.spill_slots) return;
     int want = 64;
     while (want < slots) want *= 2;
-    want = std::min(want, kSpillSlots);
-    HIP_CHECK(hipDeviceSynchronize());
-    if (s.spill) HIP_CHECK(hipFree(s.spill));
-    HIP_CHECK(hipMalloc(&s.spill, sizeof(int) * (size_t)want * kSpillWaveInts));
-    s.spill_slots = want;
+    s.spill.ensure((size_t)std::min(want, kSpillSlots) * kSpillWaveInts);
 }
-// the wave slots of one resident generation of 16-wave workgroups (what every persistent BVH2 kernel launches)
-int resident_wave_slots(const DeviceState& s) { return ((s.num_cus * 2 + kStripes - 1) / kStripes) * kStripes * 16; }
-
-// a persistent grid's wave slots must fit the context's spill blocks (they do on every gfx950 part: 256 CUs x 32 waves)
-int spill_checked(int groups, int waves) {
+// One resident generation of persistent workgroups of `waves` waves, `occ` waves per CU, the same number in every stripe.  Their wave slots
+// must fit the context's spill blocks (they do on every gfx950 part: 256 CUs x 32 waves).
+int persistent_groups(const DeviceState& s, int occ, int waves) {
+    const int groups = ((s.num_cus * (occ / waves) + kStripes - 1) / kStripes) * kStripes;
     if ((long)groups * waves > kSpillSlots) {
         fprintf(stderr, "rodent_hip: %d x %d resident waves exceed the %d stack spill blocks\n", groups, waves, kSpillSlots); abort(); }
     return groups;
@@ -958,78 +917,69 @@ constexpr int kFinishGroups = 256;
 // more than tiles gain (64 Ki camera rays 0.078 -> 0.083 ms, 128 Ki 0.088 = 0.089, 256 Ki 0.106 -> 0.102, 384 Ki 0.130 -> 0.118:
 // profiles/r05_threshold_sweep_grid.txt)
 constexpr int kGridMinRays = 2048 * kWave;
+// The one-chunk kernel's buffers: the deep list and, for its spilling form (`spill`) when every chunk has a spill block, the spill blocks.
+// Returns whether the launch takes the spilling form.
+bool reserve_single(DeviceState& s, int n, bool spill) {
+    s.deep_list.ensure(n);
+    spill = spill && blocks_for(n) <= kSpillSlots;
+    if (spill) ensure_spill(s, blocks_for(n));
+    return spill;
+}
 template <bool ANY, int LDS_N, int XCD, bool TR = false, int PRIO = 0> void L_single(LAUNCH_ARGS) {
-    ensure_deep_list(s, n);
-    if (PRIO == 0 && !TR && blocks_for(n) <= kSpillSlots) {        // every chunk has a spill block: deep stacks stay in their lanes
-        ensure_spill(s, blocks_for(n));
+    if (reserve_single(s, n, PRIO == 0 && !TR))                 // every chunk has a spill block: deep stacks stay in their lanes
         hipLaunchKernelGGL((k_bvh2_single<ANY, LDS_N, XCD, false, 0, true>), dim3(blocks_for(n)), dim3(kWave), 0, stream, nodes, tris,
-            rays, hits, n, s.ctl(), s.deep_list, (const int*)nullptr, s.spill, n >= kGridMinRays ? g_ray_grid : 0);
-    } else
+            rays, hits, n, s.ctl(), s.deep_list.ptr, (const int*)nullptr, s.spill.ptr, n >= kGridMinRays ? g_ray_grid : 0);
+    else
         hipLaunchKernelGGL((k_bvh2_single<ANY, LDS_N, XCD, TR, PRIO>), dim3(blocks_for(n)), dim3(kWave), 0, stream, nodes, tris, rays,
-            hits, n, s.ctl(), s.deep_list, (const int*)nullptr, (int*)nullptr, 0);
-    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(kFinishGroups), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list,
-        s.deep_stack, (int*)nullptr);
+            hits, n, s.ctl(), s.deep_list.ptr, (const int*)nullptr, (int*)nullptr, 0);
+    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(kFinishGroups), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(),
+        s.deep_list.ptr, s.deep_stack, (int*)nullptr);
 }
 
 
 template <bool ANY, int LDS_N, int TOPN, int WAVES, bool PREFETCH, bool SORTED, int OCC, bool TRACE = false, int PRIO = 0, int FUSED = 0,
     bool LAZY = false> void launch_top_persist(LAUNCH_ARGS, int max_id) {
-    ensure_deep_list(s, n);
-    ensure_spill(s, ((s.num_cus * (OCC / WAVES) + kStripes - 1) / kStripes) * kStripes * WAVES);
-    if (!s.top_image || !s.tickets) {
-        std::lock_guard<std::mutex> lock(g_mutex);
-        if (!s.top_image) { HIP_CHECK(hipMalloc(&s.top_image, kMaxTopNodes * sizeof(Node2)));
-            HIP_CHECK(hipMemset(s.top_image, 0, kMaxTopNodes * sizeof(Node2))); }
-        if (!s.tickets) {
-            HIP_CHECK(hipMalloc(&s.tickets, sizeof(int) * kMaxPhases * kStripes * kCounterStride));      // the size k_bvh2_finish clears
-            HIP_CHECK(hipMemset(s.tickets, 0, sizeof(int) * kMaxPhases * kStripes * kCounterStride));
-        }
-    }
+    const int groups = persistent_groups(s, OCC, WAVES);
+    s.deep_list.ensure(n);
+    ensure_spill(s, groups * WAVES);
+    ensure_top_buffers(s);
     s.top_image_nodes = nullptr;
     const int* perm = nullptr;
     if (SORTED) {
         ensure_sort_buffers(s, n);
         const int blocks = (n + kSortBlockRays - 1) / kSortBlockRays;
-        hipLaunchKernelGGL(k_raysort_count, dim3(blocks), dim3(kSortThreads), 0, stream, nodes, rays, n, s.sort_keys, s.sort_totals);
-        hipLaunchKernelGGL(k_raysort_scan, dim3(1), dim3(kSortCells), 0, stream, s.sort_totals, s.sort_totals + kSortCells);
-        hipLaunchKernelGGL(k_raysort_scatter, dim3(blocks), dim3(kSortThreads), 0, stream, s.sort_keys, n, s.sort_totals + kSortCells,
-            s.sort_perm);
-        perm = s.sort_perm;
+        hipLaunchKernelGGL(k_raysort_count, dim3(blocks), dim3(kSortThreads), 0, stream, nodes, rays, n, s.sort_keys.ptr,
+            s.sort_totals.ptr);
+        hipLaunchKernelGGL(k_raysort_scan, dim3(1), dim3(kSortCells), 0, stream, s.sort_totals.ptr, s.sort_totals.ptr + kSortCells);
+        hipLaunchKernelGGL(k_raysort_scatter, dim3(blocks), dim3(kSortThreads), 0, stream, s.sort_keys.ptr, n,
+            s.sort_totals.ptr + kSortCells, s.sort_perm.ptr);
+        perm = s.sort_perm.ptr;
     }
     if (!SORTED && PRIO == -1) perm = s.debug_perm;                          // lab "top-userperm"
-    // one resident generation, the same number in every stripe
-    const int groups = spill_checked(((s.num_cus * (OCC / WAVES) + kStripes - 1) / kStripes) * kStripes, WAVES);
-    // chunks of the fullest stripe
-    const int total_chunks = blocks_for(n), stride = ((total_chunks + 31) / 32 + kStripes - 1) / kStripes * 32;
+    const int total_chunks = blocks_for(n), stride = stripe_chunks(n);
     // (with the history on, the launch is followed by k_bvh2_top_finish_history whatever FUSED says)
     if (g_schedule_history && !SORTED && !TRACE && PRIO == 0 && FUSED != 1 && !PREFETCH && stride <= kMaxStripeChunks) {
         // schedule history: this launch records its chunks' costs; it draws them in the order the previous launch of the same
         // size left behind, if there is one (all on `stream`: the follow-up kernel writes the order before the next launch reads it)
-        if (!s.chunk_cost) {
-            std::lock_guard<std::mutex> lock(g_mutex);
-            HIP_CHECK(hipMalloc(&s.chunk_cost, sizeof(int) * kStripes * kMaxStripeChunks));
-            HIP_CHECK(hipMalloc(&s.chunk_order, sizeof(int) * kStripes * kMaxStripeChunks));
-            HIP_CHECK(hipMalloc(&s.order_agree, sizeof(int) * 2 * kStripes));
-            HIP_CHECK(hipMemset(s.order_agree, 0xFF, sizeof(int) * 2 * kStripes));
-        }
+        ensure_history(s);
         const bool have_previous = s.order_rays == n;
-        const History hist{have_previous ? s.chunk_order : nullptr, s.chunk_cost, stride, s.order_agree};
+        const History hist{have_previous ? s.chunk_order.ptr : nullptr, s.chunk_cost.ptr, stride, s.order_agree.ptr};
         hipLaunchKernelGGL((k_bvh2_top_persist<ANY, LDS_N, TOPN, WAVES, false, OCC, false, 0, false, true>), dim3(groups),
             dim3(kWave * WAVES), 0, stream, nodes, tris, rays, hits, n, s.ctl(),
-                           s.deep_list, perm, s.top_image, s.tickets, max_id, s.spill, hist);
+                           s.deep_list.ptr, perm, s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, hist);
         hipLaunchKernelGGL((k_bvh2_top_finish_history<ANY>), dim3(kStripes), dim3(kHistoryThreads), 0, stream, nodes, tris, rays, hits,
-            s.ctl(), s.deep_list, s.deep_stack, s.tickets,
-                           s.top_image, TOPN, total_chunks, (const int*)s.chunk_cost, s.chunk_order, stride, have_previous ? 1 : 0,
-                               s.order_agree);
+            s.ctl(), s.deep_list.ptr, s.deep_stack, s.tickets.ptr,
+                           s.top_image.ptr, TOPN, total_chunks, (const int*)s.chunk_cost.ptr, s.chunk_order.ptr, stride,
+                               have_previous ? 1 : 0, s.order_agree.ptr);
         s.order_rays = n;
         return;
     }
     s.order_rays = 0;
     hipLaunchKernelGGL((k_bvh2_top_persist<ANY, LDS_N, TOPN, WAVES, PREFETCH, OCC, TRACE, PRIO, FUSED, false, LAZY>), dim3(groups),
-        dim3(kWave * WAVES), 0, stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list,
-                       perm, s.top_image, s.tickets, max_id, s.spill, History{nullptr, nullptr, 0, nullptr});
+        dim3(kWave * WAVES), 0, stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
+                       perm, s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, History{nullptr, nullptr, 0, nullptr});
     if (!FUSED) hipLaunchKernelGGL((k_bvh2_top_finish<ANY>), dim3(kFinishGroups), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(),
-        s.deep_list, s.deep_stack, s.tickets, s.top_image, TOPN);
+        s.deep_list.ptr, s.deep_stack, s.tickets.ptr, s.top_image.ptr, TOPN);
 }
 template <bool ANY, int LDS_N, int TOPN, int WAVES, bool PREFETCH = true, bool SORTED = false, int OCC = 32, bool TRACE = false,
     int PRIO = 0, int FUSED = 0, bool LAZY = false> void L_top_persist(LAUNCH_ARGS) {
@@ -1059,30 +1009,30 @@ template <bool ANY, int LDS_N, int TOPN, int WAVES, bool PREFETCH, int FUSED = 2
     if (max_id == 0) L_single<ANY, 16, 32>(s, nodes, tris, rays, hits, n, stream);
     else launch_top_persist<ANY, LDS_N, TOPN, WAVES, PREFETCH, false, 32, false, 0, FUSED>(s, nodes, tris, rays, hits, n, stream, max_id);
 }
+// Ensures what the default mapping's launch of n rays uses (L_default; timed_sync_call before its first event): the one-chunk kernel's
+// buffers, or the persistent kernel's and, with the schedule history on, the history's.  Returns the node ids the persistent kernel may
+// assume mapped, 0 when the launch takes the one-chunk kernel.
+int reserve_default(DeviceState& s, const Node2* nodes, int n, int waves = 16) {
+    const int max_id = top_kernel_ids(nodes, n);
+    if (max_id == 0) { reserve_single(s, n, true); return 0; }
+    const int groups = persistent_groups(s, 32, waves);
+    s.deep_list.ensure(n);
+    ensure_top_buffers(s);
+    ensure_spill(s, groups * waves);
+    if (g_schedule_history && stripe_chunks(n) <= kMaxStripeChunks) ensure_history(s);
+    return max_id;
+}
 // Round 4: the persistent kernel chooses per wave -- once, from the first 64 rays the wave draws -- between whole chunks (rays that share
 // an origin or a direction) and lane refill (anything else): k_bvh2_top_auto, traversal_top.h.  With the schedule history on, launches keep
 // the chunk kernel (the history orders CHUNKS).
-void ensure_top_buffers(DeviceState& s) {
-    if (s.top_image && s.tickets) return;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    if (!s.top_image) { HIP_CHECK(hipMalloc(&s.top_image, kMaxTopNodes * sizeof(Node2)));
-        HIP_CHECK(hipMemset(s.top_image, 0, kMaxTopNodes * sizeof(Node2))); }
-    if (!s.tickets) {
-        HIP_CHECK(hipMalloc(&s.tickets, sizeof(int) * kMaxPhases * kStripes * kCounterStride));      // the size k_bvh2_finish clears
-        HIP_CHECK(hipMemset(s.tickets, 0, sizeof(int) * kMaxPhases * kStripes * kCounterStride));
-    }
-}
 template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL, int MODE = 0, bool FUSED = true,
     bool LAZY = false> void L_default(LAUNCH_ARGS) {
-    const int max_id = top_kernel_ids(nodes, n);
+    const int max_id = reserve_default(s, nodes, n, WAVES);
     if (max_id == 0) { L_single<ANY, 16, 32>(s, nodes, tris, rays, hits, n, stream); return; }
     if (g_schedule_history) {
         launch_top_persist<ANY, LDS_N, TOPN, WAVES, false, false, 32, false, 0, 2>(s, nodes, tris, rays, hits, n, stream, max_id); return; }
-    ensure_deep_list(s, n);
-    ensure_top_buffers(s);
-    const int groups = spill_checked(((s.num_cus * (32 / WAVES) + kStripes - 1) / kStripes) * kStripes, WAVES);
-    ensure_spill(s, groups * WAVES);
-    s.top_image_nodes = nullptr; s.order_rays = 0;   // one resident generation, the same number in every stripe
+    const int groups = persistent_groups(s, 32, WAVES);
+    s.top_image_nodes = nullptr; s.order_rays = 0;
     // Which kernel?  k_bvh2_top_auto decides per wave and is right for any list; but its refill loop, compiled under the chunk loop's
     // register budget, runs a few per cent behind k_bvh2_top_refill's (profiles/r04_sweep_auto.log).  With the ray-kind hint ON (off by
     // default, see g_kind_hint) every workgroup reports what its first wave saw (report_ray_kind) and a list that earlier launches found
@@ -1098,17 +1048,17 @@ template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL, int MODE = 0, bo
     const bool incoherent = hinting && kinds[1] >= s.hint_first_id && kinds[0] < kinds[1];
     if (incoherent) {
         hipLaunchKernelGGL((k_bvh2_top_refill<ANY, LDS_N, TOPN, WAVES, REFILL, false, false>), dim3(groups), dim3(kWave * WAVES), 0,
-            stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list,
-                           (const int4*)s.top_image, s.tickets, max_id, s.spill, report_to, id);
-        hipLaunchKernelGGL((k_bvh2_top_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list,
-            s.deep_stack, s.tickets, s.top_image, TOPN);
+            stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
+                           (const int4*)s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, report_to, id);
+        hipLaunchKernelGGL((k_bvh2_top_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list.ptr,
+            s.deep_stack, s.tickets.ptr, s.top_image.ptr, TOPN);
         return;
     }
     hipLaunchKernelGGL((k_bvh2_top_auto<ANY, LDS_N, TOPN, WAVES, REFILL, MODE, FUSED, LAZY>), dim3(groups), dim3(kWave * WAVES), 0, stream,
-        nodes, tris, rays, hits, n, s.ctl(), s.deep_list,
-                       s.top_image, s.tickets, max_id, s.spill, report_to, id, g_ray_grid);
+        nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
+                       s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, report_to, id, g_ray_grid);
     if (!FUSED) hipLaunchKernelGGL((k_bvh2_top_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(),
-        s.deep_list, s.deep_stack, s.tickets, s.top_image, TOPN);
+        s.deep_list.ptr, s.deep_stack, s.tickets.ptr, s.top_image.ptr, TOPN);
 }
 
 // "refill": the persistent kernel with lane refill (traversal_top.h), for ray sets whose rays differ widely in cost -- incoherent ones: the
@@ -1117,24 +1067,16 @@ template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL, int MODE = 0, bo
 // is a variant the caller asks for and not the default.
 template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL, bool ADAPT = false, bool FENCE = false> void L_top_refill(LAUNCH_ARGS) {
     if (top_kernel_ids(nodes, n) == 0) { L_single<ANY, 16, 32>(s, nodes, tris, rays, hits, n, stream); return; }      // (as L_default)
-    ensure_deep_list(s, n);
-    if (!s.top_image || !s.tickets) {
-        std::lock_guard<std::mutex> lock(g_mutex);
-        if (!s.top_image) { HIP_CHECK(hipMalloc(&s.top_image, kMaxTopNodes * sizeof(Node2)));
-            HIP_CHECK(hipMemset(s.top_image, 0, kMaxTopNodes * sizeof(Node2))); }
-        if (!s.tickets) {
-            HIP_CHECK(hipMalloc(&s.tickets, sizeof(int) * kMaxPhases * kStripes * kCounterStride));      // the size k_bvh2_finish clears
-            HIP_CHECK(hipMemset(s.tickets, 0, sizeof(int) * kMaxPhases * kStripes * kCounterStride));
-        }
-    }
+    const int groups = persistent_groups(s, 32, WAVES);
+    s.deep_list.ensure(n);
+    ensure_top_buffers(s);
     s.top_image_nodes = nullptr;
-    const int groups = spill_checked(((s.num_cus * (32 / WAVES) + kStripes - 1) / kStripes) * kStripes, WAVES);
     ensure_spill(s, groups * WAVES);
     hipLaunchKernelGGL((k_bvh2_top_refill<ANY, LDS_N, TOPN, WAVES, REFILL, ADAPT, FENCE>), dim3(groups), dim3(kWave * WAVES), 0, stream,
-        nodes, tris, rays, hits, n, s.ctl(), s.deep_list,
-                       (const int4*)s.top_image, s.tickets, mapped_node_ids(nodes), s.spill, (int*)nullptr, 0);
-    hipLaunchKernelGGL((k_bvh2_top_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list,
-        s.deep_stack, s.tickets, s.top_image, TOPN);
+        nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
+                       (const int4*)s.top_image.ptr, s.tickets.ptr, mapped_node_ids(nodes), s.spill.ptr, (int*)nullptr, 0);
+    hipLaunchKernelGGL((k_bvh2_top_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list.ptr,
+        s.deep_stack, s.tickets.ptr, s.top_image.ptr, TOPN);
 }
 
 
@@ -1143,17 +1085,17 @@ template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL, bool ADAPT = fal
 // once take the single kernel.
 // "sorted": permutation by origin cell, then the single kernel through it
 template <bool ANY, int LDS_N> void L_sorted(LAUNCH_ARGS) {
-    ensure_deep_list(s, n);
+    s.deep_list.ensure(n);
     ensure_sort_buffers(s, n);
     const int blocks = (n + kSortBlockRays - 1) / kSortBlockRays;
-    hipLaunchKernelGGL(k_raysort_count, dim3(blocks), dim3(kSortThreads), 0, stream, nodes, rays, n, s.sort_keys, s.sort_totals);
-    hipLaunchKernelGGL(k_raysort_scan, dim3(1), dim3(kSortCells), 0, stream, s.sort_totals, s.sort_totals + kSortCells);
-    hipLaunchKernelGGL(k_raysort_scatter, dim3(blocks), dim3(kSortThreads), 0, stream, s.sort_keys, n, s.sort_totals + kSortCells,
-        s.sort_perm);
+    hipLaunchKernelGGL(k_raysort_count, dim3(blocks), dim3(kSortThreads), 0, stream, nodes, rays, n, s.sort_keys.ptr, s.sort_totals.ptr);
+    hipLaunchKernelGGL(k_raysort_scan, dim3(1), dim3(kSortCells), 0, stream, s.sort_totals.ptr, s.sort_totals.ptr + kSortCells);
+    hipLaunchKernelGGL(k_raysort_scatter, dim3(blocks), dim3(kSortThreads), 0, stream, s.sort_keys.ptr, n, s.sort_totals.ptr + kSortCells,
+        s.sort_perm.ptr);
     hipLaunchKernelGGL((k_bvh2_single<ANY, LDS_N, 32, false, 0>), dim3(blocks_for(n)), dim3(kWave), 0, stream, nodes, tris, rays, hits, n,
-        s.ctl(), s.deep_list, (const int*)s.sort_perm, (int*)nullptr, 0);
-    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(kFinishGroups), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list,
-        s.deep_stack, (int*)nullptr);
+        s.ctl(), s.deep_list.ptr, (const int*)s.sort_perm.ptr, (int*)nullptr, 0);
+    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(kFinishGroups), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(),
+        s.deep_list.ptr, s.deep_stack, (int*)nullptr);
 }
 
 int g_phased_min_rays = 4096 * kWave;           // rodent_hip_phased_min_rays()
@@ -1164,7 +1106,7 @@ template <bool ANY, int LDS_N, int CAPS, int LAST_RAYS = kWave> void L_phased(LA
     constexpr PhaseCaps caps = kPhaseCaps[CAPS];
     static_assert(caps.count + 1 <= kMaxPhases, "too many phases");
     if (n < g_phased_min_rays) { L_single<ANY, LDS_N, 32>(s, nodes, tris, rays, hits, n, stream); return; }
-    ensure_deep_list(s, n);
+    s.deep_list.ensure(n);
     RayQueue q[2] = {ensure_queue(s, 0, n), ensure_queue(s, 1, n)};
     const int blocks = blocks_for(n);
     // grids of the resuming phases: sized for the share of rays expected to survive (a multiple of kStripes; if more
@@ -1172,15 +1114,15 @@ template <bool ANY, int LDS_N, int CAPS, int LAST_RAYS = kWave> void L_phased(LA
     auto resume_grid = [&](int p) { const int g = blocks >> p; return ((g < kStripes ? kStripes : g) + kStripes - 1) / kStripes * kStripes;
         };
     hipLaunchKernelGGL((k_bvh2_phase<ANY, LDS_N, false, true>), dim3(blocks), dim3(kWave), 0, stream, nodes, tris, rays, hits, n, s.ctl(),
-        s.deep_list, s.qcount, q[1], 0, caps.cap[0], q[0]);
+        s.deep_list.ptr, s.qcount.ptr, q[1], 0, caps.cap[0], q[0]);
     for (int p = 1; p < caps.count; p++)
         hipLaunchKernelGGL((k_bvh2_phase<ANY, LDS_N, true, true>), dim3(resume_grid(p)), dim3(kWave), 0, stream, nodes, tris, rays, hits,
-            n, s.ctl(), s.deep_list, s.qcount, q[(p - 1) & 1], p, caps.cap[p], q[p & 1]);
+            n, s.ctl(), s.deep_list.ptr, s.qcount.ptr, q[(p - 1) & 1], p, caps.cap[p], q[p & 1]);
     hipLaunchKernelGGL((k_bvh2_phase<ANY, LDS_N, true, false, LAST_RAYS>), dim3(resume_grid(caps.count) * (kWave / LAST_RAYS)),
-        dim3(kWave), 0, stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list, s.qcount, q[(caps.count - 1) & 1], caps.count, 0,
+        dim3(kWave), 0, stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr, s.qcount.ptr, q[(caps.count - 1) & 1], caps.count, 0,
         q[caps.count & 1]);
-    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(kFinishGroups), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(), s.deep_list,
-        s.deep_stack, s.qcount);
+    hipLaunchKernelGGL((k_bvh2_finish<ANY>), dim3(kFinishGroups), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(),
+        s.deep_list.ptr, s.deep_stack, s.qcount.ptr);
 }
 
 #include "traversal_wide.h"          // BVH4 / BVH8 + Tri4: k_wide_single, k_wide_top_persist, k_wide_finish, L_wide_single, L_wide_top
@@ -1292,6 +1234,7 @@ void hip_traverse_bvh2_tri1_async(int32_t dev, const Node2* nodes, const Tri1* t
                                   int32_t num_rays, int32_t any_hit, int32_t variant, void* stream) {
     DeviceGuard on(dev);
     DeviceState& s = device_state(dev, (hipStream_t)stream);
+    std::lock_guard<std::mutex> launching(s.mutex);
     if (any_hit) launch_bvh2<true>(s, nodes, tris, rays, hits, num_rays, variant, (hipStream_t)stream);
     else         launch_bvh2<false>(s, nodes, tris, rays, hits, num_rays, variant, (hipStream_t)stream);
 }
@@ -1300,6 +1243,7 @@ void hip_traverse_bvh4_tri4_async(int32_t dev, const Node4* nodes, const Tri4* t
                                   int32_t num_rays, int32_t any_hit, int32_t variant, void* stream) {
     DeviceGuard on(dev);
     DeviceState& s = device_state(dev, (hipStream_t)stream);
+    std::lock_guard<std::mutex> launching(s.mutex);
     launch_wide(4, any_hit != 0, s, nodes, tris, rays, hits, num_rays, variant, (hipStream_t)stream);
 }
 
@@ -1307,6 +1251,7 @@ void hip_traverse_bvh8_tri4_async(int32_t dev, const Node8* nodes, const Tri4* t
                                   int32_t num_rays, int32_t any_hit, int32_t variant, void* stream) {
     DeviceGuard on(dev);
     DeviceState& s = device_state(dev, (hipStream_t)stream);
+    std::lock_guard<std::mutex> launching(s.mutex);
     launch_wide(8, any_hit != 0, s, nodes, tris, rays, hits, num_rays, variant, (hipStream_t)stream);
 }
 
@@ -1318,25 +1263,26 @@ int32_t rodent_hip_check_errors(int32_t dev, void* stream) {
 
 // The reference's host times its GPU kernels with anydsl_get_kernel_time() (tools/bench_traversal/bench_traversal.cpp:125-133): the AnyDSL
 // runtime's accumulated KERNEL time in microseconds -- no synchronisation, no copy.  The synchronous entry points keep the same account:
-// HIP events around what they enqueue -- the context's buffers are allocated BEFORE the first event, so a first call does not book its
-// hipMalloc as kernel time; where a mapping is two kernels (the one-chunk kernel + its follow-up) the microsecond between them is included
-// -- added up after the call's own synchronisation in one process-wide sum over all devices, like the reference's.  One synchronous call at
-// a time per (device, null stream) context.
+// HIP events around what they enqueue -- the default mapping's buffers are allocated BEFORE the first event (reserve_default,
+// reserve_wide), so a first call does not book its hipMalloc as kernel time; where a mapping is two kernels (the one-chunk kernel + its
+// follow-up) the microsecond between them is included -- added up after the call's own synchronisation in one process-wide sum over all
+// devices, like the reference's.  One synchronous call at a time per (device, null stream) context.
 }  // extern "C"
 namespace {
 std::atomic<uint64_t> g_kernel_ns{0};
-template <typename Launch> void timed_sync_call(int32_t dev, int32_t num_rays, Launch launch) {
+// `nodes`: a BVH2's, nullptr for BVH4 / BVH8
+template <typename Launch> void timed_sync_call(int32_t dev, int32_t num_rays, const Node2* nodes, Launch launch) {
     DeviceGuard on(dev);
     DeviceState& s = device_state(dev, nullptr);
     std::lock_guard<std::mutex> one_call(s.sync_mutex);
     if (!s.timer[0]) { HIP_CHECK(hipEventCreate(&s.timer[0])); HIP_CHECK(hipEventCreate(&s.timer[1])); }
-    if (num_rays > 0) {                                                   // every lazy allocation of the default mappings
-        ensure_deep_list(s, num_rays); ensure_top_buffers(s);
-        ensure_spill(s, num_rays < g_top_min_rays && blocks_for(num_rays) <= kSpillSlots ? blocks_for(num_rays) : resident_wave_slots(s));
+    {
+        std::lock_guard<std::mutex> launching(s.mutex);
+        if (num_rays > 0) { if (nodes) reserve_default(s, nodes, num_rays); else reserve_wide(s, num_rays); }
+        HIP_CHECK(hipEventRecord(s.timer[0], nullptr));
+        launch(s);
+        HIP_CHECK(hipEventRecord(s.timer[1], nullptr));
     }
-    HIP_CHECK(hipEventRecord(s.timer[0], nullptr));
-    launch(s);
-    HIP_CHECK(hipEventRecord(s.timer[1], nullptr));
     // synchronises; aborts on a stack overflow like the reference's error()
     check_error_flag(s, nullptr);
     float ms = 0.0f;
@@ -1349,30 +1295,30 @@ uint64_t rodent_hip_get_kernel_time(void) { return g_kernel_ns.load(std::memory_
 
 void amdgpu_intersect_single_ray1_bvh2_tri1(int32_t dev, const Node2* nodes, const Tri1* tris, const Ray1* rays, Hit1* hits,
     int32_t num_rays) {
-    timed_sync_call(dev, num_rays,
+    timed_sync_call(dev, num_rays, nodes,
         [&](DeviceState& s) { launch_bvh2<false>(s, nodes, tris, rays, hits, num_rays, default_variant(2), nullptr); });
 }
 void amdgpu_occluded_single_ray1_bvh2_tri1(int32_t dev, const Node2* nodes, const Tri1* tris, const Ray1* rays, Hit1* hits,
     int32_t num_rays) {
-    timed_sync_call(dev, num_rays,
+    timed_sync_call(dev, num_rays, nodes,
         [&](DeviceState& s) { launch_bvh2<true>(s, nodes, tris, rays, hits, num_rays, default_variant(2), nullptr); });
 }
 void hip_intersect_single_ray1_bvh4_tri4(int32_t dev, const Node4* nodes, const Tri4* tris, const Ray1* rays, Hit1* hits,
     int32_t num_rays) {
-    timed_sync_call(dev, num_rays,
+    timed_sync_call(dev, num_rays, nullptr,
         [&](DeviceState& s) { launch_wide(4, false, s, nodes, tris, rays, hits, num_rays, default_variant(4), nullptr); });
 }
 void hip_occluded_single_ray1_bvh4_tri4(int32_t dev, const Node4* nodes, const Tri4* tris, const Ray1* rays, Hit1* hits, int32_t num_rays) {
-    timed_sync_call(dev, num_rays,
+    timed_sync_call(dev, num_rays, nullptr,
         [&](DeviceState& s) { launch_wide(4, true, s, nodes, tris, rays, hits, num_rays, default_variant(4), nullptr); });
 }
 void hip_intersect_single_ray1_bvh8_tri4(int32_t dev, const Node8* nodes, const Tri4* tris, const Ray1* rays, Hit1* hits,
     int32_t num_rays) {
-    timed_sync_call(dev, num_rays,
+    timed_sync_call(dev, num_rays, nullptr,
         [&](DeviceState& s) { launch_wide(8, false, s, nodes, tris, rays, hits, num_rays, default_variant(8), nullptr); });
 }
 void hip_occluded_single_ray1_bvh8_tri4(int32_t dev, const Node8* nodes, const Tri4* tris, const Ray1* rays, Hit1* hits, int32_t num_rays) {
-    timed_sync_call(dev, num_rays,
+    timed_sync_call(dev, num_rays, nullptr,
         [&](DeviceState& s) { launch_wide(8, true, s, nodes, tris, rays, hits, num_rays, default_variant(8), nullptr); });
 }
 
@@ -1416,14 +1362,14 @@ void rodent_hip_read_trace(int32_t dev, uint64_t* out) {
     DeviceState& s = device_state(dev);
     HIP_CHECK(hipSetDevice(dev));
     HIP_CHECK(hipDeviceSynchronize());
+    std::lock_guard<std::mutex> launching(s.mutex);
     const size_t bytes = 16384 * 4 * sizeof(uint64_t);
-    if (!s.trace) {
-        HIP_CHECK(hipMalloc(&s.trace, bytes));
-        HIP_CHECK(hipMemset(s.trace, 0, bytes));
-        HIP_CHECK(hipMemcpy(&s.ctl()->trace, &s.trace, sizeof(void*), hipMemcpyHostToDevice));
+    if (!s.trace.ptr) {
+        s.trace.ensure(16384 * 4, 0);
+        HIP_CHECK(hipMemcpy(&s.ctl()->trace, &s.trace.ptr, sizeof(void*), hipMemcpyHostToDevice));
     }
-    if (out) HIP_CHECK(hipMemcpy(out, s.trace, bytes, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemset(s.trace, 0, bytes));
+    if (out) HIP_CHECK(hipMemcpy(out, s.trace.ptr, bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemset(s.trace.ptr, 0, bytes));
 }
 void rodent_hip_read_stats(int32_t dev, uint64_t* out) {
     DeviceState& s = device_state(dev);

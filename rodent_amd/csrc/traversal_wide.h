@@ -344,29 +344,27 @@ __global__ __launch_bounds__(kWave) void k_wide_finish(const char* __restrict__ 
 
 #define WIDE_LAUNCH_ARGS DeviceState& s, const void* nodes, const Tri4* tris, const Ray1* rays, Hit1* hits, int n, hipStream_t stream
 template <bool ANY, int N, int LDS_N, int XCD> void L_wide_single(WIDE_LAUNCH_ARGS) {
-    ensure_deep_list(s, n);
+    s.deep_list.ensure(n);
     hipLaunchKernelGGL((k_wide_single<ANY, N, LDS_N, XCD>), dim3(blocks_for(n)), dim3(kWave), 0, stream, (const char*)nodes, tris, rays,
-        hits, n, s.ctl(), s.deep_list, n >= kGridMinRays ? g_ray_grid : 0);
+        hits, n, s.ctl(), s.deep_list.ptr, n >= kGridMinRays ? g_ray_grid : 0);
     hipLaunchKernelGGL((k_wide_finish<ANY, N>), dim3(kFinishGroups), dim3(kWave), 0, stream, (const char*)nodes, tris, rays, hits, s.ctl(),
-        s.deep_list, s.deep_stack, (int*)nullptr);
+        s.deep_list.ptr, s.deep_stack, (int*)nullptr);
 }
 // "top": the persistent form with the staged top levels for launches that fill the chip (as the BVH2 default: rodent_hip_top_min_rays),
 // the one-chunk kernel below that
 int wide_top_min_rays();
+// what "top" uses (L_wide_top; timed_sync_call before its first event): the deep list and, for the persistent form, the tickets
+void reserve_wide(DeviceState& s, int n) {
+    s.deep_list.ensure(n);
+    if (n >= wide_top_min_rays()) s.tickets.ensure(kCounterInts, 0);
+}
 template <bool ANY, int N, int LDS_N> void L_wide_top(WIDE_LAUNCH_ARGS) {
     if (n < wide_top_min_rays()) { L_wide_single<ANY, N, LDS_N, 32>(s, nodes, tris, rays, hits, n, stream); return; }
-    ensure_deep_list(s, n);
-    if (!s.tickets) {
-        std::lock_guard<std::mutex> lock(g_mutex);
-        if (!s.tickets) {
-            HIP_CHECK(hipMalloc(&s.tickets, sizeof(int) * kMaxPhases * kStripes * kCounterStride));
-            HIP_CHECK(hipMemset(s.tickets, 0, sizeof(int) * kMaxPhases * kStripes * kCounterStride));
-        }
-    }
+    reserve_wide(s, n);
     constexpr int kWaves = 16;
     const int groups = ((s.num_cus + kStripes - 1) / kStripes) * kStripes;   // one workgroup per CU, the same number in every stripe
     hipLaunchKernelGGL((k_wide_top_persist<ANY, N, LDS_N, kWaves>), dim3(groups), dim3(kWave * kWaves), 0, stream, (const char*)nodes,
-        tris, rays, hits, n, s.ctl(), s.deep_list, s.tickets, g_ray_grid);
+        tris, rays, hits, n, s.ctl(), s.deep_list.ptr, s.tickets.ptr, g_ray_grid);
     hipLaunchKernelGGL((k_wide_finish<ANY, N>), dim3(kFinishGroups), dim3(kWave), 0, stream, (const char*)nodes, tris, rays, hits, s.ctl(),
-        s.deep_list, s.deep_stack, s.tickets);
+        s.deep_list.ptr, s.deep_stack, s.tickets.ptr);
 }
