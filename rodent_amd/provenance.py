@@ -12,7 +12,7 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 FILES = {
     "traversal": ["traversal.hip", "traversal_top.h", "traversal_wide.h", "traversal_device.h"],
-    "render": ["render.hip", "shading.h", "traversal_device.h"],
+    "render": ["render.hip", "render_trace.h", "render_shade.h", "render_mega.h", "render_sort.h", "shading.h", "traversal_device.h"],
 }
 
 
