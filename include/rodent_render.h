@@ -231,6 +231,14 @@ void    hip_traverse_primary(int32_t dev, struct PrimaryStream* primary, void* s
  * exclusive end of bin g like mapping_gpu.impala:203-207.  Synchronises the stream (the reference does too). */
 void    hip_sort_primary(int32_t dev, struct PrimaryStream* primary, struct PrimaryStream* other, int32_t* ray_ends, void* stream);
 void    hip_shade(int32_t dev, struct PrimaryStream* primary, struct SecondaryStream* secondary, int32_t num_rays, void* stream);
+/* The shader in the forms the renderer's own loop launches (rodent_hip_render_fused_sort / _fused_compact): thread i shades ray perm[i]
+ * of `from` (perm: DEVICE array of num_rays stream indices, or NULL: ray i), writes its shadow ray at index i of `secondary` and the
+ * ray that goes on to its compacted slot of `to` (another stream than `from`, which is left as it is).  mode 1: slots from the look-back
+ * scan (stable order), 2: one atomic per workgroup (workgroups in order of arrival).  block: rays per workgroup, 256 / 512 / 1024, 0 =
+ * the library's (RODENT_HIP_SHADE_BLOCK).  Rays that missed end here, as in hip_shade.  Returns the new size, also in to->size
+ * (synchronises the stream).  Invalid arguments abort. */
+int32_t hip_shade_compact(int32_t dev, struct PrimaryStream* from, struct PrimaryStream* to, struct SecondaryStream* secondary,
+                          const int32_t* perm, int32_t num_rays, int32_t mode, int32_t block, void* stream);
 void    hip_traverse_secondary(int32_t dev, struct SecondaryStream* secondary, void* stream);
 /* Order-preserving compaction of rays with id >= 0; returns the new size (synchronises the stream). */
 int32_t hip_compact_primary(int32_t dev, struct PrimaryStream* primary, struct PrimaryStream* other, void* stream);

@@ -184,6 +184,63 @@ def render(scene, cam, iter_, spp, max_path_len, width, height, film=None, rows=
     return film, counts.sum(axis=0)
 
 
+# struct OracleVertex / struct OracleShade of render_oracle.c, field for field
+ORACLE_VERTEX = np.dtype([("org", "<f4", (3,)), ("dir", "<f4", (3,)), ("prim", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"),
+                          ("rnd", "<u4"), ("mis", "<f4"), ("contrib", "<f4", (3,)), ("depth", "<i4")])
+ORACLE_SHADE = np.dtype([("emits", "<i4"), ("emitted", "<f4", (3,)), ("shadow", "<i4"), ("s_org", "<f4", (3,)), ("s_dir", "<f4", (3,)),
+                         ("s_color", "<f4", (3,)), ("bounce", "<i4"), ("b_org", "<f4", (3,)), ("b_dir", "<f4", (3,)),
+                         ("contrib", "<f4", (3,)), ("rnd", "<u4"), ("mis", "<f4")])
+
+
+def _settings_struct(cam):
+    return _Settings((C.c_float * 3)(*cam["eye"]), (C.c_float * 3)(*cam["dir"]), (C.c_float * 3)(*cam["up"]),
+                     (C.c_float * 3)(*cam["right"]), float(cam["w"]), float(cam["h"]))
+
+
+def _check_render_abi(l):
+    l.oracle_render_abi_sizes.restype = C.c_uint32
+    l.oracle_render_abi_sizes.argtypes = [C.c_int]
+    assert ORACLE_VERTEX.itemsize == l.oracle_render_abi_sizes(0), (ORACLE_VERTEX.itemsize, l.oracle_render_abi_sizes(0))
+    assert ORACLE_SHADE.itemsize == l.oracle_render_abi_sizes(1), (ORACLE_SHADE.itemsize, l.oracle_render_abi_sizes(1))
+    assert C.sizeof(_Settings) == l.oracle_render_abi_sizes(2)
+
+
+def shade_vertices(scene, vertices, max_path_len):
+    """oracle_shade_vertex over an ORACLE_VERTEX array -> ORACLE_SHADE array (what shading each path vertex produces: emission
+    sample, shadow ray, continuation).  Fields behind a flag that is 0 are zero."""
+    l = lib()
+    _check_render_abi(l)
+    v = np.ascontiguousarray(vertices, ORACLE_VERTEX)
+    prim = v["prim"]
+    if len(v) and (prim.min() < 0 or prim.max() >= scene.num_tris):
+        raise ValueError("shade_vertices: prim outside the scene's triangles")
+    out = np.zeros(len(v), ORACLE_SHADE)
+    s, keep = _scene_struct(scene)
+    l.oracle_shade_vertices.restype = None
+    l.oracle_shade_vertices.argtypes = [C.POINTER(_Scene), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    if len(v):
+        l.oracle_shade_vertices(C.byref(s), _ptr(v), len(v), int(max_path_len), _ptr(out))
+    return out
+
+
+def emit_samples(cam, iter_, width, height, x, y, sample):
+    """oracle_emit_sample for arrays of pixels (x, y) and sample numbers -> (rnd uint32 (n,), dir float32 (n, 3))."""
+    l = lib()
+    _check_render_abi(l)
+    x, y, sample = np.broadcast_arrays(np.asarray(x, "<i4"), np.asarray(y, "<i4"), np.asarray(sample, "<i4"))
+    xy = np.ascontiguousarray(np.stack([x.reshape(-1), y.reshape(-1)], -1), "<i4")
+    sample = np.ascontiguousarray(sample.reshape(-1), "<i4")
+    n = len(sample)
+    rnd = np.zeros(n, "<u4"); d = np.zeros((n, 3), "<f4")
+    st = _settings_struct(cam)
+    l.oracle_emit_samples.restype = None
+    l.oracle_emit_samples.argtypes = [C.POINTER(_Settings), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p]
+    if n:
+        l.oracle_emit_samples(C.byref(st), int(iter_), int(width), int(height), _ptr(xy), _ptr(sample), n, _ptr(rnd), _ptr(d))
+    return rnd, d
+
+
 def tex_lookup(scene, tex, uv):
     """Bilinear / repeat lookup of texture `tex` at uv (n, 2) -> (n, 3) float32."""
     l = lib()

@@ -409,6 +409,27 @@ void oracle_render(const struct Scene* sc, const struct Settings* st, int32_t it
     if (ray_counts) { ray_counts[0] += n_primary; ray_counts[1] += n_shadow; }
 }
 
+/* Batch forms for the per-vertex tests: n vertices -> n results (fields a vertex does not produce are zero), and n samples of
+ * pixels xy[2i], xy[2i+1] -> their seed states and camera directions. */
+void oracle_shade_vertices(const struct Scene* sc, const struct OracleVertex* pv, int32_t n, int32_t max_path_len,
+    struct OracleShade* o) {
+    memset(o, 0, sizeof(struct OracleShade) * (size_t)n);
+    for (int32_t i = 0; i < n; i++) oracle_shade_vertex(sc, pv + i, max_path_len, o + i);
+}
+void oracle_emit_samples(const struct Settings* st, int32_t iter, int32_t width, int32_t height, const int32_t* xy, const int32_t* sample,
+    int32_t n, uint32_t* rnd_out, float* dir3) {
+    for (int32_t i = 0; i < n; i++)
+        oracle_emit_sample(st, iter, width, height, xy[2 * i], xy[2 * i + 1], sample[i], rnd_out + i, dir3 + 3 * i);
+}
+/* sizeof probe for the bindings' structured dtypes: 0 OracleVertex, 1 OracleShade, 2 Settings, 3 Material, 4 Light */
+uint32_t oracle_render_abi_sizes(int which) {
+    switch (which) {
+        case 0: return sizeof(struct OracleVertex); case 1: return sizeof(struct OracleShade); case 2: return sizeof(struct Settings);
+        case 3: return sizeof(struct Material);     case 4: return sizeof(struct Light);
+    }
+    return 0;
+}
+
 /* Single-function probes for property tests */
 void oracle_sincos_2pi(const float* u, float* c, float* s, int32_t n) { for (int32_t i = 0; i < n; i++) sincos_2pi(u[i], &c[i], &s[i]); }
 /* probes for the tests: texture lookup and the per-hit material of a textured scene */

@@ -364,8 +364,9 @@ bool stream_slab(const SecondaryStream& s, StreamSlab& out) {
 // (profiles/r05_shade_block.txt).  RODENT_HIP_SHADE_BLOCK=256|512|1024.
 int shade_block() { static const int v = [] { const char* e = getenv("RODENT_HIP_SHADE_BLOCK");
     const int b = e ? atoi(e) : kShadeBlockDefault; return b == 256 || b == 512 || b == 1024 ? b : kShadeBlockDefault; }(); return v; }
-template <typename... Args> void launch_k_shade(hipStream_t stream, int rays, Args... args) {
-    const int b = shade_block(), blocks = (rays + b - 1) / b;
+// b: threads per workgroup, 256 / 512 / 1024 (the renderer's own launches pass shade_block())
+template <typename... Args> void launch_k_shade(hipStream_t stream, int b, int rays, Args... args) {
+    const int blocks = (rays + b - 1) / b;
     if (b == 256) hipLaunchKernelGGL(k_shade<256>, dim3(blocks), dim3(256), 0, stream, args...);
     else if (b == 512) hipLaunchKernelGGL(k_shade<512>, dim3(blocks), dim3(512), 0, stream, args...);
     else hipLaunchKernelGGL(k_shade<1024>, dim3(blocks), dim3(1024), 0, stream, args...);
@@ -556,8 +557,8 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
             if (r.fused_compact != 2) HIP_CHECK(hipMemsetAsync(r.scan.ptr, 0, sizeof(unsigned) * (size_t)blocks, stream));
             // (d_alive was zeroed by the primary pass's follow-up kernel, k_trace_deep<false>)
         }
-        launch_k_shade(stream, blocks * kBlock, r.scene.dev, from, to, perm, sec, size_ptr, n_value, r.film, inv_spp, r.max_path_len,
-            unsorted,
+        launch_k_shade(stream, shade_block(), blocks * kBlock, r.scene.dev, from, to, perm, sec, size_ptr, n_value, r.film, inv_spp,
+            r.max_path_len, unsorted,
                        fused ? (r.fused_compact == 2 ? kScanAtomic : r.scan.ptr) : (unsigned*)nullptr, d_alive);
     };
     while (id < num_rays || size > 0) {
@@ -1108,12 +1109,36 @@ void hip_shade(int32_t dev, PrimaryStream* primary, SecondaryStream* secondary, 
     RenderDevice& r = open_scene(rdev(dev));
     primary->size = num_rays; secondary->size = num_rays; primary->pad = 0;
     if (num_rays <= 0) return;
-    launch_k_shade((hipStream_t)stream, num_rays, r.scene.dev, *primary, *primary, (const int*)nullptr, *secondary, (const int*)nullptr,
-        num_rays, r.film,
+    launch_k_shade((hipStream_t)stream, shade_block(), num_rays, r.scene.dev, *primary, *primary, (const int*)nullptr, *secondary,
+        (const int*)nullptr, num_rays, r.film,
                    1.0f / (float)r.spp, r.max_path_len,
                        /* a ray that missed ends here instead of indexing the material table with the miss id: */ 1, (unsigned*)nullptr,
                        (int*)nullptr);
     HIP_CHECK(hipGetLastError());
+}
+
+int32_t hip_shade_compact(int32_t dev, PrimaryStream* from, PrimaryStream* to, SecondaryStream* secondary, const int32_t* perm,
+    int32_t num_rays, int32_t mode, int32_t block, void* stream) {
+    RenderDevice& r = open_scene(rdev(dev));
+    if ((mode != 1 && mode != 2) || (block != 0 && block != 256 && block != 512 && block != 1024) || from->rays.id == to->rays.id) {
+        fprintf(stderr, "rodent_hip: hip_shade_compact: mode must be 1 or 2, block 0, 256, 512 or 1024, and `to` another stream than "
+        "`from` (mode %d, block %d)\n", mode, block); abort(); }
+    from->size = num_rays; secondary->size = num_rays; from->pad = 0; to->pad = 0; to->size = 0;
+    if (num_rays <= 0) return 0;
+    const int b = block ? block : shade_block(), blocks = (num_rays + b - 1) / b;
+    int* d_alive = r.ctl + 6;                            // as in render_rows: the slot counter / the last block's new size
+    HIP_CHECK(hipMemsetAsync(d_alive, 0, sizeof(int), (hipStream_t)stream));
+    if (mode == 1) {
+        r.growing(r.scan, blocks).ensure(blocks);
+        HIP_CHECK(hipMemsetAsync(r.scan.ptr, 0, sizeof(unsigned) * (size_t)blocks, (hipStream_t)stream));
+    }
+    launch_k_shade((hipStream_t)stream, b, num_rays, r.scene.dev, *from, *to, (const int*)perm, *secondary, (const int*)nullptr, num_rays,
+        r.film, 1.0f / (float)r.spp, r.max_path_len, 1, mode == 2 ? kScanAtomic : r.scan.ptr, d_alive);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(r.host_pinned + 8, d_alive, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    to->size = r.host_pinned[8];
+    return to->size;
 }
 
 void hip_traverse_secondary(int32_t dev, SecondaryStream* secondary, void* stream) {
