@@ -184,6 +184,53 @@ int32_t rodent_hip_build_bvh2_tri1_split_sync(int32_t dev, const float* vertices
                                               const struct RodentSplitOptions* split, struct Node2* nodes, struct Tri1* tris,
                                               int32_t* info);
 
+/* ---- refit: new boxes and Tri1 records for an existing hierarchy whose vertices moved ------------------------------------------------
+ *
+ * The topology stays: the child, pad and w words (pad, geom_id, prim_id with its end-of-leaf bit) are read and never written; only the
+ * 12 bounds of a Node2 and v0 / e1 / e2 of a Tri1 are.  No sort, no hierarchy search, no emission: three launches.  The hierarchy may
+ * come from any of the builders above or from a host builder (any BVH2 / Tri1 of rodent_traversal.h whose records name their
+ * triangles by prim_id & 0x7FFFFFFF); builder scratch is not looked at.  The result is a pure function of (nodes, tris, vertices,
+ * indices), byte for byte (fp32, exact min / max, which do not depend on the order they are taken in); tests/refit_model.py restates it.
+ *
+ * Tri1 record p, t = prim_id & 0x7FFFFFFF: the corners are read as the builders read them (an index outside [0, num_vertices) reads
+ *   as the origin and raises RODENT_BUILD_BAD_INDEX, a non-finite coordinate raises RODENT_BUILD_NON_FINITE); v0, e1 = v0 - v1,
+ *   e2 = v2 - v0 by the builders' own statements.  t >= num_tris raises RODENT_BUILD_BAD_TOPOLOGY: the record stays as it is and its
+ *   box is empty.  The box of a record: per axis the min and max of c + 0 over the three corners.
+ * Child slot k of node i: child == 0: the 6 bounds stay as stored.  child < 0: the union of the boxes of records ~child, ~child + 1, ...
+ *   up to and including the first with the end-of-leaf bit; a walk that reaches num_bvh_tris without one raises the flag and leaves the
+ *   slot as stored.  child > 0: the union of the two boxes of node child - 1 (min of the lows, max of the highs; an empty slot's
+ *   (+inf, -inf) drops out by itself).
+ * Malformed trees: a child id > num_nodes, the root as a child (id 1), a leaf start >= num_bvh_tris and a node named by two slots (the
+ *   second one found) raise RODENT_BUILD_BAD_TOPOLOGY; such a slot stays as stored, and a node with such an inner slot, and every node
+ *   above it, is not completed: info[0] < num_nodes.  Nothing is read out of bounds and every walk is bounded (a leaf by num_bvh_tris;
+ *   a node is completed at most once, so the climb by num_nodes).
+ * info: [0] nodes completed (num_nodes for a sound tree) [1] Tri1 records rewritten [2] flags [3] 0.
+ *
+ * Identity: a hierarchy written by rodent_hip_build_bvh2_tri1 or _opt, refitted with the vertices it was built from, keeps its bytes:
+ *   those builders' boxes are exact unions of the same triangle boxes.
+ * Split trees: rodent_hip_build_bvh2_tri1_split stores CLIPPED reference boxes; after a refit every reference carries its whole
+ *   triangle's box, which contains the clipped one: correct and conservative, but looser, so a split tree refitted with its own vertices
+ *   is not byte-identical, and every refitted box contains the box it replaces. */
+#define RODENT_BUILD_BAD_TOPOLOGY      4    /* info[2], refit: a child id out of range, a leaf without an end bit, a prim_id outside the
+                                               index array, a node claimed by two parents */
+#define RODENT_BUILD_ERR_NUM_NODES   -11    /* num_nodes < 1 or num_bvh_tris < 1 */
+
+/* Bytes of device scratch rodent_hip_refit_bvh2_tri1 needs (-1 when num_nodes < 1 or num_bvh_tris < 1). */
+int64_t rodent_hip_refit_scratch_bytes(int32_t num_nodes, int32_t num_bvh_tris);
+
+/* Refits nodes[num_nodes] / tris[num_bvh_tris] in place from vertices (num_vertices x 4 floats) and indices (num_tris x 4 ints).  All
+ * pointers are DEVICE pointers; scratch: rodent_hip_refit_scratch_bytes, contents ignored; info_dev: RODENT_BUILD_INFO_WORDS ints,
+ * zeroed at the start of the call.  Asynchronous on `stream` like the builders: nothing is allocated, nothing waits for the device.
+ * The argument checks and return values are the builders'; a failed check enqueues nothing. */
+int32_t rodent_hip_refit_bvh2_tri1(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
+                                   struct Node2* nodes, int32_t num_nodes, struct Tri1* tris, int32_t num_bvh_tris, void* scratch,
+                                   int32_t* info_dev, void* stream);
+
+/* Synchronous form on the null stream with its own scratch; RODENT_BUILD_ERR_INPUT when a flag is raised or info[0] != num_nodes. */
+int32_t rodent_hip_refit_bvh2_tri1_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                        int32_t num_tris, struct Node2* nodes, int32_t num_nodes, struct Tri1* tris,
+                                        int32_t num_bvh_tris, int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

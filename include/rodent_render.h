@@ -87,6 +87,14 @@ void    rodent_hip_scene_create_device_bvh_opt(int32_t dev, const struct RodentS
 struct RodentSplitOptions;
 void    rodent_hip_scene_create_device_bvh_split(int32_t dev, const struct RodentSceneDesc* desc, const struct RodentBuildOptions* opt,
                                                  const struct RodentSplitOptions* split);
+/* The current scene after its geometry moved: new HOST tables with the counts given at creation (vertices, normals: num_vertices x 4
+ * floats; face_normals: num_tris x 4; lights: num_lights); indices, materials, light ids, textures and the hierarchy's topology stay.
+ * Overwrites the device copies in place, refits the hierarchy in place (rodent_build.h: rodent_hip_refit_bvh2_tri1; the pointers of
+ * rodent_hip_scene_bvh stay valid) and rebuilds what the scene derives from positions or bounds (the LDS top images, the gathered
+ * shading records) in their existing allocations; the rules that depend on node counts stay as they are.  Synchronous: waits for the
+ * device before and after.  A flag raised by the refit aborts with a message, as a flagged device build does. */
+void    rodent_hip_scene_refit(int32_t dev, const float* vertices, const float* normals, const float* face_normals,
+                               const struct RodentLight* lights);
 /* The current scene's hierarchy on device `dev`: DEVICE pointers (owned by the scene) and counts -- for tests and tools. */
 void    rodent_hip_scene_bvh(int32_t dev, const struct Node2** nodes, const struct Tri1** tris, int32_t* num_nodes, int32_t* num_tris);
 void    rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len);   /* defaults 4 / 64 (converter.cpp:1007-1012) */

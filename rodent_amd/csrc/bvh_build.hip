@@ -28,6 +28,8 @@
 //   k_emit_opt_nodes / k_emit_opt_tris   Node2 in depth-first pre-order, Tri1 in left-to-right leaf order (O(depth) walks)
 // Split, n' is known on the device only: the tree and tail stages get grids sized for max_refs and read n' (`nref`) from info[4];
 // without `nref` the host sizes them for the n triangles.
+// Refit (section 11, rodent_hip_refit_bvh2_tri1): k_refit_links, k_refit_tris, k_refit_climb rewrite the boxes and Tri1 records of an
+// existing hierarchy in place from moved vertices; the topology stays.  CPU model: tests/refit_model.py.
 // Every value is a function of the inputs alone: min / max are exact and do not depend on the order they are taken in, the sort is
 // stable, and arrival order decides only WHICH thread computes a node, never what it computes.
 #include <hip/hip_runtime.h>
@@ -122,6 +124,25 @@ __device__ __forceinline__ int load_triangle(const float4* __restrict__ vertices
     *geom = ix.w;
     if (info && flags) atomicOr(&info[kInfoFlags], flags);
     return flags;
+}
+
+// The geometry of a Tri1 record: v0, e1 = v0 - v1, e2 = v2 - v0 (k_leaves, k_emit_opt_tris and the refit write these very values).
+struct TriGeometry { float3 v0, e1, e2; };
+__device__ __forceinline__ TriGeometry tri1_geometry(const float3 v[3]) {
+    TriGeometry g;
+    g.v0 = v[0];
+    g.e1 = make_float3(v[0].x - v[1].x, v[0].y - v[1].y, v[0].z - v[1].z);
+    g.e2 = make_float3(v[2].x - v[0].x, v[2].y - v[0].y, v[2].z - v[0].z);
+    return g;
+}
+
+// The box of a triangle's corners taken as x + 0: lo_x hi_x lo_y hi_y lo_z hi_z.
+__device__ __forceinline__ void triangle_box(const float3 v[3], float* box) {
+    const float c[3][3] = {{v[0].x, v[1].x, v[2].x}, {v[0].y, v[1].y, v[2].y}, {v[0].z, v[1].z, v[2].z}};
+    for (int a = 0; a < 3; a++) {
+        box[2 * a] = fminf(fminf(canon(c[a][0]), canon(c[a][1])), canon(c[a][2]));
+        box[2 * a + 1] = fmaxf(fmaxf(canon(c[a][0]), canon(c[a][1])), canon(c[a][2]));
+    }
 }
 
 // ---- 1. centroids and their bounds ----------------------------------------------------------------------------------------------
@@ -283,19 +304,16 @@ __global__ __launch_bounds__(kBlock) void k_leaves(const float4* __restrict__ ve
     const int r = (int)order[p], t = reftri ? reftri[r] : r;      // the split entry sorts references: triangle and box through them
     float3 v[3]; int geom;
     load_triangle(vertices, nv, indices, t, v, &geom, nullptr);
+    const TriGeometry g = tri1_geometry(v);
     float4* out = reinterpret_cast<float4*>(tris + p);
-    out[0] = make_float4(v[0].x, v[0].y, v[0].z, 0.0f);
-    out[1] = make_float4(v[0].x - v[1].x, v[0].y - v[1].y, v[0].z - v[1].z, __int_as_float(geom));
-    out[2] = make_float4(v[2].x - v[0].x, v[2].y - v[0].y, v[2].z - v[0].z, __int_as_float(t));
+    out[0] = make_float4(g.v0.x, g.v0.y, g.v0.z, 0.0f);
+    out[1] = make_float4(g.e1.x, g.e1.y, g.e1.z, __int_as_float(geom));
+    out[2] = make_float4(g.e2.x, g.e2.y, g.e2.z, __int_as_float(t));
     if (refbox) {
         for (int k = 0; k < 6; k++) leafbox[6 * (size_t)p + k] = refbox[6 * (size_t)r + k];
         return;
     }
-    const float c[3][3] = {{v[0].x, v[1].x, v[2].x}, {v[0].y, v[1].y, v[2].y}, {v[0].z, v[1].z, v[2].z}};
-    for (int a = 0; a < 3; a++) {
-        leafbox[6 * (size_t)p + 2 * a] = fminf(fminf(canon(c[a][0]), canon(c[a][1])), canon(c[a][2]));
-        leafbox[6 * (size_t)p + 2 * a + 1] = fmaxf(fmaxf(canon(c[a][0]), canon(c[a][1])), canon(c[a][2]));
-    }
+    triangle_box(v, leafbox + 6 * (size_t)p);
 }
 
 // ---- 5. Karras hierarchy ----------------------------------------------------------------------------------------------------
@@ -792,10 +810,11 @@ __global__ __launch_bounds__(kBlock) void k_emit_opt_tris(Opt o, const float4* _
     const int t = reftri ? reftri[order[p]] : (int)order[p];
     float3 v[3]; int geom;
     load_triangle(vertices, nv, indices, t, v, &geom, nullptr);
+    const TriGeometry g = tri1_geometry(v);
     float4* out = reinterpret_cast<float4*>(tris + off);
-    out[0] = make_float4(v[0].x, v[0].y, v[0].z, 0.0f);
-    out[1] = make_float4(v[0].x - v[1].x, v[0].y - v[1].y, v[0].z - v[1].z, __int_as_float(geom));
-    out[2] = make_float4(v[2].x - v[0].x, v[2].y - v[0].y, v[2].z - v[0].z, __int_as_float((int)((uint32_t)t | (last ? kLastInLeaf : 0u))));
+    out[0] = make_float4(g.v0.x, g.v0.y, g.v0.z, 0.0f);
+    out[1] = make_float4(g.e1.x, g.e1.y, g.e1.z, __int_as_float(geom));
+    out[2] = make_float4(g.e2.x, g.e2.y, g.e2.z, __int_as_float((int)((uint32_t)t | (last ? kLastInLeaf : 0u))));
 }
 
 // ---- 9. triangle pre-splitting (Karras & Aila 2013, section 5; the rules in include/rodent_build.h) -----------------------------
@@ -1136,6 +1155,136 @@ __global__ __launch_bounds__(kBlock) void k_refs(const float4* __restrict__ vert
     block_bounds(lo, hi, kpartial + 6 * blockIdx.x);
 }
 
+// ---- 11. refit: the boxes and Tri1 records of an existing hierarchy from moved vertices (rules: include/rodent_build.h) --------------
+// The topology (child, pad and w words) is read and never written.  k_refit_links gives every inner child its parent slot, k_refit_tris
+// rewrites the records and leaves their boxes in scratch, k_refit_climb fills the boxes bottom-up.  A node is complete after
+// 1 + (children with id > 0) arrivals at its counter: its own thread's, once its leaf slots are filled, and one per inner child.  The
+// last arriver unions the node's 12 bounds into its slot of the parent and arrives there; nobody waits for anybody, and since every
+// value of a counter is returned once, a node is completed at most once: a malformed tree (a cycle, a child id out of range, a child
+// claimed twice) leaves nodes incomplete, never a thread looping or a read out of bounds.
+enum { kInfoRefitNodes = 0, kInfoRefitTris = 1 };
+
+struct RefitScratch {
+    int* parent;                  // per node: 2 * parent + slot, -1 = none (the root)
+    uint32_t* arrivals;           // per node
+    float* tribox;                // per Tri1 record: the box of its triangle
+    size_t bytes;
+};
+
+RefitScratch carve_refit(char* base, int num_nodes, int num_bvh_tris) {
+    RefitScratch s{};
+    size_t off = 0;
+    const auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~size_t(255); return p; };
+    s.parent = (int*)take(4 * (size_t)num_nodes);
+    s.arrivals = (uint32_t*)take(4 * (size_t)num_nodes);
+    s.tribox = (float*)take(4 * 6 * (size_t)num_bvh_tris);
+    s.bytes = off;
+    return s;
+}
+
+// Sum of `v` over the wave (every lane takes part), in every lane.
+__device__ __forceinline__ int wave_sum(int v) {
+    for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w);
+    return v;
+}
+
+__global__ __launch_bounds__(kBlock) void k_refit_links(const Node2* __restrict__ nodes, int num_nodes, int num_bvh_tris, int* parent,
+                                                        uint32_t* __restrict__ arrivals, int* info) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= num_nodes) return;
+    arrivals[i] = 0u;
+    int flags = 0;
+    for (int k = 0; k < 2; k++) {
+        const int c = nodes[i].child[k];
+        if (c > 0) {
+            // node 0 is the root: nobody's child.  A child that already has a parent slot keeps it.
+            if (c > num_nodes || c == 1 || atomicCAS(&parent[c - 1], -1, 2 * i + k) != -1) flags |= RODENT_BUILD_BAD_TOPOLOGY;
+        } else if (c < 0 && ~c >= num_bvh_tris) {
+            flags |= RODENT_BUILD_BAD_TOPOLOGY;
+        }
+    }
+    if (flags) atomicOr(&info[kInfoFlags], flags);
+}
+
+__global__ __launch_bounds__(kBlock) void k_refit_tris(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices,
+                                                       int num_tris, Tri1* __restrict__ tris, int num_bvh_tris,
+                                                       float* __restrict__ tribox, int* info) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    bool done = false;
+    if (p < num_bvh_tris) {
+        float4* rec = reinterpret_cast<float4*>(tris + p);
+        const float4 w2 = rec[2];
+        const int t = (int)((uint32_t)__float_as_int(w2.w) & ~kLastInLeaf);
+        float box[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+        if (t < num_tris) {
+            float3 v[3]; int geom;
+            load_triangle(vertices, nv, indices, t, v, &geom, info);
+            const TriGeometry g = tri1_geometry(v);
+            rec[0] = make_float4(g.v0.x, g.v0.y, g.v0.z, rec[0].w);
+            rec[1] = make_float4(g.e1.x, g.e1.y, g.e1.z, rec[1].w);
+            rec[2] = make_float4(g.e2.x, g.e2.y, g.e2.z, w2.w);
+            triangle_box(v, box);
+            done = true;
+        } else {
+            atomicOr(&info[kInfoFlags], RODENT_BUILD_BAD_TOPOLOGY);      // the record stays as it is, its box is empty
+        }
+        for (int k = 0; k < 6; k++) tribox[6 * (size_t)p + k] = box[k];
+    }
+    const int count = __syncthreads_count(done);
+    if (threadIdx.x == 0 && count) atomicAdd(&info[kInfoRefitTris], count);
+}
+
+__global__ __launch_bounds__(kBlock) void k_refit_climb(Node2* nodes, int num_nodes, const Tri1* __restrict__ tris, int num_bvh_tris,
+                                                        const float* __restrict__ tribox, const int* __restrict__ parent,
+                                                        uint32_t* arrivals, int* info) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    int node = i < num_nodes ? i : -1;
+    if (node >= 0) {
+        for (int k = 0; k < 2; k++) {
+            const int c = nodes[node].child[k];
+            if (c >= 0 || ~c >= num_bvh_tris) continue;          // empty, inner, or flagged by k_refit_links: the slot stays as stored
+            float b[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+            bool ended = false;
+            for (int p = ~c; p < num_bvh_tris && !ended; p++) {
+                const float* tb = tribox + 6 * (size_t)p;
+                for (int a = 0; a < 3; a++) { b[2 * a] = fminf(b[2 * a], tb[2 * a]); b[2 * a + 1] = fmaxf(b[2 * a + 1], tb[2 * a + 1]); }
+                ended = tris[p].prim_id < 0;
+            }
+            if (ended) for (int j = 0; j < 6; j++) nodes[node].bounds[6 * k + j] = b[j];
+            else atomicOr(&info[kInfoFlags], RODENT_BUILD_BAD_TOPOLOGY);       // a leaf without an end bit
+        }
+    }
+    bool active = node >= 0;
+    int completed = 0;
+    // wave-uniform: the release and its wait cover the stores of every lane before any lane of the wave adds
+    for (int step = 0; step <= num_nodes; step++) {
+        if (__ballot(active) == 0) break;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        bool last = false;
+        if (active) {
+            const uint32_t needed = 1u + (nodes[node].child[0] > 0) + (nodes[node].child[1] > 0);
+            last = __hip_atomic_fetch_add(&arrivals[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == needed - 1u;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        active = false;
+        if (last) {
+            completed++;
+            const int up = parent[node];
+            if (up >= 0) {
+                const float* b = nodes[node].bounds;
+                float u[6];
+                for (int a = 0; a < 3; a++) { u[2 * a] = fminf(b[2 * a], b[6 + 2 * a]); u[2 * a + 1] = fmaxf(b[2 * a + 1], b[7 + 2 * a]); }
+                node = up >> 1;
+                for (int j = 0; j < 6; j++) nodes[node].bounds[6 * (up & 1) + j] = u[j];
+                active = true;
+            }
+        }
+    }
+    completed = wave_sum(completed);
+    if (lane_id() == 0 && completed) atomicAdd(&info[kInfoRefitNodes], completed);
+}
+
 inline int blocks_for(long long items) { return (int)((items + kBlock - 1) / kBlock); }
 
 bool set_device(int32_t dev) {
@@ -1292,6 +1441,23 @@ int32_t launch_build(const float* vertices, int nv, const int32_t* indices, int 
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
 
+// The refit after its argument checks: info words zeroed, parent slots set to -1, then the three kernels of section 11.
+int32_t launch_refit(const float* vertices, int nv, const int32_t* indices, int n, Node2* nodes, int num_nodes, Tri1* tris,
+                     int num_bvh_tris, void* scratch, int32_t* info_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const RefitScratch s = carve_refit(static_cast<char*>(scratch), num_nodes, num_bvh_tris);
+    if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess
+        || hipMemsetAsync(s.parent, 0xFF, 4 * (size_t)num_nodes, stream) != hipSuccess)
+        return RODENT_BUILD_ERR_LAUNCH;
+    hipLaunchKernelGGL(k_refit_links, dim3(blocks_for(num_nodes)), dim3(kBlock), 0, stream, nodes, num_nodes, num_bvh_tris, s.parent,
+                       s.arrivals, info_dev);
+    hipLaunchKernelGGL(k_refit_tris, dim3(blocks_for(num_bvh_tris)), dim3(kBlock), 0, stream, reinterpret_cast<const float4*>(vertices),
+                       nv, reinterpret_cast<const int4*>(indices), n, tris, num_bvh_tris, s.tribox, info_dev);
+    hipLaunchKernelGGL(k_refit_climb, dim3(blocks_for(num_nodes)), dim3(kBlock), 0, stream, nodes, num_nodes, tris, num_bvh_tris,
+                       s.tribox, s.parent, s.arrivals, info_dev);
+    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
 // The sync forms after their own checks: scratch and `words` info words in one allocation, the entry (`build(scratch, info_dev)`) on
 // the null stream, the info words copied to `info`; RODENT_BUILD_ERR_INPUT when the device raised a flag.
 template <class Build>
@@ -1405,6 +1571,37 @@ int32_t rodent_hip_build_bvh2_tri1_split_sync(int32_t dev, const float* vertices
         return rodent_hip_build_bvh2_tri1_split(dev, vertices, num_vertices, indices, num_tris, opt, split, nodes, tris, scratch,
                                                 info_dev, nullptr);
     });
+}
+
+int64_t rodent_hip_refit_scratch_bytes(int32_t num_nodes, int32_t num_bvh_tris) {
+    if (num_nodes < 1 || num_bvh_tris < 1) return -1;
+    return (int64_t)carve_refit(nullptr, num_nodes, num_bvh_tris).bytes;
+}
+
+int32_t rodent_hip_refit_bvh2_tri1(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
+                                   struct Node2* nodes, int32_t num_nodes, struct Tri1* tris, int32_t num_bvh_tris, void* scratch,
+                                   int32_t* info_dev, void* stream) {
+    if (num_tris < 1 || num_tris > kMaxTris) return RODENT_BUILD_ERR_NUM_TRIS;
+    if (num_vertices < 1) return RODENT_BUILD_ERR_NUM_VERTICES;
+    if (num_nodes < 1 || num_bvh_tris < 1) return RODENT_BUILD_ERR_NUM_NODES;
+    if (!vertices || !indices || !nodes || !tris || !scratch || !info_dev) return RODENT_BUILD_ERR_NULL;
+    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
+    return launch_refit(vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_bvh_tris, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_refit_bvh2_tri1_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                        int32_t num_tris, struct Node2* nodes, int32_t num_nodes, struct Tri1* tris,
+                                        int32_t num_bvh_tris, int32_t* info) {
+    const int64_t bytes = rodent_hip_refit_scratch_bytes(num_nodes, num_bvh_tris);
+    if (bytes < 0) return RODENT_BUILD_ERR_NUM_NODES;
+    int32_t words[RODENT_BUILD_INFO_WORDS] = {};
+    int32_t rc = build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, words, [&](void* scratch, int32_t* info_dev) {
+        return rodent_hip_refit_bvh2_tri1(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_bvh_tris, scratch,
+                                          info_dev, nullptr);
+    });
+    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
+    if (rc == RODENT_BUILD_OK && words[kInfoRefitNodes] != num_nodes) rc = RODENT_BUILD_ERR_INPUT;    // a malformed topology
+    return rc;
 }
 
 } // extern "C"

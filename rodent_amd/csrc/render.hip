@@ -133,7 +133,7 @@ __global__ void k_copy_int(const int* src, int* dst) { *dst = *src; }
 // ---------------------------------------------------------------------------------------------
 struct DevScene {
     bool loaded = false;
-    int num_nodes = 0, num_bvh_tris = 0;
+    int num_nodes = 0, num_bvh_tris = 0, num_vertices = 0;
     // k_trace_refill's addressing of nodes and triangles from one base (rodent_hip_scene_create); 0 = not possible for this scene
     unsigned tri_delta = 0;
     SceneDev dev{};
@@ -713,6 +713,40 @@ void rodent_hip_scene_destroy(int32_t dev) {
 
 namespace {
 
+// Top-of-tree image of the stream traversal kernels (record layout: traversal_device.h build_top_image), `capacity` records of 16 words:
+// breadth first from the root; a child that got a slot is a link (kLdsTag + byte offset of its record), the others keep their ids.
+std::vector<int32_t> build_image(const Node2* nodes, int capacity) {
+    std::vector<int32_t> image((size_t)capacity * 16, 0), slots{1};
+    for (size_t k = 0; k < slots.size(); k++) {
+        const Node2& nd = nodes[slots[k] - 1];
+        int32_t* rec = image.data() + 16 * k;
+        memcpy(rec, nd.bounds, 12 * sizeof(float));
+        for (int j = 0; j < 2; j++) {
+            const int32_t c = nd.child[j];
+            rec[12 + j] = c;
+            if (c > 0 && (int)slots.size() < capacity) { rec[12 + j] = kLdsTag + (int32_t)slots.size() * (int32_t)sizeof(Node2);
+                slots.push_back(c); }
+        }
+        rec[14] = slots[k];
+    }
+    return image;
+}
+
+// SceneDev::tri_shade records (12 floats per triangle): the face normal, then the three corners' vertex normals, gathered.
+std::vector<float> tri_shade(const float* face_normals, const float* normals, const int32_t* indices, int32_t num_tris) {
+    std::vector<float> rec(12 * (size_t)num_tris);
+    for (int32_t t = 0; t < num_tris; t++) {
+        float* o = rec.data() + 12 * (size_t)t;
+        const float* fn = face_normals + 4 * (size_t)t;
+        o[0] = fn[0]; o[1] = fn[1]; o[2] = fn[2];
+        for (int k = 0; k < 3; k++) {
+            const float* n = normals + 4 * (size_t)indices[4 * (size_t)t + k];
+            o[3 + 3 * k] = n[0]; o[4 + 3 * k] = n[1]; o[5 + 3 * k] = n[2];
+        }
+    }
+    return rec;
+}
+
 // rodent_hip_scene_create and rodent_hip_scene_create_device_bvh(_opt / _split): build = NULL uploads the caller's hierarchy
 // (desc->nodes / tris), build options build one on the device from the vertices and indices just uploaded (bvh_build.hip; with
 // `split`, over pre-split references) and takes a host copy of it; from there on both are the same code: checks, LDS images, per-scene
@@ -822,42 +856,19 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOption
             || (uint64_t)d->textures[k].offset + (uint64_t)d->textures[k].width * (uint64_t)d->textures[k].height
             > d->num_texels) invalid("texture outside the texel pool");
     s.dev.num_tris = d->num_tris; s.dev.num_materials = d->num_materials; s.dev.num_lights = d->num_lights;
-    // top-of-tree images of the stream traversal kernels (record layout: traversal_device.h build_top_image): breadth first from
-    // the root; a child that got a slot is a link (kLdsTag + byte offset of its record), the others keep their ids
-    const auto build_image = [&](int capacity) {
-        std::vector<int32_t> image((size_t)capacity * 16, 0), slots{1};
-        for (size_t k = 0; k < slots.size(); k++) {
-            const Node2& nd = d->nodes[slots[k] - 1];
-            int32_t* rec = image.data() + 16 * k;
-            memcpy(rec, nd.bounds, 12 * sizeof(float));
-            for (int j = 0; j < 2; j++) {
-                const int32_t c = nd.child[j];
-                rec[12 + j] = c;
-                if (c > 0 && (int)slots.size() < capacity) { rec[12 + j] = kLdsTag + (int32_t)slots.size() * (int32_t)sizeof(Node2);
-                    slots.push_back(c); }
-            }
-            rec[14] = slots[k];
-        }
-        return reinterpret_cast<const int4*>(upload(s, image.data(), image.size()));
-    };
-    s.dev.top_image = build_image(kSceneTopNodes);
-    s.dev.top_image_large = build_image(kPersistTopNodes);
+    // top-of-tree images of the stream traversal kernels (build_image)
+    for (const int capacity : {kSceneTopNodes, kPersistTopNodes}) {
+        const std::vector<int32_t> image = build_image(d->nodes, capacity);
+        (capacity == kSceneTopNodes ? s.dev.top_image : s.dev.top_image_large) =
+            reinterpret_cast<const int4*>(upload(s, image.data(), image.size()));
+    }
     // SceneDev::tri_shade: per triangle face normal + its three vertex normals, gathered (RODENT_HIP_TRI_SHADE=0: not built, the shader
     // goes through indices -> normals)
     {
         static const bool on = [] { const char* e = getenv("RODENT_HIP_TRI_SHADE"); return !e || atoi(e) != 0; }();
         s.dev.tri_shade = nullptr;
         if (on && d->num_tris > 0) {
-            std::vector<float> rec(12 * (size_t)d->num_tris);
-            for (int32_t t = 0; t < d->num_tris; t++) {
-                float* o = rec.data() + 12 * (size_t)t;
-                const float* fn = d->face_normals + 4 * (size_t)t;
-                o[0] = fn[0]; o[1] = fn[1]; o[2] = fn[2];
-                for (int k = 0; k < 3; k++) {
-                    const float* n = d->normals + 4 * (size_t)d->indices[4 * (size_t)t + k];
-                    o[3 + 3 * k] = n[0]; o[4 + 3 * k] = n[1]; o[5 + 3 * k] = n[2];
-                }
-            }
+            const std::vector<float> rec = tri_shade(d->face_normals, d->normals, d->indices, d->num_tris);
             s.dev.tri_shade = reinterpret_cast<const float4*>(upload(s, rec.data(), rec.size()));
         }
         s.dev.tri_tex = nullptr;
@@ -874,6 +885,7 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOption
     }
     s.num_nodes = d->num_nodes;
     s.num_bvh_tris = d->num_bvh_tris;
+    s.num_vertices = d->num_vertices;
     s.loaded = true;
     r.mapping = resolve_mapping(r);
     r.trace_persistent = resolve_trace(r);
@@ -912,6 +924,54 @@ void rodent_hip_scene_create_device_bvh_split(int32_t dev, const RodentSceneDesc
         abort();
     }
     scene_create(dev, d, opt, split);
+}
+
+void rodent_hip_scene_refit(int32_t dev, const float* vertices, const float* normals, const float* face_normals,
+                            const RodentLight* lights) {
+    RenderDevice& r = rdev(dev);
+    DevScene& s = r.scene;
+    if (!s.loaded) { fprintf(stderr, "rodent_hip: no scene loaded on device %d (call rodent_hip_scene_create)\n", dev); abort(); }
+    if (!vertices || !normals || !face_normals || (s.dev.num_lights > 0 && !lights)) {
+        fprintf(stderr, "rodent_hip: rodent_hip_scene_refit: a NULL table\n"); abort(); }
+    HIP_CHECK(hipSetDevice(dev));
+    HIP_CHECK(hipDeviceSynchronize());                   // no frame still reads the tables that are overwritten
+    const size_t nv = (size_t)s.num_vertices, nt = (size_t)s.dev.num_tris;
+    HIP_CHECK(hipMemcpy(const_cast<float*>(s.dev.vertices), vertices, sizeof(float) * 4 * nv, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(const_cast<float*>(s.dev.normals), normals, sizeof(float) * 4 * nv, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(const_cast<float*>(s.dev.face_normals), face_normals, sizeof(float) * 4 * nt, hipMemcpyHostToDevice));
+    if (s.dev.num_lights > 0)
+        HIP_CHECK(hipMemcpy(const_cast<RodentLight*>(s.dev.lights), lights, sizeof(RodentLight) * (size_t)s.dev.num_lights,
+                            hipMemcpyHostToDevice));
+    // the hierarchy, in place: rodent_hip_scene_bvh's pointers stay valid
+    Node2* nodes = const_cast<Node2*>(s.dev.nodes);
+    Tri1* tris = const_cast<Tri1*>(s.dev.tris);
+    const int64_t scratch_bytes = rodent_hip_refit_scratch_bytes(s.num_nodes, s.num_bvh_tris);
+    char* scratch = nullptr;
+    int32_t info[RODENT_BUILD_INFO_WORDS] = {};
+    HIP_CHECK(hipMalloc(&scratch, (size_t)std::max<int64_t>(scratch_bytes, 0) + sizeof(info)));
+    int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + std::max<int64_t>(scratch_bytes, 0));
+    const int32_t rc = rodent_hip_refit_bvh2_tri1(dev, s.dev.vertices, s.num_vertices, s.dev.indices, s.dev.num_tris, nodes, s.num_nodes,
+                                                  tris, s.num_bvh_tris, scratch, info_dev, nullptr);
+    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: device BVH refit refused (%d)\n", rc); abort(); }
+    HIP_CHECK(hipMemcpy(info, info_dev, sizeof(info), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipFree(scratch));
+    if (info[2] || info[0] != s.num_nodes) {
+        fprintf(stderr, "rodent_hip: invalid scene: device BVH refit flagged the mesh or the hierarchy (flags %d, %d of %d nodes)\n",
+                info[2], info[0], s.num_nodes); abort(); }
+    // what scene_create derives from positions or bounds, into its existing allocations: both LDS images and the tri_shade records
+    std::vector<Node2> host_nodes((size_t)s.num_nodes);
+    HIP_CHECK(hipMemcpy(host_nodes.data(), nodes, sizeof(Node2) * host_nodes.size(), hipMemcpyDeviceToHost));
+    for (const int capacity : {kSceneTopNodes, kPersistTopNodes}) {
+        const std::vector<int32_t> image = build_image(host_nodes.data(), capacity);
+        const int4* dst = capacity == kSceneTopNodes ? s.dev.top_image : s.dev.top_image_large;
+        HIP_CHECK(hipMemcpy(const_cast<int4*>(dst), image.data(), sizeof(int32_t) * image.size(), hipMemcpyHostToDevice));
+    }
+    if (s.dev.tri_shade) {
+        std::vector<int32_t> indices(4 * nt);
+        HIP_CHECK(hipMemcpy(indices.data(), s.dev.indices, sizeof(int32_t) * indices.size(), hipMemcpyDeviceToHost));
+        const std::vector<float> rec = tri_shade(face_normals, normals, indices.data(), s.dev.num_tris);
+        HIP_CHECK(hipMemcpy(const_cast<float4*>(s.dev.tri_shade), rec.data(), sizeof(float) * rec.size(), hipMemcpyHostToDevice));
+    }
 }
 
 void rodent_hip_scene_bvh(int32_t dev, const Node2** nodes, const Tri1** tris, int32_t* num_nodes, int32_t* num_tris) {

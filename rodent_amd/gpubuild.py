@@ -4,6 +4,7 @@
     bvh = build_bvh2(vertices, indices, treelet_passes=2)   # + treelet restructuring and an SAH leaf collapse
     bvh = build_bvh2(vertices, indices, treelet_passes=3, split_budget=1.0)   # + triangle pre-splitting (bvh.num_tris references)
     hits = abi.traverse(bvh, rays)
+    refit_bvh2(bvh, moved_vertices, indices)       # the vertices moved: new boxes and Tri1 records in place, the topology stays
 
 The result is a pure function of the inputs, byte for byte.  As a tool:
 
@@ -28,11 +29,13 @@ NODE_COST, TRI_COST = 1.2, 1.0         # RODENT_BUILD_DEFAULT_NODE_COST / _TRI_C
 INFO_WORDS = 4
 SPLIT_INFO_WORDS = 8                   # + [4] Tri1 count (references) [5] triangles split [6] splits allotted but not made [7] 0
 MAX_PIECES, MAX_SPLIT_BUDGET = 64, 4.0
-BAD_INDEX, NON_FINITE = 1, 2
-ERR_SPLIT = -10
+BAD_INDEX, NON_FINITE, BAD_TOPOLOGY = 1, 2, 4
+ERR_SPLIT, ERR_NUM_NODES = -10, -11
 _ERRORS = {-1: "num_tris outside [1, 2^25]", -2: "max_leaf outside [1, 8]", -3: "no vertices", -4: "NULL pointer",
            -5: "no such device", -6: "launch failed", -8: "treelet_passes outside [0, 3]", -9: "node_cost / tri_cost outside (0, 1e6]",
-           ERR_SPLIT: "split budget outside [0, 4] or max_pieces outside [1, 64]"}
+           ERR_SPLIT: "split budget outside [0, 4] or max_pieces outside [1, 64]", ERR_NUM_NODES: "a hierarchy without nodes or triangles"}
+_FLAGS = ((BAD_INDEX, "vertex index outside the vertex array"), (NON_FINITE, "non-finite vertex coordinate"),
+          (BAD_TOPOLOGY, "malformed hierarchy (child id or prim_id out of range, leaf without end bit, node with two parents)"))
 
 
 class BuildError(RuntimeError):
@@ -131,11 +134,56 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
             t.record_stream(stream)
         words = info.cpu().numpy()
     if words[2]:
-        what = [s for bit, s in ((BAD_INDEX, "vertex index outside the vertex array"), (NON_FINITE, "non-finite vertex coordinate"))
-                if words[2] & bit]
+        what = [s for bit, s in _FLAGS if words[2] & bit]
         raise BuildError(f"{entry}: " + ", ".join(what))
     bvh = abi.DeviceBvh.from_tensors(2, nodes, tris, int(words[0]), int(words[4]) if splitting else n, dev)
     bvh.depth, bvh.info, bvh.scratch = int(words[1]), words.copy(), scratch
+    return bvh
+
+
+def refit_bvh2(bvh: abi.DeviceBvh, vertices, indices, stream=None, scratch=None) -> abi.DeviceBvh:
+    """Refits the BVH2 / Tri1 hierarchy `bvh` in place to moved `vertices` (rodent_hip_refit_bvh2_tri1): new boxes and Tri1 records,
+    the same topology.  `indices` is the triangle table the hierarchy's prim ids refer to; arrays and stream as in build_bvh2.  `bvh` may
+    come from build_bvh2 (any options) or from a host builder.  Returns `bvh` itself with `info` replaced ([0] nodes completed, [1]
+    records rewritten, [2] flags).  Raises BuildError on invalid arguments, on the device's flags (an index outside the vertex array, a
+    non-finite coordinate, a malformed hierarchy) and when not every node was completed.
+
+    Refitted with the vertices it was built from, an unsplit build_bvh2 tree keeps its bytes.  A split tree's references get their
+    whole triangles' boxes: correct, but looser than the clipped boxes the builder stored."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
+    if bvh.width != 2:
+        raise ValueError("refit_bvh2: a BVH2 / Tri1 hierarchy is needed")
+    dev = bvh.dev
+    v = _columns4(vertices, torch.float32, dev)
+    ix = _columns4(indices, torch.int32, dev)
+    n, nv = ix.shape[0], v.shape[0]
+    if not 1 <= n <= MAX_TRIS:
+        raise BuildError(f"num_tris = {n}: outside [1, 2^25]")
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    l = abi.lib()
+    entry = "rodent_hip_refit_bvh2_tri1"
+    need = l.rodent_hip_refit_scratch_bytes(bvh.num_nodes, bvh.num_tris)
+    if need < 0:
+        raise BuildError(f"{entry}: {_ERRORS[ERR_NUM_NODES]}")
+    if scratch is None or scratch.numel() * scratch.element_size() < need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{dev}")
+    info = torch.empty(INFO_WORDS, dtype=torch.int32, device=f"cuda:{dev}")
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(stream):
+        rc = l.rodent_hip_refit_bvh2_tri1(dev, v.data_ptr(), nv, ix.data_ptr(), n, bvh.nodes.data_ptr(), bvh.num_nodes, bvh.tris.data_ptr(),
+                                          bvh.num_tris, scratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise BuildError(f"{entry}: {_ERRORS.get(rc, rc)}")
+        for t in (v, ix, scratch, info, bvh.nodes, bvh.tris):
+            t.record_stream(stream)
+        words = info.cpu().numpy()
+    bvh.info, bvh.scratch = words.copy(), scratch
+    if words[2]:
+        raise BuildError(f"{entry}: " + ", ".join(s for bit, s in _FLAGS if words[2] & bit))
+    if words[0] != bvh.num_nodes:
+        raise BuildError(f"{entry}: malformed hierarchy ({words[0]} of {bvh.num_nodes} nodes completed)")
     return bvh
 
 

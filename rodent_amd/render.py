@@ -30,7 +30,7 @@ class SceneDesc(C.Structure):
 
 RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_create_device_bvh_opt",
                   "rodent_hip_scene_create_device_bvh_split",
-    "rodent_hip_scene_bvh", "rodent_hip_scene_destroy",
+    "rodent_hip_scene_bvh", "rodent_hip_scene_refit", "rodent_hip_scene_destroy",
     "rodent_hip_render_config", "rodent_hip_render_mapping",
     "rodent_hip_render_capacity", "rodent_hip_render_sort", "rodent_hip_render_hit_records", "rodent_hip_render_overlap",
     "rodent_hip_render_fused_sort", "rodent_hip_render_fused_compact", "rodent_hip_render_mapping_in_effect", "rodent_hip_render_defaults",
@@ -65,6 +65,7 @@ def lib():
         l.rodent_hip_scene_create_device_bvh_split.restype = None
         l.rodent_hip_scene_bvh.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
         l.rodent_hip_scene_bvh.restype = None
+        l.rodent_hip_scene_refit.argtypes = [i32, vp, vp, vp, vp]; l.rodent_hip_scene_refit.restype = None
         l.rodent_hip_render_config.argtypes = [i32, i32, i32]; l.rodent_hip_render_config.restype = None
         l.rodent_hip_render_mapping.argtypes = [i32, i32]; l.rodent_hip_render_mapping.restype = None
         l.rodent_hip_render_capacity.argtypes = [i32, i32]; l.rodent_hip_render_capacity.restype = None
@@ -137,6 +138,9 @@ class Renderer:
         desc = SceneDesc(*[a.ctypes.data_as(vp) for a in keep], len(scene.vertices), scene.num_tris, len(scene.nodes), len(scene.tris),
                          len(scene.materials), len(scene.lights), *[a.ctypes.data_as(vp) for a in tex], len(scene.textures),
                              len(scene.texels))
+        # what update_geometry() compares a moved scene against: the tables a refit leaves alone
+        self._fixed = {n: np.array(getattr(scene, n), copy=True) for n in ("indices", "materials", "light_ids", "texcoords", "textures")}
+        self._counts = (len(scene.vertices), len(scene.lights), len(scene.texels))
         l.rodent_hip_set_device(dev)
         l.rodent_hip_render_defaults(dev)                    # options of an earlier Renderer in this process do not leak into this one
         if gpu_bvh:
@@ -233,6 +237,19 @@ class Renderer:
             C.cdll.LoadLibrary("libamdhip64.so").hipMemcpy(C.c_void_p(t.data_ptr()), ptr, C.c_size_t(count * dt.itemsize), 3)
             out.append(t.cpu().numpy()[: count * dt.itemsize].view(dt).copy())
         return tuple(out)
+
+    def update_geometry(self, scene):
+        """The scene's vertices moved: `scene` is a Scene with the same index table (and the same materials, light ids and textures)
+        and new vertices, normals, face normals and lights.  Overwrites the device tables, refits the hierarchy in place and rebuilds
+        what depends on positions (rodent_hip_scene_refit); synchronous.  The film is not cleared."""
+        if (len(scene.vertices), len(scene.lights), len(scene.texels)) != self._counts:
+            raise ValueError("update_geometry: the scene's vertex, light or texel count differs from the one the renderer was created with")
+        for n, mine in self._fixed.items():
+            theirs = np.asarray(getattr(scene, n))
+            if theirs.shape != mine.shape or theirs.tobytes() != mine.tobytes():
+                raise ValueError(f"update_geometry: the scene's `{n}` table differs from the one the renderer was created with")
+        tables = [np.ascontiguousarray(getattr(scene, n)) for n in ("vertices", "normals", "face_normals", "lights")]
+        lib().rodent_hip_scene_refit(self.dev, *[a.ctypes.data_as(vp) for a in tables])
 
     def close(self):
         lib().rodent_hip_scene_destroy(self.dev)

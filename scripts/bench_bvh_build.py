@@ -13,9 +13,14 @@ For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> conve
     --max-pieces K, N passes) in the "split F" columns: build ms, split ms (split build - unsplit build with the same passes),
     references, triangles split, leaves holding one triangle twice ("dup").
 
+  * with --refit, beside each build time the device-event time of rodent_hip_refit_bvh2_tri1 on that tree (median of 20 after 3
+    warm-ups; "refit ms"), and after the deformation of the refit tests (tests/refit_model.py deform, seed 1) the SAH cost of the
+    refitted tree against a tree rebuilt from the moved vertices with the same options ("SAH refit" / "rebuilt").
+
     python scripts/bench_bvh_build.py [--scenes atrium gallery crown plant] [--builds 20] [-o profiles/gpu_bvh_build.txt]
     python scripts/bench_bvh_build.py --treelet-passes 3 -o profiles/gpu_bvh_build_opt.txt
     python scripts/bench_bvh_build.py --treelet-passes 3 --split-budget 0.25 1 -o profiles/gpu_bvh_build_split.txt
+    python scripts/bench_bvh_build.py --scenes atrium --treelet-passes 3 --split-budget 1 --refit -o profiles/gpu_bvh_refit.txt
 """
 from __future__ import annotations
 
@@ -71,10 +76,12 @@ def main():
     ap.add_argument("--treelet-passes", type=int, default=0, help="also measure the optimised build with N passes (1 ... 3)")
     ap.add_argument("--split-budget", type=float, nargs="*", default=[], help="also measure pre-split builds with these budgets")
     ap.add_argument("--max-pieces", type=int, default=64)
+    ap.add_argument("--refit", action="store_true", help="also time a refit of every built tree and compare refitted with rebuilt SAH")
     ap.add_argument("-o", "--output", default=str(ROOT / "profiles" / "gpu_bvh_build.txt"))
     a = ap.parse_args()
     from oracle import binding as O
     import lbvh_model as L
+    import refit_model as RM
     build.build_all()
     lines = [f"# scripts/bench_bvh_build.py on {torch.cuda.get_device_name(0)}; builds: median of {a.builds} after 3 warm-ups, "
              "device events; traversal: default BVH2 variant, closest hit, median of 10 launches; steps: oracle, every 16th ray"]
@@ -91,6 +98,9 @@ def main():
                 f"{'rand Mr/s':>9} | {'steps prim':>10} {'rand':>6} | {'SAH':>6}")
     if a.split_budget:
         lines[0] += f"; split: max_pieces {a.max_pieces}, {P} treelet passes, max_leaf 2"
+    if a.refit:
+        lines[0] += "; refit: median of 20 after 3 warm-ups, SAH after tests/refit_model.py deform(seed 1)"
+        hdr += f" ||| {'refit of':>10} {'refit ms':>8} {'build ms':>8} {'SAH refit':>9} {'rebuilt':>7}"
     lines.append(hdr)
     print(hdr, flush=True)
     out_dir = scenes.DATA
@@ -185,6 +195,29 @@ def main():
             row += (f" || {split_ms[B]:>10.3f} {split_ms[B] - base_ms:>8.3f} {refs:>8} {nsplit:>7} {dup:>6} {depth:>5} | "
                     f"{rate['primary', B]:>9.0f} {rate['random', B]:>9.0f} | {steps['primary', B]:>10.1f} {steps['random', B]:>6.1f} | "
                     f"{L.sah_cost(*host[B]):>6.1f}")
+        if a.refit:
+            moved = torch.from_numpy(RM.deform(sc.vertices, sc.indices, seed=1)).cuda()
+            kinds = [("gpu", bvh, build_ms, {})]
+            if P:
+                kinds.append(("opt", opt, opt_ms, {"treelet_passes": P}))
+            kinds += [(f"split {B}", trees[B], split_ms[B], {"treelet_passes": P, "split_budget": B, "max_pieces": a.max_pieces})
+                      for B in a.split_budget]
+            for label, tree, ms, kw in kinds:
+                rscratch = torch.empty(abi.lib().rodent_hip_refit_scratch_bytes(tree.num_nodes, tree.num_tris), dtype=torch.uint8,
+                                       device="cuda")
+
+                def one_refit(verts=v):
+                    rc = abi.lib().rodent_hip_refit_bvh2_tri1(0, verts.data_ptr(), len(sc.vertices), ix.data_ptr(), n,
+                                                              tree.nodes.data_ptr(), tree.num_nodes, tree.tris.data_ptr(), tree.num_tris,
+                                                              rscratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
+                    assert rc == 0
+                refit_ms = event_ms(one_refit, 3, 20)            # with the build's own vertices: the same work, the tree keeps its shape
+                assert info.cpu().numpy().tolist() == [tree.num_nodes, tree.num_tris, 0, 0]
+                gpubuild.refit_bvh2(tree, moved, ix)
+                rebuilt = gpubuild.build_bvh2(moved, ix, 2, **kw)
+                row += (f" ||| {label:>10} {refit_ms:>8.3f} {ms:>8.3f} {L.sah_cost(*gpubuild.download(tree)):>9.1f} "
+                        f"{L.sah_cost(*gpubuild.download(rebuilt)):>7.1f}")
+                del rebuilt, rscratch
         trees.clear()
         lines.append(row)
         print(row, flush=True)
