@@ -53,6 +53,35 @@ def _columns4(a, dtype, dev):
     return t.contiguous()
 
 
+def _mesh(vertices, indices, dev, stream):
+    """What build_bvh2 and refit_bvh2 start with: the GPU check, the (n, 4) device tensors, the num_tris range, the stream default.
+    Returns (v, ix, stream)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
+    v, ix = _columns4(vertices, torch.float32, dev), _columns4(indices, torch.int32, dev)
+    if not 1 <= ix.shape[0] <= MAX_TRIS:
+        raise BuildError(f"num_tris = {ix.shape[0]}: outside [1, 2^25]")
+    return v, ix, torch.cuda.current_stream(dev) if stream is None else stream
+
+
+def _enqueue(entry, dev, stream, info, used, *args):
+    """Calls `entry`(dev, *args, info, stream) on `stream` once it has waited for the caller's current stream (the tensors may come from
+    there), records `used` and `info` on it and returns the info words on the host.  Raises BuildError when the entry refuses."""
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(stream):
+        rc = getattr(abi.lib(), entry)(dev, *args, info.data_ptr(), C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise BuildError(f"{entry}: {_ERRORS.get(rc, rc)}")
+        for t in (*used, info):
+            t.record_stream(stream)
+        return info.cpu().numpy()
+
+
+def _raise_flags(entry, words):
+    if words[2]:
+        raise BuildError(f"{entry}: " + ", ".join(s for bit, s in _FLAGS if words[2] & bit))
+
+
 def options(max_leaf=2, treelet_passes=0, node_cost=NODE_COST, tri_cost=TRI_COST) -> abi.BuildOptions:
     """A checked RodentBuildOptions; raises BuildError on values the library would refuse."""
     if not 1 <= max_leaf <= MAX_LEAF:
@@ -89,18 +118,11 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
     split_budget > 0 or max_pieces given: pre-split the triangles first (rodent_hip_build_bvh2_tri1_split; up to split_budget * n
     extra references, at most max_pieces (default 64) per triangle); bvh.num_tris is then the reference count info[4], and info has
     8 words."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
-    v = _columns4(vertices, torch.float32, dev)
-    ix = _columns4(indices, torch.int32, dev)
+    v, ix, stream = _mesh(vertices, indices, dev, stream)
     n, nv = ix.shape[0], v.shape[0]
-    if not 1 <= n <= MAX_TRIS:
-        raise BuildError(f"num_tris = {n}: outside [1, 2^25]")
     opt = options(max_leaf, treelet_passes, node_cost, tri_cost)
     splitting = bool(split_budget) or max_pieces is not None
     sp = split_options(split_budget, MAX_PIECES if max_pieces is None else max_pieces) if splitting else None
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
     l = abi.lib()
     # the entry and its option arguments, its scratch bytes, the Tri1 records it may write, its info words
     if splitting:
@@ -123,19 +145,9 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
                 or tris.numel() * tris.element_size() < refs * F.TRI1.itemsize):
             raise ValueError("build_bvh2: the buffers of `out` are too small for this mesh")
     info = torch.empty(info_words, dtype=torch.int32, device=cuda)
-    # the caller's tensors may come from another stream: make this one wait for the inputs
-    stream.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(stream):
-        rc = getattr(l, entry)(dev, v.data_ptr(), nv, ix.data_ptr(), n, *args, nodes.data_ptr(), tris.data_ptr(), scratch.data_ptr(),
-                               info.data_ptr(), C.c_void_p(stream.cuda_stream))
-        if rc != 0:
-            raise BuildError(f"{entry}: {_ERRORS.get(rc, rc)}")
-        for t in (v, ix, scratch, info):
-            t.record_stream(stream)
-        words = info.cpu().numpy()
-    if words[2]:
-        what = [s for bit, s in _FLAGS if words[2] & bit]
-        raise BuildError(f"{entry}: " + ", ".join(what))
+    words = _enqueue(entry, dev, stream, info, (v, ix, scratch), v.data_ptr(), nv, ix.data_ptr(), n, *args, nodes.data_ptr(),
+                     tris.data_ptr(), scratch.data_ptr())
+    _raise_flags(entry, words)
     bvh = abi.DeviceBvh.from_tensors(2, nodes, tris, int(words[0]), int(words[4]) if splitting else n, dev)
     bvh.depth, bvh.info, bvh.scratch = int(words[1]), words.copy(), scratch
     return bvh
@@ -155,33 +167,18 @@ def refit_bvh2(bvh: abi.DeviceBvh, vertices, indices, stream=None, scratch=None)
     if bvh.width != 2:
         raise ValueError("refit_bvh2: a BVH2 / Tri1 hierarchy is needed")
     dev = bvh.dev
-    v = _columns4(vertices, torch.float32, dev)
-    ix = _columns4(indices, torch.int32, dev)
-    n, nv = ix.shape[0], v.shape[0]
-    if not 1 <= n <= MAX_TRIS:
-        raise BuildError(f"num_tris = {n}: outside [1, 2^25]")
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
-    l = abi.lib()
+    v, ix, stream = _mesh(vertices, indices, dev, stream)
     entry = "rodent_hip_refit_bvh2_tri1"
-    need = l.rodent_hip_refit_scratch_bytes(bvh.num_nodes, bvh.num_tris)
+    need = abi.lib().rodent_hip_refit_scratch_bytes(bvh.num_nodes, bvh.num_tris)
     if need < 0:
         raise BuildError(f"{entry}: {_ERRORS[ERR_NUM_NODES]}")
     if scratch is None or scratch.numel() * scratch.element_size() < need:
         scratch = torch.empty(need, dtype=torch.uint8, device=f"cuda:{dev}")
     info = torch.empty(INFO_WORDS, dtype=torch.int32, device=f"cuda:{dev}")
-    stream.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(stream):
-        rc = l.rodent_hip_refit_bvh2_tri1(dev, v.data_ptr(), nv, ix.data_ptr(), n, bvh.nodes.data_ptr(), bvh.num_nodes, bvh.tris.data_ptr(),
-                                          bvh.num_tris, scratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
-        if rc != 0:
-            raise BuildError(f"{entry}: {_ERRORS.get(rc, rc)}")
-        for t in (v, ix, scratch, info, bvh.nodes, bvh.tris):
-            t.record_stream(stream)
-        words = info.cpu().numpy()
+    words = _enqueue(entry, dev, stream, info, (v, ix, scratch, bvh.nodes, bvh.tris), v.data_ptr(), v.shape[0], ix.data_ptr(), ix.shape[0],
+                     bvh.nodes.data_ptr(), bvh.num_nodes, bvh.tris.data_ptr(), bvh.num_tris, scratch.data_ptr())
     bvh.info, bvh.scratch = words.copy(), scratch
-    if words[2]:
-        raise BuildError(f"{entry}: " + ", ".join(s for bit, s in _FLAGS if words[2] & bit))
+    _raise_flags(entry, words)
     if words[0] != bvh.num_nodes:
         raise BuildError(f"{entry}: malformed hierarchy ({words[0]} of {bvh.num_nodes} nodes completed)")
     return bvh

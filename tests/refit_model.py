@@ -1,4 +1,4 @@
-"""CPU model of the device refit (rodent_hip_refit_bvh2_tri1, section 11 of rodent_amd/csrc/bvh_build.hip) in numpy.
+"""CPU model of the device refit (rodent_hip_refit_bvh2_tri1, rodent_amd/csrc/build_refit.h) in numpy.
 
 It predicts the refitted bytes: the topology (child, pad and w words) stays, every Tri1 record gets v0, e1 = v0 - v1, e2 = v2 - v0 of
 the moved triangle it names, every leaf slot the union of its records' triangle boxes (corners taken as x + 0), every inner slot the

@@ -73,7 +73,7 @@ def assert_same_bytes(bvh, gb, model):
 @pytest.mark.parametrize("max_leaf", MAX_LEAVES)
 def test_bytes_equal_the_model_cornell_and_soups(gb, cornell_scene, max_leaf):
     cases = [("cornell", cornell_scene.vertices, cornell_scene.indices)]
-    cases += [(f"soup{n}", *soup(n, n + max_leaf)) for n in (1, 2, 3, 63, 64, 65, 1000, 100003)]
+    cases += [(f"soup{n}", *soup(n, n + max_leaf)) for n in (1, 2, 3, 63, 64, 65, 255, 256, 257, 1000, 4096, 4097, 100003)]
     for name, v, ix in cases:
         model = L.build(v, ix, max_leaf)
         bvh = gb.build_bvh2(v, ix, max_leaf)

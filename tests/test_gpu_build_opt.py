@@ -48,7 +48,7 @@ def assert_same_bytes(gb, bvh, model, num_tris, max_leaf):
 @pytest.mark.parametrize("max_leaf", MAX_LEAVES)
 def test_bytes_equal_the_model_cornell_and_soups(gb, cornell_scene, max_leaf, passes):
     cases = [("cornell", cornell_scene.vertices, cornell_scene.indices)]
-    cases += [(f"soup{n}", *soup(n, n + max_leaf)) for n in (1, 2, 3, 8, 63, 64, 65, 1000, 20001)]
+    cases += [(f"soup{n}", *soup(n, n + max_leaf)) for n in (1, 2, 3, 8, 63, 64, 65, 256, 257, 1000, 20001)]
     for name, v, ix in cases:
         bvh = gb.build_bvh2(v, ix, max_leaf, treelet_passes=passes)
         try:

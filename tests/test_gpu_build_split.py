@@ -53,7 +53,7 @@ def assert_same_bytes(gb, bvh, model, num_tris, max_leaf, max_pieces, passes):
 @pytest.mark.parametrize("max_leaf", [1, 2, 8])
 def test_bytes_equal_the_model(gb, cornell_scene, max_leaf, passes):
     cases = [("cornell", cornell_scene.vertices, cornell_scene.indices)]
-    cases += [(f"soup{n}", *soup(n, n + max_leaf)) for n in (1, 2, 3, 65, 1000)]
+    cases += [(f"soup{n}", *soup(n, n + max_leaf)) for n in (1, 2, 3, 65, 256, 257, 1000)]
     cases += [("slivers", *slivers(2000, max_leaf)), ("unmade", *sliver_soup_with_unmade_splits())]
     unmade = 0
     for name, v, ix in cases:

@@ -1,4 +1,4 @@
-"""The device refit (rodent_hip_refit_bvh2_tri1, section 11 of csrc/bvh_build.hip; gpubuild.refit_bvh2) on the GPU.
+"""The device refit (rodent_hip_refit_bvh2_tri1, csrc/build_refit.h; gpubuild.refit_bvh2) on the GPU.
 
 * its nodes, Tri1 records and info words equal tests/refit_model.py's byte for byte after a deformation (Cornell box, seeded soups
   around the block and wave sizes, max_leaf 1 / 2 / 8, LBVH and 3-pass trees, a pre-split tree, a host SBVH tree);
@@ -23,7 +23,7 @@ from test_gpu_build import soup
 
 pytestmark = pytest.mark.gpu
 FILM_RTOL, FILM_ATOL = 1e-5, 1e-6
-SOUPS = (1, 2, 3, 63, 64, 65, 1000, 100003)
+SOUPS = (1, 2, 3, 63, 64, 65, 256, 257, 1000, 100003)
 
 
 @pytest.fixture(scope="module")
