@@ -231,6 +231,58 @@ int32_t rodent_hip_refit_bvh2_tri1_sync(int32_t dev, const float* vertices, int3
                                         int32_t num_tris, struct Node2* nodes, int32_t num_nodes, struct Tri1* tris,
                                         int32_t num_bvh_tris, int32_t* info);
 
+/* ---- refit of the wide layouts: Node4 / Node8 + Tri4 ------------------------------------------------------------------------------------
+ *
+ * The BVH2 refit above for the hierarchies of hip_traverse_bvh4_tri4_async / _bvh8_tri4_async (N = 4 or 8 slots to a node, Tri4 packets
+ * of four lanes).  Any tree of the layout, from any builder; three launches, no builder scratch.  tests/refit_wide_model.py restates it.
+ *
+ * Touched: the topology stays: child, pad, every prim_id and every geom_id are read and never written.  Written: the 6 x N bounds of a
+ *   node, and columns v0, e1, e2, n of the VALID lanes of a Tri4.  Lanes that are not valid keep their stored bytes (the host builder
+ *   leaves them 0).
+ * Valid lanes: lane k of a packet is valid when none of prim_id[0 .. k] equals -1 (the traversal kernels' rule: == -1 ends the packet);
+ *   its triangle is t = prim_id[k] & 0x7FFFFFFF.  A packet ends its leaf when prim_id[3] < 0.
+ * A valid lane, t < num_tris: the corners are read as the builders read them (an index outside [0, num_vertices) reads as the origin
+ *   and raises RODENT_BUILD_BAD_INDEX, a non-finite coordinate raises RODENT_BUILD_NON_FINITE); v0, e1 = v0 - v1, e2 = v2 - v0 by the
+ *   builders' own statements; n = e1 x e2 component by component as the host builder's cross: nx = e1y * e2z - e1z * e2y,
+ *   ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x, each product rounded on its own (no fused multiply-add).  Its box: per axis
+ *   the min and max of c + 0 over the three corners.
+ * A valid lane, t >= num_tris: raises RODENT_BUILD_BAD_TOPOLOGY; the lane stays as stored and its box is empty.
+ * A packet's box: the union of its valid lanes' boxes; (+inf, -inf) when it has none.
+ * Slot k of node i: child == 0: the six bounds stay as stored.  child < 0: the union of the boxes of packets ~child, ~child + 1, ... up to
+ *   and including the first that ends its leaf; a start >= num_packets, and a walk that reaches num_packets without an end, raise the
+ *   flag and leave the slot as stored.  child > 0: the union of all N slot boxes of node child - 1 (an empty slot's (+inf, -inf) drops
+ *   out by itself).
+ * Malformed trees: as for BVH2: a child id > num_nodes, the root as a child (id 1) and a node named by two slots (the second one found)
+ *   raise RODENT_BUILD_BAD_TOPOLOGY; such a slot stays as stored, and a node with such an inner slot, and every node above it, is not
+ *   completed: info[0] < num_nodes.  Nothing is read out of bounds and every walk is bounded (a leaf by num_packets, the climb by
+ *   num_nodes).
+ * info: [0] nodes completed (num_nodes for a sound tree) [1] lanes rewritten [2] flags [3] 0.
+ * Determinism: the result is a pure function of (nodes, packets, vertices, indices), byte for byte.
+ *
+ * Identity: a tree of the host builder refitted with the vertices it was built from keeps its Tri4 bytes; every refitted box contains
+ *   the stored one (the host builder's leaf boxes may be clipped by its spatial splits, and are then tighter than the triangles'). */
+
+/* Bytes of device scratch rodent_hip_refit_bvh4_tri4 (width 4) / _bvh8_tri4 (width 8) needs; -1 for another width and when
+ * num_nodes < 1 or num_packets < 1. */
+int64_t rodent_hip_refit_wide_scratch_bytes(int32_t width, int32_t num_nodes, int32_t num_packets);
+
+/* Refits nodes[num_nodes] / tris[num_packets] in place.  Arguments, checks, return values and asynchrony are those of
+ * rodent_hip_refit_bvh2_tri1 (RODENT_BUILD_ERR_NUM_NODES: num_nodes < 1 or num_packets < 1); a failed check enqueues nothing. */
+int32_t rodent_hip_refit_bvh4_tri4(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
+                                   struct Node4* nodes, int32_t num_nodes, struct Tri4* tris, int32_t num_packets, void* scratch,
+                                   int32_t* info_dev, void* stream);
+int32_t rodent_hip_refit_bvh8_tri4(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
+                                   struct Node8* nodes, int32_t num_nodes, struct Tri4* tris, int32_t num_packets, void* scratch,
+                                   int32_t* info_dev, void* stream);
+
+/* Synchronous forms, as rodent_hip_refit_bvh2_tri1_sync. */
+int32_t rodent_hip_refit_bvh4_tri4_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                        int32_t num_tris, struct Node4* nodes, int32_t num_nodes, struct Tri4* tris,
+                                        int32_t num_packets, int32_t* info);
+int32_t rodent_hip_refit_bvh8_tri4_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                        int32_t num_tris, struct Node8* nodes, int32_t num_nodes, struct Tri4* tris,
+                                        int32_t num_packets, int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

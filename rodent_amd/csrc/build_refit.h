@@ -109,3 +109,129 @@ __global__ __launch_bounds__(kBlock) void k_refit_climb(Node2* nodes, int num_no
     completed = wave_sum(completed);
     if (lane_id() == 0 && completed) atomicAdd(&info[kInfoRefitNodes], completed);
 }
+
+// ---- the same for Node4 / Node8 + Tri4 (rules: include/rodent_build.h, "refit of the wide layouts") ---------------------------------
+// Three launches again: k_refit_wide_links (parent slot N * i + k), k_refit_tri4 (the valid lanes' columns and the packets' boxes),
+// k_refit_wide_climb (leaf slots from the packet boxes, then k_refit_climb's hand-off with N slots to a node).
+template <class Node> constexpr int kArity = sizeof(Node::child) / sizeof(int32_t);
+
+// Children of `nd` with an id > 0: its inner slots, sound or not.
+template <class Node> __device__ __forceinline__ uint32_t inner_slots(const Node& nd) {
+    uint32_t inner = 0;
+    for (int k = 0; k < kArity<Node>; k++) inner += nd.child[k] > 0;
+    return inner;
+}
+
+template <class Node>
+__global__ __launch_bounds__(kBlock) void k_refit_wide_links(const Node* __restrict__ nodes, int num_nodes, int num_packets, int* parent,
+                                                             uint32_t* __restrict__ arrivals, int* info) {
+    constexpr int N = kArity<Node>;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= num_nodes) return;
+    arrivals[i] = 0u;
+    int flags = 0;
+    for (int k = 0; k < N; k++) {
+        const int c = nodes[i].child[k];
+        if (c > 0) {
+            // node 0 is the root: nobody's child.  A child that already has a parent slot keeps it.
+            if (c > num_nodes || c == 1 || atomicCAS(&parent[c - 1], -1, N * i + k) != -1) flags |= RODENT_BUILD_BAD_TOPOLOGY;
+        } else if (c < 0 && ~c >= num_packets) {
+            flags |= RODENT_BUILD_BAD_TOPOLOGY;
+        }
+    }
+    if (flags) atomicOr(&info[kInfoFlags], flags);
+}
+
+// Four adjacent threads to a packet, one to a lane: a row of the packet is one 16-byte piece across them.  They share a wave, so the
+// packet's box is two __shfl_xor steps away; every thread of the block reaches the shuffles.
+__global__ __launch_bounds__(kBlock) void k_refit_tri4(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices,
+                                                       int num_tris, Tri4* __restrict__ tris, int num_packets, float* __restrict__ pbox,
+                                                       int* info) {
+    const int p = blockIdx.x * (kBlock / 4) + (threadIdx.x >> 2), lane = threadIdx.x & 3;
+    float box[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+    bool done = false;
+    if (p < num_packets) {
+        Tri4& q = tris[p];
+        const int4 id = *reinterpret_cast<const int4*>(q.prim_id);
+        // the traversal kernels' rule: the first -1 ends the packet
+        const bool valid = id.x != -1 && (lane < 1 || id.y != -1) && (lane < 2 || id.z != -1) && (lane < 3 || id.w != -1);
+        const int t = (lane == 0 ? id.x : lane == 1 ? id.y : lane == 2 ? id.z : id.w) & 0x7FFFFFFF;
+        if (valid && t < num_tris) {
+            float3 v[3]; int geom;
+            load_triangle(vertices, nv, indices, t, v, &geom, info);
+            const TriGeometry g = tri1_geometry(v);
+            // n = e1 x e2 as host/vec.h's cross: every product rounded on its own, no fused multiply-add
+            const float nx = __fmul_rn(g.e1.y, g.e2.z) - __fmul_rn(g.e1.z, g.e2.y);
+            const float ny = __fmul_rn(g.e1.z, g.e2.x) - __fmul_rn(g.e1.x, g.e2.z);
+            const float nz = __fmul_rn(g.e1.x, g.e2.y) - __fmul_rn(g.e1.y, g.e2.x);
+            q.v0[0][lane] = g.v0.x; q.v0[1][lane] = g.v0.y; q.v0[2][lane] = g.v0.z;
+            q.e1[0][lane] = g.e1.x; q.e1[1][lane] = g.e1.y; q.e1[2][lane] = g.e1.z;
+            q.e2[0][lane] = g.e2.x; q.e2[1][lane] = g.e2.y; q.e2[2][lane] = g.e2.z;
+            q.n[0][lane] = nx; q.n[1][lane] = ny; q.n[2][lane] = nz;
+            triangle_box(v, box);
+            done = true;
+        } else if (valid) {
+            atomicOr(&info[kInfoFlags], RODENT_BUILD_BAD_TOPOLOGY);      // the lane stays as it is, its box is empty
+        }
+    }
+    for (int w = 1; w <= 2; w <<= 1)
+        for (int a = 0; a < 3; a++) {
+            box[2 * a] = fminf(box[2 * a], __shfl_xor(box[2 * a], w));
+            box[2 * a + 1] = fmaxf(box[2 * a + 1], __shfl_xor(box[2 * a + 1], w));
+        }
+    if (p < num_packets && lane == 0)
+        for (int k = 0; k < 6; k++) pbox[6 * (size_t)p + k] = box[k];
+    const int count = __syncthreads_count(done);
+    if (threadIdx.x == 0 && count) atomicAdd(&info[kInfoRefitTris], count);
+}
+
+template <class Node>
+__global__ __launch_bounds__(kBlock) void k_refit_wide_climb(Node* nodes, int num_nodes, const Tri4* __restrict__ tris, int num_packets,
+                                                             const float* __restrict__ pbox, const int* __restrict__ parent,
+                                                             uint32_t* arrivals, int* info) {
+    constexpr int N = kArity<Node>;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    int node = i < num_nodes ? i : -1;
+    if (node >= 0) {
+        for (int k = 0; k < N; k++) {
+            const int c = nodes[node].child[k];
+            if (c >= 0 || ~c >= num_packets) continue;           // empty, inner, or flagged by k_refit_wide_links: the slot stays as stored
+            float b[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+            bool ended = false;
+            for (int p = ~c; p < num_packets && !ended; p++) {
+                unite(b, b, pbox + 6 * (size_t)p);
+                ended = tris[p].prim_id[3] < 0;
+            }
+            if (ended) for (int j = 0; j < 6; j++) nodes[node].bounds[j][k] = b[j];
+            else atomicOr(&info[kInfoFlags], RODENT_BUILD_BAD_TOPOLOGY);       // a leaf without an end
+        }
+    }
+    bool active = node >= 0;
+    int completed = 0;
+    // the wave-uniform form of the hand-off (build_device.h), as in k_refit_climb
+    for (int step = 0; step <= num_nodes; step++) {
+        if (__ballot(active) == 0) break;
+        publish();
+        bool last = false;
+        if (active) last = arrive(&arrivals[node]) == inner_slots(nodes[node]);      // 1 + inner slots arrivals complete it
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        active = false;
+        if (last) {
+            completed++;
+            const int up = parent[node];
+            if (up >= 0) {
+                float u[6];
+                for (int j = 0; j < 6; j++) {                    // rows 0 2 4: the lows, rows 1 3 5: the highs; an empty slot drops out
+                    const float* row = nodes[node].bounds[j];
+                    u[j] = row[0];
+                    for (int k = 1; k < N; k++) u[j] = j & 1 ? fmaxf(u[j], row[k]) : fminf(u[j], row[k]);
+                }
+                node = up / N;
+                for (int j = 0; j < 6; j++) nodes[node].bounds[j][up % N] = u[j];
+                active = true;
+            }
+        }
+    }
+    completed = wave_sum(completed);
+    if (lane_id() == 0 && completed) atomicAdd(&info[kInfoRefitNodes], completed);
+}

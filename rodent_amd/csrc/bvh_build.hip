@@ -1,7 +1,7 @@
 // bvh_build.hip -- BVH builder on the device writing BVH2 / Tri1 in the layout of include/rodent_traversal.h: a linear BVH (Morton
 // codes + Karras 2012 hierarchy), optionally restructured by treelets with an SAH leaf collapse, optionally over pre-split triangles.
 // C ABI: include/rodent_build.h.  CPU models of every stage, byte for byte: tests/lbvh_model.py, tests/trbvh_model.py (treelets),
-// tests/split_model.py (pre-splitting), tests/refit_model.py (refit).
+// tests/split_model.py (pre-splitting), tests/refit_model.py and tests/refit_wide_model.py (refit).
 // The kernels lie in build_device.h (what the stages share), build_lbvh.h, build_treelet.h, build_split.h and build_refit.h.
 // One pipeline (launch_build), all on the caller's stream, nothing allocated, no host synchronisation.  The three entry points only
 // choose its options: rodent_hip_build_bvh2_tri1 the LBVH, _opt treelet_passes (0, or one triangle: the LBVH), _split the split front.
@@ -29,7 +29,8 @@
 // Split, n' is known on the device only: the tree and tail stages get grids sized for max_refs and read n' (`nref`) from info[4];
 // without `nref` the host sizes them for the n triangles.
 // Refit (build_refit.h, rodent_hip_refit_bvh2_tri1): k_refit_links, k_refit_tris, k_refit_climb rewrite the boxes and Tri1 records of an
-// existing hierarchy in place from moved vertices; the topology stays.
+// existing hierarchy in place from moved vertices; the topology stays.  rodent_hip_refit_bvh4_tri4 / _bvh8_tri4 do the same for
+// Node4 / Node8 + Tri4 (k_refit_wide_links, k_refit_tri4, k_refit_wide_climb; CPU model: tests/refit_wide_model.py).
 // Every value is a function of the inputs alone: min / max are exact and do not depend on the order they are taken in, the sort is
 // stable, and arrival order decides only WHICH thread computes a node, never what it computes.
 #include <hip/hip_runtime.h>
@@ -120,7 +121,7 @@ SplitScratch carve_split(char* base, int n, int max_refs) {
 struct RefitScratch {
     int* parent;                  // per node: 2 * parent + slot, -1 = none (the root)
     uint32_t* arrivals;           // per node
-    float* tribox;                // per Tri1 record: the box of its triangle
+    float* tribox;                // per Tri1 record: the box of its triangle; per Tri4 packet: the box of its valid lanes
     size_t bytes;
 };
 
@@ -318,6 +319,45 @@ int32_t launch_refit(const float* vertices, int nv, const int32_t* indices, int 
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
 
+// The same for Node4 / Node8 + Tri4: one launcher for both widths.
+template <class Node>
+int32_t launch_refit_wide(const float* vertices, int nv, const int32_t* indices, int n, Node* nodes, int num_nodes, Tri4* tris,
+                          int num_packets, void* scratch, int32_t* info_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const RefitScratch s = carve_refit(static_cast<char*>(scratch), num_nodes, num_packets);
+    if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess
+        || hipMemsetAsync(s.parent, 0xFF, 4 * (size_t)num_nodes, stream) != hipSuccess)
+        return RODENT_BUILD_ERR_LAUNCH;
+    hipLaunchKernelGGL(k_refit_wide_links<Node>, dim3(blocks_for(num_nodes)), dim3(kBlock), 0, stream, nodes, num_nodes, num_packets,
+                       s.parent, s.arrivals, info_dev);
+    hipLaunchKernelGGL(k_refit_tri4, dim3(blocks_for(4LL * num_packets)), dim3(kBlock), 0, stream,
+                       reinterpret_cast<const float4*>(vertices), nv, reinterpret_cast<const int4*>(indices), n, tris, num_packets,
+                       s.tribox, info_dev);
+    hipLaunchKernelGGL(k_refit_wide_climb<Node>, dim3(blocks_for(num_nodes)), dim3(kBlock), 0, stream, nodes, num_nodes, tris,
+                       num_packets, s.tribox, s.parent, s.arrivals, info_dev);
+    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
+// The argument checks of the refit entries (the builders' own, in their order); `num_leaf_records`: Tri1 records or Tri4 packets.
+int32_t check_refit_args(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
+                         const void* nodes, int32_t num_nodes, const void* tris, int32_t num_leaf_records, const void* scratch,
+                         const int32_t* info_dev) {
+    if (bad_num_tris(num_tris)) return RODENT_BUILD_ERR_NUM_TRIS;
+    if (num_vertices < 1) return RODENT_BUILD_ERR_NUM_VERTICES;
+    if (num_nodes < 1 || num_leaf_records < 1) return RODENT_BUILD_ERR_NUM_NODES;
+    if (!vertices || !indices || !nodes || !tris || !scratch || !info_dev) return RODENT_BUILD_ERR_NULL;
+    return set_device(dev) ? RODENT_BUILD_OK : RODENT_BUILD_ERR_DEVICE;
+}
+
+template <class Node>
+int32_t refit_wide(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris, Node* nodes,
+                   int32_t num_nodes, Tri4* tris, int32_t num_packets, void* scratch, int32_t* info_dev, void* stream) {
+    const int32_t rc = check_refit_args(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_packets, scratch,
+                                        info_dev);
+    if (rc != RODENT_BUILD_OK) return rc;
+    return launch_refit_wide(vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_packets, scratch, info_dev, stream);
+}
+
 // The sync forms after their own checks: scratch and `words` info words in one allocation, the entry (`build(scratch, info_dev)`) on
 // the null stream, the info words copied to `info`; RODENT_BUILD_ERR_INPUT when the device raised a flag.
 template <class Build>
@@ -333,6 +373,17 @@ int32_t build_sync(int32_t dev, int64_t scratch_bytes, int words, int32_t* info,
     (void)hipFree(scratch);
     if (info) std::copy(host, host + words, info);
     if (rc == RODENT_BUILD_OK && host[kInfoFlags]) rc = RODENT_BUILD_ERR_INPUT;
+    return rc;
+}
+
+// The refits' sync forms: build_sync around `refit(scratch, info_dev)`, and RODENT_BUILD_ERR_INPUT too when a node stayed incomplete.
+template <class Refit>
+int32_t refit_sync(int32_t dev, int64_t scratch_bytes, int32_t num_nodes, int32_t* info, Refit refit) {
+    if (scratch_bytes < 0) return RODENT_BUILD_ERR_NUM_NODES;
+    int32_t words[RODENT_BUILD_INFO_WORDS] = {};
+    int32_t rc = build_sync(dev, scratch_bytes, RODENT_BUILD_INFO_WORDS, words, refit);
+    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
+    if (rc == RODENT_BUILD_OK && words[kInfoRefitNodes] != num_nodes) rc = RODENT_BUILD_ERR_INPUT;    // a malformed topology
     return rc;
 }
 
@@ -441,27 +492,55 @@ int64_t rodent_hip_refit_scratch_bytes(int32_t num_nodes, int32_t num_bvh_tris) 
 int32_t rodent_hip_refit_bvh2_tri1(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
                                    struct Node2* nodes, int32_t num_nodes, struct Tri1* tris, int32_t num_bvh_tris, void* scratch,
                                    int32_t* info_dev, void* stream) {
-    if (bad_num_tris(num_tris)) return RODENT_BUILD_ERR_NUM_TRIS;
-    if (num_vertices < 1) return RODENT_BUILD_ERR_NUM_VERTICES;
-    if (num_nodes < 1 || num_bvh_tris < 1) return RODENT_BUILD_ERR_NUM_NODES;
-    if (!vertices || !indices || !nodes || !tris || !scratch || !info_dev) return RODENT_BUILD_ERR_NULL;
-    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
+    const int32_t rc = check_refit_args(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_bvh_tris, scratch,
+                                        info_dev);
+    if (rc != RODENT_BUILD_OK) return rc;
     return launch_refit(vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_bvh_tris, scratch, info_dev, stream);
 }
 
 int32_t rodent_hip_refit_bvh2_tri1_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
                                         int32_t num_tris, struct Node2* nodes, int32_t num_nodes, struct Tri1* tris,
                                         int32_t num_bvh_tris, int32_t* info) {
-    const int64_t bytes = rodent_hip_refit_scratch_bytes(num_nodes, num_bvh_tris);
-    if (bytes < 0) return RODENT_BUILD_ERR_NUM_NODES;
-    int32_t words[RODENT_BUILD_INFO_WORDS] = {};
-    int32_t rc = build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, words, [&](void* scratch, int32_t* info_dev) {
+    return refit_sync(dev, rodent_hip_refit_scratch_bytes(num_nodes, num_bvh_tris), num_nodes, info,
+                      [&](void* scratch, int32_t* info_dev) {
         return rodent_hip_refit_bvh2_tri1(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_bvh_tris, scratch,
                                           info_dev, nullptr);
     });
-    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
-    if (rc == RODENT_BUILD_OK && words[kInfoRefitNodes] != num_nodes) rc = RODENT_BUILD_ERR_INPUT;    // a malformed topology
-    return rc;
+}
+
+int64_t rodent_hip_refit_wide_scratch_bytes(int32_t width, int32_t num_nodes, int32_t num_packets) {
+    if ((width != 4 && width != 8) || num_nodes < 1 || num_packets < 1) return -1;
+    return (int64_t)carve_refit(nullptr, num_nodes, num_packets).bytes;
+}
+
+int32_t rodent_hip_refit_bvh4_tri4(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
+                                   struct Node4* nodes, int32_t num_nodes, struct Tri4* tris, int32_t num_packets, void* scratch,
+                                   int32_t* info_dev, void* stream) {
+    return refit_wide(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_packets, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_refit_bvh8_tri4(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
+                                   struct Node8* nodes, int32_t num_nodes, struct Tri4* tris, int32_t num_packets, void* scratch,
+                                   int32_t* info_dev, void* stream) {
+    return refit_wide(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_packets, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_refit_bvh4_tri4_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                        int32_t num_tris, struct Node4* nodes, int32_t num_nodes, struct Tri4* tris,
+                                        int32_t num_packets, int32_t* info) {
+    return refit_sync(dev, rodent_hip_refit_wide_scratch_bytes(4, num_nodes, num_packets), num_nodes, info,
+                      [&](void* scratch, int32_t* info_dev) {
+        return refit_wide(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_packets, scratch, info_dev, nullptr);
+    });
+}
+
+int32_t rodent_hip_refit_bvh8_tri4_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                        int32_t num_tris, struct Node8* nodes, int32_t num_nodes, struct Tri4* tris,
+                                        int32_t num_packets, int32_t* info) {
+    return refit_sync(dev, rodent_hip_refit_wide_scratch_bytes(8, num_nodes, num_packets), num_nodes, info,
+                      [&](void* scratch, int32_t* info_dev) {
+        return refit_wide(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_packets, scratch, info_dev, nullptr);
+    });
 }
 
 } // extern "C"

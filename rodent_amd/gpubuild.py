@@ -5,6 +5,7 @@
     bvh = build_bvh2(vertices, indices, treelet_passes=3, split_budget=1.0)   # + triangle pre-splitting (bvh.num_tris references)
     hits = abi.traverse(bvh, rays)
     refit_bvh2(bvh, moved_vertices, indices)       # the vertices moved: new boxes and Tri1 records in place, the topology stays
+    refit_wide(wide, moved_vertices, indices)      # the same for a BVH4 / BVH8 + Tri4 DeviceBvh (of the host builder)
 
 The result is a pure function of the inputs, byte for byte.  As a tool:
 
@@ -153,23 +154,10 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
     return bvh
 
 
-def refit_bvh2(bvh: abi.DeviceBvh, vertices, indices, stream=None, scratch=None) -> abi.DeviceBvh:
-    """Refits the BVH2 / Tri1 hierarchy `bvh` in place to moved `vertices` (rodent_hip_refit_bvh2_tri1): new boxes and Tri1 records,
-    the same topology.  `indices` is the triangle table the hierarchy's prim ids refer to; arrays and stream as in build_bvh2.  `bvh` may
-    come from build_bvh2 (any options) or from a host builder.  Returns `bvh` itself with `info` replaced ([0] nodes completed, [1]
-    records rewritten, [2] flags).  Raises BuildError on invalid arguments, on the device's flags (an index outside the vertex array, a
-    non-finite coordinate, a malformed hierarchy) and when not every node was completed.
-
-    Refitted with the vertices it was built from, an unsplit build_bvh2 tree keeps its bytes.  A split tree's references get their
-    whole triangles' boxes: correct, but looser than the clipped boxes the builder stored."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
-    if bvh.width != 2:
-        raise ValueError("refit_bvh2: a BVH2 / Tri1 hierarchy is needed")
+def _refit(entry, need, bvh, vertices, indices, stream, scratch):
+    """refit_bvh2 and refit_wide after their width checks: `entry` on `bvh` with at least `need` bytes of scratch."""
     dev = bvh.dev
     v, ix, stream = _mesh(vertices, indices, dev, stream)
-    entry = "rodent_hip_refit_bvh2_tri1"
-    need = abi.lib().rodent_hip_refit_scratch_bytes(bvh.num_nodes, bvh.num_tris)
     if need < 0:
         raise BuildError(f"{entry}: {_ERRORS[ERR_NUM_NODES]}")
     if scratch is None or scratch.numel() * scratch.element_size() < need:
@@ -184,11 +172,48 @@ def refit_bvh2(bvh: abi.DeviceBvh, vertices, indices, stream=None, scratch=None)
     return bvh
 
 
+def refit_bvh2(bvh: abi.DeviceBvh, vertices, indices, stream=None, scratch=None) -> abi.DeviceBvh:
+    """Refits the BVH2 / Tri1 hierarchy `bvh` in place to moved `vertices` (rodent_hip_refit_bvh2_tri1): new boxes and Tri1 records,
+    the same topology.  `indices` is the triangle table the hierarchy's prim ids refer to; arrays and stream as in build_bvh2.  `bvh` may
+    come from build_bvh2 (any options) or from a host builder.  Returns `bvh` itself with `info` replaced ([0] nodes completed, [1]
+    records rewritten, [2] flags).  Raises BuildError on invalid arguments, on the device's flags (an index outside the vertex array, a
+    non-finite coordinate, a malformed hierarchy) and when not every node was completed.
+
+    Refitted with the vertices it was built from, an unsplit build_bvh2 tree keeps its bytes.  A split tree's references get their
+    whole triangles' boxes: correct, but looser than the clipped boxes the builder stored."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
+    if bvh.width != 2:
+        raise ValueError("refit_bvh2: a BVH2 / Tri1 hierarchy is needed")
+    need = abi.lib().rodent_hip_refit_scratch_bytes(bvh.num_nodes, bvh.num_tris)
+    return _refit("rodent_hip_refit_bvh2_tri1", need, bvh, vertices, indices, stream, scratch)
+
+
+def refit_wide(bvh: abi.DeviceBvh, vertices, indices, stream=None, scratch=None) -> abi.DeviceBvh:
+    """refit_bvh2 for a BVH4 / BVH8 + Tri4 hierarchy (rodent_hip_refit_bvh4_tri4 / _bvh8_tri4; bvh.num_tris counts its Tri4 packets):
+    new slot boxes and new v0 / e1 / e2 / n columns in the valid lanes of every packet, the same topology.  Arguments, result and
+    errors as refit_bvh2; info[1] counts the lanes rewritten."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
+    if bvh.width not in (4, 8):
+        raise ValueError("refit_wide: a BVH4 / BVH8 + Tri4 hierarchy is needed")
+    need = abi.lib().rodent_hip_refit_wide_scratch_bytes(bvh.width, bvh.num_nodes, bvh.num_tris)
+    return _refit(f"rodent_hip_refit_bvh{bvh.width}_tri4", need, bvh, vertices, indices, stream, scratch)
+
+
+def download_wide(bvh: abi.DeviceBvh):
+    """(nodes, tris) host copies of a DeviceBvh of any width: NODE2 / TRI1, NODE4 / TRI4 or NODE8 / TRI4."""
+    node_dt, tri_dt = {2: (F.NODE2, F.TRI1), 4: (F.NODE4, F.TRI4), 8: (F.NODE8, F.TRI4)}[bvh.width]
+    nodes = bvh.nodes.view(torch.uint8)[: bvh.num_nodes * node_dt.itemsize].cpu().numpy().view(node_dt).copy()
+    tris = bvh.tris.view(torch.uint8)[: bvh.num_tris * tri_dt.itemsize].cpu().numpy().view(tri_dt).copy()
+    return nodes, tris
+
+
 def download(bvh: abi.DeviceBvh):
     """(nodes NODE2, tris TRI1) host copies of a BVH2 / Tri1 DeviceBvh."""
-    nodes = bvh.nodes.view(torch.uint8)[: bvh.num_nodes * F.NODE2.itemsize].cpu().numpy().view(F.NODE2).copy()
-    tris = bvh.tris.view(torch.uint8)[: bvh.num_tris * F.TRI1.itemsize].cpu().numpy().view(F.TRI1).copy()
-    return nodes, tris
+    if bvh.width != 2:
+        raise ValueError("download: a BVH2 / Tri1 hierarchy is needed (download_wide takes any width)")
+    return download_wide(bvh)
 
 
 def main(argv=None):

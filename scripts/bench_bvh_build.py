@@ -17,10 +17,16 @@ For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> conve
     warm-ups; "refit ms"), and after the deformation of the refit tests (tests/refit_model.py deform, seed 1) the SAH cost of the
     refitted tree against a tree rebuilt from the moved vertices with the same options ("SAH refit" / "rebuilt").
 
+  * with --refit-wide, nothing of the above: the host builder's BVH4 and BVH8 + Tri4 trees of every scene (bvh_extractor), the
+    device-event time of rodent_hip_refit_bvh4_tri4 / _bvh8_tri4 on them (median of 20 after 3 warm-ups), beside it
+    rodent_hip_refit_bvh2_tri1 on the BVH2 block of the same file and the wall time of bvh_extractor, which parses the OBJ and builds
+    the three layouts side by side on three threads: an upper bound of one layout's host build.
+
     python scripts/bench_bvh_build.py [--scenes atrium gallery crown plant] [--builds 20] [-o profiles/gpu_bvh_build.txt]
     python scripts/bench_bvh_build.py --treelet-passes 3 -o profiles/gpu_bvh_build_opt.txt
     python scripts/bench_bvh_build.py --treelet-passes 3 --split-budget 0.25 1 -o profiles/gpu_bvh_build_split.txt
     python scripts/bench_bvh_build.py --scenes atrium --treelet-passes 3 --split-budget 1 --refit -o profiles/gpu_bvh_refit.txt
+    python scripts/bench_bvh_build.py --scenes atrium gallery --refit-wide -o profiles/gpu_bvh_refit_wide.txt
 """
 from __future__ import annotations
 
@@ -69,6 +75,54 @@ def tree_depth(nodes):
     return depth
 
 
+def refit_wide_table(a):
+    """--refit-wide: the refit of host-built BVH4 / BVH8 + Tri4 trees against the BVH2 refit and the host build."""
+    build.build_all()
+    lines = [f"# scripts/bench_bvh_build.py --refit-wide on {torch.cuda.get_device_name(0)}; refits: median of 20 after 3 warm-ups, device "
+             "events around the enqueued operations, the tree's own vertices; host s: wall time of bvh_extractor (OBJ parse + BVH2, BVH4 "
+             "and BVH8 side by side on three threads)",
+             f"{'scene':>8} {'tris':>9} {'layout':>6} {'nodes':>8} {'leaf recs':>9} {'lanes':>9} | {'refit ms':>8} {'bvh2 ms':>8} "
+             f"{'host s':>7} {'host / refit':>12}"]
+    print("\n".join(lines), flush=True)
+    scenes.DATA.mkdir(parents=True, exist_ok=True)
+    stream = torch.cuda.current_stream()
+    info = torch.empty(4, dtype=torch.int32, device="cuda")
+    for name in a.scenes:
+        obj = scenes.scene_obj(name)
+        stem = name.replace("/", "-")
+        sc = S.convert(obj, scenes.DATA / f"{stem}.rscene")
+        path = scenes.DATA / f"{stem}-refit-wide.bvh"
+        t0 = time.perf_counter()
+        subprocess.run([str(build.BIN_DIR / "bvh_extractor"), "-obj", str(obj), "-o", str(path)], check=True, stdout=subprocess.DEVNULL)
+        host_s = time.perf_counter() - t0
+        v, ix = torch.from_numpy(sc.vertices).cuda(), torch.from_numpy(sc.indices).cuda()
+        ms = {}
+        for width in (2, 4, 8):
+            tree = abi.DeviceBvh.load(path, width)
+            entry = getattr(abi.lib(), "rodent_hip_refit_bvh2_tri1" if width == 2 else f"rodent_hip_refit_bvh{width}_tri4")
+            need = (abi.lib().rodent_hip_refit_scratch_bytes(tree.num_nodes, tree.num_tris) if width == 2 else
+                    abi.lib().rodent_hip_refit_wide_scratch_bytes(width, tree.num_nodes, tree.num_tris))
+            scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
+
+            def one_refit():
+                rc = entry(0, v.data_ptr(), len(sc.vertices), ix.data_ptr(), sc.num_tris, tree.nodes.data_ptr(), tree.num_nodes,
+                           tree.tris.data_ptr(), tree.num_tris, scratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
+                assert rc == 0
+            ms[width] = event_ms(one_refit, 3, 20)
+            words = info.cpu().numpy().tolist()
+            assert words[0] == tree.num_nodes and words[2:] == [0, 0], words
+            if width > 2:
+                row = (f"{name:>8} {sc.num_tris:>9} {'bvh' + str(width):>6} {tree.num_nodes:>8} {tree.num_tris:>9} {words[1]:>9} | "
+                       f"{ms[width]:>8.3f} {ms[2]:>8.3f} {host_s:>7.1f} {host_s * 1e3 / ms[width]:>12.0f}")
+                lines.append(row)
+                print(row, flush=True)
+            del tree, scratch
+        del v, ix
+        torch.cuda.empty_cache()
+    Path(a.output).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.output).write_text("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", nargs="+", default=["atrium", "gallery", "crown", "plant"])
@@ -77,8 +131,12 @@ def main():
     ap.add_argument("--split-budget", type=float, nargs="*", default=[], help="also measure pre-split builds with these budgets")
     ap.add_argument("--max-pieces", type=int, default=64)
     ap.add_argument("--refit", action="store_true", help="also time a refit of every built tree and compare refitted with rebuilt SAH")
+    ap.add_argument("--refit-wide", action="store_true",
+                    help="only time the refit of the host builder's BVH4 / BVH8 + Tri4 trees (beside: the BVH2 refit, the host build)")
     ap.add_argument("-o", "--output", default=str(ROOT / "profiles" / "gpu_bvh_build.txt"))
     a = ap.parse_args()
+    if a.refit_wide:
+        return refit_wide_table(a)
     from oracle import binding as O
     import lbvh_model as L
     import refit_model as RM
