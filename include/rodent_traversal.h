@@ -174,6 +174,15 @@ void        rodent_hip_ray_kind_hint(int32_t enable);
  * their places in `hits` do not change. width: -1 = recognise (default), 0 = never (list order, as until round 4), > 0 = take this image
  * width on trust (experiments; multiples of 8 only, others mean 0). */
 void        rodent_hip_ray_grid(int32_t width);
+/* One-octant chunks of the default BVH2 kernel (RODENT_HIP_OCTANT_LOOPS).  A 64-ray chunk whose rays all have the same three direction
+ * signs, and finite origins, directions and reciprocals, is traced by a copy of the loop compiled for that octant: the slab tests take the
+ * near and the far plane of each axis by the known sign instead of with min / max (the reference's CPU path: intersection.impala:128-132,
+ * mapping_cpu.impala:88-106) -- 12 instructions less per node step.  Decided per chunk from the chunk's own rays: no state between
+ * launches.  Hit records do not change for hierarchies whose real children have lo <= hi on every axis and no NaN bound (what every builder
+ * and refit of this library emits: DESIGN.md 3.1 lists them; INTEGRATION.md 3 states the precondition for hierarchies from elsewhere).
+ * enable: 1 = on (default), 0 = every chunk takes the generic loop; the environment variable RODENT_HIP_OCTANT_LOOPS=0 / 1 sets the
+ * initial value (the A/B handle of a benchmark run that cannot call this function). */
+void        rodent_hip_octant_loops(int32_t enable);
 /* 1 = librodent_hip_lab.so (-DRODENT_HIP_LAB: also the measured-and-lost kernels) */
 int32_t     rodent_hip_is_lab_build(void);
 const char* rodent_hip_variant_name(int32_t bvh_width, int32_t variant);
@@ -184,7 +193,8 @@ const char* rodent_hip_version(void);
 const char* rodent_hip_source_digest(void);
 /* Debug aid: reads and clears the 8 phase counters of the instrumented "stats-*" variants
  * ([0] descent iterations, [1] lanes active in them, [2] leaf iterations, [3] lanes, [4] refills, [5] lanes refilled, [6] outer
- * iterations); from the shipped BVH2 mappings: [2] image width a launch traced 8 x 8 tiles of, [4] launches of the refill kernel by the
+ * iterations); from the shipped BVH2 mappings: [2] image width a launch traced 8 x 8 tiles of, [3] chunks that workgroup
+ * 0 traced with a one-octant loop, [4] launches of the refill kernel by the
  * ray-kind hint, [5] launches whose first wavefront chose the refill loop, [6] launches that ran on a validated LDS image, [7] stack blocks
  * spilled + rays handed to the deep pass. */
 void        rodent_hip_read_stats(int32_t dev, uint64_t* out8);

@@ -38,7 +38,7 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "rodent_hip_check_errors", "rodent_hip_get_kernel_time", "rodent_hip_device_count", "rodent_hip_num_variants",
         "rodent_hip_variant_name",
     "rodent_hip_kernel_name", "rodent_hip_version", "rodent_hip_source_digest", "rodent_hip_is_lab_build", "rodent_hip_phased_min_rays",
-        "rodent_hip_top_min_rays", "rodent_hip_ray_kind_hint", "rodent_hip_ray_grid", "rodent_hip_schedule_history",
+        "rodent_hip_top_min_rays", "rodent_hip_ray_kind_hint", "rodent_hip_ray_grid", "rodent_hip_octant_loops", "rodent_hip_schedule_history",
         "rodent_hip_read_stats", "rodent_hip_read_trace", "rodent_hip_debug_set_perm",
     "rodent_hip_build_scratch_bytes", "rodent_hip_build_bvh2_tri1", "rodent_hip_build_bvh2_tri1_sync",
     "rodent_hip_build_opt_scratch_bytes", "rodent_hip_build_bvh2_tri1_opt", "rodent_hip_build_bvh2_tri1_opt_sync",
@@ -86,6 +86,7 @@ def lib():
         l.rodent_hip_get_kernel_time.restype = C.c_uint64; l.rodent_hip_get_kernel_time.argtypes = []
         l.rodent_hip_ray_kind_hint.restype = None; l.rodent_hip_ray_kind_hint.argtypes = [i32]
         l.rodent_hip_ray_grid.restype = None; l.rodent_hip_ray_grid.argtypes = [i32]
+        l.rodent_hip_octant_loops.restype = None; l.rodent_hip_octant_loops.argtypes = [i32]
         l.rodent_hip_schedule_history.restype = None; l.rodent_hip_schedule_history.argtypes = [i32]
         l.rodent_hip_device_count.restype = i32; l.rodent_hip_device_count.argtypes = []
         l.rodent_hip_num_variants.restype = i32; l.rodent_hip_num_variants.argtypes = [i32]
@@ -258,6 +259,12 @@ def ray_grid(width: int = -1):
     """rodent_hip_ray_grid: -1 = the default BVH2 kernel recognises camera rays in image order and traces them as 8 x 8-pixel tiles
     (default), 0 = never, > 0 = that image width on trust (hit records do not depend on it)."""
     lib().rodent_hip_ray_grid(int(width))
+
+
+def octant_loops(enable: bool = True):
+    """rodent_hip_octant_loops: may the default BVH2 kernel trace a chunk whose rays share their direction signs with the loop compiled for
+    that octant (default: yes; hit records do not depend on it; read_stats()[3] counts workgroup 0's chunks that took such a loop)."""
+    lib().rodent_hip_octant_loops(int(bool(enable)))
 
 
 def check_errors(dev=0, stream=None):

@@ -244,13 +244,16 @@ typedef __attribute__((address_space(3))) float lds_float;
 // to its wave's block of `spill` (the context's buffer; WPG = waves per workgroup) and the ray goes on in its lane (stack_spill /
 // stack_reload, traversal_device.h); 0: the ray is handed to the launch's deep list and traced again from the root by the follow-up pass
 // (finish_launch).
+// OCT (>= 0: k_bvh2_top_auto's one-octant chunks): the signs of the ray's reciprocal direction are known at compile time and the two slab
+// tests take their near / far planes without fminf / fmaxf (slab_canonical<OCT>, traversal_device.h; `splat`: the ray's fma operands, built by
+// the caller in front of its loops); everything else is the same step.
 template <bool ANY, bool PF = false, bool TOP = false, bool LAZY = false, bool FENCE = false, bool SHARED = false, int SPILL = 0,
-    int WPG = 1>
+    int WPG = 1, int OCT = -1>
 __device__ __forceinline__ void bvh2_step(Lane& L, const Bases& base, Hit1* __restrict__ hits, lds_int* sp_limit, Ctl* ctl,
     int* __restrict__ deep_list,
                                           bool prefetch = false, lds_int* pf_row = nullptr, lds_int* image = nullptr,
                                               lds_float* shared_tmax = nullptr,
-                                          int* __restrict__ spill = nullptr) {
+                                          int* __restrict__ spill = nullptr, const RaySplat* splat = nullptr) {
     const bool is_node = L.top > 0;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     typedef int i32x2 __attribute__((ext_vector_type(2)));
@@ -304,8 +307,8 @@ __device__ __forceinline__ void bvh2_step(Lane& L, const Bases& base, Hit1* __re
     }
     if (is_node) {
         float te0, te1;
-        const bool h0 = slab_canonical(L.ray, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, te0) && ch.x != 0;
-        const bool h1 = slab_canonical(L.ray, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, te1) && ch.y != 0;
+        const bool h0 = slab_canonical<OCT>(L.ray, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, te0, splat) && ch.x != 0;
+        const bool h1 = slab_canonical<OCT>(L.ray, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, te1, splat) && ch.y != 0;
         const bool c0first = te0 < te1, both = h0 && h1;
         L.sp[kWave] = c0first ? ch.y : ch.x;
         L.top = both ? (c0first ? ch.x : ch.y) : (h0 ? ch.x : (h1 ? ch.y : popped));
@@ -906,6 +909,9 @@ int mapped_node_ids(const Node2* nodes) {
 // RODENT_HIP_RAY_GRID: -1 (default) = k_bvh2_top_auto recognises camera rays in image order by itself (detect_ray_grid) and traces them as
 // 8 x 8-pixel tiles; 0 = never (rays in list order, as until round 5); > 0 = the image's width, taken on trust (experiments)
 int g_ray_grid = [] { const char* e = getenv("RODENT_HIP_RAY_GRID"); return e ? atoi(e) : -1; }();
+// rodent_hip_octant_loops() / RODENT_HIP_OCTANT_LOOPS: 1 (default) = k_bvh2_top_auto traces a chunk whose rays share the signs of their
+// directions with the loop compiled for that octant (traversal_top.h: chunk_octant); 0 = every chunk takes the generic loop
+int g_octant_loops = [] { const char* e = getenv("RODENT_HIP_OCTANT_LOOPS"); return e ? (atoi(e) ? 1 : 0) : 1; }();
 // rodent_hip_schedule_history()
 int g_schedule_history = [] { const char* e = getenv("RODENT_HIP_SCHEDULE_HISTORY"); return e && atoi(e) ? 1 : 0; }();
 // workgroups (of one wave) of the follow-up kernels in the shipped mappings: a launch's deep rays are restarted 256 x 64 at a time
@@ -1056,7 +1062,7 @@ template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL, int MODE = 0, bo
     }
     hipLaunchKernelGGL((k_bvh2_top_auto<ANY, LDS_N, TOPN, WAVES, REFILL, MODE, FUSED, LAZY>), dim3(groups), dim3(kWave * WAVES), 0, stream,
         nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
-                       s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, report_to, id, g_ray_grid);
+                       s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, report_to, id, g_ray_grid, g_octant_loops);
     if (!FUSED) hipLaunchKernelGGL((k_bvh2_top_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(),
         s.deep_list.ptr, s.deep_stack, s.tickets.ptr, s.top_image.ptr, TOPN);
 }
@@ -1348,6 +1354,7 @@ void rodent_hip_schedule_history(int32_t enable) { g_schedule_history = enable ?
 void rodent_hip_top_min_rays(int32_t rays) { g_top_min_rays = rays < 0 ? kTopMinRays : rays; }
 void rodent_hip_ray_kind_hint(int32_t enable) { g_kind_hint = enable ? 1 : 0; }
 void rodent_hip_ray_grid(int32_t width) { g_ray_grid = width; }
+void rodent_hip_octant_loops(int32_t enable) { g_octant_loops = enable ? 1 : 0; }
 int32_t rodent_hip_is_lab_build(void) {
 #ifdef RODENT_HIP_LAB
     return 1;

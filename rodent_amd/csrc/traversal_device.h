@@ -68,18 +68,59 @@ __device__ __forceinline__ bool slab(const RayX& r, float lox, float hix, float 
 // cannot see across loop iterations that these two already are: it re-canonicalises both in every iteration (two
 // v_max_f32 x, x).  The two operations that touch them are therefore issued as plain v_max_f32 / v_min_f32, which on
 // canonical operands compute exactly fmaxf / fminf.
+//
+// OCT: -1 = any ray (the near and the far plane of an axis are picked with fminf / fmaxf, as above).  0 ... 7 = the caller knows the signs of
+// the ray's reciprocal direction -- bit a set: axis a's is negative -- and that idir, oidir are finite: the planes are then taken straight
+// from the fma pair (intersection.impala:128-132 `ordered_box`, mapping_cpu.impala:88-106 `ray_octant`: the reference's CPU path does the
+// same), six fminf / fmaxf less per box.  A correctly rounded fma is monotone in each operand, so for a box with lo <= hi on the axis and a
+// positive idir fma(idir, lo, oidir) <= fma(idir, hi, oidir): the value fminf would have picked IS the first of the pair (the second for a
+// negative idir), up to the sign of a zero, which no comparison behind it sees.  PRECONDITION: lo <= hi and no NaN bound for
+// every child the caller does not discard by its id.  An inverted box can only turn what the generic form reports as hit into a miss.
+// These forms, and kAnyOctantSplat (the generic form beside them), read the ray's six fma operands from `splat`: the 2-vectors built ONCE
+// for all loops of a kernel (RaySplat).
 __device__ __forceinline__ float canonical(float x) { return __builtin_canonicalizef(x); }
+// {idir, idir} and {oidir, oidir} per axis, as v_pk_fma_f32 takes them, behind an opaque barrier: a kernel that holds several copies of
+// its loop (one per octant) builds the pairs in front of them all; left to the compiler, every copy builds its own from the scalars, which
+// then stay live through the copies in front of it -- VGPRs a loop compiled under a 64-register budget does not have.
+struct RaySplat { f32x2 idx, idy, idz, iox, ioy, ioz; };
+constexpr int kAnyOctant = -1, kAnyOctantSplat = -2;    // OCT: any ray, operands from the RayX / from the caller's RaySplat
+__device__ __forceinline__ RaySplat splat_ray(const RayX& r) {
+    RaySplat s{(f32x2){r.idx, r.idx}, (f32x2){r.idy, r.idy}, (f32x2){r.idz, r.idz}, (f32x2){r.iox, r.iox}, (f32x2){r.ioy, r.ioy},
+        (f32x2){r.ioz, r.ioz}};
+    asm volatile("" : "+v"(s.idx), "+v"(s.idy), "+v"(s.idz), "+v"(s.iox), "+v"(s.ioy), "+v"(s.ioz));
+    return s;
+}
+template <int OCT = -1>
 __device__ __forceinline__ bool slab_canonical(const RayX& r, float lox, float hix, float loy, float hiy, float loz, float hiz,
-    float& tentry) {
-    const f32x2 tx = __builtin_elementwise_fma((f32x2){r.idx, r.idx}, (f32x2){lox, hix}, (f32x2){r.iox, r.iox});
-    const f32x2 ty = __builtin_elementwise_fma((f32x2){r.idy, r.idy}, (f32x2){loy, hiy}, (f32x2){r.ioy, r.ioy});
-    const f32x2 tz = __builtin_elementwise_fma((f32x2){r.idz, r.idz}, (f32x2){loz, hiz}, (f32x2){r.ioz, r.ioz});
-    float nz, fz;
-    asm("v_max_f32 %0, %1, %2" : "=v"(nz) : "v"(fminf(tz.x, tz.y)), "v"(r.tmin));
-    asm("v_min_f32 %0, %1, %2" : "=v"(fz) : "v"(fmaxf(tz.x, tz.y)), "v"(r.tmax));
-    tentry = fmaxf(fmaxf(fminf(tx.x, tx.y), fminf(ty.x, ty.y)), nz);
-    const float texit = fminf(fminf(fmaxf(tx.x, tx.y), fmaxf(ty.x, ty.y)), fz);
-    return tentry <= texit;
+    float& tentry, const RaySplat* splat = nullptr) {
+    if constexpr (OCT < 0) {
+        const bool pairs = OCT == kAnyOctantSplat;
+        const f32x2 tx = pairs ? __builtin_elementwise_fma(splat->idx, (f32x2){lox, hix}, splat->iox)
+            : __builtin_elementwise_fma((f32x2){r.idx, r.idx}, (f32x2){lox, hix}, (f32x2){r.iox, r.iox});
+        const f32x2 ty = pairs ? __builtin_elementwise_fma(splat->idy, (f32x2){loy, hiy}, splat->ioy)
+            : __builtin_elementwise_fma((f32x2){r.idy, r.idy}, (f32x2){loy, hiy}, (f32x2){r.ioy, r.ioy});
+        const f32x2 tz = pairs ? __builtin_elementwise_fma(splat->idz, (f32x2){loz, hiz}, splat->ioz)
+            : __builtin_elementwise_fma((f32x2){r.idz, r.idz}, (f32x2){loz, hiz}, (f32x2){r.ioz, r.ioz});
+        float nz, fz;
+        asm("v_max_f32 %0, %1, %2" : "=v"(nz) : "v"(fminf(tz.x, tz.y)), "v"(r.tmin));
+        asm("v_min_f32 %0, %1, %2" : "=v"(fz) : "v"(fmaxf(tz.x, tz.y)), "v"(r.tmax));
+        tentry = fmaxf(fmaxf(fminf(tx.x, tx.y), fminf(ty.x, ty.y)), nz);
+        const float texit = fminf(fminf(fmaxf(tx.x, tx.y), fmaxf(ty.x, ty.y)), fz);
+        return tentry <= texit;
+    } else {
+        const f32x2 tx = __builtin_elementwise_fma(splat->idx, (f32x2){lox, hix}, splat->iox);
+        const f32x2 ty = __builtin_elementwise_fma(splat->idy, (f32x2){loy, hiy}, splat->ioy);
+        const f32x2 tz = __builtin_elementwise_fma(splat->idz, (f32x2){loz, hiz}, splat->ioz);
+        const float nearx = (OCT & 1) ? tx.y : tx.x, farx = (OCT & 1) ? tx.x : tx.y;
+        const float neary = (OCT & 2) ? ty.y : ty.x, fary = (OCT & 2) ? ty.x : ty.y;
+        const float nearz = (OCT & 4) ? tz.y : tz.x, farz = (OCT & 4) ? tz.x : tz.y;
+        float nz, fz;
+        asm("v_max_f32 %0, %1, %2" : "=v"(nz) : "v"(nearz), "v"(r.tmin));
+        asm("v_min_f32 %0, %1, %2" : "=v"(fz) : "v"(farz), "v"(r.tmax));
+        tentry = fmaxf(fmaxf(nearx, neary), nz);
+        const float texit = fminf(fminf(farx, fary), fz);
+        return tentry <= texit;
+    }
 }
 
 // intersection.impala:164-192, no back-face culling

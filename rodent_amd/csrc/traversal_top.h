@@ -424,6 +424,31 @@ __global__ __launch_bounds__(kWave * WAVES, 32 / WAVES) void k_bvh2_top_refill(c
         spill, host_kinds, launch_id);
 }
 
+// One octant for a whole chunk?  Returns it (bit a: axis a's reciprocal direction is negative) when every lane that holds a ray (ray_id >=
+// 0; the padded lanes' copies do not vote) has the same three sign bits in idir AND finite o, d, idir, oidir -- what slab_canonical<OCT>
+// asks for: a direction of +-inf (idir 0), a NaN anywhere, or a ray on safe_rcp's branch whose oidir overflows send the chunk to the
+// generic loop (-1).  Wave-uniform, from the chunk's own rays; call in uniform control flow.  About 12 v_cmp_class and a ballot per chunk.
+__device__ __forceinline__ int chunk_octant(const Lane& L) {
+    const RayX& r = L.ray;
+    const auto negative = [](float x) { return (int)((unsigned)__float_as_int(x) >> 31); };
+    const int oct = negative(r.idx) | (negative(r.idy) << 1) | (negative(r.idz) << 2);
+    const auto finite3 = [](float x, float y, float z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); };
+    const bool finite = finite3(r.ox, r.oy, r.oz) && finite3(r.dx, r.dy, r.dz) && finite3(r.idx, r.idy, r.idz)
+        && finite3(r.iox, r.ioy, r.ioz);
+    // (lane 0 holds a ray whenever the chunk has one: rays are handed out in lane order)
+    const int first = __builtin_amdgcn_readfirstlane(oct);
+    return __ballot(L.ray_id >= 0 && !(finite && oct == first)) == 0ull ? first : -1;
+}
+// A chunk's step loop (k_bvh2_top_auto), stated once for the generic form and the eight octants.
+template <bool ANY, bool LAZY, int LDS_N, int WAVES, int OCT>
+__device__ __forceinline__ void trace_chunk(Lane& L, const Bases& base, Hit1* __restrict__ hits, lds_int* sp_limit, Ctl* ctl,
+    int* __restrict__ deep_list, lds_int* image, int* __restrict__ spill, const RaySplat* splat) {
+    while (__ballot(L.top != 0)) {
+        if (L.top != 0) bvh2_step<ANY, false, true, LAZY, false, false, LDS_N, WAVES, OCT>(L, base, hits, sp_limit, ctl, deep_list,
+            false, nullptr, image, nullptr, spill, splat);
+    }
+}
+
 // The default from round 4 on: ONE persistent kernel that chooses per wave between the two loop forms above (compaction
 // that switches itself on -- the reference compacts unconditionally, render/mapping_gpu.impala:267-300; Aila's kernel refills
 // unconditionally, tools/bench_aila/kepler_dynamic_fetch.cu:116-127,361-362).  A wave draws 64 consecutive tickets of its stripe
@@ -438,6 +463,12 @@ __global__ __launch_bounds__(kWave * WAVES, 32 / WAVES) void k_bvh2_top_refill(c
 // without one, from the tmax the lane still holds (finish_lane_reg): nearly every camera ray finds a triangle, and the record stored up
 // front was written back to memory before the hit overwrote it (WRITE_SIZE 1.64 x the Hit1 array, profiles/r05_traffic.json).  Round 3's
 // lazy form re-read the ray at the end of every chunk (a dependent load on the critical path: -4 %).
+// One-octant chunks (octant_loops; rodent_hip_octant_loops): the 64 camera rays of an 8 x 8 tile share their three direction signs unless
+// an axis-sign boundary crosses the tile (about 2 % of a 1 Mi-ray image's tiles).  Such a chunk (chunk_octant) is traced by the copy of the
+// step loop compiled for its octant, whose slab tests need no fminf / fmaxf to tell the near plane from the far one (12 VALU instructions
+// less per node step); any other chunk takes the generic loop.  Per chunk, from the chunk's own rays: no state between launches, no
+// probe, the same rays in the same waves.  stats[3]: workgroup 0's chunks that took an octant's loop (read by the tests).  The refill loop
+// keeps the generic step.
 template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL,
     int MODE = 0 /* lab: 1 = whole chunks whatever the rays, 2 = refill whatever the rays */,
     bool FUSED = true /* lab: false = a follow-up kernel finishes the launch */, bool LAZY = false>
@@ -446,7 +477,8 @@ __global__ __launch_bounds__(kWave * WAVES) __attribute__((amdgpu_waves_per_eu(8
                                                                   const Ray1* __restrict__ rays, Hit1* __restrict__ hits, int n,
                                                                   Ctl* ctl, int* __restrict__ deep_list, int4* __restrict__ top_image,
                                                                       int* __restrict__ tickets, int max_id,
-                                                                  int* spill, int* host_kinds, int launch_id, int grid_w) {
+                                                                  int* spill, int* host_kinds, int launch_id, int grid_w,
+                                                                      int octant_loops) {
     constexpr int kStackInts = WAVES * (LDS_N + 1) * kWave, kGroupRays = 32 * kWave;
     static_assert((kStackInts + TOPN * 16) * 4 * (32 / WAVES) <= 160 * 1024, "32 waves per CU must fit their stacks and images in LDS");
     __shared__ __attribute__((aligned(16))) int lds_raw[kStackInts + TOPN * 16];
@@ -490,12 +522,33 @@ __global__ __launch_bounds__(kWave * WAVES) __attribute__((amdgpu_waves_per_eu(8
             if (first_ray >= n) break;
             int r = ray_of(t + lane);
             if (first_ray < tiled_rays) r = tile_ray(first_ray, lane, grid_w);   // (first_ray: the tile's first pixel)
-            Lane L = start_lane<LAZY>(rays, hits, r < n ? r : -1, first_ray, col);
+            // (the lane's column from its window limit, behind window_base's barrier: one VGPR less to carry through the step loops)
+            Lane L = start_lane<LAZY>(rays, hits, r < n ? r : -1, first_ray, window_base<LDS_N>(sp_limit));
             if (L.top != 0) L.top = root;
-            while (__ballot(L.top != 0)) {
-                if (L.top != 0) bvh2_step<ANY, false, true, LAZY, false, false, LDS_N, WAVES>(L, base, hits, sp_limit, ctl, deep_list,
-                    false, nullptr, image, nullptr, spill);
-            }
+            const int oct = octant_loops ? chunk_octant(L) : -1;
+            if (oct >= 0 && lane == 0 && blockIdx.x == 0) atomicAdd(&ctl->stats[3], 1ull);
+            // One loop after the other ON THE SAME L, the octant opaque in between.  Compiled as the arms of a switch the loops are
+            // serialised all the same (they contain divergent branches), and every loop's initial state then stays live through the loops
+            // laid out in front of it: three VGPRs more than the budget holds, the hit record's address reloaded from scratch in every
+            // loop (LAB_NOTES 16).  A loop that is not the chunk's costs one scalar compare.
+            int arm = oct;
+            const RaySplat splat = splat_ray(L.ray);
+            // ... and the lane's hit record behind one opaque pointer, for the same reason: every loop would compute hits + ray_id for itself
+            // and keep the id's sign extension for the next one.  (The step uses the id for nothing else: stacks spill, no deep list.)
+            static_assert(LDS_N > 0, "bvh2_step<SPILL = LDS_N>: the ray id is only the hit record's index");
+            const int ray_id = L.ray_id;
+            Hit1* lane_hit = hits + ray_id;
+            asm volatile("" : "+v"(lane_hit));
+            L.ray_id = 0;
+#define RODENT_TRACE_CHUNK(OCT) if (arm == OCT) trace_chunk<ANY, LAZY, LDS_N, WAVES, OCT>(L, base, lane_hit, sp_limit, ctl, deep_list, image, spill, \
+                &splat); \
+            asm volatile("" : "+s"(arm))
+            RODENT_TRACE_CHUNK(0); RODENT_TRACE_CHUNK(1); RODENT_TRACE_CHUNK(2); RODENT_TRACE_CHUNK(3);
+            RODENT_TRACE_CHUNK(4); RODENT_TRACE_CHUNK(5); RODENT_TRACE_CHUNK(6); RODENT_TRACE_CHUNK(7);
+#undef RODENT_TRACE_CHUNK
+            // the generic loop last, on the same pairs (behind a loop that ran it finds no live lane)
+            trace_chunk<ANY, LAZY, LDS_N, WAVES, kAnyOctantSplat>(L, base, lane_hit, sp_limit, ctl, deep_list, image, spill, &splat);
+            L.ray_id = ray_id;
             if (LAZY) finish_lane_reg(L, rays, hits);
             int t_next = 0;
             if (lane == 0) t_next = atomicAdd(counter, kWave);
