@@ -283,6 +283,68 @@ int32_t rodent_hip_refit_bvh8_tri4_sync(int32_t dev, const float* vertices, int3
                                         int32_t num_tris, struct Node8* nodes, int32_t num_nodes, struct Tri4* tris,
                                         int32_t num_packets, int32_t* info);
 
+/* ---- collapse into the wide layouts: BVH2 / Tri1 -> Node4 / Node8 + Tri4 ----------------------------------------------------------------
+ *
+ * Any BVH2 / Tri1 of rodent_traversal.h (of the builders above or of a host builder) becomes a hierarchy of N = 4 or 8 slots to a node
+ * with Tri4 packets, as hip_traverse_bvh4_tri4_async / _bvh8_tri4_async and the wide refit take it.  No vertices: every word written is
+ * a bit copy or an exact function of the Node2 and Tri1 records, so the result is a pure function of (N, nodes, tris), byte for byte;
+ * tests/collapse_model.py restates it.  A fixed list of launches whatever the tree; no thread waits for another.
+ *
+ * Runs: a run is the records from a leaf start (~child) up to and including the first with the end-of-leaf bit.
+ * Small subtrees: walk an inner node's subtree left to right (child 0 before child 1, child == 0 skipped).  It is SMALL when its runs
+ *   hold at most 4 records in all and each run starts at the record after the previous run's last.  (It then has at most 3 inner nodes:
+ *   the walk stops at the 5th record or the 4th inner node.)
+ * Packet leaves: a child reference is a packet leaf when it is a BVH2 leaf (child < 0) or a small inner node; the topmost packet leaf
+ *   on a path counts.  Its records are its runs in that order.  A small subtree makes exactly one Tri4 packet, a plain run of k
+ *   records ceil(k / 4) packets (4 records each, the rest in the last).
+ * Slots of the wide node rooted at BVH2 node r: r's children that are not 0, in order, each with the 6 bounds r stores for it.  While
+ *   there are fewer than N slots: the candidates are the slots holding an inner node that is not small; A = (dx * dy + dy * dz) + dz * dx
+ *   in fp32, every operation rounded on its own, d = hi - lo of the slot's stored bounds; the slots are scanned in order with
+ *   best = -1 and a strict >, so the first of equals wins and a NaN never does; when none wins the growth stops.  The winning slot takes
+ *   that node's child 0, that node's child 1 becomes the next slot, each with the bounds stored in the expanded node (the treelet growth
+ *   rule above).  Slots keep this order.  Every slot that still holds an inner node which is not small is a wide root; the root of the
+ *   tree is node 0.
+ * Whole tree small (node 0 is small; the single-leaf form child[1] == 0 with at most 4 records too): one wide node whose slot 0 is the
+ *   leaf over the union of node 0's two stored slot boxes (the (+inf, -inf) of an empty slot drops out by itself).
+ * Numbering: wide nodes by ascending BVH2 index of their root (node 0 becomes wide node 0), packets by ascending first record: a
+ *   pre-order BVH2 gives a pre-order wide tree.
+ * Node record: column j of bounds is a bit copy of slot j's 6 stored bounds; child = wide id + 1 for an inner slot, ~first packet for
+ *   a leaf slot; unused slots: child 0, bounds (+inf, -inf), as the host builder writes them; pad = 0.
+ * Packet: lane j takes v0 / e1 / e2 of its record bit for bit; n = e1 x e2 component by component, every product rounded on its own
+ *   (the wide refit's statement); prim_id = the record's prim_id & 0x7FFFFFFF, geom_id copied.  Unused lanes: prim_id -1, every other
+ *   word 0.  The last packet of a leaf has bit 31 of prim_id[3] set (a -1 there has it already).
+ * info: [0] wide nodes [1] packets [2] flags [3] the stack bound B: the maximum over the wide nodes of the sum, over the node and its
+ *   ancestors, of (filled slots - 1).  A ray's traversal stack never holds more than B real entries, so B <= 63 guarantees that no ray
+ *   overflows the kernels' 64 entries; above that nothing is guaranteed, exactly as for a host builder's tree.  B is information for
+ *   the caller, not an error.
+ * Malformed trees raise RODENT_BUILD_BAD_TOPOLOGY; the output is then undefined, but nothing is read or written out of bounds and every
+ *   loop keeps its bound: a child id > num_nodes, the root as a child (id 1), a node named by two slots, a node that does not reach
+ *   the root within 64 parents, a leaf start >= num_bvh_tris, a leaf start whose predecessor has no end-of-leaf bit, a run longer than
+ *   64 records, a run that reaches num_bvh_tris without an end bit; also a record held by two leaves, and an empty slot (child == 0) in
+ *   a node other than the root or in both of the root's.
+ *
+ * Identity: a collapsed tree of an unsplit device build, refitted by rodent_hip_refit_bvh4_tri4 / _bvh8_tri4 with the vertices it was
+ *   built from, keeps every byte: its slot boxes are bit copies of exact unions, and n is computed by the refit's own rule. */
+#define RODENT_BUILD_ERR_WIDTH       -12    /* width other than 4 or 8 */
+
+/* Bytes of device scratch rodent_hip_collapse_bvh2_tri1 needs; -1 for a width other than 4 or 8 and when num_nodes < 1 or
+ * num_bvh_tris < 1. */
+int64_t rodent_hip_collapse_scratch_bytes(int32_t width, int32_t num_nodes, int32_t num_bvh_tris);
+
+/* Collapses nodes[num_nodes] / tris[num_bvh_tris] into wide_nodes (room for num_nodes Node4 when width = 4, Node8 when width = 8) and
+ * packets (room for num_bvh_tris Tri4).  All pointers are DEVICE pointers; the input is only read; scratch:
+ * rodent_hip_collapse_scratch_bytes, contents ignored; info_dev: RODENT_BUILD_INFO_WORDS ints, zeroed at the start of the call.
+ * Asynchronous on `stream` like the builders: nothing is allocated, nothing waits for the device.  Checks, in this order, each enqueuing
+ * nothing when it fails: RODENT_BUILD_ERR_WIDTH, then the refit's RODENT_BUILD_ERR_NUM_NODES, _NULL and _DEVICE. */
+int32_t rodent_hip_collapse_bvh2_tri1(int32_t dev, int32_t width, const struct Node2* nodes, int32_t num_nodes, const struct Tri1* tris,
+                                      int32_t num_bvh_tris, void* wide_nodes, struct Tri4* packets, void* scratch, int32_t* info_dev,
+                                      void* stream);
+
+/* Synchronous form on the null stream with its own scratch; RODENT_BUILD_ERR_INPUT when the device raised a flag. */
+int32_t rodent_hip_collapse_bvh2_tri1_sync(int32_t dev, int32_t width, const struct Node2* nodes, int32_t num_nodes,
+                                           const struct Tri1* tris, int32_t num_bvh_tris, void* wide_nodes, struct Tri4* packets,
+                                           int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,7 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "rodent_hip_refit_scratch_bytes", "rodent_hip_refit_bvh2_tri1", "rodent_hip_refit_bvh2_tri1_sync",
     "rodent_hip_refit_wide_scratch_bytes", "rodent_hip_refit_bvh4_tri4", "rodent_hip_refit_bvh4_tri4_sync",
     "rodent_hip_refit_bvh8_tri4", "rodent_hip_refit_bvh8_tri4_sync",
+    "rodent_hip_collapse_scratch_bytes", "rodent_hip_collapse_bvh2_tri1", "rodent_hip_collapse_bvh2_tri1_sync",
 ]
 BLOCK_OF_WIDTH = {2: F.BVH2_TRI1, 4: F.BVH4_TRI4, 8: F.BVH8_TRI4}
 
@@ -126,6 +127,11 @@ def lib():
         for name in ("rodent_hip_refit_bvh4_tri4", "rodent_hip_refit_bvh8_tri4"):
             fn = getattr(l, name); fn.restype = i32; fn.argtypes = l.rodent_hip_refit_bvh2_tri1.argtypes
             fn = getattr(l, name + "_sync"); fn.restype = i32; fn.argtypes = l.rodent_hip_refit_bvh2_tri1_sync.argtypes
+        l.rodent_hip_collapse_scratch_bytes.restype = C.c_int64; l.rodent_hip_collapse_scratch_bytes.argtypes = [i32, i32, i32]
+        l.rodent_hip_collapse_bvh2_tri1.restype = i32
+        l.rodent_hip_collapse_bvh2_tri1.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+        l.rodent_hip_collapse_bvh2_tri1_sync.restype = i32
+        l.rodent_hip_collapse_bvh2_tri1_sync.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, C.POINTER(i32)]
         _lib = l
     return _lib
 

@@ -2,7 +2,8 @@
 // codes + Karras 2012 hierarchy), optionally restructured by treelets with an SAH leaf collapse, optionally over pre-split triangles.
 // C ABI: include/rodent_build.h.  CPU models of every stage, byte for byte: tests/lbvh_model.py, tests/trbvh_model.py (treelets),
 // tests/split_model.py (pre-splitting), tests/refit_model.py and tests/refit_wide_model.py (refit).
-// The kernels lie in build_device.h (what the stages share), build_lbvh.h, build_treelet.h, build_split.h and build_refit.h.
+// The kernels lie in build_device.h (what the stages share), build_lbvh.h, build_treelet.h, build_split.h, build_refit.h and
+// build_collapse.h.
 // One pipeline (launch_build), all on the caller's stream, nothing allocated, no host synchronisation.  The three entry points only
 // choose its options: rodent_hip_build_bvh2_tri1 the LBVH, _opt treelet_passes (0, or one triangle: the LBVH), _split the split front.
 // Front, one of:
@@ -31,6 +32,8 @@
 // Refit (build_refit.h, rodent_hip_refit_bvh2_tri1): k_refit_links, k_refit_tris, k_refit_climb rewrite the boxes and Tri1 records of an
 // existing hierarchy in place from moved vertices; the topology stays.  rodent_hip_refit_bvh4_tri4 / _bvh8_tri4 do the same for
 // Node4 / Node8 + Tri4 (k_refit_wide_links, k_refit_tri4, k_refit_wide_climb; CPU model: tests/refit_wide_model.py).
+// Collapse (build_collapse.h, rodent_hip_collapse_bvh2_tri1): any BVH2 / Tri1 becomes Node4 / Node8 + Tri4 by bounded walks per node,
+// no thread waiting for another (CPU model: tests/collapse_model.py).
 // Every value is a function of the inputs alone: min / max are exact and do not depend on the order they are taken in, the sort is
 // stable, and arrival order decides only WHICH thread computes a node, never what it computes.
 #include <hip/hip_runtime.h>
@@ -133,10 +136,32 @@ RefitScratch carve_refit(char* base, int num_nodes, int num_bvh_tris) {
     return s;
 }
 
+struct CollapseScratch {
+    int* parent;                  // per node, as RefitScratch
+    uint32_t* arrivals;           // per node: k_refit_links zeroes it, nobody arrives
+    int *small, *small_first, *root;
+    uint32_t *wide_id, *nodetot;  // per node / per block of nodes
+    int* mark;                    // per Tri1 record
+    uint32_t *packet_id, *rectot; // per record / per block of records
+    size_t bytes;
+};
+
+CollapseScratch carve_collapse(char* base, int num_nodes, int num_bvh_tris) {
+    CollapseScratch s{};
+    Carver c{base};
+    const size_t N = (size_t)num_nodes, T = (size_t)num_bvh_tris;
+    c.take(s.parent, N); c.take(s.arrivals, N); c.take(s.small, N); c.take(s.small_first, N); c.take(s.root, N);
+    c.take(s.wide_id, N); c.take(s.nodetot, (N + kBlock - 1) / kBlock);
+    c.take(s.mark, T); c.take(s.packet_id, T); c.take(s.rectot, (T + kBlock - 1) / kBlock);
+    s.bytes = c.bytes;
+    return s;
+}
+
 #include "build_lbvh.h"
 #include "build_treelet.h"
 #include "build_split.h"
 #include "build_refit.h"
+#include "build_collapse.h"
 
 inline int blocks_for(long long items) { return (int)((items + kBlock - 1) / kBlock); }
 
@@ -338,15 +363,59 @@ int32_t launch_refit_wide(const float* vertices, int nv, const int32_t* indices,
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
 
-// The argument checks of the refit entries (the builders' own, in their order); `num_leaf_records`: Tri1 records or Tri4 packets.
+// What the refit and collapse entries check of an existing hierarchy, in this order; `num_leaf_records`: Tri1 records or Tri4 packets.
+int32_t check_tree_args(int32_t dev, int32_t num_nodes, int32_t num_leaf_records, bool null_pointer) {
+    if (num_nodes < 1 || num_leaf_records < 1) return RODENT_BUILD_ERR_NUM_NODES;
+    if (null_pointer) return RODENT_BUILD_ERR_NULL;
+    return set_device(dev) ? RODENT_BUILD_OK : RODENT_BUILD_ERR_DEVICE;
+}
+
+// The argument checks of the refit entries (the builders' own, in their order).
 int32_t check_refit_args(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_tris,
                          const void* nodes, int32_t num_nodes, const void* tris, int32_t num_leaf_records, const void* scratch,
                          const int32_t* info_dev) {
     if (bad_num_tris(num_tris)) return RODENT_BUILD_ERR_NUM_TRIS;
     if (num_vertices < 1) return RODENT_BUILD_ERR_NUM_VERTICES;
-    if (num_nodes < 1 || num_leaf_records < 1) return RODENT_BUILD_ERR_NUM_NODES;
-    if (!vertices || !indices || !nodes || !tris || !scratch || !info_dev) return RODENT_BUILD_ERR_NULL;
-    return set_device(dev) ? RODENT_BUILD_OK : RODENT_BUILD_ERR_DEVICE;
+    return check_tree_args(dev, num_nodes, num_leaf_records, !vertices || !indices || !nodes || !tris || !scratch || !info_dev);
+}
+
+// The collapse after its argument checks: info words and record marks zeroed, parent slots set to -1, then the kernels of
+// build_collapse.h: a fixed list of launches whatever the tree.
+template <class Node>
+int32_t launch_collapse(const Node2* nodes, int num_nodes, const Tri1* tris, int num_bvh_tris, Node* wide_nodes, Tri4* packets,
+                        void* scratch, int32_t* info_dev, void* stream_) {
+    constexpr int N = kArity<Node>;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const CollapseScratch s = carve_collapse(static_cast<char*>(scratch), num_nodes, num_bvh_tris);
+    if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess
+        || hipMemsetAsync(s.parent, 0xFF, 4 * (size_t)num_nodes, stream) != hipSuccess
+        || hipMemsetAsync(s.mark, 0, 4 * (size_t)num_bvh_tris, stream) != hipSuccess)
+        return RODENT_BUILD_ERR_LAUNCH;
+    const Collapse c{nodes, num_nodes, tris, num_bvh_tris, s.parent, s.small, s.small_first, s.root, s.mark, s.wide_id, s.packet_id,
+                     info_dev};
+    const int nb = blocks_for(num_nodes), tb = blocks_for(num_bvh_tris);
+    hipLaunchKernelGGL(k_refit_links, dim3(nb), dim3(kBlock), 0, stream, nodes, num_nodes, num_bvh_tris, s.parent, s.arrivals, info_dev);
+    hipLaunchKernelGGL(k_collapse_small, dim3(nb), dim3(kBlock), 0, stream, c);
+    hipLaunchKernelGGL(k_collapse_flags<N>, dim3(nb), dim3(kBlock), 0, stream, c);
+    hipLaunchKernelGGL(k_collapse_totals, dim3(nb), dim3(kBlock), 0, stream, s.root, num_nodes, s.nodetot);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.nodetot, nb, info_dev + kInfoWideNodes);
+    hipLaunchKernelGGL(k_collapse_ids, dim3(nb), dim3(kBlock), 0, stream, s.root, num_nodes, s.nodetot, s.wide_id);
+    hipLaunchKernelGGL(k_collapse_totals, dim3(tb), dim3(kBlock), 0, stream, s.mark, num_bvh_tris, s.rectot);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.rectot, tb, info_dev + kInfoPackets);
+    hipLaunchKernelGGL(k_collapse_ids, dim3(tb), dim3(kBlock), 0, stream, s.mark, num_bvh_tris, s.rectot, s.packet_id);
+    hipLaunchKernelGGL(k_collapse_packets, dim3(tb), dim3(kBlock), 0, stream, c, packets);
+    hipLaunchKernelGGL(k_collapse_nodes<Node>, dim3(nb), dim3(kBlock), 0, stream, c, wide_nodes);
+    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
+int32_t collapse(int32_t dev, int32_t width, const Node2* nodes, int32_t num_nodes, const Tri1* tris, int32_t num_bvh_tris,
+                 void* wide_nodes, Tri4* packets, void* scratch, int32_t* info_dev, void* stream) {
+    if (width != 4 && width != 8) return RODENT_BUILD_ERR_WIDTH;
+    const int32_t rc = check_tree_args(dev, num_nodes, num_bvh_tris, !nodes || !tris || !wide_nodes || !packets || !scratch || !info_dev);
+    if (rc != RODENT_BUILD_OK) return rc;
+    return width == 4
+        ? launch_collapse(nodes, num_nodes, tris, num_bvh_tris, static_cast<Node4*>(wide_nodes), packets, scratch, info_dev, stream)
+        : launch_collapse(nodes, num_nodes, tris, num_bvh_tris, static_cast<Node8*>(wide_nodes), packets, scratch, info_dev, stream);
 }
 
 template <class Node>
@@ -540,6 +609,28 @@ int32_t rodent_hip_refit_bvh8_tri4_sync(int32_t dev, const float* vertices, int3
     return refit_sync(dev, rodent_hip_refit_wide_scratch_bytes(8, num_nodes, num_packets), num_nodes, info,
                       [&](void* scratch, int32_t* info_dev) {
         return refit_wide(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_packets, scratch, info_dev, nullptr);
+    });
+}
+
+int64_t rodent_hip_collapse_scratch_bytes(int32_t width, int32_t num_nodes, int32_t num_bvh_tris) {
+    if ((width != 4 && width != 8) || num_nodes < 1 || num_bvh_tris < 1) return -1;
+    return (int64_t)carve_collapse(nullptr, num_nodes, num_bvh_tris).bytes;
+}
+
+int32_t rodent_hip_collapse_bvh2_tri1(int32_t dev, int32_t width, const struct Node2* nodes, int32_t num_nodes, const struct Tri1* tris,
+                                      int32_t num_bvh_tris, void* wide_nodes, struct Tri4* packets, void* scratch, int32_t* info_dev,
+                                      void* stream) {
+    return collapse(dev, width, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_collapse_bvh2_tri1_sync(int32_t dev, int32_t width, const struct Node2* nodes, int32_t num_nodes,
+                                           const struct Tri1* tris, int32_t num_bvh_tris, void* wide_nodes, struct Tri4* packets,
+                                           int32_t* info) {
+    if (width != 4 && width != 8) return RODENT_BUILD_ERR_WIDTH;
+    const int64_t bytes = rodent_hip_collapse_scratch_bytes(width, num_nodes, num_bvh_tris);
+    if (bytes < 0) return RODENT_BUILD_ERR_NUM_NODES;
+    return build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
+        return collapse(dev, width, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, nullptr);
     });
 }
 

@@ -1,17 +1,22 @@
-"""BVH2 / Tri1 hierarchies built on the GPU (the LBVH builder of csrc/bvh_build.hip, C ABI include/rodent_build.h).
+"""BVH2 / Tri1 hierarchies built on the GPU (the LBVH builder of csrc/bvh_build.hip, C ABI include/rodent_build.h), and their collapse
+into BVH4 / BVH8 + Tri4.
 
     bvh = build_bvh2(vertices, indices)            # numpy arrays or CUDA tensors, (n, 3) or (n, 4)
     bvh = build_bvh2(vertices, indices, treelet_passes=2)   # + treelet restructuring and an SAH leaf collapse
     bvh = build_bvh2(vertices, indices, treelet_passes=3, split_budget=1.0)   # + triangle pre-splitting (bvh.num_tris references)
     hits = abi.traverse(bvh, rays)
     refit_bvh2(bvh, moved_vertices, indices)       # the vertices moved: new boxes and Tri1 records in place, the topology stays
-    refit_wide(wide, moved_vertices, indices)      # the same for a BVH4 / BVH8 + Tri4 DeviceBvh (of the host builder)
+    refit_wide(wide, moved_vertices, indices)      # the same for a BVH4 / BVH8 + Tri4 DeviceBvh (collapsed, or of the host builder)
+    wide = collapse_wide(bvh, 8)                   # the BVH2 collapsed into BVH8 / Tri4 on the device; wide.info[3]: its stack bound
+    wide = build_wide(vertices, indices, 8, max_leaf=4, treelet_passes=3)    # build_bvh2 then collapse_wide; wide.bvh2 is the BVH2
 
 The result is a pure function of the inputs, byte for byte.  As a tool:
 
     python -m rodent_amd.gpubuild scene.rscene -o out.bvh [--max-leaf N] [--treelet-passes N] [--split-budget F [--max-pieces K]]
+                                  [--width 4] [--width 8]
 
-writes a .bvh holding the BVH2_TRI1 block of the scene's mesh (bench_traversal reads it).
+writes a .bvh holding the BVH2_TRI1 block of the scene's mesh and, for every --width, its collapsed BVH4_TRI4 / BVH8_TRI4 block
+(bench_traversal reads them).
 """
 from __future__ import annotations
 
@@ -31,10 +36,11 @@ INFO_WORDS = 4
 SPLIT_INFO_WORDS = 8                   # + [4] Tri1 count (references) [5] triangles split [6] splits allotted but not made [7] 0
 MAX_PIECES, MAX_SPLIT_BUDGET = 64, 4.0
 BAD_INDEX, NON_FINITE, BAD_TOPOLOGY = 1, 2, 4
-ERR_SPLIT, ERR_NUM_NODES = -10, -11
+ERR_SPLIT, ERR_NUM_NODES, ERR_WIDTH = -10, -11, -12
 _ERRORS = {-1: "num_tris outside [1, 2^25]", -2: "max_leaf outside [1, 8]", -3: "no vertices", -4: "NULL pointer",
            -5: "no such device", -6: "launch failed", -8: "treelet_passes outside [0, 3]", -9: "node_cost / tri_cost outside (0, 1e6]",
-           ERR_SPLIT: "split budget outside [0, 4] or max_pieces outside [1, 64]", ERR_NUM_NODES: "a hierarchy without nodes or triangles"}
+           ERR_SPLIT: "split budget outside [0, 4] or max_pieces outside [1, 64]", ERR_NUM_NODES: "a hierarchy without nodes or triangles",
+           ERR_WIDTH: "width other than 4 or 8"}
 _FLAGS = ((BAD_INDEX, "vertex index outside the vertex array"), (NON_FINITE, "non-finite vertex coordinate"),
           (BAD_TOPOLOGY, "malformed hierarchy (child id or prim_id out of range, leaf without end bit, node with two parents)"))
 
@@ -201,6 +207,49 @@ def refit_wide(bvh: abi.DeviceBvh, vertices, indices, stream=None, scratch=None)
     return _refit(f"rodent_hip_refit_bvh{bvh.width}_tri4", need, bvh, vertices, indices, stream, scratch)
 
 
+def collapse_wide(bvh2: abi.DeviceBvh, width, stream=None, scratch=None) -> abi.DeviceBvh:
+    """Collapses the BVH2 / Tri1 hierarchy `bvh2` (of build_bvh2, any options, or of a host builder) into a new BVH4 / BVH8 + Tri4
+    DeviceBvh of `width` slots to a node (rodent_hip_collapse_bvh2_tri1); `bvh2` is only read.  The result's num_tris counts its Tri4
+    packets, as for a host builder's wide tree, and its `info` holds [0] wide nodes [1] packets [2] flags [3] the stack bound B: no ray's
+    traversal stack holds more than B entries, so B <= 63 rules an overflow out (B is not checked here).  Stream and scratch as in
+    build_bvh2.  Raises BuildError on a malformed hierarchy."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
+    if bvh2.width != 2:
+        raise ValueError("collapse_wide: a BVH2 / Tri1 hierarchy is needed")
+    if width not in (4, 8):
+        raise BuildError(f"collapse_wide: {_ERRORS[ERR_WIDTH]}")
+    dev, entry = bvh2.dev, "rodent_hip_collapse_bvh2_tri1"
+    need = abi.lib().rodent_hip_collapse_scratch_bytes(width, bvh2.num_nodes, bvh2.num_tris)
+    if need < 0:
+        raise BuildError(f"{entry}: {_ERRORS[ERR_NUM_NODES]}")
+    cuda = f"cuda:{dev}"
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    if scratch is None or scratch.numel() * scratch.element_size() < need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=cuda)
+    node_dt = {4: F.NODE4, 8: F.NODE8}[width]
+    nodes = torch.empty(bvh2.num_nodes * node_dt.itemsize, dtype=torch.uint8, device=cuda)
+    tris = torch.empty(bvh2.num_tris * F.TRI4.itemsize, dtype=torch.uint8, device=cuda)
+    info = torch.empty(INFO_WORDS, dtype=torch.int32, device=cuda)
+    words = _enqueue(entry, dev, stream, info, (bvh2.nodes, bvh2.tris, nodes, tris, scratch), int(width), bvh2.nodes.data_ptr(),
+                     bvh2.num_nodes, bvh2.tris.data_ptr(), bvh2.num_tris, nodes.data_ptr(), tris.data_ptr(), scratch.data_ptr())
+    _raise_flags(entry, words)
+    wide = abi.DeviceBvh.from_tensors(width, nodes, tris, int(words[0]), int(words[1]), dev)
+    wide.info, wide.scratch = words.copy(), scratch
+    return wide
+
+
+def build_wide(vertices, indices, width, dev=0, stream=None, **options) -> abi.DeviceBvh:
+    """build_bvh2(vertices, indices, **options) then collapse_wide(..., width) on one stream: a BVH4 / BVH8 + Tri4 hierarchy built
+    without the host builder.  The BVH2 it came from stays reachable as `.bvh2` (refit_wide needs only the wide tree)."""
+    if width not in (4, 8):
+        raise BuildError(f"build_wide: {_ERRORS[ERR_WIDTH]}")
+    bvh2 = build_bvh2(vertices, indices, dev=dev, stream=stream, **options)
+    wide = collapse_wide(bvh2, width, stream=stream)
+    wide.bvh2 = bvh2
+    return wide
+
+
 def download_wide(bvh: abi.DeviceBvh):
     """(nodes, tris) host copies of a DeviceBvh of any width: NODE2 / TRI1, NODE4 / TRI4 or NODE8 / TRI4."""
     node_dt, tri_dt = {2: (F.NODE2, F.TRI1), 4: (F.NODE4, F.TRI4), 8: (F.NODE8, F.TRI4)}[bvh.width]
@@ -227,14 +276,21 @@ def main(argv=None):
     ap.add_argument("--split-budget", type=float, default=0.0,
                     help="pre-split triangles into up to this fraction of extra references (0 ... 4, default 0: no splitting)")
     ap.add_argument("--max-pieces", type=int, default=None, help="the most references one triangle may become (1 ... 64, default 64)")
+    ap.add_argument("--width", type=int, action="append", choices=(4, 8), default=[],
+                    help="also write the BVH2 collapsed into this width (BVH4_TRI4 / BVH8_TRI4 block); may be given twice")
     ap.add_argument("--dev", type=int, default=0)
     a = ap.parse_args(argv)
     sc = Scene(a.scene)
     bvh = build_bvh2(sc.vertices, sc.indices, a.max_leaf, a.dev, treelet_passes=a.treelet_passes, split_budget=a.split_budget,
                      max_pieces=a.max_pieces)
     nodes, tris = download(bvh)
-    F.write_bvh(a.output, [(F.BVH2_TRI1, nodes, tris)])
+    blocks = [(F.BVH2_TRI1, nodes, tris)]
     print(f"{a.output}: {len(tris)} triangles, {len(nodes)} nodes, depth {bvh.depth}")
+    for width in sorted(set(a.width)):
+        wide = collapse_wide(bvh, width)
+        blocks.append((abi.BLOCK_OF_WIDTH[width], *download_wide(wide)))
+        print(f"{a.output}: BVH{width}: {wide.num_nodes} nodes, {wide.num_tris} packets, stack bound {wide.info[3]}")
+    F.write_bvh(a.output, blocks)
 
 
 if __name__ == "__main__":

@@ -22,11 +22,17 @@ For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> conve
     rodent_hip_refit_bvh2_tri1 on the BVH2 block of the same file and the wall time of bvh_extractor, which parses the OBJ and builds
     the three layouts side by side on three threads: an upper bound of one layout's host build.
 
+  * with --collapse, nothing of the above: for the LBVH (max_leaf 4) and the 3-pass build (max_leaf 4) of every scene, the device-event
+    time of rodent_hip_collapse_bvh2_tri1 into BVH4 and BVH8 (median of 20 after 3 warm-ups) beside the build before it, the wide
+    nodes, packets, lane fill (records / (4 x packets)) and stack bound B, and Mrays/s (camera and random rays, closest and any hit,
+    default variants) of the collapsed tree, of the host builder's tree of the same width (bvh_extractor) and of the BVH2 it came from.
+
     python scripts/bench_bvh_build.py [--scenes atrium gallery crown plant] [--builds 20] [-o profiles/gpu_bvh_build.txt]
     python scripts/bench_bvh_build.py --treelet-passes 3 -o profiles/gpu_bvh_build_opt.txt
     python scripts/bench_bvh_build.py --treelet-passes 3 --split-budget 0.25 1 -o profiles/gpu_bvh_build_split.txt
     python scripts/bench_bvh_build.py --scenes atrium --treelet-passes 3 --split-budget 1 --refit -o profiles/gpu_bvh_refit.txt
     python scripts/bench_bvh_build.py --scenes atrium gallery --refit-wide -o profiles/gpu_bvh_refit_wide.txt
+    python scripts/bench_bvh_build.py --scenes atrium gallery --collapse -o profiles/gpu_bvh_collapse.txt
 """
 from __future__ import annotations
 
@@ -123,6 +129,92 @@ def refit_wide_table(a):
     Path(a.output).write_text("\n".join(lines) + "\n")
 
 
+def collapse_table(a):
+    """--collapse: the device collapse of device-built BVH2 trees into BVH4 / BVH8 + Tri4 against the build before it, and the collapsed
+    trees' trace rates against the host builder's wide trees and the BVH2 they came from."""
+    from oracle import binding as O
+    build.build_all()
+    lines = [f"# scripts/bench_bvh_build.py --collapse on {torch.cuda.get_device_name(0)}; builds and collapses: median of {a.builds} "
+             "/ of 20 after 3 warm-ups, device events around the enqueued operations; fill: Tri1 records / (4 x packets); B: the stack "
+             "bound info[3]; Mrays/s: 1 Mi camera rays / 1 Mi random segments, default variant, median of 10 launches after 2 warm-ups, "
+             "closest / any hit: collapsed tree, host builder's tree of the same width, the BVH2 it came from",
+             f"{'scene':>8} {'tris':>9} {'bvh2':>6} {'build ms':>8} {'nodes2':>8} | {'wide':>4} {'clps ms':>7} {'nodes':>8} {'packets':>8} "
+             f"{'fill':>5} {'B':>3} {'host nodes':>10} {'host pk':>8} | {'cam closest':>17} {'cam any':>17} {'rand closest':>17} "
+             f"{'rand any':>17}"]
+    print("\n".join(lines), flush=True)
+    scenes.DATA.mkdir(parents=True, exist_ok=True)
+    stream = torch.cuda.current_stream()
+    info = torch.empty(4, dtype=torch.int32, device="cuda")
+    for name in a.scenes:
+        obj = scenes.scene_obj(name)
+        stem = name.replace("/", "-")
+        sc = S.convert(obj, scenes.DATA / f"{stem}.rscene")
+        path = scenes.DATA / f"{stem}-collapse.bvh"
+        subprocess.run([str(build.BIN_DIR / "bvh_extractor"), "-obj", str(obj), "-o", str(path)], check=True, stdout=subprocess.DEVNULL)
+        n = sc.num_tris
+        v, ix = torch.from_numpy(sc.vertices).cuda(), torch.from_numpy(sc.indices).cuda()
+        eye, d, up, fov = scenes.CAMERAS[name.split("/")[0]]
+        lo, hi = sc.vertices[:, :3].min(0), sc.vertices[:, :3].max(0)
+        ray_sets = {"cam": raygen.primary_rays(eye, d, up, fov, 1024, 1024, 0.0, scenes.PRIMARY_TMAX),
+                    "rand": raygen.random_rays(lo, hi, 1 << 20, 42, 0.0, scenes.RANDOM_TMAX)}
+        rays_dev = {k: abi.to_device(r) for k, r in ray_sets.items()}
+        hits = torch.empty((1 << 20) * 16, dtype=torch.uint8, device="cuda")
+
+        def rates(tree):
+            out = {}
+            for rk, rd in rays_dev.items():
+                for any_hit in (False, True):
+                    ms = event_ms(lambda: abi.traverse_async(tree, rd, hits, 1 << 20, any_hit), 2, 10)
+                    abi.check_errors()
+                    out[rk, any_hit] = (1 << 20) / ms / 1e3
+            return out
+        for label, passes in (("lbvh", 0), ("3 pass", 3)):
+            bvh = gpubuild.build_bvh2(v, ix, 4, treelet_passes=passes)
+            copt = gpubuild.options(4, passes)
+
+            def one_build():
+                rc = abi.lib().rodent_hip_build_bvh2_tri1_opt(0, v.data_ptr(), len(sc.vertices), ix.data_ptr(), n, C.byref(copt),
+                                                              bvh.nodes.data_ptr(), bvh.tris.data_ptr(), bvh.scratch.data_ptr(),
+                                                              info.data_ptr(), C.c_void_p(stream.cuda_stream))
+                assert rc == 0
+            build_ms = event_ms(one_build, 3, a.builds)
+            assert info.cpu().numpy().tolist() == bvh.info.tolist()
+            assert tree_depth(gpubuild.download(bvh)[0]) == bvh.depth <= 56          # checked before anything traces it
+            rate2 = rates(bvh)
+            for width in (4, 8):
+                wide = gpubuild.collapse_wide(bvh, width)
+
+                def one_collapse():
+                    rc = abi.lib().rodent_hip_collapse_bvh2_tri1(0, width, bvh.nodes.data_ptr(), bvh.num_nodes, bvh.tris.data_ptr(),
+                                                                 bvh.num_tris, wide.nodes.data_ptr(), wide.tris.data_ptr(),
+                                                                 wide.scratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
+                    assert rc == 0
+                collapse_ms = event_ms(one_collapse, 3, 20)
+                assert info.cpu().numpy().tolist() == wide.info.tolist()
+                B = int(wide.info[3])
+                if B > 63:
+                    # no guarantee from B: the CPU oracle looks at every 16th ray first, and nothing is traced past 64 entries
+                    wn, wt = gpubuild.download_wide(wide)
+                    peak = max(O.traverse(width, wn, wt, r[::16], any_hit=h, algo="gpu")[1]["max_stack"]
+                               for r in ray_sets.values() for h in (False, True))
+                    assert peak <= 64, f"{name} {label} bvh{width}: a stack of {peak} entries"
+                host = abi.DeviceBvh.load(path, width)
+                rate, rate_host = rates(wide), rates(host)
+                cells = " ".join(f"{rate[k]:>5.0f} {rate_host[k]:>5.0f} {rate2[k]:>5.0f}" for k in
+                                 (("cam", False), ("cam", True), ("rand", False), ("rand", True)))
+                row = (f"{name:>8} {n:>9} {label:>6} {build_ms:>8.3f} {bvh.num_nodes:>8} | {'bvh' + str(width):>4} {collapse_ms:>7.3f} "
+                       f"{wide.num_nodes:>8} {wide.num_tris:>8} {bvh.num_tris / (4 * wide.num_tris):>5.2f} {B:>3} {host.num_nodes:>10} "
+                       f"{host.num_tris:>8} | {cells}")
+                lines.append(row)
+                print(row, flush=True)
+                del wide, host
+            del bvh
+        del v, ix, rays_dev, hits
+        torch.cuda.empty_cache()
+    Path(a.output).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.output).write_text("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", nargs="+", default=["atrium", "gallery", "crown", "plant"])
@@ -133,10 +225,14 @@ def main():
     ap.add_argument("--refit", action="store_true", help="also time a refit of every built tree and compare refitted with rebuilt SAH")
     ap.add_argument("--refit-wide", action="store_true",
                     help="only time the refit of the host builder's BVH4 / BVH8 + Tri4 trees (beside: the BVH2 refit, the host build)")
+    ap.add_argument("--collapse", action="store_true",
+                    help="only time the collapse of device-built BVH2 trees into BVH4 / BVH8 + Tri4 and trace the collapsed trees")
     ap.add_argument("-o", "--output", default=str(ROOT / "profiles" / "gpu_bvh_build.txt"))
     a = ap.parse_args()
     if a.refit_wide:
         return refit_wide_table(a)
+    if a.collapse:
+        return collapse_table(a)
     from oracle import binding as O
     import lbvh_model as L
     import refit_model as RM
