@@ -317,6 +317,21 @@ int32_t rodent_hip_refit_bvh8_tri4_sync(int32_t dev, const float* vertices, int3
  *   ancestors, of (filled slots - 1).  A ray's traversal stack never holds more than B real entries, so B <= 63 guarantees that no ray
  *   overflows the kernels' 64 entries; above that nothing is guaranteed, exactly as for a host builder's tree.  B is information for
  *   the caller, not an error.
+ * Stack limit (the _bounded entries; stack_limit L in [0, 63], L = 0: none, the collapse above byte for byte and launch for launch):
+ *   Open: a child reference is open when it names a sound inner node that is not small: the candidates of the growth above.
+ *   Height: for an inner node i that is not small, H(i) = 1 + max(h(child 0), h(child 1)), where h(ref) = H(ref - 1) when ref is open
+ *     and 0 otherwise (leaves, small nodes and empty slots count 0).  H(i) is the stack bound of i's subtree left binary; no collapse
+ *     of that subtree has a smaller one.  H is at most the number of nodes on the longest path: at most the builders' info[1] (<= 56)
+ *     for a tree of this library.
+ *   Growth: a wide node rooted at r is entered with S, the sum of (filled slots - 1) over its ancestors.  It starts with r's children
+ *     as above.  While it has f < N slots, the candidates are the candidates above that also satisfy: for every OTHER filled slot s,
+ *     S + f + h(s) <= L (f counted before the expansion).  The slot of largest A among them is expanded as above (the first of equals,
+ *     never a NaN); growth stops when no candidate is left.
+ *   Guarantee: B <= max(L, H(0)).  So L = 63 gives B <= 63 for every tree the builders above produce; for a deeper host tree
+ *     info[3] > L says that the bound could not be met (then info[3] = H(0)).  B stays information, not an error.  When L is at least
+ *     the B of the collapse without a limit, the result equals that collapse byte for byte.
+ *   Everything else is as above: small subtrees, packets, numbering, bit-copied bounds, n, unused slots, flags, the malformed-tree
+ *     list and the whole-tree-small form.  tests/collapse_bounded_model.py restates it.  One launch more (the heights).
  * Malformed trees raise RODENT_BUILD_BAD_TOPOLOGY; the output is then undefined, but nothing is read or written out of bounds and every
  *   loop keeps its bound: a child id > num_nodes, the root as a child (id 1), a node named by two slots, a node that does not reach
  *   the root within 64 parents, a leaf start >= num_bvh_tris, a leaf start whose predecessor has no end-of-leaf bit, a run longer than
@@ -326,6 +341,8 @@ int32_t rodent_hip_refit_bvh8_tri4_sync(int32_t dev, const float* vertices, int3
  * Identity: a collapsed tree of an unsplit device build, refitted by rodent_hip_refit_bvh4_tri4 / _bvh8_tri4 with the vertices it was
  *   built from, keeps every byte: its slot boxes are bit copies of exact unions, and n is computed by the refit's own rule. */
 #define RODENT_BUILD_ERR_WIDTH       -12    /* width other than 4 or 8 */
+#define RODENT_BUILD_ERR_STACK_LIMIT -13    /* stack_limit outside [0, 63] */
+#define RODENT_BUILD_MAX_STACK_LIMIT 63
 
 /* Bytes of device scratch rodent_hip_collapse_bvh2_tri1 needs; -1 for a width other than 4 or 8 and when num_nodes < 1 or
  * num_bvh_tris < 1. */
@@ -344,6 +361,22 @@ int32_t rodent_hip_collapse_bvh2_tri1(int32_t dev, int32_t width, const struct N
 int32_t rodent_hip_collapse_bvh2_tri1_sync(int32_t dev, int32_t width, const struct Node2* nodes, int32_t num_nodes,
                                            const struct Tri1* tris, int32_t num_bvh_tris, void* wide_nodes, struct Tri4* packets,
                                            int32_t* info);
+
+/* Bytes of device scratch rodent_hip_collapse_bvh2_tri1_bounded needs (two ints per node more than
+ * rodent_hip_collapse_scratch_bytes, whatever stack_limit); -1 as there. */
+int64_t rodent_hip_collapse_bounded_scratch_bytes(int32_t width, int32_t num_nodes, int32_t num_bvh_tris);
+
+/* rodent_hip_collapse_bvh2_tri1 with a stack limit (rules above; 0: none, the same bytes, info words and launches as that entry).
+ * scratch: rodent_hip_collapse_bounded_scratch_bytes.  Checks, in this order, each enqueuing nothing when it fails:
+ * RODENT_BUILD_ERR_WIDTH, RODENT_BUILD_ERR_STACK_LIMIT, then RODENT_BUILD_ERR_NUM_NODES, _NULL and _DEVICE. */
+int32_t rodent_hip_collapse_bvh2_tri1_bounded(int32_t dev, int32_t width, int32_t stack_limit, const struct Node2* nodes,
+                                              int32_t num_nodes, const struct Tri1* tris, int32_t num_bvh_tris, void* wide_nodes,
+                                              struct Tri4* packets, void* scratch, int32_t* info_dev, void* stream);
+
+/* Synchronous form on the null stream with its own scratch; RODENT_BUILD_ERR_INPUT when the device raised a flag. */
+int32_t rodent_hip_collapse_bvh2_tri1_bounded_sync(int32_t dev, int32_t width, int32_t stack_limit, const struct Node2* nodes,
+                                                   int32_t num_nodes, const struct Tri1* tris, int32_t num_bvh_tris, void* wide_nodes,
+                                                   struct Tri4* packets, int32_t* info);
 
 #ifdef __cplusplus
 }

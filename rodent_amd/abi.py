@@ -48,6 +48,7 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "rodent_hip_refit_wide_scratch_bytes", "rodent_hip_refit_bvh4_tri4", "rodent_hip_refit_bvh4_tri4_sync",
     "rodent_hip_refit_bvh8_tri4", "rodent_hip_refit_bvh8_tri4_sync",
     "rodent_hip_collapse_scratch_bytes", "rodent_hip_collapse_bvh2_tri1", "rodent_hip_collapse_bvh2_tri1_sync",
+    "rodent_hip_collapse_bounded_scratch_bytes", "rodent_hip_collapse_bvh2_tri1_bounded", "rodent_hip_collapse_bvh2_tri1_bounded_sync",
 ]
 BLOCK_OF_WIDTH = {2: F.BVH2_TRI1, 4: F.BVH4_TRI4, 8: F.BVH8_TRI4}
 
@@ -132,6 +133,12 @@ def lib():
         l.rodent_hip_collapse_bvh2_tri1.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
         l.rodent_hip_collapse_bvh2_tri1_sync.restype = i32
         l.rodent_hip_collapse_bvh2_tri1_sync.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, C.POINTER(i32)]
+        l.rodent_hip_collapse_bounded_scratch_bytes.restype = C.c_int64
+        l.rodent_hip_collapse_bounded_scratch_bytes.argtypes = [i32, i32, i32]
+        l.rodent_hip_collapse_bvh2_tri1_bounded.restype = i32
+        l.rodent_hip_collapse_bvh2_tri1_bounded.argtypes = [i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+        l.rodent_hip_collapse_bvh2_tri1_bounded_sync.restype = i32
+        l.rodent_hip_collapse_bvh2_tri1_bounded_sync.argtypes = [i32, i32, i32, vp, i32, vp, i32, vp, vp, C.POINTER(i32)]
         _lib = l
     return _lib
 

@@ -5,14 +5,18 @@
 // thread derives what it needs by bounded walks of its own, there are no arrival counters, and the launches do not depend on the tree.
 //   k_refit_links      (build_refit.h) parent slots, child ids and leaf starts checked
 //   k_collapse_small   per node: the records of its subtree when it is small (at most 4, one behind the other), else 0
+//   k_collapse_height  only with a stack limit: per inner node that is not small, H = the inner nodes that are not small on the longest
+//                      path below it, itself included: each thread climbs its parent links and raises the heights with atomicMax
 //   k_collapse_flags   per node: the climb to the root (at most 64 parents, the turns kept in a 64-bit word), then down again through the
 //                      wide roots above it, simulating each one's expansion with "which slot is on my path": is this node a wide root?
 //                      A wide root expands itself too and raises the stack bound B (atomicMax).  Leaf slots and topmost small nodes
-//                      mark their packets per record.
+//                      mark their packets per record.  With a stack limit every growth takes its root's S, the sum of
+//                      (filled slots - 1) over the wide nodes above it, and a wide root's S is kept for k_collapse_nodes.
 //   k_collapse_totals, k_scan, k_collapse_ids   twice: wide ids from the root flags, packet ids from the record marks
 //   k_collapse_packets per marked record: its Tri4
 //   k_collapse_nodes   per wide root: the expansion again, keeping per slot its source (node, side); the 6 bounds are copied at the end
 // The N slots live in registers: every access is an unrolled compare-and-select, never a runtime index.
+// Limited = false is the collapse without a stack limit: it reads no height and no S, and keeps no h in its slots.
 enum { kInfoWideNodes = 0, kInfoPackets = 1, kInfoStackBound = 3 };
 constexpr int kMaxRun = 64;                              // records of the longest run
 // a record's mark: lanes of the packet that starts here (0: none starts), its last-in-leaf bit, "a leaf holds this record"
@@ -27,6 +31,8 @@ struct Collapse {
     int* mark;                    // per record (zeroed for every call)
     uint32_t *wide_id, *packet_id;    // exclusive scans of the root flags / of the records where a packet starts
     int* info;
+    int *height, *above;          // with a stack limit only, per node: H (0: small) / the S a wide root is entered with
+    int limit;                    // the stack limit L, 0 = none
 };
 
 __device__ __forceinline__ bool ends_leaf(const Collapse& c, int p) { return c.tris[p].prim_id < 0; }
@@ -67,6 +73,23 @@ __global__ __launch_bounds__(kBlock) void k_collapse_small(Collapse c) {
     int first = 0;
     c.small[i] = small_records(c, i, &first);
     c.small_first[i] = first;
+    if (c.limit > 0) c.height[i] = 0;
+}
+
+// H of every inner node that is not small (a small node keeps 0): 1 above the larger H of its children.  Thread i brings 1 to node i,
+// 2 to its parent, 3 to the parent's parent ... and stops where the value already there is not smaller: the thread that put it there is
+// carrying it on upward itself, so the array ends as the exact maximum whatever the order of the threads.  Nobody waits.  The parents
+// of a node that is not small are not small either.
+__global__ __launch_bounds__(kBlock) void k_collapse_height(Collapse c) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= c.num_nodes || c.small[i] != 0) return;
+    int at = i;
+    for (int h = 1; h <= kMaxClimb + 1; h++) {                    // the node and at most 64 parents
+        if (atomicMax(&c.height[at], h) >= h) break;
+        const int up = c.parent[at];
+        if (up < 0) break;
+        at = up >> 1;
+    }
 }
 
 // `lanes` records from `first` become one packet, the last of its leaf when `last`.  A record two leaves hold raises the flag.
@@ -95,39 +118,55 @@ __device__ int mark_run(const Collapse& c, int s) {
 }
 
 // The slots of a wide node while it grows.  area: A of the slot's stored bounds when it can be expanded (a sound inner node that is
-// not small), NaN otherwise: a NaN never wins.
+// not small), NaN otherwise: a NaN never wins.  h (with a stack limit): H of that inner node, 0 otherwise.
 template <int N> struct Slots {
     int ref[N], src[N];           // the child reference and where its bounds are stored: 2 * node + side
     float area[N];
+    int h[N];
     int count;
 };
 
-template <int N> __device__ __forceinline__ void set_slot(const Collapse& c, Slots<N>& s, int j, int node, int side) {
+template <int N, bool Limited>
+__device__ __forceinline__ void set_slot(const Collapse& c, Slots<N>& s, int j, int node, int side) {
     const Node2& nd = c.nodes[node];
     const int ref = nd.child[side];
     const bool open = ref > 1 && ref <= c.num_nodes && c.small[ref - 1] == 0;
     const float a = open ? half_area(nd.bounds + 6 * side) : __int_as_float(0x7FC00000);
+    const int h = Limited && open ? c.height[ref - 1] : 0;
 #pragma unroll
     for (int q = 0; q < N; q++)
-        if (q == j) { s.ref[q] = ref; s.src[q] = 2 * node + side; s.area[q] = a; }
+        if (q == j) { s.ref[q] = ref; s.src[q] = 2 * node + side; s.area[q] = a; s.h[q] = h; }
 }
 
 // The slots a wide node rooted at r starts with: r's children that are not 0, in order.
-template <int N> __device__ __forceinline__ void first_slots(const Collapse& c, Slots<N>& s, int r) {
+template <int N, bool Limited> __device__ __forceinline__ void first_slots(const Collapse& c, Slots<N>& s, int r) {
 #pragma unroll
-    for (int q = 0; q < N; q++) { s.ref[q] = 0; s.src[q] = 0; s.area[q] = __int_as_float(0x7FC00000); }
+    for (int q = 0; q < N; q++) { s.ref[q] = 0; s.src[q] = 0; s.area[q] = __int_as_float(0x7FC00000); s.h[q] = 0; }
     s.count = 0;
     for (int k = 0; k < 2; k++)
-        if (c.nodes[r].child[k] != 0) set_slot(c, s, s.count++, r, k);
+        if (c.nodes[r].child[k] != 0) set_slot<N, Limited>(c, s, s.count++, r, k);
 }
 
-// The slot to expand next: the largest A, the first of equals; -1 when none can be.
-template <int N> __device__ __forceinline__ int widest_slot(const Slots<N>& s) {
+// The slot to expand next: the largest A, the first of equals; -1 when none can be.  With a stack limit, in a node entered with S,
+// slot j is a candidate only when S + count + h(s) <= limit for every other filled slot s: the largest h and the second largest
+// (the largest of the others, for the slot that holds the largest) are found first.
+template <int N, bool Limited> __device__ __forceinline__ int widest_slot(const Collapse& c, const Slots<N>& s, int S) {
+    int h1 = -(1 << 20), h2 = -(1 << 20), at1 = -1;              // a slot without others passes whatever S
+    if (Limited) {
+#pragma unroll
+        for (int q = 0; q < N; q++)
+            if (q < s.count) {
+                const bool top = s.h[q] > h1;
+                h2 = top ? h1 : max(h2, s.h[q]);
+                at1 = top ? q : at1;
+                h1 = top ? s.h[q] : h1;
+            }
+    }
     int best = -1;
     float top = -1.0f;
 #pragma unroll
     for (int q = 0; q < N; q++)
-        if (q < s.count && s.area[q] > top) { top = s.area[q]; best = q; }
+        if (q < s.count && s.area[q] > top && (!Limited || S + s.count + (q == at1 ? h2 : h1) <= c.limit)) { top = s.area[q]; best = q; }
     return best;
 }
 
@@ -139,23 +178,23 @@ template <int N> __device__ __forceinline__ int slot_ref(const Slots<N>& s, int 
 }
 
 // Slot j takes its node's child 0; the node's child 1 becomes the next slot.
-template <int N> __device__ __forceinline__ void expand_slot(const Collapse& c, Slots<N>& s, int j) {
+template <int N, bool Limited> __device__ __forceinline__ void expand_slot(const Collapse& c, Slots<N>& s, int j) {
     const int node = slot_ref(s, j) - 1;
-    set_slot(c, s, j, node, 0);
-    if (c.nodes[node].child[1] != 0) set_slot(c, s, s.count++, node, 1);
+    set_slot<N, Limited>(c, s, j, node, 0);
+    if (c.nodes[node].child[1] != 0) set_slot<N, Limited>(c, s, s.count++, node, 1);
 }
 
-// The whole growth of the wide node rooted at r.
-template <int N> __device__ __forceinline__ void grow(const Collapse& c, Slots<N>& s, int r) {
-    first_slots(c, s, r);
+// The whole growth of the wide node rooted at r and entered with S.
+template <int N, bool Limited> __device__ __forceinline__ void grow(const Collapse& c, Slots<N>& s, int r, int S) {
+    first_slots<N, Limited>(c, s, r);
     for (int e = 0; e < N - 1 && s.count < N; e++) {
-        const int best = widest_slot(s);
+        const int best = widest_slot<N, Limited>(c, s, S);
         if (best < 0) break;
-        expand_slot(c, s, best);
+        expand_slot<N, Limited>(c, s, best);
     }
 }
 
-template <int N> __global__ __launch_bounds__(kBlock) void k_collapse_flags(Collapse c) {
+template <int N, bool Limited> __global__ __launch_bounds__(kBlock) void k_collapse_flags(Collapse c) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= c.num_nodes) return;
     int flags = 0, is_root = 0;
@@ -190,12 +229,12 @@ template <int N> __global__ __launch_bounds__(kBlock) void k_collapse_flags(Coll
         bool inside = false;                                      // i is expanded inside one of them
         for (int w = 0; w < kMaxClimb && at != i && !inside; w++) {
             Slots<N> s;
-            first_slots(c, s, at);
+            first_slots<N, Limited>(c, s, at);
             // the slot on my path: the turn's side (a root without child 0 keeps child 1 in slot 0)
             int on = (int)(turns & 1) != 0 && c.nodes[at].child[0] != 0;
             turns >>= 1; depth--;
             for (int e = 0; e < N - 1 && s.count < N; e++) {
-                const int best = widest_slot(s);
+                const int best = widest_slot<N, Limited>(c, s, above);
                 if (best < 0) break;
                 int next = on;
                 if (best == on) {
@@ -203,7 +242,7 @@ template <int N> __global__ __launch_bounds__(kBlock) void k_collapse_flags(Coll
                     if (turns & 1) next = s.count;
                     turns >>= 1; depth--;
                 }
-                expand_slot(c, s, best);
+                expand_slot<N, Limited>(c, s, best);
                 on = next;
             }
             above += s.count - 1;
@@ -212,8 +251,9 @@ template <int N> __global__ __launch_bounds__(kBlock) void k_collapse_flags(Coll
         }
         if (!inside && at == i) {
             Slots<N> s;
-            grow(c, s, i);
+            grow<N, Limited>(c, s, i, above);
             atomicMax(&c.info[kInfoStackBound], above + s.count - 1);
+            if (Limited) c.above[i] = above;
             is_root = 1;
         }
     }
@@ -265,14 +305,14 @@ __global__ __launch_bounds__(kBlock) void k_collapse_packets(Collapse c, Tri4* _
     reinterpret_cast<int4*>(out)[13] = make_int4(geom[0], geom[1], geom[2], geom[3]);
 }
 
-template <class Node> __global__ __launch_bounds__(kBlock) void k_collapse_nodes(Collapse c, Node* __restrict__ wide) {
+template <class Node, bool Limited> __global__ __launch_bounds__(kBlock) void k_collapse_nodes(Collapse c, Node* __restrict__ wide) {
     constexpr int N = kArity<Node>;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= c.num_nodes || c.root[i] == 0) return;
     Node& out = wide[c.wide_id[i]];
     const bool whole = c.small[i] != 0;                           // node 0 only: the whole tree is one packet
     Slots<N> s;
-    if (whole) s.count = 0; else grow(c, s, i);
+    if (whole) s.count = 0; else grow<N, Limited>(c, s, i, Limited ? c.above[i] : 0);
 #pragma unroll
     for (int q = 0; q < N; q++) {
         if (whole && q == 0) {

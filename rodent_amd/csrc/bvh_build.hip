@@ -33,7 +33,8 @@
 // existing hierarchy in place from moved vertices; the topology stays.  rodent_hip_refit_bvh4_tri4 / _bvh8_tri4 do the same for
 // Node4 / Node8 + Tri4 (k_refit_wide_links, k_refit_tri4, k_refit_wide_climb; CPU model: tests/refit_wide_model.py).
 // Collapse (build_collapse.h, rodent_hip_collapse_bvh2_tri1): any BVH2 / Tri1 becomes Node4 / Node8 + Tri4 by bounded walks per node,
-// no thread waiting for another (CPU model: tests/collapse_model.py).
+// no thread waiting for another (CPU model: tests/collapse_model.py); rodent_hip_collapse_bvh2_tri1_bounded: the same under a stack limit
+// (tests/collapse_bounded_model.py).
 // Every value is a function of the inputs alone: min / max are exact and do not depend on the order they are taken in, the sort is
 // stable, and arrival order decides only WHICH thread computes a node, never what it computes.
 #include <hip/hip_runtime.h>
@@ -143,16 +144,18 @@ struct CollapseScratch {
     uint32_t *wide_id, *nodetot;  // per node / per block of nodes
     int* mark;                    // per Tri1 record
     uint32_t *packet_id, *rectot; // per record / per block of records
+    int *height, *above;          // per node, behind everything else: only a collapse with a stack limit has them
     size_t bytes;
 };
 
-CollapseScratch carve_collapse(char* base, int num_nodes, int num_bvh_tris) {
+CollapseScratch carve_collapse(char* base, int num_nodes, int num_bvh_tris, bool bounded) {
     CollapseScratch s{};
     Carver c{base};
     const size_t N = (size_t)num_nodes, T = (size_t)num_bvh_tris;
     c.take(s.parent, N); c.take(s.arrivals, N); c.take(s.small, N); c.take(s.small_first, N); c.take(s.root, N);
     c.take(s.wide_id, N); c.take(s.nodetot, (N + kBlock - 1) / kBlock);
     c.take(s.mark, T); c.take(s.packet_id, T); c.take(s.rectot, (T + kBlock - 1) / kBlock);
+    if (bounded) { c.take(s.height, N); c.take(s.above, N); }
     s.bytes = c.bytes;
     return s;
 }
@@ -380,23 +383,24 @@ int32_t check_refit_args(int32_t dev, const float* vertices, int32_t num_vertice
 }
 
 // The collapse after its argument checks: info words and record marks zeroed, parent slots set to -1, then the kernels of
-// build_collapse.h: a fixed list of launches whatever the tree.
-template <class Node>
-int32_t launch_collapse(const Node2* nodes, int num_nodes, const Tri1* tris, int num_bvh_tris, Node* wide_nodes, Tri4* packets,
+// build_collapse.h: a fixed list of launches whatever the tree.  Limited: with a stack limit (`limit` > 0), one launch more.
+template <class Node, bool Limited>
+int32_t launch_collapse(int limit, const Node2* nodes, int num_nodes, const Tri1* tris, int num_bvh_tris, Node* wide_nodes, Tri4* packets,
                         void* scratch, int32_t* info_dev, void* stream_) {
     constexpr int N = kArity<Node>;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const CollapseScratch s = carve_collapse(static_cast<char*>(scratch), num_nodes, num_bvh_tris);
+    const CollapseScratch s = carve_collapse(static_cast<char*>(scratch), num_nodes, num_bvh_tris, Limited);
     if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess
         || hipMemsetAsync(s.parent, 0xFF, 4 * (size_t)num_nodes, stream) != hipSuccess
         || hipMemsetAsync(s.mark, 0, 4 * (size_t)num_bvh_tris, stream) != hipSuccess)
         return RODENT_BUILD_ERR_LAUNCH;
     const Collapse c{nodes, num_nodes, tris, num_bvh_tris, s.parent, s.small, s.small_first, s.root, s.mark, s.wide_id, s.packet_id,
-                     info_dev};
+                     info_dev, s.height, s.above, Limited ? limit : 0};
     const int nb = blocks_for(num_nodes), tb = blocks_for(num_bvh_tris);
     hipLaunchKernelGGL(k_refit_links, dim3(nb), dim3(kBlock), 0, stream, nodes, num_nodes, num_bvh_tris, s.parent, s.arrivals, info_dev);
     hipLaunchKernelGGL(k_collapse_small, dim3(nb), dim3(kBlock), 0, stream, c);
-    hipLaunchKernelGGL(k_collapse_flags<N>, dim3(nb), dim3(kBlock), 0, stream, c);
+    if (Limited) hipLaunchKernelGGL(k_collapse_height, dim3(nb), dim3(kBlock), 0, stream, c);
+    hipLaunchKernelGGL((k_collapse_flags<N, Limited>), dim3(nb), dim3(kBlock), 0, stream, c);
     hipLaunchKernelGGL(k_collapse_totals, dim3(nb), dim3(kBlock), 0, stream, s.root, num_nodes, s.nodetot);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.nodetot, nb, info_dev + kInfoWideNodes);
     hipLaunchKernelGGL(k_collapse_ids, dim3(nb), dim3(kBlock), 0, stream, s.root, num_nodes, s.nodetot, s.wide_id);
@@ -404,18 +408,28 @@ int32_t launch_collapse(const Node2* nodes, int num_nodes, const Tri1* tris, int
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.rectot, tb, info_dev + kInfoPackets);
     hipLaunchKernelGGL(k_collapse_ids, dim3(tb), dim3(kBlock), 0, stream, s.mark, num_bvh_tris, s.rectot, s.packet_id);
     hipLaunchKernelGGL(k_collapse_packets, dim3(tb), dim3(kBlock), 0, stream, c, packets);
-    hipLaunchKernelGGL(k_collapse_nodes<Node>, dim3(nb), dim3(kBlock), 0, stream, c, wide_nodes);
+    hipLaunchKernelGGL((k_collapse_nodes<Node, Limited>), dim3(nb), dim3(kBlock), 0, stream, c, wide_nodes);
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
 
-int32_t collapse(int32_t dev, int32_t width, const Node2* nodes, int32_t num_nodes, const Tri1* tris, int32_t num_bvh_tris,
-                 void* wide_nodes, Tri4* packets, void* scratch, int32_t* info_dev, void* stream) {
+template <class Node>
+int32_t launch_collapse(int limit, const Node2* nodes, int num_nodes, const Tri1* tris, int num_bvh_tris, void* wide_nodes, Tri4* packets,
+                        void* scratch, int32_t* info_dev, void* stream) {
+    Node* wide = static_cast<Node*>(wide_nodes);
+    return limit > 0 ? launch_collapse<Node, true>(limit, nodes, num_nodes, tris, num_bvh_tris, wide, packets, scratch, info_dev, stream)
+                     : launch_collapse<Node, false>(0, nodes, num_nodes, tris, num_bvh_tris, wide, packets, scratch, info_dev, stream);
+}
+
+// Every collapse entry: stack_limit = 0 is the collapse without a limit.
+int32_t collapse(int32_t dev, int32_t width, int32_t stack_limit, const Node2* nodes, int32_t num_nodes, const Tri1* tris,
+                 int32_t num_bvh_tris, void* wide_nodes, Tri4* packets, void* scratch, int32_t* info_dev, void* stream) {
     if (width != 4 && width != 8) return RODENT_BUILD_ERR_WIDTH;
+    if (stack_limit < 0 || stack_limit > RODENT_BUILD_MAX_STACK_LIMIT) return RODENT_BUILD_ERR_STACK_LIMIT;
     const int32_t rc = check_tree_args(dev, num_nodes, num_bvh_tris, !nodes || !tris || !wide_nodes || !packets || !scratch || !info_dev);
     if (rc != RODENT_BUILD_OK) return rc;
     return width == 4
-        ? launch_collapse(nodes, num_nodes, tris, num_bvh_tris, static_cast<Node4*>(wide_nodes), packets, scratch, info_dev, stream)
-        : launch_collapse(nodes, num_nodes, tris, num_bvh_tris, static_cast<Node8*>(wide_nodes), packets, scratch, info_dev, stream);
+        ? launch_collapse<Node4>(stack_limit, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, stream)
+        : launch_collapse<Node8>(stack_limit, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, stream);
 }
 
 template <class Node>
@@ -614,13 +628,18 @@ int32_t rodent_hip_refit_bvh8_tri4_sync(int32_t dev, const float* vertices, int3
 
 int64_t rodent_hip_collapse_scratch_bytes(int32_t width, int32_t num_nodes, int32_t num_bvh_tris) {
     if ((width != 4 && width != 8) || num_nodes < 1 || num_bvh_tris < 1) return -1;
-    return (int64_t)carve_collapse(nullptr, num_nodes, num_bvh_tris).bytes;
+    return (int64_t)carve_collapse(nullptr, num_nodes, num_bvh_tris, false).bytes;
+}
+
+int64_t rodent_hip_collapse_bounded_scratch_bytes(int32_t width, int32_t num_nodes, int32_t num_bvh_tris) {
+    if ((width != 4 && width != 8) || num_nodes < 1 || num_bvh_tris < 1) return -1;
+    return (int64_t)carve_collapse(nullptr, num_nodes, num_bvh_tris, true).bytes;
 }
 
 int32_t rodent_hip_collapse_bvh2_tri1(int32_t dev, int32_t width, const struct Node2* nodes, int32_t num_nodes, const struct Tri1* tris,
                                       int32_t num_bvh_tris, void* wide_nodes, struct Tri4* packets, void* scratch, int32_t* info_dev,
                                       void* stream) {
-    return collapse(dev, width, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, stream);
+    return collapse(dev, width, 0, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, stream);
 }
 
 int32_t rodent_hip_collapse_bvh2_tri1_sync(int32_t dev, int32_t width, const struct Node2* nodes, int32_t num_nodes,
@@ -630,7 +649,25 @@ int32_t rodent_hip_collapse_bvh2_tri1_sync(int32_t dev, int32_t width, const str
     const int64_t bytes = rodent_hip_collapse_scratch_bytes(width, num_nodes, num_bvh_tris);
     if (bytes < 0) return RODENT_BUILD_ERR_NUM_NODES;
     return build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
-        return collapse(dev, width, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, nullptr);
+        return collapse(dev, width, 0, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, nullptr);
+    });
+}
+
+int32_t rodent_hip_collapse_bvh2_tri1_bounded(int32_t dev, int32_t width, int32_t stack_limit, const struct Node2* nodes,
+                                              int32_t num_nodes, const struct Tri1* tris, int32_t num_bvh_tris, void* wide_nodes,
+                                              struct Tri4* packets, void* scratch, int32_t* info_dev, void* stream) {
+    return collapse(dev, width, stack_limit, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_collapse_bvh2_tri1_bounded_sync(int32_t dev, int32_t width, int32_t stack_limit, const struct Node2* nodes,
+                                                   int32_t num_nodes, const struct Tri1* tris, int32_t num_bvh_tris, void* wide_nodes,
+                                                   struct Tri4* packets, int32_t* info) {
+    if (width != 4 && width != 8) return RODENT_BUILD_ERR_WIDTH;
+    if (stack_limit < 0 || stack_limit > RODENT_BUILD_MAX_STACK_LIMIT) return RODENT_BUILD_ERR_STACK_LIMIT;
+    const int64_t bytes = rodent_hip_collapse_bounded_scratch_bytes(width, num_nodes, num_bvh_tris);
+    if (bytes < 0) return RODENT_BUILD_ERR_NUM_NODES;
+    return build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
+        return collapse(dev, width, stack_limit, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, nullptr);
     });
 }
 

@@ -9,14 +9,15 @@ into BVH4 / BVH8 + Tri4.
     refit_wide(wide, moved_vertices, indices)      # the same for a BVH4 / BVH8 + Tri4 DeviceBvh (collapsed, or of the host builder)
     wide = collapse_wide(bvh, 8)                   # the BVH2 collapsed into BVH8 / Tri4 on the device; wide.info[3]: its stack bound
     wide = build_wide(vertices, indices, 8, max_leaf=4, treelet_passes=3)    # build_bvh2 then collapse_wide; wide.bvh2 is the BVH2
+    wide = build_wide(vertices, indices, 8, stack_limit=63)    # a tree no ray can overflow the traversal stack of: info[3] <= 63
 
 The result is a pure function of the inputs, byte for byte.  As a tool:
 
     python -m rodent_amd.gpubuild scene.rscene -o out.bvh [--max-leaf N] [--treelet-passes N] [--split-budget F [--max-pieces K]]
-                                  [--width 4] [--width 8]
+                                  [--width 4] [--width 8] [--stack-limit L]
 
 writes a .bvh holding the BVH2_TRI1 block of the scene's mesh and, for every --width, its collapsed BVH4_TRI4 / BVH8_TRI4 block
-(bench_traversal reads them).
+(bench_traversal reads them), collapsed under the stack limit L when one is given.
 """
 from __future__ import annotations
 
@@ -36,11 +37,12 @@ INFO_WORDS = 4
 SPLIT_INFO_WORDS = 8                   # + [4] Tri1 count (references) [5] triangles split [6] splits allotted but not made [7] 0
 MAX_PIECES, MAX_SPLIT_BUDGET = 64, 4.0
 BAD_INDEX, NON_FINITE, BAD_TOPOLOGY = 1, 2, 4
-ERR_SPLIT, ERR_NUM_NODES, ERR_WIDTH = -10, -11, -12
+ERR_SPLIT, ERR_NUM_NODES, ERR_WIDTH, ERR_STACK_LIMIT = -10, -11, -12, -13
+MAX_STACK_LIMIT = 63
 _ERRORS = {-1: "num_tris outside [1, 2^25]", -2: "max_leaf outside [1, 8]", -3: "no vertices", -4: "NULL pointer",
            -5: "no such device", -6: "launch failed", -8: "treelet_passes outside [0, 3]", -9: "node_cost / tri_cost outside (0, 1e6]",
            ERR_SPLIT: "split budget outside [0, 4] or max_pieces outside [1, 64]", ERR_NUM_NODES: "a hierarchy without nodes or triangles",
-           ERR_WIDTH: "width other than 4 or 8"}
+           ERR_WIDTH: "width other than 4 or 8", ERR_STACK_LIMIT: "stack_limit outside [0, 63]"}
 _FLAGS = ((BAD_INDEX, "vertex index outside the vertex array"), (NON_FINITE, "non-finite vertex coordinate"),
           (BAD_TOPOLOGY, "malformed hierarchy (child id or prim_id out of range, leaf without end bit, node with two parents)"))
 
@@ -207,20 +209,28 @@ def refit_wide(bvh: abi.DeviceBvh, vertices, indices, stream=None, scratch=None)
     return _refit(f"rodent_hip_refit_bvh{bvh.width}_tri4", need, bvh, vertices, indices, stream, scratch)
 
 
-def collapse_wide(bvh2: abi.DeviceBvh, width, stream=None, scratch=None) -> abi.DeviceBvh:
+def collapse_wide(bvh2: abi.DeviceBvh, width, stream=None, scratch=None, stack_limit=0) -> abi.DeviceBvh:
     """Collapses the BVH2 / Tri1 hierarchy `bvh2` (of build_bvh2, any options, or of a host builder) into a new BVH4 / BVH8 + Tri4
     DeviceBvh of `width` slots to a node (rodent_hip_collapse_bvh2_tri1); `bvh2` is only read.  The result's num_tris counts its Tri4
     packets, as for a host builder's wide tree, and its `info` holds [0] wide nodes [1] packets [2] flags [3] the stack bound B: no ray's
     traversal stack holds more than B entries, so B <= 63 rules an overflow out (B is not checked here).  Stream and scratch as in
-    build_bvh2.  Raises BuildError on a malformed hierarchy."""
+    build_bvh2.  Raises BuildError on a malformed hierarchy.
+
+    stack_limit = L in 1 ... 63 (rodent_hip_collapse_bvh2_tri1_bounded): the growth stops widening where that would take B past L, so
+    B <= max(L, H(0)), H(0) being the bound of the BVH2 itself: 63 gives B <= 63 for every build_bvh2 tree.  0: no limit."""
     if not torch.cuda.is_available():
         raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
     if bvh2.width != 2:
         raise ValueError("collapse_wide: a BVH2 / Tri1 hierarchy is needed")
     if width not in (4, 8):
         raise BuildError(f"collapse_wide: {_ERRORS[ERR_WIDTH]}")
-    dev, entry = bvh2.dev, "rodent_hip_collapse_bvh2_tri1"
-    need = abi.lib().rodent_hip_collapse_scratch_bytes(width, bvh2.num_nodes, bvh2.num_tris)
+    if not 0 <= stack_limit <= MAX_STACK_LIMIT:
+        raise BuildError(f"collapse_wide: {_ERRORS[ERR_STACK_LIMIT]}")
+    dev = bvh2.dev
+    # without a limit the entry, its arguments and its scratch are what they were
+    entry, limit, sizes = (("rodent_hip_collapse_bvh2_tri1_bounded", (int(stack_limit),), "rodent_hip_collapse_bounded_scratch_bytes")
+                           if stack_limit else ("rodent_hip_collapse_bvh2_tri1", (), "rodent_hip_collapse_scratch_bytes"))
+    need = getattr(abi.lib(), sizes)(width, bvh2.num_nodes, bvh2.num_tris)
     if need < 0:
         raise BuildError(f"{entry}: {_ERRORS[ERR_NUM_NODES]}")
     cuda = f"cuda:{dev}"
@@ -231,7 +241,7 @@ def collapse_wide(bvh2: abi.DeviceBvh, width, stream=None, scratch=None) -> abi.
     nodes = torch.empty(bvh2.num_nodes * node_dt.itemsize, dtype=torch.uint8, device=cuda)
     tris = torch.empty(bvh2.num_tris * F.TRI4.itemsize, dtype=torch.uint8, device=cuda)
     info = torch.empty(INFO_WORDS, dtype=torch.int32, device=cuda)
-    words = _enqueue(entry, dev, stream, info, (bvh2.nodes, bvh2.tris, nodes, tris, scratch), int(width), bvh2.nodes.data_ptr(),
+    words = _enqueue(entry, dev, stream, info, (bvh2.nodes, bvh2.tris, nodes, tris, scratch), int(width), *limit, bvh2.nodes.data_ptr(),
                      bvh2.num_nodes, bvh2.tris.data_ptr(), bvh2.num_tris, nodes.data_ptr(), tris.data_ptr(), scratch.data_ptr())
     _raise_flags(entry, words)
     wide = abi.DeviceBvh.from_tensors(width, nodes, tris, int(words[0]), int(words[1]), dev)
@@ -239,13 +249,16 @@ def collapse_wide(bvh2: abi.DeviceBvh, width, stream=None, scratch=None) -> abi.
     return wide
 
 
-def build_wide(vertices, indices, width, dev=0, stream=None, **options) -> abi.DeviceBvh:
-    """build_bvh2(vertices, indices, **options) then collapse_wide(..., width) on one stream: a BVH4 / BVH8 + Tri4 hierarchy built
-    without the host builder.  The BVH2 it came from stays reachable as `.bvh2` (refit_wide needs only the wide tree)."""
+def build_wide(vertices, indices, width, dev=0, stream=None, stack_limit=0, **options) -> abi.DeviceBvh:
+    """build_bvh2(vertices, indices, **options) then collapse_wide(..., width, stack_limit=stack_limit) on one stream: a BVH4 / BVH8 +
+    Tri4 hierarchy built without the host builder.  The BVH2 it came from stays reachable as `.bvh2` (refit_wide needs only the wide
+    tree)."""
     if width not in (4, 8):
         raise BuildError(f"build_wide: {_ERRORS[ERR_WIDTH]}")
+    if not 0 <= stack_limit <= MAX_STACK_LIMIT:
+        raise BuildError(f"build_wide: {_ERRORS[ERR_STACK_LIMIT]}")
     bvh2 = build_bvh2(vertices, indices, dev=dev, stream=stream, **options)
-    wide = collapse_wide(bvh2, width, stream=stream)
+    wide = collapse_wide(bvh2, width, stream=stream, stack_limit=stack_limit)
     wide.bvh2 = bvh2
     return wide
 
@@ -278,6 +291,8 @@ def main(argv=None):
     ap.add_argument("--max-pieces", type=int, default=None, help="the most references one triangle may become (1 ... 64, default 64)")
     ap.add_argument("--width", type=int, action="append", choices=(4, 8), default=[],
                     help="also write the BVH2 collapsed into this width (BVH4_TRI4 / BVH8_TRI4 block); may be given twice")
+    ap.add_argument("--stack-limit", type=int, default=0,
+                    help="collapse under this stack limit: the stack bound is then at most max(L, the BVH2's own) (0 ... 63, default 0: none)")
     ap.add_argument("--dev", type=int, default=0)
     a = ap.parse_args(argv)
     sc = Scene(a.scene)
@@ -287,7 +302,7 @@ def main(argv=None):
     blocks = [(F.BVH2_TRI1, nodes, tris)]
     print(f"{a.output}: {len(tris)} triangles, {len(nodes)} nodes, depth {bvh.depth}")
     for width in sorted(set(a.width)):
-        wide = collapse_wide(bvh, width)
+        wide = collapse_wide(bvh, width, stack_limit=a.stack_limit)
         blocks.append((abi.BLOCK_OF_WIDTH[width], *download_wide(wide)))
         print(f"{a.output}: BVH{width}: {wide.num_nodes} nodes, {wide.num_tris} packets, stack bound {wide.info[3]}")
     F.write_bvh(a.output, blocks)

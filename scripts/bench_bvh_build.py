@@ -26,6 +26,8 @@ For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> conve
     time of rodent_hip_collapse_bvh2_tri1 into BVH4 and BVH8 (median of 20 after 3 warm-ups) beside the build before it, the wide
     nodes, packets, lane fill (records / (4 x packets)) and stack bound B, and Mrays/s (camera and random rays, closest and any hit,
     default variants) of the collapsed tree, of the host builder's tree of the same width (bvh_extractor) and of the BVH2 it came from.
+    With --stack-limit L one more row per tree and width: the collapse under that limit (rodent_hip_collapse_bvh2_tri1_bounded) beside
+    the one without: time with min and max, wide nodes, B, the BVH2's own H(0), closest-hit rates of both trees.
 
     python scripts/bench_bvh_build.py [--scenes atrium gallery crown plant] [--builds 20] [-o profiles/gpu_bvh_build.txt]
     python scripts/bench_bvh_build.py --treelet-passes 3 -o profiles/gpu_bvh_build_opt.txt
@@ -33,6 +35,7 @@ For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> conve
     python scripts/bench_bvh_build.py --scenes atrium --treelet-passes 3 --split-budget 1 --refit -o profiles/gpu_bvh_refit.txt
     python scripts/bench_bvh_build.py --scenes atrium gallery --refit-wide -o profiles/gpu_bvh_refit_wide.txt
     python scripts/bench_bvh_build.py --scenes atrium gallery --collapse -o profiles/gpu_bvh_collapse.txt
+    python scripts/bench_bvh_build.py --scenes atrium gallery --collapse --stack-limit 63 -o profiles/gpu_bvh_collapse_bounded.txt
 """
 from __future__ import annotations
 
@@ -54,7 +57,8 @@ import torch  # noqa: E402
 from rodent_amd import abi, build, formats as F, gpubuild, raygen, scene as S, scenes  # noqa: E402
 
 
-def event_ms(fn, warmup, reps):
+def event_ms(fn, warmup, reps, spread=False):
+    """The median device-event time of fn() in ms; with `spread`: (median, min, max)."""
     for _ in range(warmup):
         fn()
     times = []
@@ -65,7 +69,7 @@ def event_ms(fn, warmup, reps):
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b))
-    return float(np.median(times))
+    return (float(np.median(times)), min(times), max(times)) if spread else float(np.median(times))
 
 
 def tree_depth(nodes):
@@ -79,6 +83,17 @@ def tree_depth(nodes):
         c = child[frontier].reshape(-1)
         frontier = c[c > 0] - 1
     return depth
+
+
+def input_height(nodes, tris):
+    """H(0) of a BVH2 (include/rodent_build.h, "Stack limit"): the bound of the tree left binary, by the model's level-wise pass."""
+    import collapse_bounded_model as BM
+    import collapse_model as M
+    child = nodes["child"].astype(np.int64)
+    flags, levels, run = M.guards(child, tris["prim_id"] < 0)
+    assert flags == 0
+    small, _ = M.small_subtrees(child, levels, run)
+    return int(BM.heights(child, levels, small)[0])
 
 
 def refit_wide_table(a):
@@ -141,6 +156,10 @@ def collapse_table(a):
              f"{'scene':>8} {'tris':>9} {'bvh2':>6} {'build ms':>8} {'nodes2':>8} | {'wide':>4} {'clps ms':>7} {'nodes':>8} {'packets':>8} "
              f"{'fill':>5} {'B':>3} {'host nodes':>10} {'host pk':>8} | {'cam closest':>17} {'cam any':>17} {'rand closest':>17} "
              f"{'rand any':>17}"]
+    if a.stack_limit:
+        lines.insert(1, f"# with --stack-limit {a.stack_limit}, a second row per tree and width: rodent_hip_collapse_bvh2_tri1_bounded under that "
+                     "limit beside the collapse without one: ms = median [min, max] of the 20; H0: the BVH2's own bound H(0); same: the "
+                     "two trees are equal byte for byte; Mrays/s closest hit: bounded tree / tree without a limit")
     print("\n".join(lines), flush=True)
     scenes.DATA.mkdir(parents=True, exist_ok=True)
     stream = torch.cuda.current_stream()
@@ -189,7 +208,7 @@ def collapse_table(a):
                                                                  bvh.num_tris, wide.nodes.data_ptr(), wide.tris.data_ptr(),
                                                                  wide.scratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
                     assert rc == 0
-                collapse_ms = event_ms(one_collapse, 3, 20)
+                collapse_ms, collapse_min, collapse_max = event_ms(one_collapse, 3, 20, spread=True)
                 assert info.cpu().numpy().tolist() == wide.info.tolist()
                 B = int(wide.info[3])
                 if B > 63:
@@ -207,6 +226,29 @@ def collapse_table(a):
                        f"{host.num_tris:>8} | {cells}")
                 lines.append(row)
                 print(row, flush=True)
+                if a.stack_limit:
+                    tight = gpubuild.collapse_wide(bvh, width, stack_limit=a.stack_limit)
+
+                    def one_bounded():
+                        rc = abi.lib().rodent_hip_collapse_bvh2_tri1_bounded(
+                            0, width, a.stack_limit, bvh.nodes.data_ptr(), bvh.num_nodes, bvh.tris.data_ptr(), bvh.num_tris,
+                            tight.nodes.data_ptr(), tight.tris.data_ptr(), tight.scratch.data_ptr(), info.data_ptr(),
+                            C.c_void_p(stream.cuda_stream))
+                        assert rc == 0
+                    ms, lo_ms, hi_ms = event_ms(one_bounded, 3, 20, spread=True)
+                    assert info.cpu().numpy().tolist() == tight.info.tolist()
+                    h0 = input_height(*gpubuild.download(bvh))
+                    assert tight.info[3] <= max(a.stack_limit, h0)
+                    same = all(x.tobytes() == y.tobytes() for x, y in zip(gpubuild.download_wide(tight), gpubuild.download_wide(wide)))
+                    rate_t = rate if same else rates(tight)       # equal bytes: the same tree, traced above
+                    row = (f"{name:>8} {n:>9} {label:>6} {'L = ' + str(a.stack_limit):>17} | {'bvh' + str(width):>4} "
+                           f"{ms:>7.3f} [{lo_ms:.3f}, {hi_ms:.3f}] no limit {collapse_ms:.3f} [{collapse_min:.3f}, {collapse_max:.3f}] "
+                           f"nodes {tight.num_nodes} / {wide.num_nodes} fill {bvh.num_tris / (4 * tight.num_tris):.2f} "
+                           f"B {int(tight.info[3])} / {B} H0 {h0} same {same} | "
+                           f"cam {rate_t['cam', False]:.0f} / {rate['cam', False]:.0f} rand {rate_t['rand', False]:.0f} / {rate['rand', False]:.0f}")
+                    lines.append(row)
+                    print(row, flush=True)
+                    del tight
                 del wide, host
             del bvh
         del v, ix, rays_dev, hits
@@ -227,6 +269,8 @@ def main():
                     help="only time the refit of the host builder's BVH4 / BVH8 + Tri4 trees (beside: the BVH2 refit, the host build)")
     ap.add_argument("--collapse", action="store_true",
                     help="only time the collapse of device-built BVH2 trees into BVH4 / BVH8 + Tri4 and trace the collapsed trees")
+    ap.add_argument("--stack-limit", type=int, default=0,
+                    help="with --collapse: one more row per tree and width, the collapse under this stack limit (1 ... 63)")
     ap.add_argument("-o", "--output", default=str(ROOT / "profiles" / "gpu_bvh_build.txt"))
     a = ap.parse_args()
     if a.refit_wide:
