@@ -95,6 +95,51 @@ void    rodent_hip_scene_create_device_bvh_split(int32_t dev, const struct Roden
  * device before and after.  A flag raised by the refit aborts with a message, as a flagged device build does. */
 void    rodent_hip_scene_refit(int32_t dev, const float* vertices, const float* normals, const float* face_normals,
                                const struct RodentLight* lights);
+/* ---- moved geometry that is already on the device ----
+ * rodent_hip_scene_refit above takes HOST tables the caller computed, waits for the device and walks the hierarchy on the host.  The
+ * entries below take moved vertices that live in HBM, derive everything the scene keeps from positions on the device and enqueue it on
+ * a stream.  The rules, all in fp32 with every operation rounded on its own (they restate host/mesh.cpp, host/scene.cpp and host/vec.h:
+ * a scene loaded from an OBJ without `vn` lines reproduces the loader's own tables; CPU model: tests/scene_update_model.py):
+ *   Face normal of triangle t: a = v1 - v0, b = v2 - v0 (through `indices`); c = (a.y b.z - a.z b.y, a.z b.x - a.x b.z,
+ *     a.x b.y - a.y b.x); l = sqrt((c.x c.x + c.y c.y) + c.z c.z); the normal is c * (1.0f / l), w = 0.  A degenerate triangle gives
+ *     NaN, as on the host: nothing special is done for it.
+ *   Smooth vertex normals (normals_dev == NULL): s = (0, 0, 0); for every corner (t, k) that names the vertex, in ascending (t, k)
+ *     order, s += face normal of t (a triangle naming a vertex twice counts twice); l2 = (s.x s.x + s.y s.y) + s.z s.z; if
+ *     l2 <= FLT_EPSILON or l2 is NaN the normal is (0, 1, 0), otherwise s * (1.0f / sqrt(l2)); w = 0.  A vertex no triangle names gets
+ *     (0, 1, 0).  The fixed order comes from incidence lists (offsets + triangle ids) built once, on the host, by the prepare call:
+ *     indices never change under a refit.
+ *   Light k is bound to the lowest triangle t whose material is emissive and whose light_ids[t] == k; a light no such triangle names
+ *     keeps its bytes.  A bound light gets v0, v1, v2 (three floats each; the fourth word stays as stored), and with c and l as above
+ *     n = c * (1.0f / l) and inv_area = 1.0f / (0.5f * l).  The colour stays as stored.
+ *   tri_shade record t (only when the scene has the table): the face normal's x, y, z, then the three corners' vertex normals, gathered.
+ *   Top images (31 and 255 records of 16 words): breadth first from the root, a node's child 0 before its child 1; a child gets a slot
+ *     (and becomes a link) only while fewer than `capacity` slots are taken; words 0 .. 11 the bounds, 12 .. 13 the child ids / links,
+ *     14 the node's 1-based id, 15 zero; unused records are all zero.  (Computed level by level: the slot of child j of the i-th node of a
+ *     level is the count of slots taken before the level's children plus the inner children of the level's earlier nodes, plus one for
+ *     j = 1 when child 0 is inner.)
+ *
+ * rodent_hip_scene_refit_prepare: one-time, synchronous: allocates what rodent_hip_scene_refit_device needs for the current scene (refit
+ * scratch and info words; the light -> triangle table; with smooth_normals != 0 the vertex -> triangle incidence lists).  Owned by the
+ * scene, freed with it.  Calling it again is harmless (smooth_normals is sticky once set). */
+void    rodent_hip_scene_refit_prepare(int32_t dev, int32_t smooth_normals);
+/* The scene's geometry moved; all pointers are DEVICE pointers on `dev`.
+ *   vertices_dev: num_vertices x 4 floats; may be the scene's own table (rodent_hip_scene_tables), then nothing is copied.
+ *   normals_dev:  num_vertices x 4 floats, or NULL: smooth normals are recomputed (rule above).
+ * Enqueues on `stream` (NULL = the null stream): the copies, face normals, light records, vertex normals, the in-place BVH2 refit
+ * (rodent_hip_refit_bvh2_tri1), both LDS top images and the tri_shade records, into the scene's existing allocations.  After the
+ * first call (which prepares if nobody did) it allocates nothing, copies nothing to or from the host and does not wait for the device.
+ * A refit starts behind the one before it, and a frame started afterwards (render(), rodent_hip_render_rows / _tiles, the stage-level
+ * entries, on any stream) behind the last refit: both are ordered with an event.  A frame call returns when its rows are in the film,
+ * so a frame started earlier has finished on the old scene.  No scene loaded or a NULL vertices_dev aborts with a message. */
+void    rodent_hip_scene_refit_device(int32_t dev, const float* vertices_dev, const float* normals_dev, void* stream);
+/* Waits for the last rodent_hip_scene_refit_device of `dev`, copies the refit's RODENT_BUILD_INFO_WORDS words to info (may be NULL).
+ * Returns 0 for a sound refit (no flag, info[0] == node count), else the flags (bit 31 set when nodes are missing).  Never aborts on a
+ * flag.  Before the first refit: 0 and a sound refit's words. */
+int32_t rodent_hip_scene_refit_status(int32_t dev, int32_t* info);
+/* DEVICE pointers of the tables the scene owns, for tools and tests (like rodent_hip_scene_bvh); out may be NULL. */
+struct RodentSceneTables { float *vertices, *normals, *face_normals; struct RodentLight* lights; float* tri_shade; /* may be NULL */
+                           int32_t *top_image, *top_image_large; int32_t num_vertices, num_tris, num_lights, top_nodes, top_nodes_large; };
+void    rodent_hip_scene_tables(int32_t dev, struct RodentSceneTables* out);
 /* The current scene's hierarchy on device `dev`: DEVICE pointers (owned by the scene) and counts -- for tests and tools. */
 void    rodent_hip_scene_bvh(int32_t dev, const struct Node2** nodes, const struct Tri1** tris, int32_t* num_nodes, int32_t* num_tris);
 void    rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len);   /* defaults 4 / 64 (converter.cpp:1007-1012) */

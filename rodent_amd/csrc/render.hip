@@ -127,6 +127,7 @@ __global__ void k_copy_int(const int* src, int* dst) { *dst = *src; }
 #include "render_shade.h"
 #include "render_mega.h"
 #include "render_sort.h"
+#include "render_update.h"
 
 // ---------------------------------------------------------------------------------------------
 // Host side: per-device state (interface.cpp:324-339), stream slabs, the streaming loop
@@ -138,6 +139,12 @@ struct DevScene {
     unsigned tri_delta = 0;
     SceneDev dev{};
     std::vector<void*> allocs;
+    // what rodent_hip_scene_refit_device needs (rodent_hip_scene_refit_prepare; in `allocs` like every table): the refit's scratch with
+    // its info words behind it, the triangle each light is bound to (-1: none), and for smooth normals the vertices' incidence lists
+    // (vertex v: corner_tri[corner_first[v] .. corner_first[v + 1]), ascending (triangle, corner))
+    char* refit_scratch = nullptr; int32_t* refit_info = nullptr;
+    int *light_tri = nullptr, *corner_first = nullptr, *corner_tri = nullptr;
+    bool refit_enqueued = false;               // RenderDevice::ev_refit marks the end of the last device refit of THIS scene
 };
 
 struct RenderDevice {
@@ -191,6 +198,7 @@ struct RenderDevice {
     DeviceBuffer<int> spill[2];
     hipStream_t aux = nullptr;                     // shadow-ray traversal runs here, beside the compaction / next primary pass
     hipEvent_t ev_shade = nullptr, ev_sec = nullptr, ev_copy = nullptr;
+    hipEvent_t ev_refit = nullptr;                 // recorded behind every rodent_hip_scene_refit_device (DevScene::refit_enqueued)
     int overlap = 1;                               // 0: everything on the caller's stream
     DeviceBuffer<int> hist;
     int* ctl = nullptr;       // [0] primary size, [1] secondary size, [2] error flag, [8..] bin_total, bin_begin, bin_end (kMaxBins each)
@@ -468,13 +476,18 @@ void ensure_film(RenderDevice& r) {
     HIP_CHECK(hipMemset(r.film, 0, sizeof(float) * 3 * (size_t)r.film_w * r.film_h));
 }
 
-// What every call that works on the scene opens with: the device current, its film and scene there.
-RenderDevice& open_scene(RenderDevice& r) { HIP_CHECK(hipSetDevice(r.dev)); ensure_film(r); require_scene(r); return r; }
+// What every call that works on the scene opens with: the device current, its film and scene there, and `stream` behind the last
+// rodent_hip_scene_refit_device, whichever stream that took (an event, not a device-wide wait).
+RenderDevice& open_scene(RenderDevice& r, hipStream_t stream) {
+    HIP_CHECK(hipSetDevice(r.dev)); ensure_film(r); require_scene(r);
+    if (r.scene.refit_enqueued) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_refit, 0));
+    return r;
+}
 
 // The head of a frame call on `stream`: open_scene, the first `ctl_words` control words zero (the streaming loop uses eight, the megakernel
 // the sizes and the error flag only) and the counters started again, or continued (rodent_hip_render_tiles)
 void frame_begin(RenderDevice& r, hipStream_t stream, int ctl_words) {
-    open_scene(r);
+    open_scene(r, stream);
     HIP_CHECK(hipMemsetAsync(r.ctl, 0, sizeof(int) * ctl_words, stream));
     if (!r.counters_continue) { HIP_CHECK(hipMemsetAsync(r.counters, 0, sizeof(unsigned long long) * kNumCounters, stream));
         r.call_iterations = r.call_generated = 0; }
@@ -892,6 +905,55 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOption
     resolve_refill(r);
 }
 
+// rodent_hip_scene_refit_prepare: one-time and synchronous.  The tables it reads back (indices, light ids, materials) never change under
+// a refit, so the lists it builds on the host hold for the scene's life.
+void refit_prepare(RenderDevice& r, bool smooth_normals) {
+    DevScene& s = r.scene;
+    HIP_CHECK(hipSetDevice(r.dev));
+    if (!r.ev_refit) HIP_CHECK(hipEventCreateWithFlags(&r.ev_refit, hipEventDisableTiming));
+    const size_t nv = (size_t)s.num_vertices, nt = (size_t)s.dev.num_tris;
+    std::vector<int32_t> indices;
+    if (!s.refit_info || (smooth_normals && !s.corner_first)) {
+        indices.resize(4 * nt);
+        HIP_CHECK(hipMemcpy(indices.data(), s.dev.indices, sizeof(int32_t) * indices.size(), hipMemcpyDeviceToHost));
+    }
+    if (!s.refit_info) {
+        const int64_t scratch_bytes = std::max<int64_t>(rodent_hip_refit_scratch_bytes(s.num_nodes, s.num_bvh_tris), 0);
+        HIP_CHECK(hipMalloc(&s.refit_scratch, (size_t)scratch_bytes + 4 * RODENT_BUILD_INFO_WORDS));
+        s.allocs.push_back(s.refit_scratch);
+        int32_t* const info = reinterpret_cast<int32_t*>(s.refit_scratch + scratch_bytes);
+        HIP_CHECK(hipMemset(info, 0, 4 * RODENT_BUILD_INFO_WORDS));
+        // light k: the lowest emissive triangle whose light id is k
+        std::vector<int32_t> light_ids(nt);
+        std::vector<RodentMaterial> materials((size_t)s.dev.num_materials);
+        HIP_CHECK(hipMemcpy(light_ids.data(), s.dev.light_ids, sizeof(int32_t) * nt, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(materials.data(), s.dev.materials, sizeof(RodentMaterial) * materials.size(), hipMemcpyDeviceToHost));
+        std::vector<int> light_tri((size_t)s.dev.num_lights, -1);
+        for (size_t t = 0; t < nt; t++) {
+            const int32_t k = light_ids[t];
+            if (materials[indices[4 * t + 3]].emissive && k >= 0 && k < s.dev.num_lights && light_tri[k] < 0) light_tri[k] = (int)t;
+        }
+        s.light_tri = upload(s, light_tri.data(), light_tri.size());
+        s.refit_info = info;
+    }
+    if (smooth_normals && !s.corner_first) {
+        std::vector<int> first(nv + 1, 0), tri(3 * nt);
+        for (size_t t = 0; t < nt; t++) for (int k = 0; k < 3; k++) first[(size_t)indices[4 * t + k] + 1]++;
+        for (size_t v = 0; v < nv; v++) first[v + 1] += first[v];
+        std::vector<int> next(first.begin(), first.end() - 1);
+        for (size_t t = 0; t < nt; t++) for (int k = 0; k < 3; k++) tri[next[indices[4 * t + k]]++] = (int)t;
+        s.corner_tri = upload(s, tri.data(), tri.size());
+        s.corner_first = upload(s, first.data(), first.size());
+    }
+}
+
+DevScene& loaded_scene(int32_t dev, const char* entry) {
+    DevScene& s = rdev(dev).scene;
+    if (!s.loaded) {
+        fprintf(stderr, "rodent_hip: %s: no scene loaded on device %d (call rodent_hip_scene_create)\n", entry, dev); abort(); }
+    return s;
+}
+
 } // namespace
 
 extern "C" {
@@ -972,6 +1034,71 @@ void rodent_hip_scene_refit(int32_t dev, const float* vertices, const float* nor
         const std::vector<float> rec = tri_shade(face_normals, normals, indices.data(), s.dev.num_tris);
         HIP_CHECK(hipMemcpy(const_cast<float4*>(s.dev.tri_shade), rec.data(), sizeof(float) * rec.size(), hipMemcpyHostToDevice));
     }
+}
+
+void rodent_hip_scene_refit_prepare(int32_t dev, int32_t smooth_normals) {
+    loaded_scene(dev, "rodent_hip_scene_refit_prepare");
+    refit_prepare(rdev(dev), smooth_normals != 0);
+}
+
+void rodent_hip_scene_refit_device(int32_t dev, const float* vertices_dev, const float* normals_dev, void* stream_) {
+    DevScene& s = loaded_scene(dev, "rodent_hip_scene_refit_device");
+    RenderDevice& r = rdev(dev);
+    if (!vertices_dev) { fprintf(stderr, "rodent_hip: rodent_hip_scene_refit_device: NULL vertices\n"); abort(); }
+    HIP_CHECK(hipSetDevice(dev));
+    if (!s.refit_info || (!normals_dev && !s.corner_first)) refit_prepare(r, !normals_dev);
+    hipStream_t stream = (hipStream_t)stream_;
+    // Behind the last device refit, whichever stream it took.  Frames need no such wait: a frame call returns when its rows are in the
+    // film (frame_end), so none is in flight; the next one waits for ev_refit (open_scene).
+    if (s.refit_enqueued) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_refit, 0));
+    const int nv = s.num_vertices, nt = s.dev.num_tris, nl = s.dev.num_lights;
+    float4* const vertices = reinterpret_cast<float4*>(const_cast<float*>(s.dev.vertices));
+    float4* const normals = reinterpret_cast<float4*>(const_cast<float*>(s.dev.normals));
+    float4* const face_normals = reinterpret_cast<float4*>(const_cast<float*>(s.dev.face_normals));
+    const int4* const indices = reinterpret_cast<const int4*>(s.dev.indices);
+    if (vertices_dev != s.dev.vertices)
+        HIP_CHECK(hipMemcpyAsync(vertices, vertices_dev, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToDevice, stream));
+    if (normals_dev && normals_dev != s.dev.normals)
+        HIP_CHECK(hipMemcpyAsync(normals, normals_dev, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToDevice, stream));
+    const auto blocks = [](int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
+    hipLaunchKernelGGL(k_face_normals, blocks(nt), dim3(kBlock), 0, stream, vertices, indices, nt, face_normals);
+    if (nl > 0) hipLaunchKernelGGL(k_light_records, blocks(nl), dim3(kBlock), 0, stream, vertices, indices, s.light_tri, nl,
+                                   const_cast<RodentLight*>(s.dev.lights));
+    if (!normals_dev) hipLaunchKernelGGL(k_smooth_normals, blocks(nv), dim3(kBlock), 0, stream, face_normals, s.corner_first,
+                                         s.corner_tri, nv, normals);
+    // the hierarchy, in place: rodent_hip_scene_bvh's pointers stay valid
+    const int32_t rc = rodent_hip_refit_bvh2_tri1(dev, s.dev.vertices, nv, s.dev.indices, nt, const_cast<Node2*>(s.dev.nodes), s.num_nodes,
+                                                  const_cast<Tri1*>(s.dev.tris), s.num_bvh_tris, s.refit_scratch, s.refit_info, stream);
+    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: device BVH refit refused (%d)\n", rc); abort(); }
+    hipLaunchKernelGGL(k_scene_images, dim3(2), dim3(kWave), 0, stream, s.dev.nodes, const_cast<int4*>(s.dev.top_image),
+                       const_cast<int4*>(s.dev.top_image_large));
+    if (s.dev.tri_shade) hipLaunchKernelGGL(k_tri_shade, blocks(nt), dim3(kBlock), 0, stream, face_normals, normals, indices, nt,
+                                            const_cast<float4*>(s.dev.tri_shade));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(r.ev_refit, stream));
+    s.refit_enqueued = true;
+}
+
+int32_t rodent_hip_scene_refit_status(int32_t dev, int32_t* info) {
+    DevScene& s = loaded_scene(dev, "rodent_hip_scene_refit_status");
+    int32_t words[RODENT_BUILD_INFO_WORDS] = {s.num_nodes, s.num_bvh_tris, 0, 0};      // before the first refit: a sound one's words
+    if (s.refit_enqueued) {
+        HIP_CHECK(hipSetDevice(dev));
+        HIP_CHECK(hipEventSynchronize(rdev(dev).ev_refit));
+        HIP_CHECK(hipMemcpy(words, s.refit_info, sizeof(words), hipMemcpyDeviceToHost));
+    }
+    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
+    return words[2] | (words[0] != s.num_nodes ? (int32_t)0x80000000u : 0);
+}
+
+void rodent_hip_scene_tables(int32_t dev, RodentSceneTables* out) {
+    const DevScene& s = loaded_scene(dev, "rodent_hip_scene_tables");
+    if (!out) return;
+    *out = RodentSceneTables{const_cast<float*>(s.dev.vertices), const_cast<float*>(s.dev.normals), const_cast<float*>(s.dev.face_normals),
+        const_cast<RodentLight*>(s.dev.lights), reinterpret_cast<float*>(const_cast<float4*>(s.dev.tri_shade)),
+        reinterpret_cast<int32_t*>(const_cast<int4*>(s.dev.top_image)),
+        reinterpret_cast<int32_t*>(const_cast<int4*>(s.dev.top_image_large)),
+        s.num_vertices, s.dev.num_tris, s.dev.num_lights, kSceneTopNodes, kPersistTopNodes};
 }
 
 void rodent_hip_scene_bvh(int32_t dev, const Node2** nodes, const Tri1** tris, int32_t* num_nodes, int32_t* num_tris) {
@@ -1146,7 +1273,7 @@ void hip_generate_rays(int32_t dev, PrimaryStream* primary, int32_t capacity, in
 }
 
 void hip_traverse_primary(int32_t dev, PrimaryStream* primary, void* stream) {
-    RenderDevice& r = open_scene(rdev(dev));
+    RenderDevice& r = open_scene(rdev(dev), (hipStream_t)stream);
     if (primary->size <= 0) return;
     // a caller's stream holds its hit records in the ABI's five arrays (store_hit_record)
     primary->pad = 0;
@@ -1155,7 +1282,7 @@ void hip_traverse_primary(int32_t dev, PrimaryStream* primary, void* stream) {
 }
 
 void hip_sort_primary(int32_t dev, PrimaryStream* primary, PrimaryStream* other, int32_t* ray_ends, void* stream) {
-    RenderDevice& r = open_scene(rdev(dev));
+    RenderDevice& r = open_scene(rdev(dev), (hipStream_t)stream);
     const int G = r.scene.dev.num_materials;
     if (G + 1 > kMaxBins) { fprintf(stderr, "rodent_hip: too many geometries (%d)\n", G); abort(); }
     bin_stream(r, 0, *primary, *other, nullptr, primary->size, KEY_GEOM, G + 1, 1, G + 1, (hipStream_t)stream);
@@ -1166,7 +1293,7 @@ void hip_sort_primary(int32_t dev, PrimaryStream* primary, PrimaryStream* other,
 }
 
 void hip_shade(int32_t dev, PrimaryStream* primary, SecondaryStream* secondary, int32_t num_rays, void* stream) {
-    RenderDevice& r = open_scene(rdev(dev));
+    RenderDevice& r = open_scene(rdev(dev), (hipStream_t)stream);
     primary->size = num_rays; secondary->size = num_rays; primary->pad = 0;
     if (num_rays <= 0) return;
     launch_k_shade((hipStream_t)stream, shade_block(), num_rays, r.scene.dev, *primary, *primary, (const int*)nullptr, *secondary,
@@ -1179,7 +1306,7 @@ void hip_shade(int32_t dev, PrimaryStream* primary, SecondaryStream* secondary, 
 
 int32_t hip_shade_compact(int32_t dev, PrimaryStream* from, PrimaryStream* to, SecondaryStream* secondary, const int32_t* perm,
     int32_t num_rays, int32_t mode, int32_t block, void* stream) {
-    RenderDevice& r = open_scene(rdev(dev));
+    RenderDevice& r = open_scene(rdev(dev), (hipStream_t)stream);
     if ((mode != 1 && mode != 2) || (block != 0 && block != 256 && block != 512 && block != 1024) || from->rays.id == to->rays.id) {
         fprintf(stderr, "rodent_hip: hip_shade_compact: mode must be 1 or 2, block 0, 256, 512 or 1024, and `to` another stream than "
         "`from` (mode %d, block %d)\n", mode, block); abort(); }
@@ -1202,7 +1329,7 @@ int32_t hip_shade_compact(int32_t dev, PrimaryStream* from, PrimaryStream* to, S
 }
 
 void hip_traverse_secondary(int32_t dev, SecondaryStream* secondary, void* stream) {
-    RenderDevice& r = open_scene(rdev(dev));
+    RenderDevice& r = open_scene(rdev(dev), (hipStream_t)stream);
     if (secondary->size <= 0) return;
     launch_trace(r, (hipStream_t)stream, {}, {secondary, nullptr, secondary->size, 1.0f / (float)r.spp});
     HIP_CHECK(hipGetLastError());

@@ -28,9 +28,16 @@ class SceneDesc(C.Structure):
                [(n, vp) for n in ("texcoords", "textures", "texels")] + [("num_textures", i32), ("num_texels", C.c_uint32)]
 
 
+class SceneTables(C.Structure):
+    """RodentSceneTables: device pointers and counts of the tables a scene owns."""
+    _fields_ = [(n, vp) for n in ("vertices", "normals", "face_normals", "lights", "tri_shade", "top_image", "top_image_large")] + \
+               [(n, i32) for n in ("num_vertices", "num_tris", "num_lights", "top_nodes", "top_nodes_large")]
+
+
 RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_create_device_bvh_opt",
                   "rodent_hip_scene_create_device_bvh_split",
     "rodent_hip_scene_bvh", "rodent_hip_scene_refit", "rodent_hip_scene_destroy",
+    "rodent_hip_scene_refit_prepare", "rodent_hip_scene_refit_device", "rodent_hip_scene_refit_status", "rodent_hip_scene_tables",
     "rodent_hip_render_config", "rodent_hip_render_mapping",
     "rodent_hip_render_capacity", "rodent_hip_render_sort", "rodent_hip_render_hit_records", "rodent_hip_render_overlap",
     "rodent_hip_render_fused_sort", "rodent_hip_render_fused_compact", "rodent_hip_render_mapping_in_effect", "rodent_hip_render_defaults",
@@ -66,6 +73,10 @@ def lib():
         l.rodent_hip_scene_bvh.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
         l.rodent_hip_scene_bvh.restype = None
         l.rodent_hip_scene_refit.argtypes = [i32, vp, vp, vp, vp]; l.rodent_hip_scene_refit.restype = None
+        l.rodent_hip_scene_refit_prepare.argtypes = [i32, i32]; l.rodent_hip_scene_refit_prepare.restype = None
+        l.rodent_hip_scene_refit_device.argtypes = [i32, vp, vp, vp]; l.rodent_hip_scene_refit_device.restype = None
+        l.rodent_hip_scene_refit_status.argtypes = [i32, C.POINTER(i32)]; l.rodent_hip_scene_refit_status.restype = i32
+        l.rodent_hip_scene_tables.argtypes = [i32, C.POINTER(SceneTables)]; l.rodent_hip_scene_tables.restype = None
         l.rodent_hip_render_config.argtypes = [i32, i32, i32]; l.rodent_hip_render_config.restype = None
         l.rodent_hip_render_mapping.argtypes = [i32, i32]; l.rodent_hip_render_mapping.restype = None
         l.rodent_hip_render_capacity.argtypes = [i32, i32]; l.rodent_hip_render_capacity.restype = None
@@ -250,6 +261,98 @@ class Renderer:
                 raise ValueError(f"update_geometry: the scene's `{n}` table differs from the one the renderer was created with")
         tables = [np.ascontiguousarray(getattr(scene, n)) for n in ("vertices", "normals", "face_normals", "lights")]
         lib().rodent_hip_scene_refit(self.dev, *[a.ctypes.data_as(vp) for a in tables])
+
+    def prepare_update(self, smooth_normals=True):
+        """One-time allocations of update_geometry_device (rodent_hip_scene_refit_prepare), so that its first call allocates nothing
+        either; smooth_normals: also the incidence lists a call without `normals` needs."""
+        lib().rodent_hip_scene_refit_prepare(self.dev, int(bool(smooth_normals)))
+
+    def _table_pointer(self, t, what):
+        """Device pointer of a (num_vertices, 4) float32 table given as a tensor on the renderer's device, or as an integer pointer."""
+        if t is None or isinstance(t, int):
+            return t
+        if t.is_cuda and t.data_ptr() == self.scene_table_pointers()[what]:
+            return t.data_ptr()                              # the scene's own table (scene_vertices_tensor)
+        nv = self._counts[0]
+        if (not t.is_cuda or t.device.index != self.dev or str(t.dtype) != "torch.float32" or tuple(t.shape) != (nv, 4)
+                or not t.is_contiguous()):
+            raise ValueError(f"update_geometry_device: `{what}` must be a contiguous float32 tensor of shape ({nv}, 4) on cuda:{self.dev} "
+                             "(or an integer device pointer)")
+        return t.data_ptr()
+
+    def update_geometry_device(self, vertices, normals=None, stream=None, check=True):
+        """The scene's vertices moved and already live on the device (rodent_hip_scene_refit_device): `vertices` -- and `normals`, or
+        None for smooth normals recomputed from the faces -- are (num_vertices, 4) float32 tensors on the renderer's device, or integer
+        device pointers (the scene's own vertex table, scene_table_pointers()["vertices"], written in place, is copied nowhere).  Face
+        normals, light records, the hierarchy's boxes and Tri1 records, both LDS top images and the shading records follow on `stream`
+        (a torch stream; None: the current one), with no host copy and no wait; the next frame, on any stream, sees the moved scene.
+        check=True waits for the refit (rodent_hip_scene_refit_status) and raises gpubuild.BuildError on a flag: a non-finite
+        coordinate, a malformed hierarchy.  The film is not cleared."""
+        import torch
+        stream = torch.cuda.current_stream(self.dev) if stream is None else stream
+        tensors = [t for t in (vertices, normals) if isinstance(t, torch.Tensor)]
+        pointers = (self._table_pointer(vertices, "vertices"), self._table_pointer(normals, "normals"))
+        if pointers[0] is None:
+            raise ValueError("update_geometry_device: `vertices` is None")
+        if tensors:
+            stream.wait_stream(torch.cuda.current_stream(self.dev))          # the tensors may come from there
+        lib().rodent_hip_scene_refit_device(self.dev, *pointers, C.c_void_p(stream.cuda_stream))
+        for t in tensors:
+            t.record_stream(stream)
+        if check:
+            self.update_status(raise_on_flag=True)
+
+    def update_status(self, raise_on_flag=False):
+        """(flags, info words) of the last update_geometry_device, once it has finished: flags 0 = sound (gpubuild.NON_FINITE, ...; bit
+        31: nodes the refit could not complete)."""
+        words = (i32 * 4)()
+        flags = lib().rodent_hip_scene_refit_status(self.dev, words)
+        if flags and raise_on_flag:
+            from . import gpubuild
+            gpubuild._raise_flags("rodent_hip_scene_refit_device", words)
+            raise gpubuild.BuildError(f"rodent_hip_scene_refit_device: malformed hierarchy ({words[0]} nodes completed)")
+        return flags, list(words)
+
+    def scene_table_pointers(self):
+        """Device pointers (integers; 0 = the scene has no such table) and counts of the tables the scene owns (rodent_hip_scene_tables)."""
+        t = SceneTables()
+        lib().rodent_hip_scene_tables(self.dev, C.byref(t))
+        return {n: (getattr(t, n) or 0) for n, _ in SceneTables._fields_}
+
+    def scene_vertices_tensor(self):
+        """The scene's own vertex table as a (num_vertices, 4) float32 torch tensor that shares its memory: write it in place with torch
+        ops, then pass it to update_geometry_device (nothing is copied).  Valid until the scene is destroyed."""
+        import torch
+        p = self.scene_table_pointers()
+
+        class Table:
+            __cuda_array_interface__ = {"shape": (p["num_vertices"], 4), "typestr": "<f4", "data": (p["vertices"], False), "version": 2,
+                                        "strides": None}
+        return torch.as_tensor(Table(), device=f"cuda:{self.dev}")
+
+    def scene_tables(self):
+        """Host copies (numpy) of the tables the scene derives from positions: vertices, normals, face_normals (float32, 4 columns),
+        lights (scene.LIGHT), tri_shade ((num_tris, 12) float32, or None) and the two LDS top images ((records, 16) int32)."""
+        import torch
+        from .scene import LIGHT
+        p = self.scene_table_pointers()
+        torch.cuda.synchronize(self.dev)
+        hip = C.cdll.LoadLibrary("libamdhip64.so")
+
+        def fetch(ptr, dtype, count, shape):
+            if not ptr:
+                return None
+            nbytes = count * np.dtype(dtype).itemsize
+            t = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=f"cuda:{self.dev}")
+            hip.hipMemcpy(C.c_void_p(t.data_ptr()), C.c_void_p(ptr), C.c_size_t(nbytes), 3)
+            return t.cpu().numpy()[:nbytes].view(dtype).reshape(shape).copy()
+        nv, nt = p["num_vertices"], p["num_tris"]
+        return {"vertices": fetch(p["vertices"], "<f4", 4 * nv, (nv, 4)), "normals": fetch(p["normals"], "<f4", 4 * nv, (nv, 4)),
+                "face_normals": fetch(p["face_normals"], "<f4", 4 * nt, (nt, 4)),
+                "lights": fetch(p["lights"], LIGHT, p["num_lights"], (p["num_lights"],)),
+                "tri_shade": fetch(p["tri_shade"], "<f4", 12 * nt, (nt, 12)),
+                "top_image": fetch(p["top_image"], "<i4", 16 * p["top_nodes"], (p["top_nodes"], 16)),
+                "top_image_large": fetch(p["top_image_large"], "<i4", 16 * p["top_nodes_large"], (p["top_nodes_large"], 16))}
 
     def close(self):
         lib().rodent_hip_scene_destroy(self.dev)
