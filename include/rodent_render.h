@@ -295,6 +295,23 @@ int32_t hip_shade_compact(int32_t dev, struct PrimaryStream* from, struct Primar
 void    hip_traverse_secondary(int32_t dev, struct SecondaryStream* secondary, void* stream);
 /* Order-preserving compaction of rays with id >= 0; returns the new size (synchronises the stream). */
 int32_t hip_compact_primary(int32_t dev, struct PrimaryStream* primary, struct PrimaryStream* other, void* stream);
+/* The binning stage in the forms the renderer's own loop launches (hip_sort_primary and hip_compact_primary are two of them): stable
+ * counting sort of the first n rays of `from` by key, n = *size_dev (DEVICE int) if size_dev is given, else max_n.
+ * mode 0: key = geom_id, 1: key = (id >= 0 ? 0 : 1).  num_bins: number of keys, 1 ... 1025 (an argument, not the scene's material count:
+ * no scene has to be loaded).  Rays with key >= drop_from_bin (1 ... num_bins) are left out; ray i with a smaller key goes to slot
+ * d = (rays with a smaller key) + (rays with its key in front of it).
+ * perm == NULL: every array of `to` (another stream than `from`) takes from[i] at d, except the five hit arrays when keep_hit == 0 and
+ * tmin / tmax when copy_interval == 0; those, and every entry behind the rays kept, stay as they are.
+ * perm != NULL (DEVICE array of at least as many ints as rays are kept): perm[d] = i and `to` is not written at all (index-only sort).
+ * The loop's sort is (0, G + 1, G, 1, 0, perm or NULL, NULL, n), its compaction (1, 2, 1, 0, 1, NULL, size_dev, max_n).
+ * bin_ends (host, num_bins ints) receives the exclusive end of every bin, dropped bins included; returns bin_ends[drop_from_bin - 1], the
+ * number of rays kept.  Neither stream's `size` is read or set.  Synchronises the stream.  Invalid arguments abort (as do streams whose
+ * `pad` asks for 20-byte hit records).
+ * PRECONDITION, not checked: every key of the first n rays lies in [0, num_bins) and *size_dev <= max_n <= the streams' capacity -- the
+ * kernels index LDS and the per-block counts with the key. */
+int32_t hip_bin_primary(int32_t dev, struct PrimaryStream* from, struct PrimaryStream* to, int32_t mode, int32_t num_bins,
+                        int32_t drop_from_bin, int32_t keep_hit, int32_t copy_interval, int32_t* perm, const int32_t* size_dev,
+                        int32_t max_n, int32_t* bin_ends, void* stream);
 
 #ifdef __cplusplus
 }

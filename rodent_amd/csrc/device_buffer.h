@@ -38,7 +38,10 @@ private:
         ptr = nullptr; count = 0;
         if (!may_fail) HIP_CHECK(hipMalloc(&ptr, sizeof(T) * n));
         else if (hipMalloc(&ptr, sizeof(T) * n) != hipSuccess) { (void)hipGetLastError(); ptr = nullptr; return nullptr; }
-        if (fill != kNoFill) HIP_CHECK(hipMemset(ptr, fill, sizeof(T) * n));
+        // The fill runs on the null stream and does not wait for the host; a stream created non-blocking does not wait for the null
+        // stream either, so a kernel enqueued there right after ensure() could run before (or while) the block is filled -- the first
+        // "sorted" launch of a fresh context counted into sort_totals and had its counts zeroed under it.  Wait for the fill here.
+        if (fill != kNoFill) { HIP_CHECK(hipMemset(ptr, fill, sizeof(T) * n)); HIP_CHECK(hipStreamSynchronize(nullptr)); }
         count = n;
         return ptr;
     }

@@ -1344,4 +1344,20 @@ int32_t hip_compact_primary(int32_t dev, PrimaryStream* primary, PrimaryStream* 
     return other->size;
 }
 
+int32_t hip_bin_primary(int32_t dev, PrimaryStream* from, PrimaryStream* to, int32_t mode, int32_t num_bins, int32_t drop_from_bin,
+    int32_t keep_hit, int32_t copy_interval, int32_t* perm, const int32_t* size_dev, int32_t max_n, int32_t* bin_ends, void* stream) {
+    RenderDevice& r = rdev(dev); HIP_CHECK(hipSetDevice(dev));
+    if ((mode != KEY_GEOM && mode != KEY_ALIVE) || num_bins < 1 || num_bins > kMaxBins || drop_from_bin < 1 || drop_from_bin > num_bins ||
+        max_n < 0 || (!perm && from->rays.id == to->rays.id) || ((from->pad | to->pad) & kHitRecordsAoS)) {
+        fprintf(stderr, "rodent_hip: hip_bin_primary: mode must be 0 or 1, num_bins 1 ... %d, drop_from_bin 1 ... num_bins, max_n >= 0, "
+        "`to` another stream than `from` unless `perm` is given, and both streams with their hit records in the five arrays (mode %d, "
+        "num_bins %d, drop_from_bin %d, max_n %d)\n", kMaxBins, mode, num_bins, drop_from_bin, max_n); abort(); }
+    // the bin arrays the renderer's loop uses for that key: set 0 = sort by geometry, set 1 = compaction
+    bin_stream(r, mode, *from, *to, size_dev, max_n, mode, num_bins, keep_hit, drop_from_bin, (hipStream_t)stream, copy_interval, perm);
+    HIP_CHECK(hipMemcpyAsync(r.host_pinned + 8, bin_end(r, mode), sizeof(int) * num_bins, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    std::memcpy(bin_ends, r.host_pinned + 8, sizeof(int) * num_bins);
+    return r.host_pinned[8 + drop_from_bin - 1];
+}
+
 } // extern "C"

@@ -48,7 +48,7 @@ RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh
                   "rodent_gpu_get_tmp_buffer", "rodent_present", "rodent_hip_set_device", "rodent_hip_render_rows",
                       "rodent_hip_render_tiles",
                   "rodent_hip_render_counters", "hip_generate_rays", "hip_traverse_primary", "hip_sort_primary", "hip_shade",
-                  "hip_shade_compact", "hip_traverse_secondary", "hip_compact_primary",
+                  "hip_shade_compact", "hip_traverse_secondary", "hip_compact_primary", "hip_bin_primary",
                   "rodent_load_buffer", "rodent_load_bvh2_tri1", "rodent_load_bvh4_tri4", "rodent_load_bvh8_tri4", "rodent_load_png",
                       "rodent_load_jpg",
                   "rodent_cpu_get_primary_stream", "rodent_cpu_get_secondary_stream", "clock_us", "rodent_hip_buffer_size",
@@ -398,6 +398,8 @@ def stage_lib():
         vp]; l.hip_shade_compact.restype = i32
     l.hip_traverse_secondary.argtypes = [i32, C.POINTER(SecondaryStream), vp]; l.hip_traverse_secondary.restype = None
     l.hip_compact_primary.argtypes = [i32, C.POINTER(PrimaryStream), C.POINTER(PrimaryStream), vp]; l.hip_compact_primary.restype = i32
+    l.hip_bin_primary.argtypes = [i32, C.POINTER(PrimaryStream), C.POINTER(PrimaryStream), i32, i32, i32, i32, i32, vp, vp, i32,
+        C.POINTER(i32), vp]; l.hip_bin_primary.restype = i32
     return l
 
 

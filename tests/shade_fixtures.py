@@ -154,6 +154,16 @@ def first_difference(got, want, row_names=None):
            f"oracle 0x{want[r, c]:08x} ({as_f32(want[r:r + 1, c])[0]!r})"
 
 
+def sentinel(stream, rows):
+    """A slab of `rows` arrays with the stream's capacity, every word the sentinel."""
+    return np.full((rows, slab_cap(stream)), SENTINEL, "<u4")
+
+
+def assert_same(got, want, what):
+    diff = first_difference(got, want)
+    assert not diff, f"{what}: {diff}"
+
+
 def compacted(primary_after, to_before, bounce):
     """The stable compaction of an in-place shaded slab into `to_before`: the rows the shader writes, survivors in stream order."""
     out = to_before.copy()

@@ -14,7 +14,7 @@ import pytest
 import shade_fixtures as SF
 from conftest import GOLDEN
 from rodent_amd import scene as S
-from shade_fixtures import H, MAXLEN, W
+from shade_fixtures import H, MAXLEN, W, assert_same, sentinel
 
 pytestmark = pytest.mark.gpu
 CAP = W * H                                                      # 6144 rays: the largest stream of this module
@@ -56,15 +56,6 @@ def staged(R, scene, cap=CAP):
         yield (r,) + streams(R, cap)
     finally:
         r.close()
-
-
-def sentinel(stream, rows):
-    return np.full((rows, SF.slab_cap(stream)), SF.SENTINEL, "<u4")
-
-
-def assert_same(got, want, what):
-    diff = SF.first_difference(got, want)
-    assert not diff, f"{what}: {diff}"
 
 
 def assert_film(got, want, what):
@@ -254,6 +245,67 @@ def test_fused_compaction_slots(R, oracle, materials_scene, bouncers, block, mod
                     assert_same(sf, s1, at + ", secondary stream")
                     if mode == 2:                                             # blocks arrive in any order: the same records
                         order = lambda a: a[:, np.lexsort([a[k, :got] for k in reversed(keys)])]
+                        assert_same(qf[:, got:], want_q[:, got:], at + ", `to` behind the new size")
+                        assert_same(order(qf[:, :got]), order(want_q[:, :got]), at + ", `to` as a multiset")
+                    else:
+                        assert_same(qf, want_q, at + ", `to`")
+
+
+def window_patterns(n, block):
+    """name -> survivor mask over thread positions, by workgroup: what the look-back scan reads are the workgroups' totals."""
+    group = np.arange(n) // block
+    last = np.zeros(n, bool); last[n - 1] = True
+    return {"everyone": np.ones(n, bool), "nobody in blocks 0 ... 63, everyone after": group >= 64, "only block 0": group == 0,
+            "every other block empty": group % 2 == 0, "one survivor in the very last ray": last}
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_fused_compaction_slots_past_one_window(R, oracle, materials_scene, bouncers, mode):
+    """test_fused_compaction_slots with more workgroups than the 64 predecessors one round of the look-back scan reads: 64, 66 and 130
+    workgroups of 256, so that the scan walks one full window, one window and a lane, two windows and a lane -- over totals that are all
+    non-zero, all zero for a whole window (the walk has to go on behind them), zero from block 1 on, alternating, and zero but for the
+    last ray.  The same assertions; no and a random permutation."""
+    import torch
+    scene, block = materials_scene, 256
+    rng = np.random.default_rng(mode)
+    with staged(R, scene, 129 * block + 5 + 32) as (r, l, p, q, s):
+        cap = SF.slab_cap(p)
+        for n in (64 * block, 65 * block + 1, 129 * block + 5):
+            for pattern, mask in window_patterns(n, block).items():
+                what = f"block {block}, mode {mode}, {n} rays, {pattern}"
+                v = bouncers[(np.arange(n) * 7 + n) % len(bouncers)].copy()
+                v["depth"] = np.where(mask, 1, MAXLEN)
+                ids = (np.arange(n) * 5 + 3) % CAP                            # pixels of the film, not in stream order
+                g0 = SF.slab_of(v, ids, scene, cap)
+                dead = np.flatnonzero(~mask)
+                SF.mark_missed(g0, dead[::5], scene)
+                s0, q0 = sentinel(s, SF.S_ROWS), sentinel(q, SF.P_ROWS)
+                SF.write_slab(R, p, g0); SF.write_slab(R, s, s0)
+                l.hip_shade(0, C.byref(p), C.byref(s), n, None)
+                p1, s1 = SF.read_slab(R, p, SF.P_ROWS), SF.read_slab(R, s, SF.S_ROWS)
+                exp = SF.Expected(scene, g0, s0, n, MAXLEN)
+                assert np.array_equal(exp.bounce[:n], mask), what
+                assert_same(p1, exp.primary, what + ", hip_shade primary")
+                assert_same(s1, exp.secondary, what + ", hip_shade secondary")
+                want_q, survivors = SF.compacted(p1, q0, p1[SF.ID].view("<i4")[:n] >= 0)
+                assert survivors == int(mask.sum())
+                for perm_name, perm in (("no", None), ("random", rng.permutation(n))):
+                    f0 = g0.copy()
+                    if perm is not None:
+                        f0[:, perm] = g0[:, :n]                               # thread i shades ray perm[i]
+                        d_perm = torch.from_numpy(np.ascontiguousarray(perm, "<i4")).cuda()
+                    SF.write_slab(R, p, f0); SF.write_slab(R, q, q0); SF.write_slab(R, s, s0)
+                    torch.cuda.synchronize()
+                    got = l.hip_shade_compact(0, C.byref(p), C.byref(q), C.byref(s), None if perm is None else d_perm.data_ptr(), n, mode,
+                        block, None)
+                    pf, qf, sf = SF.read_slab(R, p, SF.P_ROWS), SF.read_slab(R, q, SF.P_ROWS), SF.read_slab(R, s, SF.S_ROWS)
+                    at = f"{what}, {perm_name} permutation"
+                    assert got == survivors == q.size, at
+                    assert_same(pf, f0, at + ", `from`")
+                    assert_same(sf, s1, at + ", secondary stream")
+                    if mode == 2:                                             # blocks arrive in any order: the same records
+                        # (pixels and vertices repeat at these sizes: ordered by every row, so that equal keys cannot hide a difference)
+                        order = lambda a: a[:, np.lexsort(a[::-1, :got])]
                         assert_same(qf[:, got:], want_q[:, got:], at + ", `to` behind the new size")
                         assert_same(order(qf[:, :got]), order(want_q[:, :got]), at + ", `to` as a multiset")
                     else:
