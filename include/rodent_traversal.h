@@ -183,6 +183,21 @@ void        rodent_hip_ray_grid(int32_t width);
  * enable: 1 = on (default), 0 = every chunk takes the generic loop; the environment variable RODENT_HIP_OCTANT_LOOPS=0 / 1 sets the
  * initial value (the A/B handle of a benchmark run that cannot call this function). */
 void        rodent_hip_octant_loops(int32_t enable);
+/* Record offsets of the default BVH2 kernel (RODENT_HIP_RECORD_OFFSETS).  Where the node and the triangle array lie less than 4 GiB apart
+ * -- from the lower pointer to the end of the farther array's mapped range -- and neither mapped range could hold 2^23 records, a lane
+ * addresses its node or triangle as one wave-uniform base (the lower pointer, in scalar registers) + a 32-bit byte offset instead of
+ * building a 64-bit address from one of two 64-bit bases: fewer instructions per step, no 64-bit multiply-add.  Decided per launch from
+ * the two pointers (rodent_hip_record_offsets_ok); any other launch, and every launch with the switch off, builds 64-bit addresses as
+ * before.  The byte counts are those of the runtime's mapped ranges behind the two pointers, not of the arrays: both arrays in one
+ * allocation of their own always qualify (rodent_amd.abi.DeviceBvh allocates them so -- two separate allocations of one process were
+ * measured up to 32.6 GiB apart), a small tree inside an arena of 512 MiB or more (384 MiB behind the triangles) does not.
+ * The addresses are the same addresses: hit records never depend on it.  enable: 1 = on (default), 0 = off; the environment
+ * variable RODENT_HIP_RECORD_OFFSETS=0 / 1 sets the initial value (the A/B handle of a benchmark run that cannot call this function).
+ * rodent_hip_read_stats: [1] counts the launches that took the offset form, [0] those that built 64-bit addresses. */
+void        rodent_hip_record_offsets(int32_t enable);
+/* The predicate itself, on plain integers (no device needed): the two pointer values and the bytes mapped from each pointer to the end of
+ * its range (0 = unknown).  1 = such a launch takes the offset form while the switch is on. */
+int32_t     rodent_hip_record_offsets_ok(uint64_t nodes, uint64_t node_bytes, uint64_t tris, uint64_t tri_bytes);
 /* 1 = librodent_hip_lab.so (-DRODENT_HIP_LAB: also the measured-and-lost kernels) */
 int32_t     rodent_hip_is_lab_build(void);
 const char* rodent_hip_variant_name(int32_t bvh_width, int32_t variant);
@@ -193,7 +208,8 @@ const char* rodent_hip_version(void);
 const char* rodent_hip_source_digest(void);
 /* Debug aid: reads and clears the 8 phase counters of the instrumented "stats-*" variants
  * ([0] descent iterations, [1] lanes active in them, [2] leaf iterations, [3] lanes, [4] refills, [5] lanes refilled, [6] outer
- * iterations); from the shipped BVH2 mappings: [2] image width a launch traced 8 x 8 tiles of, [3] chunks that workgroup
+ * iterations); from the shipped BVH2 mappings: [0] / [1] launches of the default kernel that built 64-bit record addresses / that took
+ * record offsets (rodent_hip_record_offsets), [2] image width a launch traced 8 x 8 tiles of, [3] chunks that workgroup
  * 0 traced with a one-octant loop, [4] launches of the refill kernel by the
  * ray-kind hint, [5] launches whose first wavefront chose the refill loop, [6] launches that ran on a validated LDS image, [7] stack blocks
  * spilled + rays handed to the deep pass. */

@@ -39,6 +39,7 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
         "rodent_hip_variant_name",
     "rodent_hip_kernel_name", "rodent_hip_version", "rodent_hip_source_digest", "rodent_hip_is_lab_build", "rodent_hip_phased_min_rays",
         "rodent_hip_top_min_rays", "rodent_hip_ray_kind_hint", "rodent_hip_ray_grid", "rodent_hip_octant_loops", "rodent_hip_schedule_history",
+        "rodent_hip_record_offsets", "rodent_hip_record_offsets_ok",
         "rodent_hip_read_stats", "rodent_hip_read_trace", "rodent_hip_debug_set_perm",
     "rodent_hip_build_scratch_bytes", "rodent_hip_build_bvh2_tri1", "rodent_hip_build_bvh2_tri1_sync",
     "rodent_hip_build_opt_scratch_bytes", "rodent_hip_build_bvh2_tri1_opt", "rodent_hip_build_bvh2_tri1_opt_sync",
@@ -89,6 +90,8 @@ def lib():
         l.rodent_hip_ray_kind_hint.restype = None; l.rodent_hip_ray_kind_hint.argtypes = [i32]
         l.rodent_hip_ray_grid.restype = None; l.rodent_hip_ray_grid.argtypes = [i32]
         l.rodent_hip_octant_loops.restype = None; l.rodent_hip_octant_loops.argtypes = [i32]
+        l.rodent_hip_record_offsets.restype = None; l.rodent_hip_record_offsets.argtypes = [i32]
+        l.rodent_hip_record_offsets_ok.restype = i32; l.rodent_hip_record_offsets_ok.argtypes = [C.c_uint64] * 4
         l.rodent_hip_schedule_history.restype = None; l.rodent_hip_schedule_history.argtypes = [i32]
         l.rodent_hip_device_count.restype = i32; l.rodent_hip_device_count.argtypes = []
         l.rodent_hip_num_variants.restype = i32; l.rodent_hip_num_variants.argtypes = [i32]
@@ -186,14 +189,27 @@ def from_device(t, dtype: np.dtype) -> np.ndarray:
 
 
 class DeviceBvh:
-    """A BVH resident in HBM: nodes + tris of one layout (2 = Node2/Tri1, 4 = Node4/Tri4, 8 = Node8/Tri4)."""
+    """A BVH resident in HBM: nodes + tris of one layout (2 = Node2/Tri1, 4 = Node4/Tri4, 8 = Node8/Tri4).
+
+    Both arrays lie in ONE allocation (`buffer`; `nodes` and `tris` are views of it, the triangles 256-byte aligned behind the nodes): the
+    default BVH2 kernel addresses its records as one base + 32-bit offsets where the two arrays lie within 4 GiB of each other
+    (rodent_hip_record_offsets), and two allocations of the same process may lie tens of GiB apart -- measured: 64 ... 220 MiB in plain
+    runs, 32.6 GiB in three of four runs under a profiler's kernel trace, where the launches then built 64-bit addresses."""
 
     def __init__(self, width, nodes, tris, dev=0):
+        import torch
         assert width in (2, 4, 8)
         self.width, self.dev = width, dev
         self.num_nodes, self.num_tris = len(nodes), len(tris)
-        self.nodes = to_device(nodes, dev)
-        self.tris = to_device(tris, dev)
+        if not torch.cuda.is_available():
+            raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
+        nb, tb = (np.ascontiguousarray(a).view(np.uint8).reshape(-1) if len(a) else np.zeros(0, np.uint8) for a in (nodes, tris))
+        start = (len(nb) + 255) // 256 * 256
+        host = np.zeros(start + len(tb), np.uint8)
+        host[:len(nb)] = nb
+        host[start:] = tb
+        self.buffer = torch.from_numpy(host).to(f"cuda:{dev}")
+        self.nodes, self.tris = self.buffer[:len(nb)], self.buffer[start:]
 
     @classmethod
     def from_tensors(cls, width, nodes, tris, num_nodes, num_tris, dev=0):
@@ -278,6 +294,19 @@ def octant_loops(enable: bool = True):
     """rodent_hip_octant_loops: may the default BVH2 kernel trace a chunk whose rays share their direction signs with the loop compiled for
     that octant (default: yes; hit records do not depend on it; read_stats()[3] counts workgroup 0's chunks that took such a loop)."""
     lib().rodent_hip_octant_loops(int(bool(enable)))
+
+
+def record_offsets(enable: bool = True):
+    """rodent_hip_record_offsets: may the default BVH2 kernel address its node and triangle records as one scalar base + a 32-bit byte
+    offset per lane where the two arrays lie close enough (default: yes; hit records do not depend on it; read_stats()[1] counts the
+    launches that did, read_stats()[0] those that built 64-bit addresses)."""
+    lib().rodent_hip_record_offsets(int(bool(enable)))
+
+
+def record_offsets_ok(nodes: int, node_bytes: int, tris: int, tri_bytes: int) -> bool:
+    """rodent_hip_record_offsets_ok: the launch-time predicate on plain integers -- the two pointer values and the bytes mapped from each
+    pointer on (needs no GPU)."""
+    return bool(lib().rodent_hip_record_offsets_ok(int(nodes), int(node_bytes), int(tris), int(tri_bytes)))
 
 
 def check_errors(dev=0, stream=None):

@@ -213,10 +213,34 @@ struct Lane {
 typedef const __attribute__((address_space(1))) char* gptr;
 // Both array bases as 64-bit integers in VGPRs (the per-lane select in the step would otherwise copy them from SGPRs in
 // every iteration), turned back into GLOBAL pointers: laundering the pointers themselves leaves generic ones and flat loads.
-// (32-bit offsets from one SGPR base -- global_load ... v_off, s[base:base+1], a v_mad_u32_u24 instead of the 64-bit
-// multiply-add -- save one VALU instruction per iteration but need both arrays within 4 GiB of each other, which separate
-// hipMalloc allocations are not: measured on the test harness' arrays, the precondition never held.)
+// (32-bit offsets from one SGPR base -- global_load ... v_off, s[base:base+1] -- need both arrays within 4 GiB of each other: the form
+// k_bvh2_top_auto takes where the launcher finds them so, RecordOffsets below; this one is the form for two arrays anywhere.)
 struct Bases { gptr node, tri; };
+// The offset form of the step's fetch (joint_fetch's second form, traversal_device.h): ONE wave-uniform base -- the lower of the two array
+// pointers -- and the two arrays' distances from it, so that a record's address is base + a 32-bit unsigned byte offset:
+//   node id `top` (1-based)       base + d_node + 64 * top           d_node = (nodes - base) - 64
+//   triangle `~top`               base + d_tri  - 48 * top           d_tri  = (tris - base) - 48          (48 * ~top = -48 * top - 48)
+// in 32-bit wrap-around arithmetic (d_node is "-64" where the nodes are the lower array: the sum is the true offset again, which the host
+// has checked to lie below 4 GiB -- record_offsets_ok).  All three are kernel arguments.  The base stays in an SGPR pair; the two
+// distances are copied into VGPRs in front of the loops (make_offsets): the step selects between them per lane, and a select between two
+// SGPRs under an SGPR mask exceeds the one scalar operand a VALU instruction may read -- the compiler would copy both in every iteration.
+struct RecordOffsets { gptr base; int d_node, d_tri; };
+__device__ __forceinline__ RecordOffsets make_offsets(const char* base, int d_node, int d_tri) {
+    // (the base is "used" here as well: the wait for the kernel-argument load that brings it stands in front of the loops, not in
+    // front of every iteration's fetch, where it would also wait for the previous iteration's stack push)
+    unsigned long long base_bits = reinterpret_cast<unsigned long long>(base);
+    asm volatile("" : "+v"(d_node), "+v"(d_tri), "+s"(base_bits));
+    return RecordOffsets{(gptr)base_bits, d_node, d_tri};
+}
+constexpr int kOffsetIdBits = 23;               // |top| < 2^23 where the offset form runs (record_offsets_ok)
+__device__ __forceinline__ unsigned record_offset(int top, bool is_node, const RecordOffsets& o) {
+    // v_mad_i32_i24 (full rate; v_mul_lo_u32 and the 64-bit multiply-add are not): both factors must fit 24 signed bits.  The stride
+    // does; `top` is a node id in [1, 2^23) or ~(a triangle's index) in [-2^23, 0) in every lane that loads from memory -- the host
+    // sends a tree whose mapped arrays could hold more records than that to the 64-bit form.  (A lane on an image link, top >= kLdsTag,
+    // computes an offset that nobody loads.)
+    static_assert(sizeof(Node2) == 64 && sizeof(Tri1) == 48 && (1 << kOffsetIdBits) <= (1 << 23), "strides and ids fit v_mad_i32_i24");
+    return (unsigned)(__mul24(top, is_node ? (int)sizeof(Node2) : -(int)sizeof(Tri1)) + (is_node ? o.d_node : o.d_tri));
+}
 __device__ __forceinline__ Bases make_bases(const Node2* nodes, const Tri1* tris) {
     // node ids are 1-based
     unsigned long long node_bits = reinterpret_cast<unsigned long long>(nodes - 1), tri_bits = reinterpret_cast<unsigned long long>(tris);
@@ -247,13 +271,15 @@ typedef __attribute__((address_space(3))) float lds_float;
 // OCT (>= 0: k_bvh2_top_auto's one-octant chunks): the signs of the ray's reciprocal direction are known at compile time and the two slab
 // tests take their near / far planes without fminf / fmaxf (slab_canonical<OCT>, traversal_device.h; `splat`: the ray's fma operands, built by
 // the caller in front of its loops); everything else is the same step.
+// OFFS (k_bvh2_top_auto<.., OFFS = true>): the record's address is `offs->base` + a 32-bit byte offset (record_offset; `base` is unused).
 template <bool ANY, bool PF = false, bool TOP = false, bool LAZY = false, bool FENCE = false, bool SHARED = false, int SPILL = 0,
-    int WPG = 1, int OCT = -1>
+    int WPG = 1, int OCT = -1, bool OFFS = false>
 __device__ __forceinline__ void bvh2_step(Lane& L, const Bases& base, Hit1* __restrict__ hits, lds_int* sp_limit, Ctl* ctl,
     int* __restrict__ deep_list,
                                           bool prefetch = false, lds_int* pf_row = nullptr, lds_int* image = nullptr,
                                               lds_float* shared_tmax = nullptr,
-                                          int* __restrict__ spill = nullptr, const RaySplat* splat = nullptr) {
+                                          int* __restrict__ spill = nullptr, const RaySplat* splat = nullptr,
+                                              const RecordOffsets* offs = nullptr) {
     const bool is_node = L.top > 0;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     typedef int i32x2 __attribute__((ext_vector_type(2)));
@@ -261,7 +287,15 @@ __device__ __forceinline__ void bvh2_step(Lane& L, const Bases& base, Hit1* __re
     i32x2 ch;
     int popped;
     float shared_now = 0.0f;
-    if constexpr (TOP && !SHARED) {
+    static_assert(!OFFS || (TOP && !SHARED && !PF), "the offset form exists for the joint fetch of the LDS-image kernels");
+    if constexpr (OFFS) {
+        // (child ids of a node = its bytes 48..55, loaded by the node lanes alone)
+        // (the image lanes' mask from a compare of its own: taken as the carry of the addition that makes the LDS address -- v_add_co_u32,
+        // one VALU instruction less -- it reaches the fetch's exec masks through one more dependent scalar instruction, and the benchmark
+        // launch ran 1.5 % slower: LAB_NOTES 17)
+        joint_fetch(q0, q1, q2, ch, popped, L.top >= kLdsTag, (unsigned)(size_t)image + (unsigned)(L.top - kLdsTag), offs->base,
+            record_offset(L.top, is_node, *offs), is_node, L.sp);
+    } else if constexpr (TOP && !SHARED) {
         // both kinds of fetch -- LDS image, memory -- and the word under the cursor in flight together (joint_fetch, traversal_device.h)
         const unsigned idx = (unsigned)(is_node ? L.top : ~L.top), stride = is_node ? (unsigned)sizeof(Node2) : (unsigned)sizeof(Tri1);
         const gptr addr = (is_node ? base.node : base.tri) + (size_t)idx * stride;
@@ -897,14 +931,38 @@ void check_error_flag(DeviceState& s, hipStream_t stream) {
         fprintf(stderr, "rodent_hip: traversal stack overflow (more than %d entries)\n", kStackCap); abort(); }
 }
 
+// bytes from `p` to the end of the mapped range it lies in (0 when the runtime does not know the pointer)
+size_t mapped_bytes(const void* p) {
+    hipDeviceptr_t range_base = nullptr; size_t range_size = 0;
+    if (hipMemGetAddressRange(&range_base, &range_size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return (size_t)((const char*)range_base + range_size - (const char*)p);
+}
 // How many Node2 records the mapped range behind `nodes` can hold (0 when the runtime does not know the pointer): the bound
 // inside which the persistent kernel may dereference the ids of an image built by an earlier launch.
-int mapped_node_ids(const Node2* nodes) {
-    hipDeviceptr_t range_base = nullptr; size_t range_size = 0;
-    if (hipMemGetAddressRange(&range_base, &range_size, (hipDeviceptr_t)nodes) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    const size_t bytes = (size_t)((const char*)range_base + range_size - (const char*)nodes);
-    return (int)std::min<size_t>(bytes / sizeof(Node2), 0x3FFFFFFF);
+int mapped_node_ids(const Node2* nodes) { return (int)std::min<size_t>(mapped_bytes(nodes) / sizeof(Node2), 0x3FFFFFFF); }
+
+// May a launch on these two arrays fetch its records in the offset form (RecordOffsets; k_bvh2_top_auto<.., OFFS = true>)?  Pointer values
+// and the bytes mapped from each pointer on (mapped_bytes: every id a stale image or a damaged tree could hold stays inside them):
+//  - both ranges are known, and from the lower pointer to the end of the farther range is less than 4 GiB: every byte a lane can address
+//    is base + an unsigned 32-bit offset;
+//  - neither range holds 2^23 records or more: node ids (1-based, <= the count) and ~(triangle index) fit v_mad_i32_i24's 24 signed bits.
+// The byte counts are those of the MAPPED ranges, not of the arrays (the ABI does not pass the arrays' lengths): a small tree carved out of a
+// large arena -- 512 MiB or more behind `nodes`, 384 MiB or more behind `tris` -- takes the 64-bit form although its own ids would fit.
+// Conservative, and reported (stats[0], rodent_hip_kernel_name).
+// Anything else takes the 64-bit form.  (Plain integers: exported as rodent_hip_record_offsets_ok for the tests, no device needed.)
+bool record_offsets_ok(uint64_t nodes, uint64_t node_bytes, uint64_t tris, uint64_t tri_bytes) {
+    constexpr uint64_t kMaxIds = (1ull << kOffsetIdBits) - 1, kSpan = 1ull << 32;
+    if (node_bytes == 0 || tri_bytes == 0) return false;
+    if (node_bytes > ~nodes || tri_bytes > ~tris) return false;                      // (a range that wraps the address space: not a range)
+    if (node_bytes / sizeof(Node2) > kMaxIds || tri_bytes / sizeof(Tri1) > kMaxIds) return false;
+    const uint64_t lo = std::min(nodes, tris), end = std::max(nodes + node_bytes, tris + tri_bytes);
+    return end - lo < kSpan;
 }
+// rodent_hip_record_offsets() / RODENT_HIP_RECORD_OFFSETS: 1 (default) = k_bvh2_top_auto takes the offset form wherever record_offsets_ok
+// allows it; 0 = always the 64-bit form (the A/B arm).  Hit records do not depend on it: the addresses are the same addresses.
+int g_record_offsets = [] { const char* e = getenv("RODENT_HIP_RECORD_OFFSETS"); return e ? (atoi(e) ? 1 : 0) : 1; }();
+// the form the newest default launch took (-1: none yet): rodent_hip_kernel_name names the kernel that really ran
+std::atomic<int> g_last_record_form{-1};
 
 // RODENT_HIP_RAY_GRID: -1 (default) = k_bvh2_top_auto recognises camera rays in image order by itself (detect_ray_grid) and traces them as
 // 8 x 8-pixel tiles; 0 = never (rays in list order, as until round 5); > 0 = the image's width, taken on trust (experiments)
@@ -1060,9 +1118,23 @@ template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL, int MODE = 0, bo
             s.deep_stack, s.tickets.ptr, s.top_image.ptr, TOPN);
         return;
     }
-    hipLaunchKernelGGL((k_bvh2_top_auto<ANY, LDS_N, TOPN, WAVES, REFILL, MODE, FUSED, LAZY>), dim3(groups), dim3(kWave * WAVES), 0, stream,
-        nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
-                       s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, report_to, id, g_ray_grid, g_octant_loops);
+    // Which form of the step's fetch?  (RecordOffsets: the lower array is the base; the distances in 32-bit wrap-around arithmetic)
+    const uint64_t node_bits = (uint64_t)(uintptr_t)nodes, tri_bits = (uint64_t)(uintptr_t)tris;
+    const bool offsets = g_record_offsets && record_offsets_ok(node_bits, (uint64_t)max_id * sizeof(Node2), tri_bits, mapped_bytes(tris));
+    g_last_record_form.store(offsets ? 1 : 0, std::memory_order_relaxed);
+    if (offsets) {
+        const uint64_t lo = std::min(node_bits, tri_bits);
+        const int d_node = (int)((uint32_t)(node_bits - lo) - (uint32_t)sizeof(Node2)),
+            d_tri = (int)((uint32_t)(tri_bits - lo) - (uint32_t)sizeof(Tri1));
+        hipLaunchKernelGGL((k_bvh2_top_auto<ANY, LDS_N, TOPN, WAVES, REFILL, MODE, FUSED, LAZY, true>), dim3(groups), dim3(kWave * WAVES), 0,
+            stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
+                           s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, report_to, id, g_ray_grid, g_octant_loops,
+                               (const char*)(uintptr_t)lo, d_node, d_tri);
+    } else
+    hipLaunchKernelGGL((k_bvh2_top_auto<ANY, LDS_N, TOPN, WAVES, REFILL, MODE, FUSED, LAZY, false>), dim3(groups), dim3(kWave * WAVES), 0,
+        stream, nodes, tris, rays, hits, n, s.ctl(), s.deep_list.ptr,
+                       s.top_image.ptr, s.tickets.ptr, max_id, s.spill.ptr, report_to, id, g_ray_grid, g_octant_loops,
+                           (const char*)nullptr, 0, 0);
     if (!FUSED) hipLaunchKernelGGL((k_bvh2_top_finish<ANY>), dim3(1), dim3(kWave), 0, stream, nodes, tris, rays, hits, s.ctl(),
         s.deep_list.ptr, s.deep_stack, s.tickets.ptr, s.top_image.ptr, TOPN);
 }
@@ -1343,6 +1415,15 @@ const char* rodent_hip_variant_name(int32_t bvh_width, int32_t variant) {
     return variant >= 0 && variant < count ? t[variant].name : "";
 }
 const char* rodent_hip_kernel_name(int32_t bvh_width, int32_t variant, int32_t any_hit) {
+    // the default mapping's kernel exists in two forms (k_bvh2_top_auto<.., OFFS>): the one its newest launch took -- before the first
+    // launch, the one the switch asks for -- with every template argument spelled out, as the profiler prints it
+    if (bvh_width == 2 && variant == 0) {
+        const int last = g_last_record_form.load(std::memory_order_relaxed);
+        static const char* const names[2][2] = {
+            {"k_bvh2_top_auto<false,15,255,16,32,0,true,false,false>", "k_bvh2_top_auto<false,15,255,16,32,0,true,false,true>"},
+            {"k_bvh2_top_auto<true,15,255,16,32,0,true,false,false>", "k_bvh2_top_auto<true,15,255,16,32,0,true,false,true>"}};
+        return names[any_hit ? 1 : 0][(last < 0 ? g_record_offsets : last) ? 1 : 0];
+    }
     if (bvh_width == 2) return variant >= 0 && variant < kNumVariants2 ? kVariants2[variant].kernel[any_hit ? 1 : 0] : "";
     int count = 0; const VariantW* t = wide_variants(bvh_width, &count);
     return variant >= 0 && variant < count ? t[variant].kernel[any_hit ? 1 : 0] : "";
@@ -1355,6 +1436,10 @@ void rodent_hip_top_min_rays(int32_t rays) { g_top_min_rays = rays < 0 ? kTopMin
 void rodent_hip_ray_kind_hint(int32_t enable) { g_kind_hint = enable ? 1 : 0; }
 void rodent_hip_ray_grid(int32_t width) { g_ray_grid = width; }
 void rodent_hip_octant_loops(int32_t enable) { g_octant_loops = enable ? 1 : 0; }
+void rodent_hip_record_offsets(int32_t enable) { g_record_offsets = enable ? 1 : 0; g_last_record_form.store(-1, std::memory_order_relaxed); }
+int32_t rodent_hip_record_offsets_ok(uint64_t nodes, uint64_t node_bytes, uint64_t tris, uint64_t tri_bytes) {
+    return record_offsets_ok(nodes, node_bytes, tris, tri_bytes) ? 1 : 0;
+}
 int32_t rodent_hip_is_lab_build(void) {
 #ifdef RODENT_HIP_LAB
     return 1;

@@ -266,6 +266,42 @@ __device__ __forceinline__ void joint_fetch(vf4& q0, vf4& q1, vf4& q2, vi2& ids,
                  : "memory", "scc");               // (s_andn2_b64 / s_and_b64 write SCC)
 }
 
+// The offset form (k_bvh2_top_auto<.., OFFS = true>): the memory records addressed as ONE wave-uniform base (an SGPR pair) + an unsigned
+// 32-bit byte offset per lane (global_load ... v_off, s[b:b+1]) -- no 64-bit address per lane, no array bases in VGPR pairs.  The host
+// decides whether a launch may take it (record_offsets_ok, traversal.hip).  The LDS half, the pop and the wait are the form's above.
+// The child ids (a node's bytes 48..55) are loaded by the NODE lanes only, from the same offset register: a triangle lane has no use
+// for them -- the 64-bit form lets it re-read its own last 8 bytes, which costs a select and an add per step for an address that only
+// has to be harmless -- and reads nothing outside its own 48 bytes.  Its `ids` are undefined.
+// (`base` comes from the kernel's arguments through SALU instructions only: no VALU-written SGPR is read by the loads.)
+__device__ __forceinline__ void joint_fetch(vf4& q0, vf4& q1, vf4& q2, vi2& ids, int& popped, bool in_lds, unsigned lds_addr, gbytes base,
+    unsigned off, bool is_node, lds_int* sp) {
+    const unsigned long long lds_mask = __ballot(in_lds), node_mask = __ballot(is_node);
+    const unsigned sp_addr = (unsigned)(size_t)sp;
+    unsigned long long save;
+    asm volatile("s_mov_b64 %[save], exec\n\t"
+                 "s_andn2_b64 exec, exec, %[lm]\n\t"
+                 "s_cbranch_execz .Ljoint_e_%=\n\t"
+                 "global_load_dwordx4 %[q1], %[o], %[sb] offset:16\n\t"
+                 "global_load_dwordx4 %[q0], %[o], %[sb]\n\t"
+                 "global_load_dwordx4 %[q2], %[o], %[sb] offset:32\n\t"
+                 "s_and_b64 exec, exec, %[nm]\n\t"
+                 "global_load_dwordx2 %[ch], %[o], %[sb] offset:48\n"
+                 ".Ljoint_e_%=:\n\t"
+                 "s_and_b64 exec, %[save], %[lm]\n\t"
+                 "s_cbranch_execz .Ljoint_f_%=\n\t"
+                 "ds_read_b128 %[q0], %[l]\n\t"
+                 "ds_read_b128 %[q1], %[l] offset:16\n\t"
+                 "ds_read_b128 %[q2], %[l] offset:32\n\t"
+                 "ds_read_b64 %[ch], %[l] offset:48\n"
+                 ".Ljoint_f_%=:\n\t"
+                 "s_mov_b64 exec, %[save]\n\t"
+                 "ds_read_b32 %[pop], %[sp]\n\t"
+                 "s_waitcnt vmcnt(0) lgkmcnt(0)"
+                 : [q0] "=&v"(q0), [q1] "=&v"(q1), [q2] "=&v"(q2), [ch] "=&v"(ids), [pop] "=&v"(popped), [save] "=&s"(save)
+                 : [o] "v"(off), [sb] "s"(base), [l] "v"(lds_addr), [sp] "v"(sp_addr), [lm] "s"(lds_mask), [nm] "s"(node_mask)
+                 : "memory", "scc");               // (s_andn2_b64 / s_and_b64 write SCC)
+}
+
 __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 // One wave (the LDS operations of a wave complete in program order: between one lane's write and another lane's read the compiler only has
 // to keep that order).  Record layout: ints 0..11 bounds, 12..13 child ids / links, 14 = the node's own 1-based id (0: slot unused), 15 =

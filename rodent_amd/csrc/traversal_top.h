@@ -440,12 +440,12 @@ __device__ __forceinline__ int chunk_octant(const Lane& L) {
     return __ballot(L.ray_id >= 0 && !(finite && oct == first)) == 0ull ? first : -1;
 }
 // A chunk's step loop (k_bvh2_top_auto), stated once for the generic form and the eight octants.
-template <bool ANY, bool LAZY, int LDS_N, int WAVES, int OCT>
+template <bool ANY, bool LAZY, int LDS_N, int WAVES, int OCT, bool OFFS>
 __device__ __forceinline__ void trace_chunk(Lane& L, const Bases& base, Hit1* __restrict__ hits, lds_int* sp_limit, Ctl* ctl,
-    int* __restrict__ deep_list, lds_int* image, int* __restrict__ spill, const RaySplat* splat) {
+    int* __restrict__ deep_list, lds_int* image, int* __restrict__ spill, const RaySplat* splat, const RecordOffsets* offs) {
     while (__ballot(L.top != 0)) {
-        if (L.top != 0) bvh2_step<ANY, false, true, LAZY, false, false, LDS_N, WAVES, OCT>(L, base, hits, sp_limit, ctl, deep_list,
-            false, nullptr, image, nullptr, spill, splat);
+        if (L.top != 0) bvh2_step<ANY, false, true, LAZY, false, false, LDS_N, WAVES, OCT, OFFS>(L, base, hits, sp_limit, ctl, deep_list,
+            false, nullptr, image, nullptr, spill, splat, offs);
     }
 }
 
@@ -471,14 +471,16 @@ __device__ __forceinline__ void trace_chunk(Lane& L, const Bases& base, Hit1* __
 // keeps the generic step.
 template <bool ANY, int LDS_N, int TOPN, int WAVES, int REFILL,
     int MODE = 0 /* lab: 1 = whole chunks whatever the rays, 2 = refill whatever the rays */,
-    bool FUSED = true /* lab: false = a follow-up kernel finishes the launch */, bool LAZY = false>
+    bool FUSED = true /* lab: false = a follow-up kernel finishes the launch */, bool LAZY = false,
+    bool OFFS = false /* the step's records from one scalar base + 32-bit lane offsets (RecordOffsets, traversal.hip) */>
 __global__ __launch_bounds__(kWave * WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     k_bvh2_top_auto(const Node2* __restrict__ nodes, const Tri1* __restrict__ tris,
                                                                   const Ray1* __restrict__ rays, Hit1* __restrict__ hits, int n,
                                                                   Ctl* ctl, int* __restrict__ deep_list, int4* __restrict__ top_image,
                                                                       int* __restrict__ tickets, int max_id,
                                                                   int* spill, int* host_kinds, int launch_id, int grid_w,
-                                                                      int octant_loops) {
+                                                                      int octant_loops,
+                                                                  const char* record_base, int d_node, int d_tri) {
     constexpr int kStackInts = WAVES * (LDS_N + 1) * kWave, kGroupRays = 32 * kWave;
     static_assert((kStackInts + TOPN * 16) * 4 * (32 / WAVES) <= 160 * 1024, "32 waves per CU must fit their stacks and images in LDS");
     __shared__ __attribute__((aligned(16))) int lds_raw[kStackInts + TOPN * 16];
@@ -491,11 +493,14 @@ __global__ __launch_bounds__(kWave * WAVES) __attribute__((amdgpu_waves_per_eu(8
     // all: every workgroup validates the same image, and 512 atomics on one address cost a launch of few rays 4 us (Cornell box, 64 ... 393
     // 216 rays: 21.0 ... 24.5 us -> 16.7 ... 21.0, profiles/r05_fixed_costs.txt)
     if (root != 1 && threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(&ctl->stats[6], 1ull);
+    // stats[1] / stats[0]: the launch fetched its records in the offset form / the 64-bit form (read by the tests)
+    if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(&ctl->stats[OFFS ? 1 : 0], 1ull);
     const int stripe = blockIdx.x % kStripes, stripe_waves = (gridDim.x / kStripes) * WAVES;
     int* counter = tickets + stripe * kCounterStride;
     const auto ray_of = [&](int t) { return ((t / kGroupRays) * kStripes + stripe) * kGroupRays + t % kGroupRays; };
     lds_int* const sp_limit = col + LDS_N * kWave;
-    const Bases base = make_bases(nodes, tris);
+    const Bases base = OFFS ? Bases{nullptr, nullptr} : make_bases(nodes, tris);
+    const RecordOffsets offsets = make_offsets(record_base, d_node, d_tri);
     // the wave's first 64 tickets are its rank in the stripe; the counter hands out those behind
     int t = stripe_rank(wave) * kWave;
     bool coherent = MODE != 2;
@@ -536,18 +541,22 @@ __global__ __launch_bounds__(kWave * WAVES) __attribute__((amdgpu_waves_per_eu(8
             // ... and the lane's hit record behind one opaque pointer, for the same reason: every loop would compute hits + ray_id for itself
             // and keep the id's sign extension for the next one.  (The step uses the id for nothing else: stacks spill, no deep list.)
             static_assert(LDS_N > 0, "bvh2_step<SPILL = LDS_N>: the ray id is only the hit record's index");
+            // (the opaque value is the pointer's bits, turned back into a GLOBAL pointer: laundered as a pointer it comes back generic
+            // and the accept path stores with flat_store_dwordx4, which counts on the LDS counter as well as on the vector-memory one)
             const int ray_id = L.ray_id;
-            Hit1* lane_hit = hits + ray_id;
-            asm volatile("" : "+v"(lane_hit));
+            unsigned long long hit_bits = reinterpret_cast<unsigned long long>(hits + ray_id);
+            asm volatile("" : "+v"(hit_bits));
+            Hit1* lane_hit = (Hit1*)(__attribute__((address_space(1))) Hit1*)hit_bits;
             L.ray_id = 0;
-#define RODENT_TRACE_CHUNK(OCT) if (arm == OCT) trace_chunk<ANY, LAZY, LDS_N, WAVES, OCT>(L, base, lane_hit, sp_limit, ctl, deep_list, image, spill, \
-                &splat); \
+#define RODENT_TRACE_CHUNK(OCT) if (arm == OCT) trace_chunk<ANY, LAZY, LDS_N, WAVES, OCT, OFFS>(L, base, lane_hit, sp_limit, ctl, deep_list, image, \
+                spill, &splat, &offsets); \
             asm volatile("" : "+s"(arm))
             RODENT_TRACE_CHUNK(0); RODENT_TRACE_CHUNK(1); RODENT_TRACE_CHUNK(2); RODENT_TRACE_CHUNK(3);
             RODENT_TRACE_CHUNK(4); RODENT_TRACE_CHUNK(5); RODENT_TRACE_CHUNK(6); RODENT_TRACE_CHUNK(7);
 #undef RODENT_TRACE_CHUNK
             // the generic loop last, on the same pairs (behind a loop that ran it finds no live lane)
-            trace_chunk<ANY, LAZY, LDS_N, WAVES, kAnyOctantSplat>(L, base, lane_hit, sp_limit, ctl, deep_list, image, spill, &splat);
+            trace_chunk<ANY, LAZY, LDS_N, WAVES, kAnyOctantSplat, OFFS>(L, base, lane_hit, sp_limit, ctl, deep_list, image, spill, &splat,
+                &offsets);
             L.ray_id = ray_id;
             if (LAZY) finish_lane_reg(L, rays, hits);
             int t_next = 0;
@@ -588,8 +597,8 @@ __global__ __launch_bounds__(kWave * WAVES) __attribute__((amdgpu_waves_per_eu(8
                 continue;
             }
             if (live == 0) break;
-            if (L.top != 0) bvh2_step<ANY, false, true, LAZY, false, false, LDS_N, WAVES>(L, base, hits, sp_limit, ctl, deep_list, false,
-                nullptr, image, nullptr, spill);
+            if (L.top != 0) bvh2_step<ANY, false, true, LAZY, false, false, LDS_N, WAVES, -1, OFFS>(L, base, hits, sp_limit, ctl, deep_list,
+                false, nullptr, image, nullptr, spill, nullptr, &offsets);
         }
         if (LAZY) finish_lane_reg(L, rays, hits);
     }
