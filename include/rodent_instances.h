@@ -1,0 +1,119 @@
+/*
+ * rodent_instances.h -- C ABI of instanced scenes (librodent_hip.so): a two-level hierarchy built and traced on the device.
+ *
+ * Objects keep their own BVH2 / Tri1 hierarchies (rodent_traversal.h; of any builder of rodent_build.h or of a host builder).  An
+ * INSTANCE places one object in the world by a 3 x 4 matrix; a small top-level hierarchy (TLAS) over the instances is rebuilt on the
+ * device whenever the matrices change (rodent_hip_build_tlas: the LBVH stages of rodent_build.h over instance boxes), and
+ * hip_traverse_instanced_bvh2_tri1_async carries every ray into object space and back.  No reference counterpart; tests/instance_model.py
+ * restates everything below on the CPU and predicts the bytes.
+ *
+ * Objects: all objects' Node2 records lie in ONE array and all their Tri1 records in another.  Child ids and leaf indices inside an
+ *   object stay relative to the object's own first node and first triangle, so packing is concatenation: no id is rewritten.
+ * Matrices: 3 x 4, row-major: row a is m[4a .. 4a + 3], the last column the translation.  instance_id is the caller's, in [0, 2^31).
+ * TLAS: a plain Node2 array with the encoding of rodent_traversal.h; a leaf ~first points into the RodentInstance array, which is stored
+ *   in leaf order; bit 31 of instance_id marks the last instance of a leaf, as bit 31 of prim_id does for Tri1.
+ *
+ * All arithmetic is fp32 with every operation rounded on its own (no fused multiply-add), except where marked fp64.
+ *
+ * Inverse (fp64, every operation rounded on its own, in this order; a b c tx / d e f ty / g h i tz = the rows of object_to_world):
+ *   c0 = e*i - f*h   c1 = f*g - d*i   c2 = d*h - e*g      det = (a*c0 + b*c1) + c*c2      r = 1 / det
+ *   row 0: c0*r   (c*h - b*i)*r   (b*f - c*e)*r
+ *   row 1: c1*r   (a*i - c*g)*r   (c*d - a*f)*r
+ *   row 2: c2*r   (b*g - a*h)*r   (a*e - b*d)*r
+ *   translation of row k (q0 q1 q2): -((q0*tx + q1*ty) + q2*tz).  Each of the 12 entries is then rounded to fp32 once.
+ *   RODENT_TLAS_BAD_TRANSFORM: an entry of object_to_world is non-finite, det is 0 or non-finite, or an entry of the rounded inverse is
+ *   non-finite.
+ * World box of an instance: the object's box is the union of its root node's two child boxes (fminf of the lows, fmaxf of the highs: an
+ *   empty slot's (+inf, -inf) drops out).  Its 8 corners (x, y, z) are mapped per row by ((m0*x + m1*y) + m2*z) + m3; the box takes
+ *   fminf / fmaxf over the corners, as v + 0 (one bit pattern for a zero).  Each bound is then moved outward by
+ *   e = 2^-21 * (((|m0|*X + |m1|*Y) + |m2|*Z) + |m3|), X = fmaxf(|lo_x|, |hi_x|) and so on: lo - e, hi + e.  The rounding error of the
+ *   four-term sum is at most gamma_4 ~ 2^-22 times the sum of magnitudes and the factor 2 covers computing e itself in fp32, so the
+ *   widened box contains the exact image of the object box.
+ * TLAS build: the sort point of an instance is lo + hi of its world box per axis; from there the LBVH stages of rodent_build.h as they
+ *   stand: frame, 30-bit Morton codes, stable radix sort (code, then instance index), Karras, renumbering, bottom-up boxes, emission;
+ *   the single-leaf root for num_instances <= max_leaf.  RodentInstance k is the k-th instance in that order: world_to_object, the
+ *   object's node_offset and tri_offset, instance_id (bit 31: the last of its leaf), pad = 0.  The output is a pure function of
+ *   (the objects' root nodes, the object table, the descriptors, max_leaf), byte for byte.  info: [0] Node2 count [1] depth [2] flags
+ *   [3] 0.  An object index outside [0, num_objects) raises RODENT_TLAS_BAD_OBJECT (object 0 is read instead).  With a flag raised the
+ *   output is undefined, but nothing is read or written out of bounds.
+ * Traversal: the TLAS is walked by the step of mapping_gpu.impala:94-178 on the world ray, pushes, pops and leaves unchanged; the
+ *   instances of a leaf are taken in stored order until the marked one.  Entering an instance (rows w of world_to_object):
+ *     org' = ((w0*ox + w1*oy) + w2*oz) + w3,  dir' = (w0*dx + w1*dy) + w2*dz,  tmin unchanged, tmax = the ray's current tmax;
+ *   directions are never normalised, so t parametrises both spaces; inv_dir and inv_org come from the new ray by the make_ray rule
+ *   (intersection.impala:88-99).  The object is traversed from its root with the unchanged BVH2 / Tri1 rules; an accepted triangle sets
+ *   hit = {prim_id & 0x7FFFFFFF, t, u, v}, hit_instance = instance_id and the shared tmax = t.  The acceptance test stays <= across
+ *   instances: a later hit at an equal t replaces an earlier one.  Any-hit returns at the first acceptance.  A miss stores
+ *   {-1, tmax of the ray as given, 0, 0} and instance -1.
+ * Stack: one stack of the reference's 64 entries (stack.impala:53-54) serves both levels.  Its slots, bottom up: the word that ends the
+ *   traversal, the TLAS entries (the visited leaf's continuation stays among them while its instances are traced), the word that ends
+ *   the object's traversal, the object's entries.  With P = the TLAS entries held when an instance is entered + that object's peak
+ *   entries for the ray, a ray whose P + 2 never exceeds 64 is traced without a flag; any other ray raises the overflow flag
+ *   (rodent_hip_check_errors; the synchronous entries abort() on it), stops where it stands and stores an undefined hit: it never reads
+ *   an entry that was not pushed.  A wrong hit without a flag does not occur.
+ */
+#ifndef RODENT_INSTANCES_H
+#define RODENT_INSTANCES_H
+
+#include <stdint.h>
+#include "rodent_build.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+struct RodentObject       { int32_t node_offset, tri_offset, num_nodes, num_tris; };              /* 16 B */
+struct RodentInstanceDesc { float object_to_world[12]; int32_t object, instance_id, pad[2]; };    /* 64 B, the caller's input */
+struct RodentInstance     { float world_to_object[12]; int32_t node_offset, tri_offset,
+                            instance_id /* bit 31 = last in leaf */, pad; };                      /* 64 B, what the kernel reads */
+
+#define RODENT_TLAS_MAX_INSTANCES        (1 << 22)
+
+/* error flags in info[2], beside the builders' (rodent_build.h) */
+#define RODENT_TLAS_BAD_OBJECT           8     /* an object index outside [0, num_objects) */
+#define RODENT_TLAS_BAD_TRANSFORM        16    /* a non-finite entry, a determinant that is 0 or non-finite, a non-finite inverse */
+
+/* return values beside the builders' (RODENT_BUILD_OK, _ERR_MAX_LEAF, _ERR_NULL, _ERR_DEVICE, _ERR_LAUNCH, _ERR_INPUT) */
+#define RODENT_TLAS_ERR_NUM_INSTANCES   -14    /* num_instances outside [1, 2^22] */
+#define RODENT_TLAS_ERR_NUM_OBJECTS     -15    /* num_objects < 1 */
+
+/* Bytes of device scratch rodent_hip_build_tlas needs (-1 for num_instances outside [1, 2^22]); any 256-byte aligned buffer of that
+ * size, its contents are ignored. */
+int64_t rodent_hip_tlas_scratch_bytes(int32_t num_instances);
+
+/* Builds the TLAS of num_instances instances.  All pointers are DEVICE pointers: nodes (the objects' Node2 array: only the root node of
+ * every object is read), objects (num_objects RodentObject), descs (num_instances RodentInstanceDesc), tlas_nodes (room for
+ * max(1, num_instances - 1) Node2), instances (num_instances RodentInstance), scratch (rodent_hip_tlas_scratch_bytes), info_dev
+ * (RODENT_BUILD_INFO_WORDS ints, zeroed at the start of the call).  Asynchronous on `stream` like the builders of rodent_build.h: nothing
+ * is allocated, nothing waits for the device.  Checks, in this order, each enqueuing nothing when it fails:
+ * RODENT_TLAS_ERR_NUM_INSTANCES, RODENT_BUILD_ERR_MAX_LEAF (max_leaf outside [1, 8]), RODENT_TLAS_ERR_NUM_OBJECTS, RODENT_BUILD_ERR_NULL,
+ * RODENT_BUILD_ERR_DEVICE. */
+int32_t rodent_hip_build_tlas(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
+                              const struct RodentInstanceDesc* descs, int32_t num_instances, int32_t max_leaf, struct Node2* tlas_nodes,
+                              struct RodentInstance* instances, void* scratch, int32_t* info_dev, void* stream);
+
+/* Synchronous form on the null stream with its own scratch: copies the info words to `info` (host, may be NULL) and returns
+ * RODENT_BUILD_ERR_INPUT when the device raised a flag. */
+int32_t rodent_hip_build_tlas_sync(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
+                                   const struct RodentInstanceDesc* descs, int32_t num_instances, int32_t max_leaf,
+                                   struct Node2* tlas_nodes, struct RodentInstance* instances, int32_t* info);
+
+/* Traces num_rays rays through the TLAS and the objects below it.  DEVICE pointers; hit_instances (one int32_t per ray) may be NULL.
+ * Enqueued on `stream` without synchronising, like hip_traverse_bvh2_tri1_async; a stack overflow is reported by
+ * rodent_hip_check_errors(dev, stream). */
+void hip_traverse_instanced_bvh2_tri1_async(int32_t dev, const struct Node2* tlas_nodes, const struct RodentInstance* instances,
+                                            const struct Node2* nodes, const struct Tri1* tris, const struct Ray1* rays,
+                                            struct Hit1* hits, int32_t* hit_instances, int32_t num_rays, int32_t any_hit, void* stream);
+
+/* Synchronous forms on the null stream: closest hit / any hit.  They abort() on the overflow flag, as the synchronous entries of
+ * rodent_traversal.h do. */
+void hip_intersect_instanced_bvh2_tri1(int32_t dev, const struct Node2* tlas_nodes, const struct RodentInstance* instances,
+                                       const struct Node2* nodes, const struct Tri1* tris, const struct Ray1* rays, struct Hit1* hits,
+                                       int32_t* hit_instances, int32_t num_rays);
+void hip_occluded_instanced_bvh2_tri1(int32_t dev, const struct Node2* tlas_nodes, const struct RodentInstance* instances,
+                                      const struct Node2* nodes, const struct Tri1* tris, const struct Ray1* rays, struct Hit1* hits,
+                                      int32_t* hit_instances, int32_t num_rays);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RODENT_INSTANCES_H */

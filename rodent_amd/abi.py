@@ -50,6 +50,8 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "rodent_hip_refit_bvh8_tri4", "rodent_hip_refit_bvh8_tri4_sync",
     "rodent_hip_collapse_scratch_bytes", "rodent_hip_collapse_bvh2_tri1", "rodent_hip_collapse_bvh2_tri1_sync",
     "rodent_hip_collapse_bounded_scratch_bytes", "rodent_hip_collapse_bvh2_tri1_bounded", "rodent_hip_collapse_bvh2_tri1_bounded_sync",
+    "rodent_hip_tlas_scratch_bytes", "rodent_hip_build_tlas", "rodent_hip_build_tlas_sync",
+    "hip_traverse_instanced_bvh2_tri1_async", "hip_intersect_instanced_bvh2_tri1", "hip_occluded_instanced_bvh2_tri1",
 ]
 BLOCK_OF_WIDTH = {2: F.BVH2_TRI1, 4: F.BVH4_TRI4, 8: F.BVH8_TRI4}
 
@@ -142,6 +144,16 @@ def lib():
         l.rodent_hip_collapse_bvh2_tri1_bounded.argtypes = [i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
         l.rodent_hip_collapse_bvh2_tri1_bounded_sync.restype = i32
         l.rodent_hip_collapse_bvh2_tri1_bounded_sync.argtypes = [i32, i32, i32, vp, i32, vp, i32, vp, vp, C.POINTER(i32)]
+        # instanced scenes (include/rodent_instances.h)
+        l.rodent_hip_tlas_scratch_bytes.restype = C.c_int64; l.rodent_hip_tlas_scratch_bytes.argtypes = [i32]
+        l.rodent_hip_build_tlas.restype = i32
+        l.rodent_hip_build_tlas.argtypes = [i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+        l.rodent_hip_build_tlas_sync.restype = i32
+        l.rodent_hip_build_tlas_sync.argtypes = [i32, vp, vp, i32, vp, i32, i32, vp, vp, C.POINTER(i32)]
+        l.hip_traverse_instanced_bvh2_tri1_async.restype = None
+        l.hip_traverse_instanced_bvh2_tri1_async.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
+        for name in ("hip_intersect_instanced_bvh2_tri1", "hip_occluded_instanced_bvh2_tri1"):
+            fn = getattr(l, name); fn.restype = None; fn.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i32]
         _lib = l
     return _lib
 

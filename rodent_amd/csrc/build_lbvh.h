@@ -230,10 +230,12 @@ __global__ __launch_bounds__(kBlock) void k_bottom_up(int n, int max_leaf, const
 // ---- 7. emission ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void put_bounds(float* dst, const float* b) { for (int k = 0; k < 6; k++) dst[k] = b[k]; }
 
+// Rec: the leaf records, Tri1 or (build_tlas.h) RodentInstance; only their end-of-leaf bits are written here.
+template <class Rec>
 __global__ __launch_bounds__(kBlock) void k_emit(int m, const int* __restrict__ first, const int* __restrict__ last,
                                                  const int* __restrict__ split, const int* __restrict__ newidx,
                                                  const float* __restrict__ leafbox, const float* __restrict__ box,
-                                                 Node2* __restrict__ nodes, Tri1* __restrict__ tris, const int* nref) {
+                                                 Node2* __restrict__ nodes, Rec* __restrict__ tris, const int* nref) {
     if (nref) m = *nref - 1;                           // n' <= max_leaf: no node is kept, nothing is written
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= m || newidx[i] < 0) return;
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(kBlock) void k_emit(int m, const int* __restrict__ 
             child[k] = newidx[c] + 1;
         } else {
             child[k] = ~lo[k];
-            tris[hi[k]].prim_id = (int32_t)((uint32_t)tris[hi[k]].prim_id | kLastInLeaf);
+            mark_last_in_leaf(tris + hi[k]);
         }
     }
     float4* out = reinterpret_cast<float4*>(nodes + newidx[i]);
@@ -260,11 +262,12 @@ __global__ __launch_bounds__(kBlock) void k_emit(int m, const int* __restrict__ 
 }
 
 // n <= max_leaf: the single-leaf root.  With `nref` (the split entry: n' on the device) it writes only when n' <= limit.
+template <class Rec>
 __global__ void k_emit_root(int n, const float* __restrict__ leafbox, const float* __restrict__ box, Node2* __restrict__ nodes,
-                            Tri1* __restrict__ tris, int* info, const int* nref, int limit) {
+                            Rec* __restrict__ tris, int* info, const int* nref, int limit) {
     if (nref) { n = *nref; if (n > limit) return; }
     store_leaf_root(nodes, n == 1 ? leafbox : box);
-    tris[n - 1].prim_id = (int32_t)((uint32_t)tris[n - 1].prim_id | kLastInLeaf);
+    mark_last_in_leaf(tris + (n - 1));
     info[kInfoNodes] = 1;
     info[kInfoDepth] = 1;
 }

@@ -1,0 +1,91 @@
+// build_tlas.h -- the top level of an instanced scene (include/rodent_instances.h; included by bvh_build.hip after build_lbvh.h): the
+// instance stage in front of the LBVH's stages 2, 3, 5, 6 and 7 and the leaf stage in the place of stage 4.  CPU model:
+// tests/instance_model.py.
+#pragma once
+// world_to_object of object_to_world `m` (rows of 4): the cofactor inverse in fp64 in the header's order, each entry rounded to fp32
+// once.  Returns RODENT_TLAS_BAD_TRANSFORM or 0.
+__device__ __forceinline__ int invert_affine(const float m[12], float w[12]) {
+    bool ok = true;
+    for (int k = 0; k < 12; k++) ok = ok && isfinite(m[k]);
+    const double a = m[0], b = m[1], c = m[2], tx = m[3], d = m[4], e = m[5], f = m[6], ty = m[7], g = m[8], h = m[9], i = m[10],
+                 tz = m[11];
+    const double c0 = e * i - f * h, c1 = f * g - d * i, c2 = d * h - e * g;
+    const double det = (a * c0 + b * c1) + c * c2;
+    const double r = 1.0 / det;
+    const double q[9] = {c0 * r, (c * h - b * i) * r, (b * f - c * e) * r,
+                         c1 * r, (a * i - c * g) * r, (c * d - a * f) * r,
+                         c2 * r, (b * g - a * h) * r, (a * e - b * d) * r};
+    for (int k = 0; k < 3; k++) {
+        for (int j = 0; j < 3; j++) w[4 * k + j] = (float)q[3 * k + j];
+        w[4 * k + 3] = (float)-((q[3 * k] * tx + q[3 * k + 1] * ty) + q[3 * k + 2] * tz);
+    }
+    ok = ok && det != 0.0 && isfinite(det);
+    for (int k = 0; k < 12; k++) ok = ok && isfinite(w[k]);
+    return ok ? 0 : RODENT_TLAS_BAD_TRANSFORM;
+}
+
+// The widened world box (lo_x hi_x lo_y hi_y lo_z hi_z) of the object box olo / ohi under `m`.
+__device__ __forceinline__ void instance_world_box(const float m[12], const float olo[3], const float ohi[3], float box[6]) {
+    const float X = fmaxf(fabsf(olo[0]), fabsf(ohi[0])), Y = fmaxf(fabsf(olo[1]), fabsf(ohi[1])), Z = fmaxf(fabsf(olo[2]), fabsf(ohi[2]));
+    for (int a = 0; a < 3; a++) {
+        const float* r = m + 4 * a;
+        float mn = INFINITY, mx = -INFINITY;
+        for (int corner = 0; corner < 8; corner++) {
+            const float x = (corner & 1) ? ohi[0] : olo[0], y = (corner & 2) ? ohi[1] : olo[1], z = (corner & 4) ? ohi[2] : olo[2];
+            const float v = ((r[0] * x + r[1] * y) + r[2] * z) + r[3];
+            mn = fminf(mn, v); mx = fmaxf(mx, v);
+        }
+        const float e = 0x1p-21f * (((fabsf(r[0]) * X + fabsf(r[1]) * Y) + fabsf(r[2]) * Z) + fabsf(r[3]));
+        box[2 * a] = canon(mn) - e; box[2 * a + 1] = canon(mx) + e;
+    }
+}
+
+// ---- the instance stage: inverse, world box, sort point, flags (in the place of k_centroids) ------------------------------------------
+// staged[t]: the RodentInstance record of descriptor t without its end-of-leaf bit; wbox[6 t]: its world box; cent[t]: its sort point.
+__global__ __launch_bounds__(kBlock) void k_instances(const Node2* __restrict__ nodes, const RodentObject* __restrict__ objects,
+                                                      int num_objects, const RodentInstanceDesc* __restrict__ descs, int n,
+                                                      RodentInstance* __restrict__ staged, float* __restrict__ wbox,
+                                                      float4* __restrict__ cent, float* __restrict__ partial, int* info) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int t = blockIdx.x * kBlock + threadIdx.x; t < n; t += gridDim.x * kBlock) {
+        const float4* dp = reinterpret_cast<const float4*>(descs + t);
+        const float4 r0 = dp[0], r1 = dp[1], r2 = dp[2];
+        const int4 id = *reinterpret_cast<const int4*>(dp + 3);          // object, instance_id, pad, pad
+        const float m[12] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
+        int flags = 0, object = id.x;
+        if ((unsigned)object >= (unsigned)num_objects) { flags |= RODENT_TLAS_BAD_OBJECT; object = 0; }
+        const int4 ob = reinterpret_cast<const int4*>(objects)[object];  // node_offset, tri_offset, num_nodes, num_tris
+        float w[12];
+        flags |= invert_affine(m, w);
+        const float4* np = reinterpret_cast<const float4*>(nodes + ob.x);
+        const float4 b0 = np[0], b1 = np[1], b2 = np[2];                 // child 0: b0.x .. b1.y, child 1: b1.z .. b2.w
+        const float olo[3] = {fminf(b0.x, b1.z), fminf(b0.z, b2.x), fminf(b1.x, b2.z)};
+        const float ohi[3] = {fmaxf(b0.y, b1.w), fmaxf(b0.w, b2.y), fmaxf(b1.y, b2.w)};
+        float box[6];
+        instance_world_box(m, olo, ohi, box);
+        const float s[3] = {box[0] + box[1], box[2] + box[3], box[4] + box[5]};
+        float4* out = reinterpret_cast<float4*>(staged + t);
+        out[0] = make_float4(w[0], w[1], w[2], w[3]);
+        out[1] = make_float4(w[4], w[5], w[6], w[7]);
+        out[2] = make_float4(w[8], w[9], w[10], w[11]);
+        out[3] = make_float4(__int_as_float(ob.x), __int_as_float(ob.y), __int_as_float(id.y & 0x7FFFFFFF), 0.0f);
+        for (int k = 0; k < 6; k++) wbox[6 * (size_t)t + k] = box[k];
+        cent[t] = make_float4(s[0], s[1], s[2], 0.0f);
+        for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], s[a]); hi[a] = fmaxf(hi[a], s[a]); }
+        if (flags) atomicOr(&info[kInfoFlags], flags);
+    }
+    block_bounds(lo, hi, partial + 6 * blockIdx.x);
+}
+
+// ---- the leaf stage: RodentInstance records and leaf boxes in sorted order (in the place of k_leaves) ---------------------------------
+__global__ __launch_bounds__(kBlock) void k_tlas_leaves(const RodentInstance* __restrict__ staged, const float* __restrict__ wbox,
+                                                        const uint32_t* __restrict__ order, int n,
+                                                        RodentInstance* __restrict__ instances, float* __restrict__ leafbox) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const size_t r = order[p];
+    const float4* in = reinterpret_cast<const float4*>(staged + r);
+    float4* out = reinterpret_cast<float4*>(instances + p);
+    for (int k = 0; k < 4; k++) out[k] = in[k];
+    for (int k = 0; k < 6; k++) leafbox[6 * (size_t)p + k] = wbox[6 * r + k];
+}

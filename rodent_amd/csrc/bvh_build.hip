@@ -3,7 +3,8 @@
 // C ABI: include/rodent_build.h.  CPU models of every stage, byte for byte: tests/lbvh_model.py, tests/trbvh_model.py (treelets),
 // tests/split_model.py (pre-splitting), tests/refit_model.py and tests/refit_wide_model.py (refit).
 // The kernels lie in build_device.h (what the stages share), build_lbvh.h, build_treelet.h, build_split.h, build_refit.h and
-// build_collapse.h.
+// build_collapse.h; build_tlas.h holds the instance and leaf stages of an instanced scene's top level (rodent_hip_build_tlas,
+// include/rodent_instances.h; CPU model: tests/instance_model.py), which runs the LBVH's sort, Karras and tail stages over instance boxes.
 // One pipeline (launch_build), all on the caller's stream, nothing allocated, no host synchronisation.  The three entry points only
 // choose its options: rodent_hip_build_bvh2_tri1 the LBVH, _opt treelet_passes (0, or one triangle: the LBVH), _split the split front.
 // Front, one of:
@@ -46,6 +47,7 @@
 #include <cstdlib>
 
 #include "rodent_build.h"
+#include "rodent_instances.h"
 
 namespace {
 #include "build_device.h"
@@ -160,7 +162,22 @@ CollapseScratch carve_collapse(char* base, int num_nodes, int num_bvh_tris, bool
     return s;
 }
 
+struct TlasScratch {
+    RodentInstance* staged;       // per descriptor: its RodentInstance record, before the sort
+    float* wbox;                  // per descriptor: its world box
+    size_t bytes;
+};
+
+TlasScratch carve_tlas(char* base, int n) {
+    TlasScratch t{};
+    Carver c{base};
+    c.take(t.staged, (size_t)n); c.take(t.wbox, 6 * (size_t)n);
+    t.bytes = c.bytes;
+    return t;
+}
+
 #include "build_lbvh.h"
+#include "build_tlas.h"
 #include "build_treelet.h"
 #include "build_split.h"
 #include "build_refit.h"
@@ -218,11 +235,10 @@ Opt make_opt(const Scratch& s, int n, const RodentBuildOptions& opt, const int* 
     return o;
 }
 
-// Morton codes (from s.cent and s.frame), the sort, the sorted leaves and (n > 1) the Karras hierarchy.  With `nref` (split) the
-// grids are sized for n = max_refs and every kernel runs over the n' = *nref references (reftri / refbox: their triangles and boxes).
-void launch_tree(const Scratch& s, const float4* v4, int nv, const int4* i4, int n, int max_leaf, Tri1* tris, const int* nref,
-                 const int* reftri, const float* refbox, hipStream_t stream) {
-    const int m = n - 1;
+// launch_tree: Morton codes (from s.cent and s.frame) and the sort (launch_sort), the sorted leaves and (n > 1) the Karras hierarchy
+// (launch_karras); the TLAS build (launch_tlas) puts its own leaf stage between the two.  With `nref` (split) the grids are sized for
+// n = max_refs and every kernel runs over the n' = *nref references (reftri / refbox: their triangles and boxes).
+void launch_sort(const Scratch& s, int n, const int* nref, hipStream_t stream) {
     hipLaunchKernelGGL(k_morton, dim3(blocks_for(n)), dim3(kBlock), 0, stream, s.cent, n, s.frame, s.keys[0], s.vals[0], nref);
     const int tiles = radix_tiles(n);
     for (int pass = 0; pass < 4; pass++) {                       // 30 key bits: 8 + 8 + 8 + 6; four passes end in buffer 0
@@ -232,16 +248,27 @@ void launch_tree(const Scratch& s, const float4* v4, int nv, const int4* i4, int
         hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(kBlock), 0, stream, s.keys[in], s.vals[in], s.keys[in ^ 1],
                            s.vals[in ^ 1], s.hist, n, shift, nref);
     }
-    hipLaunchKernelGGL(k_leaves, dim3(blocks_for(n)), dim3(kBlock), 0, stream, v4, nv, i4, s.vals[0], n, tris, s.leafbox, nref,
-                       reftri, refbox);
+}
+
+void launch_karras(const Scratch& s, int n, int max_leaf, const int* nref, hipStream_t stream) {
+    const int m = n - 1;
     if (m > 0)
         hipLaunchKernelGGL(k_karras, dim3(blocks_for(m)), dim3(kBlock), 0, stream, s.keys[0], n, max_leaf, s.first, s.last, s.split,
                            s.parent, s.leaf_parent, s.blockcount, nref);
 }
 
+void launch_tree(const Scratch& s, const float4* v4, int nv, const int4* i4, int n, int max_leaf, Tri1* tris, const int* nref,
+                 const int* reftri, const float* refbox, hipStream_t stream) {
+    launch_sort(s, n, nref, stream);
+    hipLaunchKernelGGL(k_leaves, dim3(blocks_for(n)), dim3(kBlock), 0, stream, v4, nv, i4, s.vals[0], n, tris, s.leafbox, nref,
+                       reftri, refbox);
+    launch_karras(s, n, max_leaf, nref, stream);
+}
+
 // The LBVH tail: renumbering, boxes and heights, Node2 records.  Without `nref` the host knows n and launches either k_emit or the
 // single-leaf root; with it both are launched and each writes only when n' calls for it.
-void launch_lbvh_tail(const Scratch& s, int n, int max_leaf, Node2* nodes, Tri1* tris, int32_t* info_dev, const int* nref,
+template <class Rec>
+void launch_lbvh_tail(const Scratch& s, int n, int max_leaf, Node2* nodes, Rec* tris, int32_t* info_dev, const int* nref,
                       hipStream_t stream) {
     const int m = n - 1;
     if (m > 0) {
@@ -253,10 +280,10 @@ void launch_lbvh_tail(const Scratch& s, int n, int max_leaf, Node2* nodes, Tri1*
                            s.leaf_parent, s.leafbox, s.box, s.height, s.arrivals, info_dev, nref);
     }
     if (nref ? m > 0 : n > max_leaf)
-        hipLaunchKernelGGL(k_emit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.newidx, s.leafbox,
+        hipLaunchKernelGGL(k_emit<Rec>, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.newidx, s.leafbox,
                            s.box, nodes, tris, nref);
     if (nref || n <= max_leaf)
-        hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, n, s.leafbox, s.box, nodes, tris, info_dev, nref, max_leaf);
+        hipLaunchKernelGGL(k_emit_root<Rec>, dim3(1), dim3(1), 0, stream, n, s.leafbox, s.box, nodes, tris, info_dev, nref, max_leaf);
 }
 
 // The optimising tail: the explicit tree, k_fit, the treelet passes, k_fit again, pre-order emission.  Without `nref` it is only
@@ -280,7 +307,7 @@ bool launch_opt_tail(const Scratch& s, int n, const RodentBuildOptions& opt, con
         hipLaunchKernelGGL(k_emit_opt_tris, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, v4, nv, i4, s.vals[0], tris, reftri);
     }
     // one reference (one triangle, not cut): the single-leaf form, as the LBVH writes it for one triangle
-    if (nref) hipLaunchKernelGGL(k_emit_root, dim3(1), dim3(1), 0, stream, n, s.leafbox, s.box, nodes, tris, info_dev, nref, 1);
+    if (nref) hipLaunchKernelGGL(k_emit_root<Tri1>, dim3(1), dim3(1), 0, stream, n, s.leafbox, s.box, nodes, tris, info_dev, nref, 1);
     return true;
 }
 
@@ -327,6 +354,27 @@ int32_t launch_build(const float* vertices, int nv, const int32_t* indices, int 
         launch_lbvh_tail(s, R, opt.max_leaf, nodes, tris, info_dev, nref, stream);
     else if (!launch_opt_tail(s, R, opt, v4, nv, i4, nodes, tris, info_dev, nref, q.reftri, stream))
         return RODENT_BUILD_ERR_LAUNCH;
+    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
+// The TLAS build after its argument checks: info words and arrival counters zeroed, the instance stage and the frame of its sort points,
+// the sort, the leaf stage, Karras and the LBVH tail over RodentInstance records.
+int32_t launch_tlas(const Node2* nodes, const RodentObject* objects, int num_objects, const RodentInstanceDesc* descs, int n, int max_leaf,
+                    Node2* tlas_nodes, RodentInstance* instances, void* scratch, int32_t* info_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const Scratch s = carve(static_cast<char*>(scratch), n);
+    const TlasScratch t = carve_tlas(static_cast<char*>(scratch) + s.bytes, n);
+    if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess
+        || (n > 1 && hipMemsetAsync(s.arrivals, 0, 4 * (size_t)(n - 1), stream) != hipSuccess))
+        return RODENT_BUILD_ERR_LAUNCH;
+    const int cblocks = std::min(kBoundsBlocks, blocks_for(n));
+    hipLaunchKernelGGL(k_instances, dim3(cblocks), dim3(kBlock), 0, stream, nodes, objects, num_objects, descs, n, t.staged, t.wbox,
+                       s.cent, s.partial, info_dev);
+    hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, s.partial, cblocks, s.frame);
+    launch_sort(s, n, nullptr, stream);
+    hipLaunchKernelGGL(k_tlas_leaves, dim3(blocks_for(n)), dim3(kBlock), 0, stream, t.staged, t.wbox, s.vals[0], n, instances, s.leafbox);
+    launch_karras(s, n, max_leaf, nullptr, stream);
+    launch_lbvh_tail(s, n, max_leaf, tlas_nodes, instances, info_dev, nullptr, stream);
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
 
@@ -668,6 +716,34 @@ int32_t rodent_hip_collapse_bvh2_tri1_bounded_sync(int32_t dev, int32_t width, i
     if (bytes < 0) return RODENT_BUILD_ERR_NUM_NODES;
     return build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
         return collapse(dev, width, stack_limit, nodes, num_nodes, tris, num_bvh_tris, wide_nodes, packets, scratch, info_dev, nullptr);
+    });
+}
+
+int64_t rodent_hip_tlas_scratch_bytes(int32_t num_instances) {
+    if (num_instances < 1 || num_instances > RODENT_TLAS_MAX_INSTANCES) return -1;
+    return (int64_t)(carve(nullptr, num_instances).bytes + carve_tlas(nullptr, num_instances).bytes);
+}
+
+int32_t rodent_hip_build_tlas(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
+                              const struct RodentInstanceDesc* descs, int32_t num_instances, int32_t max_leaf, struct Node2* tlas_nodes,
+                              struct RodentInstance* instances, void* scratch, int32_t* info_dev, void* stream) {
+    if (num_instances < 1 || num_instances > RODENT_TLAS_MAX_INSTANCES) return RODENT_TLAS_ERR_NUM_INSTANCES;
+    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) return RODENT_BUILD_ERR_MAX_LEAF;
+    if (num_objects < 1) return RODENT_TLAS_ERR_NUM_OBJECTS;
+    if (!nodes || !objects || !descs || !tlas_nodes || !instances || !scratch || !info_dev) return RODENT_BUILD_ERR_NULL;
+    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
+    return launch_tlas(nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_build_tlas_sync(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
+                                   const struct RodentInstanceDesc* descs, int32_t num_instances, int32_t max_leaf,
+                                   struct Node2* tlas_nodes, struct RodentInstance* instances, int32_t* info) {
+    const int64_t bytes = rodent_hip_tlas_scratch_bytes(num_instances);
+    if (bytes < 0) return RODENT_TLAS_ERR_NUM_INSTANCES;
+    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) return RODENT_BUILD_ERR_MAX_LEAF;
+    return build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
+        return rodent_hip_build_tlas(dev, nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch,
+                                     info_dev, nullptr);
     });
 }
 

@@ -43,6 +43,7 @@
 
 #include "device_buffer.h"
 #include "rodent_traversal.h"
+#include "rodent_instances.h"
 #include "traversal_device.h"
 
 namespace {
@@ -1205,6 +1206,7 @@ template <bool ANY, int LDS_N, int CAPS, int LAST_RAYS = kWave> void L_phased(LA
 
 #include "traversal_wide.h"          // BVH4 / BVH8 + Tri4: k_wide_single, k_wide_top_persist, k_wide_finish, L_wide_single, L_wide_top
 int wide_top_min_rays() { return g_top_min_rays; }
+#include "traversal_instanced.h"     // instanced scenes: a TLAS over objects' BVH2 / Tri1 (k_instanced)
 #ifdef RODENT_HIP_LAB
 #include "lab/top_kernels.h"         // lab build only: superseded forms of the LDS-image kernels
 #include "lab/top_launchers.h"
@@ -1299,6 +1301,33 @@ void launch_wide(int width, bool any_hit, DeviceState& s, const void* nodes, con
     HIP_CHECK(hipGetLastError());
 }
 
+// Instanced scenes (include/rodent_instances.h): one launch, one chunk per one-wave workgroup; nothing of the context but its control
+// block is used, so nothing is reserved.
+void launch_instanced(DeviceState& s, const Node2* tlas, const RodentInstance* instances, const Node2* nodes, const Tri1* tris,
+    const Ray1* rays, Hit1* hits, int32_t* hit_instances, int n, bool any_hit, hipStream_t stream) {
+    if (n <= 0) return;
+    if (any_hit)
+        hipLaunchKernelGGL((k_instanced<true>), dim3(blocks_for(n)), dim3(kWave), 0, stream, tlas, instances, nodes, tris, rays, hits,
+            hit_instances, n, s.ctl());
+    else
+        hipLaunchKernelGGL((k_instanced<false>), dim3(blocks_for(n)), dim3(kWave), 0, stream, tlas, instances, nodes, tris, rays, hits,
+            hit_instances, n, s.ctl());
+    HIP_CHECK(hipGetLastError());
+}
+
+// The synchronous instanced entries: the launch on the null stream, then the wait; abort() on the overflow flag.
+void instanced_sync_call(int32_t dev, const Node2* tlas, const RodentInstance* instances, const Node2* nodes, const Tri1* tris,
+    const Ray1* rays, Hit1* hits, int32_t* hit_instances, int32_t num_rays, bool any_hit) {
+    DeviceGuard on(dev);
+    DeviceState& s = device_state(dev, nullptr);
+    std::lock_guard<std::mutex> one_call(s.sync_mutex);
+    {
+        std::lock_guard<std::mutex> launching(s.mutex);
+        launch_instanced(s, tlas, instances, nodes, tris, rays, hits, hit_instances, num_rays, any_hit, nullptr);
+    }
+    check_error_flag(s, nullptr);
+}
+
 int default_variant(int width) {
     const char* e = getenv(width == 2 ? "RODENT_HIP_BVH2_VARIANT" : (width == 4 ? "RODENT_HIP_BVH4_VARIANT" : "RODENT_HIP_BVH8_VARIANT"));
     return e ? atoi(e) : 0;
@@ -1331,6 +1360,25 @@ void hip_traverse_bvh8_tri4_async(int32_t dev, const Node8* nodes, const Tri4* t
     DeviceState& s = device_state(dev, (hipStream_t)stream);
     std::lock_guard<std::mutex> launching(s.mutex);
     launch_wide(8, any_hit != 0, s, nodes, tris, rays, hits, num_rays, variant, (hipStream_t)stream);
+}
+
+void hip_traverse_instanced_bvh2_tri1_async(int32_t dev, const Node2* tlas_nodes, const RodentInstance* instances, const Node2* nodes,
+                                            const Tri1* tris, const Ray1* rays, Hit1* hits, int32_t* hit_instances, int32_t num_rays,
+                                            int32_t any_hit, void* stream) {
+    DeviceGuard on(dev);
+    DeviceState& s = device_state(dev, (hipStream_t)stream);
+    std::lock_guard<std::mutex> launching(s.mutex);
+    launch_instanced(s, tlas_nodes, instances, nodes, tris, rays, hits, hit_instances, num_rays, any_hit != 0, (hipStream_t)stream);
+}
+
+void hip_intersect_instanced_bvh2_tri1(int32_t dev, const Node2* tlas_nodes, const RodentInstance* instances, const Node2* nodes,
+                                       const Tri1* tris, const Ray1* rays, Hit1* hits, int32_t* hit_instances, int32_t num_rays) {
+    instanced_sync_call(dev, tlas_nodes, instances, nodes, tris, rays, hits, hit_instances, num_rays, false);
+}
+
+void hip_occluded_instanced_bvh2_tri1(int32_t dev, const Node2* tlas_nodes, const RodentInstance* instances, const Node2* nodes,
+                                      const Tri1* tris, const Ray1* rays, Hit1* hits, int32_t* hit_instances, int32_t num_rays) {
+    instanced_sync_call(dev, tlas_nodes, instances, nodes, tris, rays, hits, hit_instances, num_rays, true);
 }
 
 int32_t rodent_hip_check_errors(int32_t dev, void* stream) {

@@ -26,8 +26,15 @@ TRI4 = np.dtype([("v0", "<f4", (3, 4)), ("e1", "<f4", (3, 4)), ("e2", "<f4", (3,
 RAY1 = np.dtype([("org", "<f4", (3,)), ("tmin", "<f4"), ("dir", "<f4", (3,)), ("tmax", "<f4")])
 HIT1 = np.dtype([("tri_id", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4")])
 
+# instanced scenes (include/rodent_instances.h): matrices are 3 x 4, row-major
+OBJECT = np.dtype([("node_offset", "<i4"), ("tri_offset", "<i4"), ("num_nodes", "<i4"), ("num_tris", "<i4")])
+INSTANCE_DESC = np.dtype([("object_to_world", "<f4", (12,)), ("object", "<i4"), ("instance_id", "<i4"), ("pad", "<i4", (2,))])
+INSTANCE = np.dtype([("world_to_object", "<f4", (12,)), ("node_offset", "<i4"), ("tri_offset", "<i4"), ("instance_id", "<i4"),
+                     ("pad", "<i4")])
+
 assert (NODE2.itemsize, TRI1.itemsize, NODE4.itemsize, NODE8.itemsize, TRI4.itemsize,
         RAY1.itemsize, HIT1.itemsize) == (64, 48, 128, 256, 224, 32, 16)
+assert (OBJECT.itemsize, INSTANCE_DESC.itemsize, INSTANCE.itemsize) == (16, 64, 64)
 
 _BLOCK_DTYPES = {BVH2_TRI1: (NODE2, TRI1), BVH4_TRI4: (NODE4, TRI4), BVH8_TRI4: (NODE8, TRI4)}
 

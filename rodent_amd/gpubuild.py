@@ -42,7 +42,8 @@ MAX_STACK_LIMIT = 63
 _ERRORS = {-1: "num_tris outside [1, 2^25]", -2: "max_leaf outside [1, 8]", -3: "no vertices", -4: "NULL pointer",
            -5: "no such device", -6: "launch failed", -8: "treelet_passes outside [0, 3]", -9: "node_cost / tri_cost outside (0, 1e6]",
            ERR_SPLIT: "split budget outside [0, 4] or max_pieces outside [1, 64]", ERR_NUM_NODES: "a hierarchy without nodes or triangles",
-           ERR_WIDTH: "width other than 4 or 8", ERR_STACK_LIMIT: "stack_limit outside [0, 63]"}
+           ERR_WIDTH: "width other than 4 or 8", ERR_STACK_LIMIT: "stack_limit outside [0, 63]",
+           -14: "num_instances outside [1, 2^22]", -15: "no objects"}      # RODENT_TLAS_ERR_* (rodent_amd/instances.py)
 _FLAGS = ((BAD_INDEX, "vertex index outside the vertex array"), (NON_FINITE, "non-finite vertex coordinate"),
           (BAD_TOPOLOGY, "malformed hierarchy (child id or prim_id out of range, leaf without end bit, node with two parents)"))
 

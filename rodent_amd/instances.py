@@ -1,0 +1,198 @@
+"""Instanced scenes: many placed copies of a few objects, traced through a two-level hierarchy built on the GPU (C ABI:
+include/rodent_instances.h; kernels: csrc/build_tlas.h, csrc/traversal_instanced.h).
+
+    objects = pack_objects([bvh_a, bvh_b])                    # width-2 DeviceBvhs (any builder) or (nodes, tris) numpy pairs
+    tlas = build_tlas(objects, transforms, object_ids)        # transforms: (n, 12) or (n, 3, 4), row-major object_to_world
+    hits, ids = trace(objects, tlas, rays)                    # Hit1 records (tri_id: the object's own prim id) + instance ids
+    build_tlas(objects, moved_transforms, object_ids, out=tlas)   # the per-frame path: the objects' hierarchies stay as they are
+
+The top-level hierarchy is a pure function of the objects' root boxes, the transforms and max_leaf, byte for byte.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import abi, formats as F
+from .gpubuild import BuildError, INFO_WORDS, MAX_LEAF, _FLAGS, _enqueue
+
+MAX_INSTANCES = 1 << 22
+BAD_OBJECT, BAD_TRANSFORM = 8, 16
+ERR_NUM_INSTANCES, ERR_NUM_OBJECTS = -14, -15              # RODENT_TLAS_ERR_*
+_TLAS_FLAGS = _FLAGS + ((BAD_OBJECT, "object index outside the object table"),
+                        (BAD_TRANSFORM, "singular or non-finite transform"))
+
+
+def _need_gpu():
+    if not torch.cuda.is_available():
+        raise RuntimeError("rodent_amd: no GPU visible (torch.cuda.is_available() is False)")
+
+
+class ObjectSet:
+    """The packed objects: every object's Node2 records in `nodes`, every object's Tri1 records in `tris` (views of ONE allocation,
+    `buffer`, the triangles 256-byte aligned behind the nodes, as in abi.DeviceBvh), and the RodentObject table on the host (`table`,
+    formats.OBJECT) and on the device (`table_dev`)."""
+
+    def __init__(self, buffer, nodes, tris, table, table_dev, dev):
+        self.buffer, self.nodes, self.tris, self.table, self.table_dev, self.dev = buffer, nodes, tris, table, table_dev, dev
+        self.num_objects, self.num_nodes, self.num_tris = len(table), int(table["num_nodes"].sum()), int(table["num_tris"].sum())
+
+    @property
+    def device_bytes(self):
+        return self.buffer.numel() + self.table_dev.numel() * self.table_dev.element_size()
+
+
+def pack_objects(bvhs, dev=0) -> ObjectSet:
+    """Packs width-2 abi.DeviceBvh objects or (nodes NODE2, tris TRI1) numpy pairs into one ObjectSet.  Child ids and leaf indices stay
+    relative to each object's own first node and triangle: packing is concatenation, no id is rewritten."""
+    _need_gpu()
+    if not len(bvhs):
+        raise ValueError("pack_objects: at least one object is needed")
+    cuda = f"cuda:{dev}"
+    parts, table = [], np.zeros(len(bvhs), F.OBJECT)
+    for k, b in enumerate(bvhs):
+        if isinstance(b, abi.DeviceBvh):
+            if b.width != 2:
+                raise ValueError("pack_objects: BVH2 / Tri1 hierarchies are needed")
+            nb = b.nodes.view(torch.uint8).reshape(-1)[: b.num_nodes * F.NODE2.itemsize].to(cuda)
+            tb = b.tris.view(torch.uint8).reshape(-1)[: b.num_tris * F.TRI1.itemsize].to(cuda)
+            count = (b.num_nodes, b.num_tris)
+        else:
+            nodes, tris = (np.ascontiguousarray(a) for a in b)
+            if nodes.dtype != F.NODE2 or tris.dtype != F.TRI1:
+                raise ValueError("pack_objects: (nodes NODE2, tris TRI1) arrays are needed")
+            nb, tb, count = abi.to_device(nodes, dev), abi.to_device(tris, dev), (len(nodes), len(tris))
+        if count[0] < 1 or count[1] < 1:
+            raise ValueError("pack_objects: an object without nodes or triangles")
+        parts.append((nb, tb))
+        table[k]["num_nodes"], table[k]["num_tris"] = count
+    table["node_offset"] = np.cumsum(table["num_nodes"]) - table["num_nodes"]
+    table["tri_offset"] = np.cumsum(table["num_tris"]) - table["num_tris"]
+    node_bytes, tri_bytes = int(table["num_nodes"].sum()) * F.NODE2.itemsize, int(table["num_tris"].sum()) * F.TRI1.itemsize
+    start = (node_bytes + 255) // 256 * 256
+    buffer = torch.zeros(start + tri_bytes, dtype=torch.uint8, device=cuda)
+    nodes, tris = buffer[:node_bytes], buffer[start:]
+    for row, (nb, tb) in zip(table, parts):
+        nodes[int(row["node_offset"]) * F.NODE2.itemsize:][: nb.numel()] = nb
+        tris[int(row["tri_offset"]) * F.TRI1.itemsize:][: tb.numel()] = tb
+    return ObjectSet(buffer, nodes, tris, table, abi.to_device(table, dev), dev)
+
+
+class Tlas:
+    """A top-level hierarchy on the device: `nodes` (Node2) and `instances` (RodentInstance, in leaf order) as uint8 tensors, the info
+    words of its build ([0] nodes [1] depth [2] flags), `depth`, and the scratch tensor for the next rebuild."""
+
+    def __init__(self, nodes, instances, num_instances, info, scratch, dev):
+        self.nodes, self.instances, self.num_instances, self.scratch, self.dev = nodes, instances, int(num_instances), scratch, dev
+        self.info, self.num_nodes, self.depth = info, int(info[0]), int(info[1])
+
+    @property
+    def device_bytes(self):
+        return self.num_nodes * F.NODE2.itemsize + self.num_instances * F.INSTANCE.itemsize
+
+
+def _descriptors(transforms, object_ids, instance_ids, cuda):
+    """The RodentInstanceDesc array on the device: (n, 16) int32 words."""
+    t = transforms if isinstance(transforms, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(transforms, np.float32))
+    n = t.shape[0] if t.dim() else 0
+    if not 1 <= n <= MAX_INSTANCES:
+        raise BuildError(f"num_instances = {n}: outside [1, 2^22]")
+    if t.numel() != 12 * n:
+        raise ValueError(f"expected (n, 12) or (n, 3, 4) transforms, got shape {tuple(t.shape)}")
+    t = t.to(device=cuda, dtype=torch.float32).reshape(n, 12).contiguous()
+    # Ids that come from the host are checked there; ids that are tensors already are taken as they are, with no copy back to the host
+    # (the per-frame path): the instance stage keeps the low 31 bits of an instance id and checks every object id itself.
+    words = []
+    for name, ids in (("object_ids", object_ids), ("instance_ids", instance_ids)):
+        if ids is None:
+            ids = torch.arange(n, dtype=torch.int32, device=cuda)
+        elif not isinstance(ids, torch.Tensor):
+            ids = np.ascontiguousarray(ids).astype(np.int64)
+            if name == "instance_ids" and ids.size and (ids.min() < 0 or ids.max() >= 1 << 31):
+                raise BuildError("instance_ids outside [0, 2^31)")
+            # (an object id past int32 becomes -1, which is outside every table too)
+            ids = torch.from_numpy(np.clip(ids, -1, (1 << 31) - 1).astype(np.int32))
+        if ids.shape != (n,):
+            raise ValueError(f"{name}: expected {n} ids, got shape {tuple(ids.shape)}")
+        words.append(ids.to(device=cuda, dtype=torch.int32))
+    desc = torch.zeros((n, 16), dtype=torch.int32, device=cuda)
+    desc[:, :12] = t.view(torch.int32)
+    desc[:, 12], desc[:, 13] = words
+    return desc
+
+
+def build_tlas(objects: ObjectSet, transforms, object_ids, instance_ids=None, max_leaf=1, stream=None, scratch=None, out=None) -> Tlas:
+    """Builds the top-level hierarchy over the instances (object_ids[k] placed by transforms[k], object_to_world, 3 x 4 row-major;
+    instance_ids default to 0 ... n - 1) on `stream` (torch stream, None = the current one).  Raises BuildError on invalid arguments and
+    on the device's flags (an object index outside the table, a singular or non-finite transform).
+
+    scratch / out: reuse the scratch tensor / the node and instance tensors of an earlier Tlas (`out` is rebuilt in place and returned:
+    the per-frame path when transforms change); they must be large enough."""
+    _need_gpu()
+    dev, cuda = objects.dev, f"cuda:{objects.dev}"
+    if not 1 <= max_leaf <= MAX_LEAF:
+        raise BuildError(f"max_leaf = {max_leaf}: outside [1, 8]")
+    desc = _descriptors(transforms, object_ids, instance_ids, cuda)
+    n = desc.shape[0]
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    need = abi.lib().rodent_hip_tlas_scratch_bytes(n)
+    if scratch is None and out is not None:
+        scratch = out.scratch
+    if scratch is None or scratch.numel() * scratch.element_size() < need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=cuda)
+    node_bytes, inst_bytes = max(1, n - 1) * F.NODE2.itemsize, n * F.INSTANCE.itemsize
+    if out is None:
+        nodes = torch.empty(node_bytes, dtype=torch.uint8, device=cuda)
+        instances = torch.empty(inst_bytes, dtype=torch.uint8, device=cuda)
+    else:
+        nodes, instances = out.nodes, out.instances
+        if nodes.numel() < node_bytes or instances.numel() < inst_bytes:
+            raise ValueError("build_tlas: the buffers of `out` are too small for these instances")
+    info = torch.empty(INFO_WORDS, dtype=torch.int32, device=cuda)
+    entry = "rodent_hip_build_tlas"
+    # (the counts were checked above, so the entry's own refusals of them cannot occur here)
+    words = _enqueue(entry, dev, stream, info, (objects.buffer, objects.table_dev, desc, scratch, nodes, instances),
+                     objects.nodes.data_ptr(), objects.table_dev.data_ptr(), objects.num_objects, desc.data_ptr(), n, int(max_leaf),
+                     nodes.data_ptr(), instances.data_ptr(), scratch.data_ptr())
+    if words[2]:
+        raise BuildError(f"{entry}: " + ", ".join(s for bit, s in _TLAS_FLAGS if words[2] & bit))
+    if out is None:
+        return Tlas(nodes, instances, n, words.copy(), scratch, dev)
+    out.num_instances, out.scratch = n, scratch
+    out.info, out.num_nodes, out.depth = words.copy(), int(words[0]), int(words[1])
+    return out
+
+
+def trace_async(objects: ObjectSet, tlas: Tlas, rays_dev, hits_dev, instances_dev, num_rays, any_hit=False, stream=None):
+    """Enqueues one instanced traversal pass on `stream` (torch stream or None = the current one): tensors of Ray1 in, Hit1 and (may
+    be None) one int32 instance id per ray out.  A stack overflow is reported by abi.check_errors(dev, stream)."""
+    if stream is None:
+        stream = torch.cuda.current_stream(objects.dev)
+    abi.lib().hip_traverse_instanced_bvh2_tri1_async(
+        objects.dev, tlas.nodes.data_ptr(), tlas.instances.data_ptr(), objects.nodes.data_ptr(), objects.tris.data_ptr(),
+        rays_dev.data_ptr(), hits_dev.data_ptr(), None if instances_dev is None else instances_dev.data_ptr(), int(num_rays),
+        int(any_hit), C.c_void_p(stream.cuda_stream))
+
+
+def trace(objects: ObjectSet, tlas: Tlas, rays: np.ndarray, any_hit=False):
+    """Synchronous convenience wrapper: host rays in, (Hit1 array, int32 instance ids) out.  tri_id is the hit object's own prim id; a
+    miss is tri_id -1, instance -1."""
+    _need_gpu()
+    dev, n = objects.dev, len(rays)
+    rays_dev = abi.to_device(rays, dev)
+    hits_dev = torch.zeros(max(n, 1) * F.HIT1.itemsize, dtype=torch.uint8, device=f"cuda:{dev}")
+    ids_dev = torch.zeros(max(n, 1), dtype=torch.int32, device=f"cuda:{dev}")
+    torch.cuda.synchronize(dev)
+    fn = abi.lib().hip_occluded_instanced_bvh2_tri1 if any_hit else abi.lib().hip_intersect_instanced_bvh2_tri1
+    fn(dev, tlas.nodes.data_ptr(), tlas.instances.data_ptr(), objects.nodes.data_ptr(), objects.tris.data_ptr(), rays_dev.data_ptr(),
+       hits_dev.data_ptr(), ids_dev.data_ptr(), n)
+    return abi.from_device(hits_dev, F.HIT1)[:n], ids_dev.cpu().numpy()[:n]
+
+
+def download(tlas: Tlas):
+    """(nodes NODE2, instances INSTANCE) host copies of a Tlas."""
+    nodes = tlas.nodes[: tlas.num_nodes * F.NODE2.itemsize].cpu().numpy().view(F.NODE2).copy()
+    instances = tlas.instances[: tlas.num_instances * F.INSTANCE.itemsize].cpu().numpy().view(F.INSTANCE).copy()
+    return nodes, instances
