@@ -184,6 +184,74 @@ int32_t rodent_hip_build_bvh2_tri1_split_sync(int32_t dev, const float* vertices
                                               const struct RodentSplitOptions* split, struct Node2* nodes, struct Tri1* tris,
                                               int32_t* info);
 
+/* ---- topology by parallel locally-ordered clustering, PLOC (Meister & Bittner, "Parallel Locally-Ordered Clustering for Bounding
+ * Volume Hierarchy Construction", TVCG 2018) ---------------------------------------------------------------------------------------------
+ *
+ * Another way to choose the topology: instead of Karras' hierarchy over the Morton codes, the references, lying in (Morton code,
+ * reference index) order, are merged bottom-up, each with the neighbour whose union with it is smallest.  Everything before (the split
+ * front, the codes, the sort, the Tri1 records in sorted order) and after (fit, treelet passes, SAH leaf collapse, pre-order emission: the
+ * optimising builder above, treelet_passes = 0 allowed and meaning clustering + collapse) is as it stands.  The output is a pure function
+ * of (vertices, indices, num_vertices, num_tris, options, split options, PLOC options radius and depth_limit), byte for byte;
+ * tests/ploc_model.py restates the rule.  wide_iterations is scheduling only and changes no byte.
+ *
+ * Ids: with n references (n' of the split front) and m = n - 1: 0 ... m-1 inner nodes, m + p the sorted reference p.
+ * Cluster: an id, a box and a height h; a reference has h = 0, a merge h = 1 + max of its two parts.  At the start the clusters are the
+ *   references in sorted order.  C: the clusters at the start of iteration t = 0, 1, ...; clog2(x) = ceil(log2 x), clog2(1) = 0;
+ *   D = depth_limit (0 means 56);  I = 4 * clog2(n) + 8.
+ * Nearest-neighbour iteration (t < I): the candidates of the cluster at position i are the positions j != i with |i - j| <= radius that
+ *   are admissible: 1 + max(h_i, h_j) <= D - clog2(C).  d(i, j) = A of the exact union of the two boxes (min of the lows, max of the highs;
+ *   A as above, fp32 in that order); a NaN d is never chosen.  i chooses the candidate of least d, equal d going to the smaller i ^ j
+ *   (for a fixed i, j -> i ^ j is injective: the choice is unique; the key (d, i ^ j) is symmetric, so the pair of least key among all
+ *   has chosen each other: while any candidate pair exists, an iteration merges; identical boxes pair up as (0,1), (2,3), ... and do not
+ *   form a chain).  Without a candidate i chooses nobody.  i and j merge when each chose the other.
+ * Forced iteration (t >= I): positions 2k and 2k + 1 merge whatever their boxes; a last odd position stays.
+ * Merging, in either kind: the lower position leads; left = the leader's id, right = the partner's; the new node's id =
+ *   (C - 2) - (leaders at lower positions in this iteration), so C - 1 merges are left for ids C - 2 ... 0 and the last merge is node 0,
+ *   the root the tail's walks start from; parent links of both parts are written, the root's is -1.  The merged cluster takes the
+ *   leader's position, the partner's slot is dropped, the others keep their order.  Iterations run until C = 1; n = 1: no iteration, the
+ *   single-leaf root as everywhere.
+ * Depth: every height is at most D - clog2(C) at the start of every iteration.  At t = 0: h = 0 and D >= clog2(n) (checked by the
+ *   entry).  A nearest-neighbour iteration only makes admissible merges, 1 + max(h_i, h_j) <= D - clog2(C), and the next C is no larger,
+ *   so D - clog2(C) does not fall.  A forced iteration turns C >= 2 clusters into ceil(C / 2), and clog2(ceil(C / 2)) = clog2(C) - 1,
+ *   while a height grows by one at most.  At C = 1 the root's height, the Node2 levels of the tree, is therefore at most D; the leaf
+ *   collapse only shortens paths.  The treelet passes' own rule is tied to 56 levels, so D < 56 with treelet_passes > 0 is refused.
+ * Iterations: at most I nearest-neighbour ones, then every iteration halves C: at most I + clog2(n) <= 4 * 25 + 8 + 25 = 133.
+ * info: the split entry's 8 words; [4] the Tri1 count (num_tris without split options), [5], [6] as there (0 without), [7] the
+ *   iterations run until one cluster was left; forced ones ran exactly when [7] > I. */
+#define RODENT_BUILD_MAX_PLOC_RADIUS   64
+#define RODENT_BUILD_MAX_DEPTH         56
+#define RODENT_BUILD_ERR_PLOC         -16  /* RodentPlocOptions out of range, depth_limit below clog2(the most references), or
+                                              depth_limit < 56 together with treelet passes */
+
+struct RodentPlocOptions {
+    int32_t radius;           /* 1 ... 64: positions searched to either side */
+    int32_t depth_limit;      /* 0 ... 56: the most Node2 levels, 0 = 56; at least clog2(the most references) */
+    int32_t wide_iterations;  /* -1 ... 255: device-wide iterations before one workgroup finishes the clustering; -1 = the library's
+                                 choice.  Scheduling only: the output does not depend on it */
+};
+
+/* Bytes of device scratch rodent_hip_build_bvh2_tri1_ploc needs (-1 on invalid arguments).  split may be NULL: no pre-splitting. */
+int64_t rodent_hip_build_ploc_scratch_bytes(int32_t num_tris, const struct RodentBuildOptions* opt,
+                                            const struct RodentSplitOptions* split, const struct RodentPlocOptions* ploc);
+
+/* rodent_hip_build_bvh2_tri1_split with the PLOC topology stage.  split may be NULL (no pre-splitting: nodes hold max(1, num_tris - 1)
+ * Node2, tris num_tris Tri1); with it the buffer sizes come from rodent_hip_build_split_max_refs.  info_dev:
+ * RODENT_BUILD_SPLIT_INFO_WORDS ints either way.  Asynchronous like the others: a fixed list of launches on `stream` that depends on
+ * num_tris and the options alone, nothing allocated, nothing waits for the device or for another workgroup.  Checks, in this order,
+ * each enqueuing nothing when it fails: the options' (as the split entry, split's only when it is given), ploc NULL
+ * (RODENT_BUILD_ERR_NULL), RODENT_BUILD_ERR_PLOC (its depth_limit against the reference count only when num_tris is in range), then
+ * the mesh arguments'. */
+int32_t rodent_hip_build_bvh2_tri1_ploc(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                        int32_t num_tris, const struct RodentBuildOptions* opt, const struct RodentSplitOptions* split,
+                                        const struct RodentPlocOptions* ploc, struct Node2* nodes, struct Tri1* tris, void* scratch,
+                                        int32_t* info_dev, void* stream);
+
+/* Synchronous form, as rodent_hip_build_bvh2_tri1_split_sync. */
+int32_t rodent_hip_build_bvh2_tri1_ploc_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                             int32_t num_tris, const struct RodentBuildOptions* opt,
+                                             const struct RodentSplitOptions* split, const struct RodentPlocOptions* ploc,
+                                             struct Node2* nodes, struct Tri1* tris, int32_t* info);
+
 /* ---- refit: new boxes and Tri1 records for an existing hierarchy whose vertices moved ------------------------------------------------
  *
  * The topology stays: the child, pad and w words (pad, geom_id, prim_id with its end-of-leaf bit) are read and never written; only the

@@ -87,6 +87,11 @@ void    rodent_hip_scene_create_device_bvh_opt(int32_t dev, const struct RodentS
 struct RodentSplitOptions;
 void    rodent_hip_scene_create_device_bvh_split(int32_t dev, const struct RodentSceneDesc* desc, const struct RodentBuildOptions* opt,
                                                  const struct RodentSplitOptions* split);
+/* The same with the PLOC topology stage (rodent_build.h: RodentPlocOptions) in place of the LBVH's; `split` may be NULL: no
+ * pre-splitting.  Invalid options abort. */
+struct RodentPlocOptions;
+void    rodent_hip_scene_create_device_bvh_ploc(int32_t dev, const struct RodentSceneDesc* desc, const struct RodentBuildOptions* opt,
+                                                const struct RodentSplitOptions* split, const struct RodentPlocOptions* ploc);
 /* The current scene after its geometry moved: new HOST tables with the counts given at creation (vertices, normals: num_vertices x 4
  * floats; face_normals: num_tris x 4; lights: num_lights); indices, materials, light ids, textures and the hierarchy's topology stay.
  * Overwrites the device copies in place, refits the hierarchy in place (rodent_build.h: rodent_hip_refit_bvh2_tri1; the pointers of

@@ -45,6 +45,7 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "rodent_hip_build_opt_scratch_bytes", "rodent_hip_build_bvh2_tri1_opt", "rodent_hip_build_bvh2_tri1_opt_sync",
     "rodent_hip_build_split_max_refs", "rodent_hip_build_split_scratch_bytes", "rodent_hip_build_bvh2_tri1_split",
     "rodent_hip_build_bvh2_tri1_split_sync",
+    "rodent_hip_build_ploc_scratch_bytes", "rodent_hip_build_bvh2_tri1_ploc", "rodent_hip_build_bvh2_tri1_ploc_sync",
     "rodent_hip_refit_scratch_bytes", "rodent_hip_refit_bvh2_tri1", "rodent_hip_refit_bvh2_tri1_sync",
     "rodent_hip_refit_wide_scratch_bytes", "rodent_hip_refit_bvh4_tri4", "rodent_hip_refit_bvh4_tri4_sync",
     "rodent_hip_refit_bvh8_tri4", "rodent_hip_refit_bvh8_tri4_sync",
@@ -66,6 +67,11 @@ class BuildOptions(C.Structure):
 class SplitOptions(C.Structure):
     """struct RodentSplitOptions (include/rodent_build.h)."""
     _fields_ = [("budget", C.c_float), ("max_pieces", C.c_int32)]
+
+
+class PlocOptions(C.Structure):
+    """struct RodentPlocOptions (include/rodent_build.h)."""
+    _fields_ = [("radius", C.c_int32), ("depth_limit", C.c_int32), ("wide_iterations", C.c_int32)]
 
 
 class MissingExtension(RuntimeError):
@@ -124,6 +130,13 @@ def lib():
         l.rodent_hip_build_bvh2_tri1_split.argtypes = [i32, vp, i32, vp, i32, opt, spl, vp, vp, vp, vp, vp]
         l.rodent_hip_build_bvh2_tri1_split_sync.restype = i32
         l.rodent_hip_build_bvh2_tri1_split_sync.argtypes = [i32, vp, i32, vp, i32, opt, spl, vp, vp, C.POINTER(i32)]
+        plo = C.POINTER(PlocOptions)
+        l.rodent_hip_build_ploc_scratch_bytes.restype = C.c_int64
+        l.rodent_hip_build_ploc_scratch_bytes.argtypes = [i32, opt, spl, plo]
+        l.rodent_hip_build_bvh2_tri1_ploc.restype = i32
+        l.rodent_hip_build_bvh2_tri1_ploc.argtypes = [i32, vp, i32, vp, i32, opt, spl, plo, vp, vp, vp, vp, vp]
+        l.rodent_hip_build_bvh2_tri1_ploc_sync.restype = i32
+        l.rodent_hip_build_bvh2_tri1_ploc_sync.argtypes = [i32, vp, i32, vp, i32, opt, spl, plo, vp, vp, C.POINTER(i32)]
         l.rodent_hip_refit_scratch_bytes.restype = C.c_int64; l.rodent_hip_refit_scratch_bytes.argtypes = [i32, i32]
         l.rodent_hip_refit_bvh2_tri1.restype = i32
         l.rodent_hip_refit_bvh2_tri1.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp]

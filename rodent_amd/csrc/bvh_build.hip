@@ -2,11 +2,12 @@
 // codes + Karras 2012 hierarchy), optionally restructured by treelets with an SAH leaf collapse, optionally over pre-split triangles.
 // C ABI: include/rodent_build.h.  CPU models of every stage, byte for byte: tests/lbvh_model.py, tests/trbvh_model.py (treelets),
 // tests/split_model.py (pre-splitting), tests/refit_model.py and tests/refit_wide_model.py (refit).
-// The kernels lie in build_device.h (what the stages share), build_lbvh.h, build_treelet.h, build_split.h, build_refit.h and
-// build_collapse.h; build_tlas.h holds the instance and leaf stages of an instanced scene's top level (rodent_hip_build_tlas,
+// The kernels lie in build_device.h (what the stages share), build_lbvh.h, build_treelet.h, build_split.h, build_ploc.h, build_refit.h
+// and build_collapse.h; build_tlas.h holds the instance and leaf stages of an instanced scene's top level (rodent_hip_build_tlas,
 // include/rodent_instances.h; CPU model: tests/instance_model.py), which runs the LBVH's sort, Karras and tail stages over instance boxes.
-// One pipeline (launch_build), all on the caller's stream, nothing allocated, no host synchronisation.  The three entry points only
-// choose its options: rodent_hip_build_bvh2_tri1 the LBVH, _opt treelet_passes (0, or one triangle: the LBVH), _split the split front.
+// One pipeline (launch_build), all on the caller's stream, nothing allocated, no host synchronisation.  The four entry points only
+// choose its options: rodent_hip_build_bvh2_tri1 the LBVH, _opt treelet_passes (0, or one triangle: the LBVH), _split the split front,
+// _ploc the topology stage.
 // Front, one of:
 //   k_centroids      per triangle: indices checked before any vertex load, centroid sum s = (v0 + v1) + v2, per-block min / max
 //   k_bounds         one block: the centroid bounds and per-axis scale = 1024 / extent (0 for an empty or non-finite extent)
@@ -28,6 +29,9 @@
 //                    climb again; each node of at least gamma triangles gets its 7-leaf treelet restructured by its wave
 //   k_fit            again: the SAH leaf collapse decisions and emitted-node counts of the final tree
 //   k_emit_opt_nodes / k_emit_opt_tris   Node2 in depth-first pre-order, Tri1 in left-to-right leaf order (O(depth) walks)
+// PLOC (build_ploc.h, rodent_hip_build_bvh2_tri1_ploc; CPU model: tests/ploc_model.py): in place of k_karras and k_explicit, the explicit
+// tree comes from locally-ordered clustering of the sorted references (k_ploc_init, per device-wide iteration k_ploc_nn, k_ploc_flags,
+// k_scan, k_ploc_compact, then k_ploc_shrink and k_ploc_finish, one workgroup each); the optimising tail follows as it stands.
 // Split, n' is known on the device only: the tree and tail stages get grids sized for max_refs and read n' (`nref`) from info[4];
 // without `nref` the host sizes them for the n triangles.
 // Refit (build_refit.h, rodent_hip_refit_bvh2_tri1): k_refit_links, k_refit_tris, k_refit_climb rewrite the boxes and Tri1 records of an
@@ -176,10 +180,29 @@ TlasScratch carve_tlas(char* base, int n) {
     return t;
 }
 
+struct PlocScratch {
+    float4* clusters[2];          // per position, the two cluster buffers: a 32-byte record (build_ploc.h: PlocCluster)
+    int* nn;                      // per position
+    uint32_t* blocktot;           // leader and survivor counts per block of positions
+    int* state;                   // C and t, two slots; the finisher's hand-over
+    size_t bytes;
+};
+
+PlocScratch carve_ploc(char* base, int max_refs) {
+    PlocScratch s{};
+    Carver c{base};
+    const size_t R = (size_t)max_refs;
+    for (int k = 0; k < 2; k++) c.take(s.clusters[k], 2 * R);
+    c.take(s.nn, R); c.take(s.blocktot, 2 * ((R + kBlock - 1) / kBlock)); c.take(s.state, 8);
+    s.bytes = c.bytes;
+    return s;
+}
+
 #include "build_lbvh.h"
 #include "build_tlas.h"
 #include "build_treelet.h"
 #include "build_split.h"
+#include "build_ploc.h"
 #include "build_refit.h"
 #include "build_collapse.h"
 
@@ -226,6 +249,27 @@ long long split_max_refs(int n, const RodentSplitOptions* split) {
     return n + std::min(split_budget(n, split), (long long)n * (split->max_pieces - 1));
 }
 
+int host_clog2(long long x) { int k = 0; while ((1LL << k) < x) k++; return k; }
+
+// The PLOC options' own checks; with num_tris in range also D >= clog2(the most references).
+int32_t check_ploc(const RodentPlocOptions* ploc, const RodentBuildOptions* opt, const RodentSplitOptions* split, int32_t num_tris) {
+    if (!ploc) return RODENT_BUILD_ERR_NULL;
+    if (ploc->radius < 1 || ploc->radius > RODENT_BUILD_MAX_PLOC_RADIUS || ploc->depth_limit < 0
+        || ploc->depth_limit > RODENT_BUILD_MAX_DEPTH || ploc->wide_iterations < -1 || ploc->wide_iterations > 255)
+        return RODENT_BUILD_ERR_PLOC;
+    const int D = ploc->depth_limit ? ploc->depth_limit : RODENT_BUILD_MAX_DEPTH;
+    if (D < RODENT_BUILD_MAX_DEPTH && opt->treelet_passes > 0) return RODENT_BUILD_ERR_PLOC;
+    if (!bad_num_tris(num_tris) && D < host_clog2(split ? split_max_refs(num_tris, split) : num_tris)) return RODENT_BUILD_ERR_PLOC;
+    return RODENT_BUILD_OK;
+}
+
+// The device-wide iterations before the finisher: about 0.75 of the clusters are left after one, so 4 per halving beyond the 1024
+// clusters the finisher keeps in LDS.
+int ploc_wide_iterations(const RodentPlocOptions& ploc, int max_refs) {
+    if (ploc.wide_iterations >= 0) return ploc.wide_iterations;
+    return std::min(255, 4 * std::max(0, host_clog2(max_refs) - 10));
+}
+
 // The optimising stages' view of the scratch arrays for n references.
 Opt make_opt(const Scratch& s, int n, const RodentBuildOptions& opt, const int* nref) {
     Opt o{};
@@ -258,11 +302,32 @@ void launch_karras(const Scratch& s, int n, int max_leaf, const int* nref, hipSt
 }
 
 void launch_tree(const Scratch& s, const float4* v4, int nv, const int4* i4, int n, int max_leaf, Tri1* tris, const int* nref,
-                 const int* reftri, const float* refbox, hipStream_t stream) {
+                 const int* reftri, const float* refbox, bool karras, hipStream_t stream) {
     launch_sort(s, n, nref, stream);
     hipLaunchKernelGGL(k_leaves, dim3(blocks_for(n)), dim3(kBlock), 0, stream, v4, nv, i4, s.vals[0], n, tris, s.leafbox, nref,
                        reftri, refbox);
-    launch_karras(s, n, max_leaf, nref, stream);
+    if (karras) launch_karras(s, n, max_leaf, nref, stream);
+}
+
+// The PLOC topology stage over n (or, with `nref`, at most n) sorted references: the clusters of iteration 0, `wide` device-wide
+// iterations, the two finishing kernels.  The list depends on n and `wide` alone.
+void launch_ploc(const Scratch& s, const PlocScratch& c, int n, const RodentPlocOptions& ploc, int wide, int32_t* info_dev, const int* nref,
+                 hipStream_t stream) {
+    Ploc p{};
+    p.n = n; p.m = n - 1; p.radius = ploc.radius; p.depth_limit = ploc.depth_limit; p.nblocks = blocks_for(n); p.nref = nref;
+    p.leafbox = s.leafbox; p.left = s.left; p.right = s.right; p.parent = s.parent; p.leaf_parent = s.leaf_parent;
+    p.buf0 = reinterpret_cast<PlocCluster*>(c.clusters[0]); p.buf1 = reinterpret_cast<PlocCluster*>(c.clusters[1]);
+    p.nn = c.nn; p.blocktot = c.blocktot; p.state = c.state; p.info = info_dev;
+    hipLaunchKernelGGL(k_ploc_init, dim3(p.nblocks), dim3(kBlock), 0, stream, p);
+    if (n < 2) return;
+    for (int k = 0; k < wide; k++) {
+        hipLaunchKernelGGL(k_ploc_nn, dim3(p.nblocks), dim3(kBlock), 0, stream, p, k);
+        hipLaunchKernelGGL(k_ploc_flags, dim3(p.nblocks), dim3(kBlock), 0, stream, p, k);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, c.blocktot, 2 * p.nblocks, (int*)nullptr);
+        hipLaunchKernelGGL(k_ploc_compact, dim3(p.nblocks), dim3(kBlock), 0, stream, p, k);
+    }
+    hipLaunchKernelGGL(k_ploc_shrink, dim3(1), dim3(kPlocFinish), 0, stream, p, wide);
+    hipLaunchKernelGGL(k_ploc_finish, dim3(1), dim3(kPlocFinish), 0, stream, p);
 }
 
 // The LBVH tail: renumbering, boxes and heights, Node2 records.  Without `nref` the host knows n and launches either k_emit or the
@@ -289,12 +354,13 @@ void launch_lbvh_tail(const Scratch& s, int n, int max_leaf, Node2* nodes, Rec* 
 // The optimising tail: the explicit tree, k_fit, the treelet passes, k_fit again, pre-order emission.  Without `nref` it is only
 // reached with n > 1; with it the single-leaf root follows, written when n' = 1.  False when a memset is refused.
 bool launch_opt_tail(const Scratch& s, int n, const RodentBuildOptions& opt, const float4* v4, int nv, const int4* i4, Node2* nodes,
-                     Tri1* tris, int32_t* info_dev, const int* nref, const int* reftri, hipStream_t stream) {
+                     Tri1* tris, int32_t* info_dev, const int* nref, const int* reftri, bool karras, hipStream_t stream) {
     const int m = n - 1;
     if (m > 0) {
         const Opt o = make_opt(s, n, opt, nref);
-        hipLaunchKernelGGL(k_explicit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.left, s.right,
-                           nref);
+        if (karras)                                              // PLOC has written the explicit tree itself
+            hipLaunchKernelGGL(k_explicit, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, s.first, s.last, s.split, s.left, s.right,
+                               nref);
         hipLaunchKernelGGL(k_fit, dim3(blocks_for(n)), dim3(kBlock), 0, stream, o, s.arrivals);
         for (int pass = 0; pass < opt.treelet_passes; pass++) {
             hipLaunchKernelGGL(k_depth, dim3(blocks_for(m)), dim3(kBlock), 0, stream, o);
@@ -313,19 +379,22 @@ bool launch_opt_tail(const Scratch& s, int n, const RodentBuildOptions& opt, con
 
 // Every entry after its argument checks: info words and arrival counters zeroed, the front (centroids, or with `split` the
 // pre-splitting stages of build_split.h), launch_tree, then the LBVH tail (treelet_passes = 0) or the optimising one.  Without `split`
-// the stages run over the n triangles; with it over the n' references, on grids sized for max_refs.
+// the stages run over the n triangles; with it over the n' references, on grids sized for max_refs.  With `ploc` the topology stage is
+// PLOC instead of Karras' and the tail the optimising one whatever treelet_passes; one reference at most: the LBVH's single leaf.
 int32_t launch_build(const float* vertices, int nv, const int32_t* indices, int n, const RodentBuildOptions& opt,
-                     const RodentSplitOptions* split, Node2* nodes, Tri1* tris, void* scratch, int32_t* info_dev, void* stream_) {
+                     const RodentSplitOptions* split, const RodentPlocOptions* ploc, Node2* nodes, Tri1* tris, void* scratch,
+                     int32_t* info_dev, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int R = split ? (int)split_max_refs(n, split) : n, M = R - 1;
-    const bool optimise = opt.treelet_passes > 0;
-    const Scratch s = carve(static_cast<char*>(scratch), R, optimise);
+    const bool optimise = ploc ? R > 1 : opt.treelet_passes > 0;
+    const Scratch s = carve(static_cast<char*>(scratch), R, optimise || ploc);
     const SplitScratch q = split ? carve_split(static_cast<char*>(scratch) + s.bytes, n, R) : SplitScratch{};
+    const PlocScratch c = ploc ? carve_ploc(static_cast<char*>(scratch) + s.bytes + q.bytes, R) : PlocScratch{};
     const float4* v4 = reinterpret_cast<const float4*>(vertices);
     const int4* i4 = reinterpret_cast<const int4*>(indices);
     const int* nref = split ? info_dev + kInfoRefs : nullptr;     // n', written by the second scan; every later stage reads it
     // an unsplit caller's info buffer may hold only RODENT_BUILD_INFO_WORDS words
-    const size_t info_bytes = 4 * (size_t)(split ? RODENT_BUILD_SPLIT_INFO_WORDS : RODENT_BUILD_INFO_WORDS);
+    const size_t info_bytes = 4 * (size_t)(split || ploc ? RODENT_BUILD_SPLIT_INFO_WORDS : RODENT_BUILD_INFO_WORDS);
     if (hipMemsetAsync(info_dev, 0, info_bytes, stream) != hipSuccess
         || (M > 0 && hipMemsetAsync(s.arrivals, 0, 4 * (size_t)M, stream) != hipSuccess)
         || (split && hipMemsetAsync(q.pmax, 0, 16, stream) != hipSuccess))
@@ -349,10 +418,11 @@ int32_t launch_build(const float* vertices, int nv, const int32_t* indices, int 
                            q.refbox, q.reftri, s.cent, q.kpartial);
         hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, q.kpartial, nb, s.frame);
     }
-    launch_tree(s, v4, nv, i4, R, opt.max_leaf, tris, nref, q.reftri, q.refbox, stream);
+    launch_tree(s, v4, nv, i4, R, opt.max_leaf, tris, nref, q.reftri, q.refbox, !ploc, stream);
+    if (ploc) launch_ploc(s, c, R, *ploc, ploc_wide_iterations(*ploc, R), info_dev, nref, stream);
     if (!optimise)
         launch_lbvh_tail(s, R, opt.max_leaf, nodes, tris, info_dev, nref, stream);
-    else if (!launch_opt_tail(s, R, opt, v4, nv, i4, nodes, tris, info_dev, nref, q.reftri, stream))
+    else if (!launch_opt_tail(s, R, opt, v4, nv, i4, nodes, tris, info_dev, nref, q.reftri, !ploc, stream))
         return RODENT_BUILD_ERR_LAUNCH;
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
@@ -533,7 +603,7 @@ int32_t rodent_hip_build_bvh2_tri1(int32_t dev, const float* vertices, int32_t n
     const int32_t rc = check_args(dev, vertices, num_vertices, indices, num_tris, max_leaf, nodes, tris, scratch, info_dev);
     if (rc != RODENT_BUILD_OK) return rc;
     const RodentBuildOptions opt{max_leaf, 0, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
-    return launch_build(vertices, num_vertices, indices, num_tris, opt, nullptr, nodes, tris, scratch, info_dev, stream);
+    return launch_build(vertices, num_vertices, indices, num_tris, opt, nullptr, nullptr, nodes, tris, scratch, info_dev, stream);
 }
 
 int32_t rodent_hip_build_bvh2_tri1_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
@@ -561,7 +631,7 @@ int32_t rodent_hip_build_bvh2_tri1_opt(int32_t dev, const float* vertices, int32
     if (rc != RODENT_BUILD_OK) return rc;
     RodentBuildOptions o = *opt;
     if (num_tris == 1) o.treelet_passes = 0;          // nothing to restructure or collapse: the LBVH, byte for byte
-    return launch_build(vertices, num_vertices, indices, num_tris, o, nullptr, nodes, tris, scratch, info_dev, stream);
+    return launch_build(vertices, num_vertices, indices, num_tris, o, nullptr, nullptr, nodes, tris, scratch, info_dev, stream);
 }
 
 int32_t rodent_hip_build_bvh2_tri1_opt_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
@@ -597,7 +667,7 @@ int32_t rodent_hip_build_bvh2_tri1_split(int32_t dev, const float* vertices, int
     if (rc == RODENT_BUILD_OK)
         rc = check_args(dev, vertices, num_vertices, indices, num_tris, opt->max_leaf, nodes, tris, scratch, info_dev);
     if (rc != RODENT_BUILD_OK) return rc;
-    return launch_build(vertices, num_vertices, indices, num_tris, *opt, split, nodes, tris, scratch, info_dev, stream);
+    return launch_build(vertices, num_vertices, indices, num_tris, *opt, split, nullptr, nodes, tris, scratch, info_dev, stream);
 }
 
 int32_t rodent_hip_build_bvh2_tri1_split_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
@@ -612,6 +682,45 @@ int32_t rodent_hip_build_bvh2_tri1_split_sync(int32_t dev, const float* vertices
     return build_sync(dev, bytes, RODENT_BUILD_SPLIT_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
         return rodent_hip_build_bvh2_tri1_split(dev, vertices, num_vertices, indices, num_tris, opt, split, nodes, tris, scratch,
                                                 info_dev, nullptr);
+    });
+}
+
+int64_t rodent_hip_build_ploc_scratch_bytes(int32_t num_tris, const struct RodentBuildOptions* opt,
+                                            const struct RodentSplitOptions* split, const struct RodentPlocOptions* ploc) {
+    if (bad_num_tris(num_tris) || check_options(opt) != RODENT_BUILD_OK || (split && check_split(split) != RODENT_BUILD_OK)
+        || check_ploc(ploc, opt, split, num_tris) != RODENT_BUILD_OK)
+        return -1;
+    const int refs = split ? (int)split_max_refs(num_tris, split) : num_tris;
+    return (int64_t)(carve(nullptr, refs, true).bytes + (split ? carve_split(nullptr, num_tris, refs).bytes : 0)
+                     + carve_ploc(nullptr, refs).bytes);
+}
+
+int32_t rodent_hip_build_bvh2_tri1_ploc(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                        int32_t num_tris, const struct RodentBuildOptions* opt, const struct RodentSplitOptions* split,
+                                        const struct RodentPlocOptions* ploc, struct Node2* nodes, struct Tri1* tris, void* scratch,
+                                        int32_t* info_dev, void* stream) {
+    int32_t rc = check_options(opt);
+    if (rc == RODENT_BUILD_OK && split) rc = check_split(split);
+    if (rc == RODENT_BUILD_OK) rc = check_ploc(ploc, opt, split, num_tris);
+    if (rc == RODENT_BUILD_OK)
+        rc = check_args(dev, vertices, num_vertices, indices, num_tris, opt->max_leaf, nodes, tris, scratch, info_dev);
+    if (rc != RODENT_BUILD_OK) return rc;
+    return launch_build(vertices, num_vertices, indices, num_tris, *opt, split, ploc, nodes, tris, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_build_bvh2_tri1_ploc_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices,
+                                             int32_t num_tris, const struct RodentBuildOptions* opt,
+                                             const struct RodentSplitOptions* split, const struct RodentPlocOptions* ploc,
+                                             struct Node2* nodes, struct Tri1* tris, int32_t* info) {
+    int32_t rc = check_options(opt);
+    if (rc == RODENT_BUILD_OK && split) rc = check_split(split);
+    if (rc == RODENT_BUILD_OK) rc = check_ploc(ploc, opt, split, num_tris);
+    if (rc != RODENT_BUILD_OK) return rc;
+    const int64_t bytes = rodent_hip_build_ploc_scratch_bytes(num_tris, opt, split, ploc);
+    if (bytes < 0) return RODENT_BUILD_ERR_NUM_TRIS;
+    return build_sync(dev, bytes, RODENT_BUILD_SPLIT_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
+        return rodent_hip_build_bvh2_tri1_ploc(dev, vertices, num_vertices, indices, num_tris, opt, split, ploc, nodes, tris, scratch,
+                                               info_dev, nullptr);
     });
 }
 

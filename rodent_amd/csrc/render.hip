@@ -764,7 +764,8 @@ std::vector<float> tri_shade(const float* face_normals, const float* normals, co
 // (desc->nodes / tris), build options build one on the device from the vertices and indices just uploaded (bvh_build.hip; with
 // `split`, over pre-split references) and takes a host copy of it; from there on both are the same code: checks, LDS images, per-scene
 // rules.
-void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* build, const RodentSplitOptions* split = nullptr) {
+void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* build, const RodentSplitOptions* split = nullptr,
+                  const RodentPlocOptions* ploc = nullptr) {
     RenderDevice& r = rdev(dev);
     rodent_hip_scene_destroy(dev);
     HIP_CHECK(hipSetDevice(dev));
@@ -786,6 +787,10 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOption
             scratch_bytes = rodent_hip_build_split_scratch_bytes(d->num_tris, build, split);
             info_words = RODENT_BUILD_SPLIT_INFO_WORDS;
         }
+        if (ploc) {                                      // the PLOC topology stage, with or without the split front: 8 info words
+            scratch_bytes = rodent_hip_build_ploc_scratch_bytes(d->num_tris, build, split, ploc);
+            info_words = RODENT_BUILD_SPLIT_INFO_WORDS;
+        }
         const size_t node_bytes = sizeof(Node2) * (size_t)(build ? std::max(1, refs - 1) : d->num_nodes);
         const size_t tri_bytes = sizeof(Tri1) * (size_t)(build ? refs : d->num_bvh_tris);
         char* bvh = nullptr;
@@ -801,7 +806,10 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOption
             int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + std::max<int64_t>(scratch_bytes, 0));
             Node2* out_nodes = reinterpret_cast<Node2*>(bvh);
             Tri1* out_tris = reinterpret_cast<Tri1*>(bvh + node_bytes);
-            const int32_t rc = split
+            const int32_t rc = ploc
+                ? rodent_hip_build_bvh2_tri1_ploc(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build, split, ploc,
+                                                  out_nodes, out_tris, scratch, info_dev, nullptr)
+                : split
                 ? rodent_hip_build_bvh2_tri1_split(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build, split,
                                                    out_nodes, out_tris, scratch, info_dev, nullptr)
                 : rodent_hip_build_bvh2_tri1_opt(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build, out_nodes,
@@ -986,6 +994,20 @@ void rodent_hip_scene_create_device_bvh_split(int32_t dev, const RodentSceneDesc
         abort();
     }
     scene_create(dev, d, opt, split);
+}
+
+void rodent_hip_scene_create_device_bvh_ploc(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* opt,
+                                             const RodentSplitOptions* split, const RodentPlocOptions* ploc) {
+    if (!opt || !ploc || d->num_tris < 1 || d->num_tris > RODENT_BUILD_MAX_TRIS
+        || rodent_hip_build_ploc_scratch_bytes(d->num_tris, opt, split, ploc) < 0 || d->num_vertices < 1 || d->nodes || d->tris
+        || d->num_nodes || d->num_bvh_tris) {
+        fprintf(stderr, "rodent_hip: rodent_hip_scene_create_device_bvh_ploc: invalid arguments (max_leaf 1 ... 8, treelet passes "
+                        "0 ... 3, costs in (0, 1e6], split budget 0 ... 4, max_pieces 1 ... 64, PLOC radius 1 ... 64, depth limit 0 or "
+                        "ceil(log2 references) ... 56 and 56 with treelet passes, wide iterations -1 ... 255, 1 ... 2^25 triangles, "
+                        "no hierarchy in the description)\n");
+        abort();
+    }
+    scene_create(dev, d, opt, split, ploc);
 }
 
 void rodent_hip_scene_refit(int32_t dev, const float* vertices, const float* normals, const float* face_normals,

@@ -10,11 +10,12 @@ into BVH4 / BVH8 + Tri4.
     wide = collapse_wide(bvh, 8)                   # the BVH2 collapsed into BVH8 / Tri4 on the device; wide.info[3]: its stack bound
     wide = build_wide(vertices, indices, 8, max_leaf=4, treelet_passes=3)    # build_bvh2 then collapse_wide; wide.bvh2 is the BVH2
     wide = build_wide(vertices, indices, 8, stack_limit=63)    # a tree no ray can overflow the traversal stack of: info[3] <= 63
+    bvh = build_bvh2(vertices, indices, ploc_radius=16, treelet_passes=1)    # topology by locally-ordered clustering (PLOC)
 
 The result is a pure function of the inputs, byte for byte.  As a tool:
 
     python -m rodent_amd.gpubuild scene.rscene -o out.bvh [--max-leaf N] [--treelet-passes N] [--split-budget F [--max-pieces K]]
-                                  [--width 4] [--width 8] [--stack-limit L]
+                                  [--ploc-radius R [--depth-limit D]] [--width 4] [--width 8] [--stack-limit L]
 
 writes a .bvh holding the BVH2_TRI1 block of the scene's mesh and, for every --width, its collapsed BVH4_TRI4 / BVH8_TRI4 block
 (bench_traversal reads them), collapsed under the stack limit L when one is given.
@@ -37,13 +38,16 @@ INFO_WORDS = 4
 SPLIT_INFO_WORDS = 8                   # + [4] Tri1 count (references) [5] triangles split [6] splits allotted but not made [7] 0
 MAX_PIECES, MAX_SPLIT_BUDGET = 64, 4.0
 BAD_INDEX, NON_FINITE, BAD_TOPOLOGY = 1, 2, 4
-ERR_SPLIT, ERR_NUM_NODES, ERR_WIDTH, ERR_STACK_LIMIT = -10, -11, -12, -13
+ERR_SPLIT, ERR_NUM_NODES, ERR_WIDTH, ERR_STACK_LIMIT, ERR_PLOC = -10, -11, -12, -13, -16
 MAX_STACK_LIMIT = 63
+MAX_PLOC_RADIUS, MAX_DEPTH = 64, 56    # RODENT_BUILD_MAX_PLOC_RADIUS / _MAX_DEPTH
 _ERRORS = {-1: "num_tris outside [1, 2^25]", -2: "max_leaf outside [1, 8]", -3: "no vertices", -4: "NULL pointer",
            -5: "no such device", -6: "launch failed", -8: "treelet_passes outside [0, 3]", -9: "node_cost / tri_cost outside (0, 1e6]",
            ERR_SPLIT: "split budget outside [0, 4] or max_pieces outside [1, 64]", ERR_NUM_NODES: "a hierarchy without nodes or triangles",
            ERR_WIDTH: "width other than 4 or 8", ERR_STACK_LIMIT: "stack_limit outside [0, 63]",
-           -14: "num_instances outside [1, 2^22]", -15: "no objects"}      # RODENT_TLAS_ERR_* (rodent_amd/instances.py)
+           -14: "num_instances outside [1, 2^22]", -15: "no objects",      # RODENT_TLAS_ERR_* (rodent_amd/instances.py)
+           ERR_PLOC: "PLOC radius outside [1, 64], depth_limit outside [0, 56] or below ceil(log2 references) or below 56 with "
+                     "treelet passes, or wide_iterations outside [-1, 255]"}
 _FLAGS = ((BAD_INDEX, "vertex index outside the vertex array"), (NON_FINITE, "non-finite vertex coordinate"),
           (BAD_TOPOLOGY, "malformed hierarchy (child id or prim_id out of range, leaf without end bit, node with two parents)"))
 
@@ -114,8 +118,19 @@ def split_options(budget=0.0, max_pieces=MAX_PIECES) -> abi.SplitOptions:
     return sp
 
 
+def ploc_options(radius, depth_limit=0, wide_iterations=-1) -> abi.PlocOptions:
+    """A checked RodentPlocOptions; raises BuildError on values the library would refuse whatever the mesh."""
+    if not 1 <= radius <= MAX_PLOC_RADIUS:
+        raise BuildError(f"ploc_radius = {radius}: outside [1, 64]")
+    if not 0 <= depth_limit <= MAX_DEPTH:
+        raise BuildError(f"depth_limit = {depth_limit}: outside [0, 56]")
+    if not -1 <= wide_iterations <= 255:
+        raise BuildError(f"wide_iterations = {wide_iterations}: outside [-1, 255]")
+    return abi.PlocOptions(int(radius), int(depth_limit), int(wide_iterations))
+
+
 def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, out=None, treelet_passes=0, node_cost=NODE_COST,
-               tri_cost=TRI_COST, split_budget=0.0, max_pieces=None) -> abi.DeviceBvh:
+               tri_cost=TRI_COST, split_budget=0.0, max_pieces=None, ploc_radius=0, depth_limit=0, wide_iterations=-1) -> abi.DeviceBvh:
     """Builds the BVH2 / Tri1 hierarchy of the triangles `indices` (v0 v1 v2 [geometry id]; 3 columns: geometry id 0) over
     `vertices` (x y z [w]) on device `dev`, on `stream` (torch stream, None = the current one).  Returns an abi.DeviceBvh whose
     `depth` and `info` are set.  Raises BuildError on invalid arguments and on the device's error flags (an index outside the
@@ -127,15 +142,28 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
     then the largest leaf allowed, not a threshold); info[3] counts the topologies the depth rule rejected.  0: the LBVH as it is.
     split_budget > 0 or max_pieces given: pre-split the triangles first (rodent_hip_build_bvh2_tri1_split; up to split_budget * n
     extra references, at most max_pieces (default 64) per triangle); bvh.num_tris is then the reference count info[4], and info has
-    8 words."""
+    8 words.
+    ploc_radius = 1 ... 64: the topology comes from locally-ordered clustering over that many Morton neighbours to either side
+    (rodent_hip_build_bvh2_tri1_ploc) instead of the LBVH's; treelet_passes (0: clustering + SAH leaf collapse) and the split options
+    act on it as above.  depth_limit: the most Node2 levels (0 = 56; below 56 only with treelet_passes = 0); wide_iterations: scheduling
+    only (-1: the library's choice).  info has 8 words, info[7] counts the clustering's iterations.  0: the entries above."""
     v, ix, stream = _mesh(vertices, indices, dev, stream)
     n, nv = ix.shape[0], v.shape[0]
     opt = options(max_leaf, treelet_passes, node_cost, tri_cost)
     splitting = bool(split_budget) or max_pieces is not None
     sp = split_options(split_budget, MAX_PIECES if max_pieces is None else max_pieces) if splitting else None
+    if not ploc_radius and (depth_limit or wide_iterations != -1):
+        raise BuildError("depth_limit and wide_iterations need ploc_radius")
     l = abi.lib()
     # the entry and its option arguments, its scratch bytes, the Tri1 records it may write, its info words
-    if splitting:
+    if ploc_radius:
+        pl = ploc_options(ploc_radius, depth_limit, wide_iterations)
+        entry, args, info_words = "rodent_hip_build_bvh2_tri1_ploc", (C.byref(opt), C.byref(sp) if splitting else None, C.byref(pl)), 8
+        need = l.rodent_hip_build_ploc_scratch_bytes(n, *args)
+        if need < 0:
+            raise BuildError(f"{entry}: {_ERRORS[ERR_PLOC]}")
+        refs = l.rodent_hip_build_split_max_refs(n, C.byref(sp)) if splitting else n
+    elif splitting:
         entry, args, info_words = "rodent_hip_build_bvh2_tri1_split", (C.byref(opt), C.byref(sp)), SPLIT_INFO_WORDS
         need, refs = l.rodent_hip_build_split_scratch_bytes(n, *args), l.rodent_hip_build_split_max_refs(n, C.byref(sp))
     else:
@@ -158,7 +186,7 @@ def build_bvh2(vertices, indices, max_leaf=2, dev=0, stream=None, scratch=None, 
     words = _enqueue(entry, dev, stream, info, (v, ix, scratch), v.data_ptr(), nv, ix.data_ptr(), n, *args, nodes.data_ptr(),
                      tris.data_ptr(), scratch.data_ptr())
     _raise_flags(entry, words)
-    bvh = abi.DeviceBvh.from_tensors(2, nodes, tris, int(words[0]), int(words[4]) if splitting else n, dev)
+    bvh = abi.DeviceBvh.from_tensors(2, nodes, tris, int(words[0]), int(words[4]) if splitting or ploc_radius else n, dev)
     bvh.depth, bvh.info, bvh.scratch = int(words[1]), words.copy(), scratch
     return bvh
 
@@ -290,6 +318,10 @@ def main(argv=None):
     ap.add_argument("--split-budget", type=float, default=0.0,
                     help="pre-split triangles into up to this fraction of extra references (0 ... 4, default 0: no splitting)")
     ap.add_argument("--max-pieces", type=int, default=None, help="the most references one triangle may become (1 ... 64, default 64)")
+    ap.add_argument("--ploc-radius", type=int, default=0,
+                    help="topology by locally-ordered clustering over this many Morton neighbours to either side (1 ... 64, default 0: the "
+                         "LBVH's)")
+    ap.add_argument("--depth-limit", type=int, default=0, help="with --ploc-radius: the most Node2 levels (default 0: 56)")
     ap.add_argument("--width", type=int, action="append", choices=(4, 8), default=[],
                     help="also write the BVH2 collapsed into this width (BVH4_TRI4 / BVH8_TRI4 block); may be given twice")
     ap.add_argument("--stack-limit", type=int, default=0,
@@ -298,7 +330,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     sc = Scene(a.scene)
     bvh = build_bvh2(sc.vertices, sc.indices, a.max_leaf, a.dev, treelet_passes=a.treelet_passes, split_budget=a.split_budget,
-                     max_pieces=a.max_pieces)
+                     max_pieces=a.max_pieces, ploc_radius=a.ploc_radius, depth_limit=a.depth_limit)
     nodes, tris = download(bvh)
     blocks = [(F.BVH2_TRI1, nodes, tris)]
     print(f"{a.output}: {len(tris)} triangles, {len(nodes)} nodes, depth {bvh.depth}")

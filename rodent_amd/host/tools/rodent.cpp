@@ -20,6 +20,8 @@
 //                       rodent_hip_scene_create_device_bvh_opt); 0 (the default) = the LBVH as it is
 //   --split-budget f    with --gpu-bvh: pre-split triangles into up to f * n extra references (0 ... 4, default 0; rodent_build.h,
 //                       rodent_hip_scene_create_device_bvh_split); --max-pieces k: at most k references per triangle (1 ... 64, default 64)
+//   --ploc-radius r     with --gpu-bvh: the topology by locally-ordered clustering over r Morton neighbours to either side (1 ... 64;
+//                       rodent_build.h, rodent_hip_scene_create_device_bvh_ploc) instead of the LBVH's; the options above act on it
 // Without --bench the reference opens an SDL window and renders until it is closed; this build is
 // headless (DISABLE_GUI, driver.cpp:236-242), so --bench or -o is required.
 #include <algorithm>
@@ -57,6 +59,7 @@ static void usage() {
               << "   --treelet-passes n  With --gpu-bvh: n passes (0 ... 3, default 0) of treelet restructuring + SAH leaf collapse\n"
               << "   --split-budget f    With --gpu-bvh: pre-split triangles into up to f * n extra references (0 ... 4, default 0)\n"
               << "   --max-pieces k      With --split-budget: at most k references per triangle (1 ... 64, default 64)\n"
+              << "   --ploc-radius r     With --gpu-bvh: topology by locally-ordered clustering over r neighbours (1 ... 64)\n"
               << "   --width  pixels     Sets the viewport horizontal dimension (in pixels)\n"
               << "   --height pixels     Sets the viewport vertical dimension (in pixels)\n"
               << "   --eye    x y z      Sets the position of the camera\n"
@@ -81,6 +84,8 @@ int main(int argc, char** argv) {
     float split_budget = 0.0f;
     int max_pieces = RODENT_BUILD_MAX_PIECES;
     bool split_given = false, pieces_given = false;
+    int ploc_radius = 0;
+    bool ploc_given = false;
     int sort = -1;                                                        // -1: the library's default
 
     for (int i = 1; i < argc; ++i) {
@@ -113,6 +118,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--treelet-passes")) { need(1); treelet_passes = strtol(argv[++i], nullptr, 10); treelet_given = true; }
         else if (!strcmp(argv[i], "--split-budget")) { need(1); split_budget = strtof(argv[++i], nullptr); split_given = true; }
         else if (!strcmp(argv[i], "--max-pieces")) { need(1); max_pieces = strtol(argv[++i], nullptr, 10); pieces_given = true; }
+        else if (!strcmp(argv[i], "--ploc-radius")) { need(1); ploc_radius = strtol(argv[++i], nullptr, 10); ploc_given = true; }
         else if (!strcmp(argv[i], "--target")) {
             need(1); ++i;
             if (!strcmp(argv[i], "amdgpu-streaming") || !strcmp(argv[i], "amdgpu")) mapping = 0;
@@ -135,6 +141,8 @@ int main(int argc, char** argv) {
     if (max_pieces < 1 || max_pieces > RODENT_BUILD_MAX_PIECES) fail("Invalid --max-pieces (1 ... 64)");
     if (split_given && !gpu_bvh) fail("--split-budget needs --gpu-bvh");
     if (pieces_given && !split_given) fail("--max-pieces needs --split-budget");
+    if (ploc_given && (ploc_radius < 1 || ploc_radius > RODENT_BUILD_MAX_PLOC_RADIUS)) fail("Invalid --ploc-radius (1 ... 64)");
+    if (ploc_given && !gpu_bvh) fail("--ploc-radius needs --gpu-bvh");
     if (is_obj ? !build_scene_from_obj(scene_file, scene, nullptr, !gpu_bvh) : !load_scene(scene_file, scene))
         fail("Cannot load scene '" + scene_file + "'");
     if (scene.lights.empty()) fail("The scene has no light source");
@@ -162,7 +170,9 @@ int main(int argc, char** argv) {
         if (gpu_bvh) {
             const RodentBuildOptions opt{max_leaf, treelet_passes, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
             const RodentSplitOptions split{split_budget, max_pieces};
-            if (split_given) rodent_hip_scene_create_device_bvh_split(d, &desc, &opt, &split);
+            const RodentPlocOptions ploc{ploc_radius, 0, -1};
+            if (ploc_given) rodent_hip_scene_create_device_bvh_ploc(d, &desc, &opt, split_given ? &split : nullptr, &ploc);
+            else if (split_given) rodent_hip_scene_create_device_bvh_split(d, &desc, &opt, &split);
             else rodent_hip_scene_create_device_bvh_opt(d, &desc, &opt);
         }
         else rodent_hip_scene_create(d, &desc);

@@ -35,7 +35,7 @@ class SceneTables(C.Structure):
 
 
 RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_create_device_bvh_opt",
-                  "rodent_hip_scene_create_device_bvh_split",
+                  "rodent_hip_scene_create_device_bvh_split", "rodent_hip_scene_create_device_bvh_ploc",
     "rodent_hip_scene_bvh", "rodent_hip_scene_refit", "rodent_hip_scene_destroy",
     "rodent_hip_scene_refit_prepare", "rodent_hip_scene_refit_device", "rodent_hip_scene_refit_status", "rodent_hip_scene_tables",
     "rodent_hip_render_config", "rodent_hip_render_mapping",
@@ -70,6 +70,9 @@ def lib():
         l.rodent_hip_scene_create_device_bvh_split.argtypes = [i32, C.POINTER(SceneDesc), C.POINTER(abi.BuildOptions),
                                                                C.POINTER(abi.SplitOptions)]
         l.rodent_hip_scene_create_device_bvh_split.restype = None
+        l.rodent_hip_scene_create_device_bvh_ploc.argtypes = [i32, C.POINTER(SceneDesc), C.POINTER(abi.BuildOptions),
+                                                              C.POINTER(abi.SplitOptions), C.POINTER(abi.PlocOptions)]
+        l.rodent_hip_scene_create_device_bvh_ploc.restype = None
         l.rodent_hip_scene_bvh.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
         l.rodent_hip_scene_bvh.restype = None
         l.rodent_hip_scene_refit.argtypes = [i32, vp, vp, vp, vp]; l.rodent_hip_scene_refit.restype = None
@@ -128,16 +131,20 @@ class Renderer:
     def __init__(self, scene, width, height, spp=4, max_path_len=64, dev=0, mapping="streaming", capacity=0, sort=None, overlap=None,
         fused_sort=None, lds_image=None,
                  trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None,
-                 gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64):
+                 gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64, gpu_bvh_ploc=0):
         """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says.
         gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh_opt);
         gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it.
         gpu_bvh_split = (0, 4]: pre-split the triangles into up to that fraction of extra references, at most gpu_bvh_max_pieces per
-        triangle (rodent_hip_scene_create_device_bvh_split)."""
+        triangle (rodent_hip_scene_create_device_bvh_split).
+        gpu_bvh_ploc = 1 ... 64: its topology by locally-ordered clustering over that many Morton neighbours to either side
+        (rodent_hip_scene_create_device_bvh_ploc); the passes and the split options act on it."""
         if gpu_bvh_passes and not gpu_bvh:
             raise ValueError("gpu_bvh_passes needs gpu_bvh (the treelet passes act on the device-built hierarchy)")
         if gpu_bvh_split and not gpu_bvh:
             raise ValueError("gpu_bvh_split needs gpu_bvh (the split references feed the device-built hierarchy)")
+        if gpu_bvh_ploc and not gpu_bvh:
+            raise ValueError("gpu_bvh_ploc needs gpu_bvh (the clustering chooses the device-built hierarchy's topology)")
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("rodent_amd: no GPU visible (the renderer has no CPU fallback)")
@@ -159,7 +166,11 @@ class Renderer:
             desc.nodes = desc.tris = None
             desc.num_nodes = desc.num_bvh_tris = 0
             opt = gpubuild.options(int(gpu_bvh), int(gpu_bvh_passes))
-            if gpu_bvh_split:
+            if gpu_bvh_ploc:
+                sp = gpubuild.split_options(float(gpu_bvh_split), int(gpu_bvh_max_pieces)) if gpu_bvh_split else None
+                pl = gpubuild.ploc_options(int(gpu_bvh_ploc))
+                l.rodent_hip_scene_create_device_bvh_ploc(dev, C.byref(desc), C.byref(opt), C.byref(sp) if sp else None, C.byref(pl))
+            elif gpu_bvh_split:
                 sp = gpubuild.split_options(float(gpu_bvh_split), int(gpu_bvh_max_pieces))
                 l.rodent_hip_scene_create_device_bvh_split(dev, C.byref(desc), C.byref(opt), C.byref(sp))
             else:

@@ -29,6 +29,12 @@ For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> conve
     With --stack-limit L one more row per tree and width: the collapse under that limit (rodent_hip_collapse_bvh2_tri1_bounded) beside
     the one without: time with min and max, wide nodes, B, the BVH2's own H(0), closest-hit rates of both trees.
 
+  * with --ploc R [R ...], nothing of the above: for every scene the LBVH, the 3-pass build and, per radius R, the PLOC build
+    (rodent_hip_build_bvh2_tri1_ploc) with 0 and 1 treelet pass, all max_leaf 2 and timed in the same run: build ms (median [min, max]),
+    nodes, depth, SAH cost (node / triangle cost 1.2 / 1.0), the clustering's iterations, the device-wide iterations launched and how
+    many of them found one cluster left, kernel launches per build, Mrays/s of 1 Mi camera rays and 1 Mi random segments (closest hit,
+    default variant) beside the host SBVH's; then the build time of the first radius over other numbers of device-wide iterations.
+
     python scripts/bench_bvh_build.py [--scenes atrium gallery crown plant] [--builds 20] [-o profiles/gpu_bvh_build.txt]
     python scripts/bench_bvh_build.py --treelet-passes 3 -o profiles/gpu_bvh_build_opt.txt
     python scripts/bench_bvh_build.py --treelet-passes 3 --split-budget 0.25 1 -o profiles/gpu_bvh_build_split.txt
@@ -36,6 +42,7 @@ For the atrium and the three 4.2 M-triangle stand-ins (scenes.scene_obj -> conve
     python scripts/bench_bvh_build.py --scenes atrium gallery --refit-wide -o profiles/gpu_bvh_refit_wide.txt
     python scripts/bench_bvh_build.py --scenes atrium gallery --collapse -o profiles/gpu_bvh_collapse.txt
     python scripts/bench_bvh_build.py --scenes atrium gallery --collapse --stack-limit 63 -o profiles/gpu_bvh_collapse_bounded.txt
+    python scripts/bench_bvh_build.py --scenes atrium gallery --ploc 8 16 -o profiles/gpu_bvh_ploc.txt
 """
 from __future__ import annotations
 
@@ -257,6 +264,105 @@ def collapse_table(a):
     Path(a.output).write_text("\n".join(lines) + "\n")
 
 
+def ploc_table(a):
+    """--ploc: the PLOC topology stage against the LBVH and the 3-pass build of the same run: build time, tree quality, trace rate."""
+    import lbvh_model as L
+    build.build_all()
+    lines = [f"# scripts/bench_bvh_build.py --ploc {' '.join(map(str, a.ploc))} on {torch.cuda.get_device_name(0)}; max_leaf 2; builds: "
+             f"median [min, max] of {a.builds} after 3 warm-ups, device events around the enqueued operations; SAH: tests/lbvh_model.py "
+             "sah_cost, node / triangle cost 1.2 / 1.0; iter: info[7]; wide: device-wide iterations launched (4 launches each), idle: those "
+             "that found one cluster left; launches: kernels per build; Mrays/s: 1 Mi camera rays / 1 Mi random segments, closest hit, "
+             "default variant, median of 10 launches after 2 warm-ups; x lbvh / x 3 pass / x sbvh: ratios to those rows",
+             f"{'scene':>8} {'tris':>9} {'tree':>14} | {'build ms':>8} {'[min, max]':>18} {'x lbvh':>6} {'x 3 pass':>8} | {'nodes':>8} "
+             f"{'depth':>5} {'SAH':>7} | {'iter':>4} {'wide':>4} {'idle':>4} {'launches':>8} | {'cam Mr/s':>8} {'x sbvh':>6} {'rand Mr/s':>9} "
+             f"{'x sbvh':>6}"]
+    print("\n".join(lines), flush=True)
+    scenes.DATA.mkdir(parents=True, exist_ok=True)
+    stream = torch.cuda.current_stream()
+    info = torch.empty(8, dtype=torch.int32, device="cuda")
+    l = abi.lib()
+    for name in a.scenes:
+        obj = scenes.scene_obj(name)
+        sc = S.convert(obj, scenes.DATA / f"{name.replace('/', '-')}.rscene")
+        n = sc.num_tris
+        v, ix = torch.from_numpy(sc.vertices).cuda(), torch.from_numpy(sc.indices).cuda()
+        eye, d, up, fov = scenes.CAMERAS[name.split("/")[0]]
+        lo, hi = sc.vertices[:, :3].min(0), sc.vertices[:, :3].max(0)
+        rays_dev = {"cam": abi.to_device(raygen.primary_rays(eye, d, up, fov, 1024, 1024, 0.0, scenes.PRIMARY_TMAX)),
+                    "rand": abi.to_device(raygen.random_rays(lo, hi, 1 << 20, 42, 0.0, scenes.RANDOM_TMAX))}
+        hits = torch.empty((1 << 20) * 16, dtype=torch.uint8, device="cuda")
+
+        def rates(tree):
+            out = {}
+            for rk, rd in rays_dev.items():
+                ms = event_ms(lambda: abi.traverse_async(tree, rd, hits, 1 << 20), 2, 10)
+                abi.check_errors()
+                out[rk] = (1 << 20) / ms / 1e3
+            return out
+
+        def timed(radius, passes, wide=-1):
+            """(the tree, (median, min, max) ms) of one kind of build: radius 0 is the LBVH entry (0 passes) or the optimising one."""
+            bvh = gpubuild.build_bvh2(v, ix, 2, treelet_passes=passes, ploc_radius=radius, wide_iterations=wide)
+            copt = gpubuild.options(2, passes)
+            cpl = abi.PlocOptions(radius, 0, wide)
+            mesh = (0, v.data_ptr(), len(sc.vertices), ix.data_ptr(), n)
+            out = (bvh.nodes.data_ptr(), bvh.tris.data_ptr(), bvh.scratch.data_ptr(), info.data_ptr(), C.c_void_p(stream.cuda_stream))
+
+            def one_build():
+                if radius:
+                    rc = l.rodent_hip_build_bvh2_tri1_ploc(*mesh, C.byref(copt), None, C.byref(cpl), *out)
+                elif passes:
+                    rc = l.rodent_hip_build_bvh2_tri1_opt(*mesh, C.byref(copt), *out)
+                else:
+                    rc = l.rodent_hip_build_bvh2_tri1(*mesh, 2, *out)
+                assert rc == 0
+            ms = event_ms(one_build, 3, a.builds, spread=True)
+            assert info.cpu().numpy().tolist()[:len(bvh.info)] == bvh.info.tolist()
+            return bvh, ms
+        sbvh_rate = rates(abi.DeviceBvh(2, sc.nodes, sc.tris, 0))
+        base = {}
+        kinds = [("lbvh", 0, 0), ("3 pass", 0, 3)] + [(f"ploc {r} + {p}", r, p) for r in a.ploc for p in (0, 1)]
+        for label, radius, passes in kinds:
+            bvh, (ms, ms_lo, ms_hi) = timed(radius, passes)
+            nodes, tris = gpubuild.download(bvh)
+            assert tree_depth(nodes) == bvh.depth <= 56                 # checked before anything traces it
+            rate = rates(bvh)
+            if not radius:
+                base[label] = ms
+            # kernels: front 2, sort 13, leaves 1, then Karras 1 + LBVH tail 4 / optimising tail 5 + 2 per pass / PLOC 3 + 4 per
+            # device-wide iteration + the optimising tail without k_explicit
+            clog = int(n - 1).bit_length()
+            wide = min(255, 4 * max(0, clog - 10)) if radius else 0
+            launches = 16 + ((3 + 4 * wide + 4 + 2 * passes) if radius else (1 + 5 + 2 * passes) if passes else 5)
+            it = int(bvh.info[7]) if radius else 0
+            x = lambda k: f"{ms / base[k]:.2f}" if k in base else ""
+            row = (f"{name:>8} {n:>9} {label:>14} | {ms:>8.3f} {'[%.3f, %.3f]' % (ms_lo, ms_hi):>18} {x('lbvh'):>6} {x('3 pass'):>8} | "
+                   f"{bvh.num_nodes:>8} {bvh.depth:>5} {L.sah_cost(nodes, tris, 1.2, 1.0):>7.2f} | {it:>4} {wide:>4} {max(0, wide - it):>4} "
+                   f"{launches:>8} | {rate['cam']:>8.0f} {rate['cam'] / sbvh_rate['cam']:>6.2f} {rate['rand']:>9.0f} "
+                   f"{rate['rand'] / sbvh_rate['rand']:>6.2f}")
+            lines.append(row)
+            print(row, flush=True)
+            del bvh
+        row = (f"{name:>8} {n:>9} {'host sbvh':>14} | {'':>8} {'':>18} {'':>6} {'':>8} | {len(sc.nodes):>8} {tree_depth(sc.nodes):>5} "
+               f"{L.sah_cost(sc.nodes, sc.tris, 1.2, 1.0):>7.2f} | {'':>4} {'':>4} {'':>4} {'':>8} | {sbvh_rate['cam']:>8.0f} {1.0:>6.2f} "
+               f"{sbvh_rate['rand']:>9.0f} {1.0:>6.2f}")
+        lines.append(row)
+        print(row, flush=True)
+        wide = min(255, 4 * max(0, int(n - 1).bit_length() - 10))
+        sweep = []
+        for w in sorted({wide // 2, 3 * wide // 4, wide, min(255, 3 * wide // 2)}):
+            bvh, (ms, ms_lo, ms_hi) = timed(a.ploc[0], 0, w)
+            sweep.append(f"{w}: {ms:.3f} [{ms_lo:.3f}, {ms_hi:.3f}]")
+            del bvh
+        row = f"# {name}: ploc {a.ploc[0]} + 0 build ms by device-wide iterations launched (the default is {wide}): " + "; ".join(sweep)
+        lines.append(row)
+        print(row, flush=True)
+        del v, ix, rays_dev, hits
+        torch.cuda.empty_cache()
+    Path(a.output).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.output).write_text("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", nargs="+", default=["atrium", "gallery", "crown", "plant"])
@@ -271,12 +377,16 @@ def main():
                     help="only time the collapse of device-built BVH2 trees into BVH4 / BVH8 + Tri4 and trace the collapsed trees")
     ap.add_argument("--stack-limit", type=int, default=0,
                     help="with --collapse: one more row per tree and width, the collapse under this stack limit (1 ... 63)")
+    ap.add_argument("--ploc", type=int, nargs="+", default=[],
+                    help="only compare the PLOC topology stage at these radii (0 and 1 treelet pass) with the LBVH and the 3-pass build")
     ap.add_argument("-o", "--output", default=str(ROOT / "profiles" / "gpu_bvh_build.txt"))
     a = ap.parse_args()
     if a.refit_wide:
         return refit_wide_table(a)
     if a.collapse:
         return collapse_table(a)
+    if a.ploc:
+        return ploc_table(a)
     from oracle import binding as O
     import lbvh_model as L
     import refit_model as RM
