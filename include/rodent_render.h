@@ -226,6 +226,21 @@ void    rodent_hip_render_trace_persistent(int32_t dev, int32_t enable);
 void    rodent_hip_render_trace_refill(int32_t dev, int32_t idle_bounce, int32_t idle_shadow);
 /* idle_bounce | idle_shadow << 8 for the scene that is loaded (0 = whole chunks) */
 int32_t rodent_hip_render_trace_refill_in_effect(int32_t dev);
+/* In those launches a closest-hit ray's miss record is stored when the ray retires without an accepted triangle (RODENT_HIP_LAZY_MISS=1,
+ * the default; 0 = up front, when the ray starts), and a shadow ray that hits both children of a node goes on with child 0
+ * (RODENT_HIP_SHADOW_ORDER=1, the default; 0 = the nearer child, 2 = the farther one).  Both are read once per process and every
+ * combination has its own kernel: the shadow order does not change which form of the miss record is used.  Either way a miss record is
+ * {num_geometries, -1, tmax, 0, 0} with tmax bit for bit as the stream holds it (a NaN's payload, a denormal). */
+/* The ray count from which a lone pass takes the persistent kernels (1, 2 above) and from which the loop lets a pending shadow pass ride
+ * in the next closest-hit launch: 524 288 by default (below one resident generation of rays the persistent form does not pay); rays < 0
+ * restores that, as does rodent_hip_render_defaults.  The renderer's counterpart of rodent_hip_top_min_rays: with 0 a test reaches the
+ * persistent kernels with a handful of rays.  Chooses kernels only: same records, same film. */
+void    rodent_hip_render_persist_min_rays(int32_t dev, int32_t rays);
+int32_t rodent_hip_render_persist_min_rays_in_effect(int32_t dev);
+/* The main kernel of the device's newest stream traversal launch (the loop's or a stage-level call's), as the sources spell it:
+ * "k_trace_primary<2,31>", "k_trace_secondary<1,0>", "k_trace_persist<2>", "k_trace_refill<1,true>" (shadow order, lazy miss record), ...;
+ * "" before the first launch.  A static string. */
+const char* rodent_hip_render_trace_kernel_name(int32_t dev);
 
 /* ---- the reference's renderer ABI ---- */
 int32_t get_spp(void);
@@ -298,6 +313,23 @@ void    hip_shade(int32_t dev, struct PrimaryStream* primary, struct SecondarySt
 int32_t hip_shade_compact(int32_t dev, struct PrimaryStream* from, struct PrimaryStream* to, struct SecondaryStream* secondary,
                           const int32_t* perm, int32_t num_rays, int32_t mode, int32_t block, void* stream);
 void    hip_traverse_secondary(int32_t dev, struct SecondaryStream* secondary, void* stream);
+/* One stream traversal launch as the renderer's own loop makes it, over a closest-hit pass, a shadow pass, or both in ONE persistent
+ * launch (the joint form, whatever rodent_hip_render_trace_persistent says); asynchronous on `stream`.
+ * primary / secondary: either may be NULL (that pass is absent); a stream of size 0 is an absent pass too.
+ * coherent_from: the closest-hit rays [coherent_from, primary->size) are coherent (camera rays: the lane refill takes them chunk by chunk),
+ *   the ones in front of them are not; < 0 = unknown (what hip_traverse_primary passes: a lone closest-hit pass then never refills).
+ *   Records do not depend on it.
+ * shadow_size_dev: NULL, or a DEVICE int in [0, secondary->size] that the kernels read when they run: only the shadow rays in front of it
+ *   are traced, counted and added to the film (the loop's shadow pass behind the sort); the grid covers secondary->size.
+ * flags: bit 0 = hit records as 20-byte records {geom_id, prim_id, t, u, v} at words [5 i, 5 i + 5) of the memory that starts at
+ *   primary->geom_id, instead of the ABI's five arrays (rodent_hip_render_hit_records).  Needs a stream whose arrays lie one capacity
+ *   apart in the order of the struct, as rodent_gpu_get_*_primary_stream carves them.  The caller's struct is not written.
+ * Which kernel runs follows the device's options as in the loop (rodent_hip_render_trace_persistent, _trace_refill, _lds_image,
+ * _persist_min_rays; the lane refill also needs both streams carved as above): rodent_hip_render_trace_kernel_name tells.
+ * Returns 0, or a negative status WITHOUT enqueueing anything: -1 both passes NULL, -2 unknown flag bits or a negative size,
+ * -3 coherent_from > primary->size, -4 bit 0 on a stream that is not carved that way. */
+int32_t hip_traverse_streams(int32_t dev, struct PrimaryStream* primary, int32_t coherent_from, struct SecondaryStream* secondary,
+                             const int32_t* shadow_size_dev, int32_t flags, void* stream);
 /* Order-preserving compaction of rays with id >= 0; returns the new size (synchronises the stream). */
 int32_t hip_compact_primary(int32_t dev, struct PrimaryStream* primary, struct PrimaryStream* other, void* stream);
 /* The binning stage in the forms the renderer's own loop launches (hip_sort_primary and hip_compact_primary are two of them): stable

@@ -170,6 +170,10 @@ struct RenderDevice {
     // shadow rays); 0 = whole chunks (k_trace_persist)
     int trace_refill = 0, trace_refill_shadow = 0;
     int trace_refill_request[2] = {-1, -1};    // -1 = per scene (resolve_refill), else the caller's thresholds
+    // rays from which a lone pass takes the persistent kernels and a pending shadow pass rides in the next closest-hit launch
+    // (rodent_hip_render_persist_min_rays; the tests' way to the persistent kernels with a few thousand rays)
+    int persist_min_rays = kPersistMinRays;
+    const char* trace_kernel = "";             // the main kernel of the newest launch_trace (rodent_hip_render_trace_kernel_name)
     DeviceBuffer<int> tickets[2]; int num_cus = 0;
     // 1 = the stream traversal kernels stage the scene's top-of-tree image in LDS (2-wave workgroups); 0 = every node from memory
     int lds_image = 1;
@@ -227,6 +231,7 @@ void render_defaults(RenderDevice& r) {
     r.hit_records_aos = 1;
     r.sort = 0; r.overlap = 1; r.fused_sort = 0; r.fused_compact = 2; r.mega_joint = 0; r.lds_image = 1; r.trace_persistent_request = -1;
     r.mapping_request = -1; r.capacity = 0; r.trace_refill_request[0] = r.trace_refill_request[1] = -1;
+    r.persist_min_rays = kPersistMinRays;
     env_int("RODENT_HIP_HIT_AOS", 0, 1, r.hit_records_aos); env_int("RODENT_HIP_SORT", 0, 1, r.sort);
     env_int("RODENT_HIP_OVERLAP", 0, 1, r.overlap); env_int("RODENT_HIP_FUSED_SORT", 0, 1, r.fused_sort);
     env_int("RODENT_HIP_FUSED_COMPACT", 0, 2, r.fused_compact); env_int("RODENT_HIP_LDS_IMAGE", 0, 1, r.lds_image);
@@ -313,24 +318,27 @@ int shadow_order() { static const int v = [] { const char* e = getenv("RODENT_HI
 // (profiles/r06_lazy_miss_render.txt), 20 bytes per closest-hit ray less to write; 0 = the record up front (until round 5).  (Through the
 // traversal ABI the same idea LOSES 2 ... 8 %: profiles/r06_lazy_miss_traversal.txt.)
 int lazy_miss() { static const int v = [] { const char* e = getenv("RODENT_HIP_LAZY_MISS"); return e ? (atoi(e) != 0) : 1; }(); return v; }
-// the k_trace_refill instantiation those two ask for
-decltype(&k_trace_refill<0>) pick_trace_refill() {
-    const int so = shadow_order();
-    if (lazy_miss() && so == 1) return k_trace_refill<1, true>;
-    if (so == 1) return k_trace_refill<1>;
-    if (so == 2) return k_trace_refill<2>;
-    return k_trace_refill<0>;
+// the k_trace_refill instantiation those two ask for (every shadow order has both forms of the miss record), and its name
+struct NamedRefill { decltype(&k_trace_refill<0>) kernel; const char* name; };
+NamedRefill pick_trace_refill() {
+    static const NamedRefill kRefill[3][2] = {
+        {{k_trace_refill<0, false>, "k_trace_refill<0,false>"}, {k_trace_refill<0, true>, "k_trace_refill<0,true>"}},
+        {{k_trace_refill<1, false>, "k_trace_refill<1,false>"}, {k_trace_refill<1, true>, "k_trace_refill<1,true>"}},
+        {{k_trace_refill<2, false>, "k_trace_refill<2,false>"}, {k_trace_refill<2, true>, "k_trace_refill<2,true>"}}};
+    return kRefill[shadow_order()][lazy_miss() ? 1 : 0];
 }
 // The other kernels of a lone pass: the whole-chunk persistent kernel, the one-chunk kernels (2-wave workgroups with the scene's
 // top-of-tree image in LDS / one wave, every node from memory: lds_image) and the follow-up kernel.  (Both passes in one launch:
 // k_trace_persist<2>.)
 template <typename OneChunk> struct PassKernels {
     decltype(&k_trace_persist<0>) persist; OneChunk image, plain; decltype(&k_trace_deep<false>) deep;
+    const char *persist_name, *image_name, *plain_name;
 };
+static_assert(kTraceWaves == 2 && kSceneTopNodes == 31, "the kernel names below");
 const PassKernels<decltype(&k_trace_primary<1, 0>)> kClosestKernels{k_trace_persist<0>, k_trace_primary<kTraceWaves, kSceneTopNodes>,
-    k_trace_primary<1, 0>, k_trace_deep<false>};
+    k_trace_primary<1, 0>, k_trace_deep<false>, "k_trace_persist<0>", "k_trace_primary<2,31>", "k_trace_primary<1,0>"};
 const PassKernels<decltype(&k_trace_secondary<1, 0>)> kShadowKernels{k_trace_persist<1>, k_trace_secondary<kTraceWaves, kSceneTopNodes>,
-    k_trace_secondary<1, 0>, k_trace_deep<true>};
+    k_trace_secondary<1, 0>, k_trace_deep<true>, "k_trace_persist<1>", "k_trace_secondary<2,31>", "k_trace_secondary<1,0>"};
 int persistent_grid(RenderDevice& r) {
     if (!r.num_cus) { hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, r.dev)); r.num_cus = prop.multiProcessorCount; }
     return ((r.num_cus * (32 / kPersistWaves) + kTraceStripes - 1) / kTraceStripes) * kTraceStripes;
@@ -381,7 +389,7 @@ template <typename... Args> void launch_k_shade(hipStream_t stream, int b, int r
 }
 bool refill_indexable(long long n_primary, long long n_secondary) { return n_primary + kWave + n_secondary <= (long long)kIndexMask; }
 // One stream traversal launch -- the main kernel, then the one-wave kernel for the rays it abandoned -- over a closest-hit pass, a shadow
-// pass, or BOTH in one persistent launch (the joint form: asked for only with persistent kernels on and n >= kPersistMinRays).  A pass
+// pass, or BOTH in one persistent launch (the joint form: asked for only with persistent kernels on and n >= persist_min_rays).  A pass
 // that is absent is the empty struct.
 // coherent_from: the rays [coherent_from, n) were generated for this launch (camera rays), the ones in front of them are what the last
 // bounce left; < 0 = the caller does not know (the stage-level hip_traverse_primary): a lone closest-hit pass then takes whole chunks
@@ -401,7 +409,7 @@ void launch_trace(RenderDevice& r, hipStream_t stream, const ClosestPass& c, con
     if (c.p) ensure_deep(r, 0, c.n);
     if (sh.s) ensure_deep(r, 1, sh.max_n);
     int* tickets = nullptr;
-    if (joint || (r.trace_persistent && (c.p ? c.n : sh.max_n) >= kPersistMinRays)) {
+    if (joint || (r.trace_persistent && (c.p ? c.n : sh.max_n) >= r.persist_min_rays)) {
         ensure_tickets(r); tickets = r.tickets[which].ptr;
         StreamSlab ps{nullptr, 0, 0}, ss{nullptr, 0, 0};
         const bool refill = r.trace_refill > 0 && r.scene.tri_delta && (sh.s || c.coherent_from >= 0) && refill_indexable(c.n, sh.max_n)
@@ -412,12 +420,16 @@ void launch_trace(RenderDevice& r, hipStream_t stream, const ClosestPass& c, con
             launch(sh.size_ptr, sh.max_n, film, sh.inv_spp, r.ctl + 3, r.ctl + 4, r.counters, r.deep_list[0].ptr, r.deep_list[1].ptr,
                 tickets, idle..., ensure_spill(r, which), r.ctl + 2);
         };
-        if (refill) with_tail([&](auto... tail) { hipLaunchKernelGGL(pick_trace_refill(), grid, block, 0, stream, r.scene.dev, ps, c.n,
-            c.coherent_from, ss, tail..., r.scene.tri_delta); }, r.trace_refill, r.trace_refill_shadow);
+        r.trace_kernel = refill ? pick_trace_refill().name : joint ? "k_trace_persist<2>" : c.p ? kClosestKernels.persist_name
+            : kShadowKernels.persist_name;
+        if (refill) with_tail([&](auto... tail) { hipLaunchKernelGGL(pick_trace_refill().kernel, grid, block, 0, stream, r.scene.dev, ps,
+            c.n, c.coherent_from, ss, tail..., r.scene.tri_delta); }, r.trace_refill, r.trace_refill_shadow);
         else with_tail([&](auto... tail) { hipLaunchKernelGGL(joint ? k_trace_persist<2> : c.p ? kClosestKernels.persist
             : kShadowKernels.persist, grid, block, 0, stream, r.scene.dev, p, c.n, s, tail...); });
     } else {
         const int waves = r.lds_image ? kTraceWaves : 1, rays = c.p ? c.n : sh.max_n;
+        r.trace_kernel = c.p ? (r.lds_image ? kClosestKernels.image_name : kClosestKernels.plain_name)
+            : (r.lds_image ? kShadowKernels.image_name : kShadowKernels.plain_name);
         const dim3 grid((rays + waves * kWave - 1) / (waves * kWave)), block(waves * kWave);
         if (c.p) hipLaunchKernelGGL(r.lds_image ? kClosestKernels.image : kClosestKernels.plain, grid, block, 0, stream, r.scene.dev, p,
             (const int*)nullptr, c.n, r.ctl + 3, r.counters, r.deep_list[0].ptr);
@@ -586,7 +598,7 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
         }
         const int blocks = (size + kBlock - 1) / kBlock;
         // joint: the pending shadow pass rides in this closest-hit launch if that is a persistent one, else it goes in front of it
-        const bool ride = pending.s && size >= kPersistMinRays;
+        const bool ride = pending.s && size >= r.persist_min_rays;
         if (pending.s && !ride) launch_trace(r, stream, {}, pending);
         launch_trace(r, stream, {primary, size, survivors}, ride ? pending : ShadowPass{});
         pending = ShadowPass{};
@@ -1155,6 +1167,10 @@ void rodent_hip_render_trace_refill(int32_t dev, int32_t idle_bounce, int32_t id
     resolve_refill(r);
 }
 
+void rodent_hip_render_persist_min_rays(int32_t dev, int32_t rays) { rdev(dev).persist_min_rays = rays < 0 ? kPersistMinRays : rays; }
+int32_t rodent_hip_render_persist_min_rays_in_effect(int32_t dev) { return rdev(dev).persist_min_rays; }
+const char* rodent_hip_render_trace_kernel_name(int32_t dev) { return rdev(dev).trace_kernel; }
+
 int32_t rodent_hip_render_trace_refill_in_effect(int32_t dev) { const RenderDevice& r = rdev(dev);
     return r.trace_refill | (r.trace_refill_shadow << 8); }
 
@@ -1355,6 +1371,26 @@ void hip_traverse_secondary(int32_t dev, SecondaryStream* secondary, void* strea
     if (secondary->size <= 0) return;
     launch_trace(r, (hipStream_t)stream, {}, {secondary, nullptr, secondary->size, 1.0f / (float)r.spp});
     HIP_CHECK(hipGetLastError());
+}
+
+int32_t hip_traverse_streams(int32_t dev, PrimaryStream* primary, int32_t coherent_from, SecondaryStream* secondary,
+    const int32_t* shadow_size_dev, int32_t flags, void* stream) {
+    if (!primary && !secondary) return -1;
+    if ((flags & ~kHitRecordsAoS) || (primary && primary->size < 0) || (secondary && secondary->size < 0)) return -2;
+    if (primary && coherent_from > primary->size) return -3;
+    StreamSlab slab;
+    if ((flags & kHitRecordsAoS) && (!primary || !stream_slab(*primary, slab) || !slab.base)) return -4;
+    RenderDevice& r = open_scene(rdev(dev), (hipStream_t)stream);
+    // an empty list is no pass (the one-chunk kernels have no launch of zero workgroups)
+    PrimaryStream p{};
+    if (primary && primary->size > 0) { p = *primary; p.pad = flags & kHitRecordsAoS; }
+    const ClosestPass c = p.size > 0 ? ClosestPass{&p, p.size, coherent_from} : ClosestPass{};
+    const ShadowPass sh = secondary && secondary->size > 0 ? ShadowPass{secondary, shadow_size_dev, secondary->size, 1.0f / (float)r.spp}
+        : ShadowPass{};
+    if (!c.p && !sh.s) return 0;
+    launch_trace(r, (hipStream_t)stream, c, sh);
+    HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 int32_t hip_compact_primary(int32_t dev, PrimaryStream* primary, PrimaryStream* other, void* stream) {

@@ -499,8 +499,8 @@ __device__ __forceinline__ void joint_fetch_off(vf4& q0, vf4& q1, vf4& q2, vi2& 
 // k_trace_persist.  flags: kHitRecordsAoS (primary).
 struct StreamSlab { float* base; int cap; int flags; };
 // LAZY_MISS (RODENT_HIP_LAZY_MISS): no miss record when a closest-hit ray starts -- it is stored when the ray retires
-// without an accepted triangle (kFoundBit), from the tmax the lane still holds.  In a closed scene nearly every ray finds a triangle and
-// the record stored up front was 20 of the ~43 bytes this kernel wrote per ray.
+// without an accepted triangle (kFoundBit), with the tmax read from the stream again.  In a closed scene nearly every ray finds a triangle
+// and the record stored up front was 20 of the ~43 bytes this kernel wrote per ray.
 template <int SHADOW_ORDER = 0, bool LAZY_MISS = false>
 __global__ __launch_bounds__(kWave * kPersistWaves) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void k_trace_refill(SceneDev sc, StreamSlab pslab, int n_primary, int coherent_from, StreamSlab sslab, const int* size_ptr, int n_value,
@@ -555,8 +555,9 @@ void k_trace_refill(SceneDev sc, StreamSlab pslab, int n_primary, int coherent_f
         if (__ballot(lit))
             film_add_wave(film, lit ? reinterpret_cast<const int*>(S_(0))[i] : -1, lit, lit ? S_(10)[i] * inv_spp : 0.0f,
                 lit ? S_(11)[i] * inv_spp : 0.0f, lit ? S_(12)[i] * inv_spp : 0.0f);
-        // (tmax: as loaded, canonicalised)
-        if (LAZY_MISS && done && i < 0 && !(L.g & kFoundBit)) hit_record((unsigned)L.g, sc.num_materials, -1, L.ray.tmax, 0.0f, 0.0f);
+        // (tmax: read again from the stream, the bits the caller gave -- the lane holds the canonical value, which differs for a
+        // signalling NaN or a denormal, and the record up front and the reference store what was loaded)
+        if (LAZY_MISS && done && i < 0 && !(L.g & kFoundBit)) hit_record((unsigned)L.g, sc.num_materials, -1, P_(8)[L.g], 0.0f, 0.0f);
         if (done) L.g = -1;
     };
     const auto start = [&](int g) {

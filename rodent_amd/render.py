@@ -42,7 +42,8 @@ RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh
     "rodent_hip_render_capacity", "rodent_hip_render_sort", "rodent_hip_render_hit_records", "rodent_hip_render_overlap",
     "rodent_hip_render_fused_sort", "rodent_hip_render_fused_compact", "rodent_hip_render_mapping_in_effect", "rodent_hip_render_defaults",
     "rodent_hip_render_lds_image", "rodent_hip_render_mega_joint", "rodent_hip_render_trace_persistent", "rodent_hip_render_trace_refill",
-    "rodent_hip_render_trace_refill_in_effect", "get_spp", "render",
+    "rodent_hip_render_trace_refill_in_effect", "rodent_hip_render_persist_min_rays", "rodent_hip_render_persist_min_rays_in_effect",
+    "rodent_hip_render_trace_kernel_name", "hip_traverse_streams", "get_spp", "render",
                   "setup_interface", "get_pixels", "clear_pixels", "cleanup_interface", "rodent_get_film_data",
                   "rodent_gpu_get_first_primary_stream", "rodent_gpu_get_second_primary_stream", "rodent_gpu_get_secondary_stream",
                   "rodent_gpu_get_tmp_buffer", "rodent_present", "rodent_hip_set_device", "rodent_hip_render_rows",
@@ -95,6 +96,9 @@ def lib():
         l.rodent_hip_render_trace_refill.argtypes = [i32, i32, i32]; l.rodent_hip_render_trace_refill.restype = None
         l.rodent_hip_render_trace_refill_in_effect.argtypes = [i32]; l.rodent_hip_render_trace_refill_in_effect.restype = i32
         l.rodent_hip_render_mega_joint.argtypes = [i32, i32]; l.rodent_hip_render_mega_joint.restype = None
+        l.rodent_hip_render_persist_min_rays.argtypes = [i32, i32]; l.rodent_hip_render_persist_min_rays.restype = None
+        l.rodent_hip_render_persist_min_rays_in_effect.argtypes = [i32]; l.rodent_hip_render_persist_min_rays_in_effect.restype = i32
+        l.rodent_hip_render_trace_kernel_name.argtypes = [i32]; l.rodent_hip_render_trace_kernel_name.restype = C.c_char_p
         l.get_spp.argtypes = []; l.get_spp.restype = i32
         l.render.argtypes = [C.POINTER(Settings), i32]; l.render.restype = None
         l.setup_interface.argtypes = [C.c_size_t, C.c_size_t]; l.setup_interface.restype = None
@@ -131,14 +135,15 @@ class Renderer:
     def __init__(self, scene, width, height, spp=4, max_path_len=64, dev=0, mapping="streaming", capacity=0, sort=None, overlap=None,
         fused_sort=None, lds_image=None,
                  trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None,
-                 gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64, gpu_bvh_ploc=0):
+                 gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64, gpu_bvh_ploc=0, persist_min_rays=None):
         """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says.
         gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh_opt);
         gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it.
         gpu_bvh_split = (0, 4]: pre-split the triangles into up to that fraction of extra references, at most gpu_bvh_max_pieces per
         triangle (rodent_hip_scene_create_device_bvh_split).
         gpu_bvh_ploc = 1 ... 64: its topology by locally-ordered clustering over that many Morton neighbours to either side
-        (rodent_hip_scene_create_device_bvh_ploc); the passes and the split options act on it."""
+        (rodent_hip_scene_create_device_bvh_ploc); the passes and the split options act on it.
+        persist_min_rays: rays from which a traversal launch takes the persistent kernels (rodent_hip_render_persist_min_rays)."""
         if gpu_bvh_passes and not gpu_bvh:
             raise ValueError("gpu_bvh_passes needs gpu_bvh (the treelet passes act on the device-built hierarchy)")
         if gpu_bvh_split and not gpu_bvh:
@@ -195,7 +200,9 @@ class Renderer:
                               # loops (default)
                               (mega_joint, l.rodent_hip_render_mega_joint),
                               # the shader writes continuing rays to their compacted slots
-                              (fused_compact, l.rodent_hip_render_fused_compact)):
+                              (fused_compact, l.rodent_hip_render_fused_compact),
+                              # rays from which a lone traversal pass takes the persistent kernels (default 524 288)
+                              (persist_min_rays, l.rodent_hip_render_persist_min_rays)):
             if value is not None:
                 setter(dev, int(value))
         # persistent traversal launches: lane refill once that many lanes of a wave are idle: n or (bounce rays, shadow rays); 0 = whole
@@ -219,6 +226,17 @@ class Renderer:
         whole chunks."""
         v = lib().rodent_hip_render_trace_refill_in_effect(self.dev)
         return v & 255, v >> 8
+
+    def persist_min_rays(self, rays=None):
+        """Sets (rays given; < 0 = the default, 524 288) and returns the ray count from which a traversal launch takes the persistent
+        kernels (rodent_hip_render_persist_min_rays)."""
+        if rays is not None:
+            lib().rodent_hip_render_persist_min_rays(self.dev, int(rays))
+        return lib().rodent_hip_render_persist_min_rays_in_effect(self.dev)
+
+    def trace_kernel_name(self):
+        """The main kernel of the newest stream traversal launch on this device, e.g. "k_trace_refill<1,true>"."""
+        return lib().rodent_hip_render_trace_kernel_name(self.dev).decode()
 
     def clear(self):
         lib().clear_pixels()
@@ -408,6 +426,8 @@ def stage_lib():
     l.hip_shade_compact.argtypes = [i32, C.POINTER(PrimaryStream), C.POINTER(PrimaryStream), C.POINTER(SecondaryStream), vp, i32, i32, i32,
         vp]; l.hip_shade_compact.restype = i32
     l.hip_traverse_secondary.argtypes = [i32, C.POINTER(SecondaryStream), vp]; l.hip_traverse_secondary.restype = None
+    l.hip_traverse_streams.argtypes = [i32, C.POINTER(PrimaryStream), i32, C.POINTER(SecondaryStream), vp, i32, vp]
+    l.hip_traverse_streams.restype = i32
     l.hip_compact_primary.argtypes = [i32, C.POINTER(PrimaryStream), C.POINTER(PrimaryStream), vp]; l.hip_compact_primary.restype = i32
     l.hip_bin_primary.argtypes = [i32, C.POINTER(PrimaryStream), C.POINTER(PrimaryStream), i32, i32, i32, i32, i32, vp, vp, i32,
         C.POINTER(i32), vp]; l.hip_bin_primary.restype = i32
