@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "rodent_traversal.h"
+#include "rodent_instances.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -147,6 +148,83 @@ struct RodentSceneTables { float *vertices, *normals, *face_normals; struct Rode
 void    rodent_hip_scene_tables(int32_t dev, struct RodentSceneTables* out);
 /* The current scene's hierarchy on device `dev`: DEVICE pointers (owned by the scene) and counts -- for tests and tools. */
 void    rodent_hip_scene_bvh(int32_t dev, const struct Node2** nodes, const struct Tri1** tris, int32_t* num_nodes, int32_t* num_tris);
+/* ---- instanced scenes: objects placed by 3 x 4 matrices, rendered through the two-level hierarchy of rodent_instances.h ----
+ * CPU model of everything below: tests/instanced_scene_model.py (over tests/instance_model.py).
+ * `desc` holds the CONCATENATED tables of all objects, in object space (vertices, normals, face normals, indices with vertex ids into the
+ * concatenated vertex table, materials, texture tables, lights, light ids); desc->nodes and desc->tris must be NULL and num_nodes /
+ * num_bvh_tris 0.  Object o is the triangle range [first_tri, first_tri + num_tris) and the light range [first_light, first_light +
+ * num_lights); the triangle ranges tile [0, desc->num_tris) in order (none empty), the light ranges tile [0, desc->num_lights) in order
+ * (empty ones allowed), and light_ids[t] of an emissive triangle lies in its object's light range.
+ * Hierarchies: every object's BVH2 / Tri1 is built on the device by rodent_hip_build_bvh2_tri1_opt over indices + 4 * first_tri (opt NULL:
+ * max_leaf 2, no treelet passes), so a Tri1's prim_id is OBJECT-LOCAL and its geom_id the material; the builds are packed into one
+ * allocation (all nodes, then, 256-byte aligned, all triangles) under a RodentObject table, child ids and leaf indices relative to each
+ * object's own first record.  rodent_hip_scene_bvh returns the packed arrays and their total counts.
+ * Instances: `instances` is a HOST array; instance ids are the descriptor indices 0 ... n - 1 (the instance_id word of the caller's
+ * descriptors is ignored and overwritten).  Object ids are fixed for the life of the scene; only the matrices change afterwards
+ * (rodent_hip_scene_set_transforms).  The top-level hierarchy is rodent_hip_build_tlas's with max_leaf 1.
+ * Derived tables, all on the device, all rebuilt when the matrices move:
+ *   TLAS and RodentInstance array   as rodent_hip_build_tlas writes them.
+ *   slot_of[k]                       the leaf-order slot of instance k (one thread per slot j: slot_of[instance_id(j) & 0x7FFFFFFF] = j).
+ *   bases[k] = {first_tri(o_k), light_base[k] - first_light(o_k)}, light_base = the exclusive prefix sum of num_lights(o_k) in instance
+ *                                    order; built on the host at creation, never changes.
+ *   world lights                     sum over k of num_lights(o_k) records (the scene's num_lights): light light_base[k] + j is object
+ *                                    light first_light(o_k) + j under instance k; light_owner[l] = k is fixed.  fp32, every operation
+ *                                    rounded on its own, m = the instance's object_to_world, w = its world_to_object:
+ *     a corner (x, y, z) maps per row to ((m0*x + m1*y) + m2*z) + m3; its fourth word stays as stored;
+ *     c = cross(v1' - v0', v2' - v0'), l = sqrt((c.x*c.x + c.y*c.y) + c.z*c.z), inv_area = 1.0f / (0.5f * l), the statements of
+ *       rodent_hip_scene_refit_device;
+ *     n = n' * (1.0f / sqrt((n'.x*n'.x + n'.y*n'.y) + n'.z*n'.z)), n' = N(n_obj) -- not the cross product of the mapped corners, which a
+ *       mirroring matrix would flip to the dark side;  the colour is copied.
+ *   N(n) = ((w0.x*n.x + w1.x*n.y) + w2.x*n.z, (w0.y*n.x + w1.y*n.y) + w2.y*n.z, (w0.z*n.x + w1.z*n.y) + w2.z*n.z): the transpose of
+ *     world_to_object, i.e. the inverse transpose of the placement.
+ * Shading an instanced hit (k_shade<.., true>): the ray's leaf-order slot j (a per-ray int32 array the traversal pass writes), the
+ * RodentInstance at j, k = instance_id & 0x7FFFFFFF; gprim = bases[k].x + prim indexes every per-triangle table; the face normal is
+ * normalize(N(fn)), the corner normals N(n_i) (NOT normalised), then the flat shader's lerp2 and normalize; org, dir, t, u, v are used as
+ * they are (t parametrises both spaces); the emitter of a hit is world light bases[k].y + light_ids[gprim].  That is, bit for bit, the
+ * flat shading of the scene baked into world space by those rules.
+ * With an instanced scene loaded: the mapping in effect is streaming and trace_persistent, both refill thresholds and the sort by material
+ * are 0 in effect, whatever was requested (the per-ray slot array is not moved by the sort; the `_in_effect` getters say so); the stream
+ * traversal launches are k_trace_instanced<false> / <true> -- one ray per lane, one 64-entry LDS stack for both levels, no follow-up
+ * kernel: a ray whose stack need exceeds rodent_instances.h's bound raises the renderer's overflow flag, on which a frame call aborts.
+ * rodent_hip_scene_refit* abort on an instanced scene, as they do on no scene.
+ *
+ * Returns RODENT_SCENE_OK, or a negative status.  The refusals below are decided on the HOST, before anything is enqueued, and leave the
+ * device's current scene as it is; a flag raised on the device (a builder's, RODENT_TLAS_BAD_TRANSFORM for a singular matrix) destroys
+ * what was half built -- no scene is loaded then -- and returns RODENT_SCENE_ERR_DEVICE (the flags: rodent_hip_scene_create_flags). */
+#define RODENT_SCENE_OK                0
+#define RODENT_SCENE_ERR_COUNTS      -20   /* a NULL table, a count < 1, more than 2^22 instances, a hierarchy in the description */
+#define RODENT_SCENE_ERR_RANGES      -21   /* the objects' triangle or light ranges do not tile the tables in order */
+#define RODENT_SCENE_ERR_LIGHT       -22   /* an emissive triangle names a light outside its object's light range */
+#define RODENT_SCENE_ERR_OBJECT      -23   /* an instance names an object outside the table */
+#define RODENT_SCENE_ERR_NO_LIGHT    -24   /* no instance places an object that has a light */
+#define RODENT_SCENE_ERR_OPTIONS     -25   /* invalid build options */
+#define RODENT_SCENE_ERR_TABLE       -26   /* a vertex, material or texture index outside its table */
+#define RODENT_SCENE_ERR_DEVICE      -27   /* the device raised a flag while building */
+struct RodentObjectRange { int32_t first_tri, num_tris, first_light, num_lights; };   /* 16 B */
+int32_t rodent_hip_scene_create_instanced(int32_t dev, const struct RodentSceneDesc* desc, const struct RodentObjectRange* objects,
+                                          int32_t num_objects, const struct RodentInstanceDesc* instances, int32_t num_instances,
+                                          const struct RodentBuildOptions* opt);
+/* The flags of the last rodent_hip_scene_create_instanced that returned RODENT_SCENE_ERR_DEVICE on `dev` (0 otherwise). */
+int32_t rodent_hip_scene_create_flags(int32_t dev);
+/* The instances moved: object_to_world_dev holds n x 12 floats on the DEVICE, instance k's matrix at 12 k.  Enqueues on `stream`: the
+ * copy of the matrices into the scene's descriptor array (the object and id words stay), rodent_hip_build_tlas into the scene's existing
+ * buffers and scratch, slot_of, the world lights.  Allocates nothing, copies nothing to or from the host, does not wait for the device.
+ * A later call, and a frame started afterwards on any stream, is ordered behind it with the event that orders frames behind
+ * rodent_hip_scene_refit_device.  No instanced scene loaded or a NULL pointer aborts with a message. */
+void    rodent_hip_scene_set_transforms(int32_t dev, const float* object_to_world_dev, void* stream);
+/* Waits for the last rodent_hip_scene_set_transforms and copies the TLAS build's info words to info (RODENT_BUILD_INFO_WORDS ints, may
+ * be NULL).  Returns its flags: 0 for a sound rebuild; never aborts.  Before the first call: the creation's words.  With a flag raised the
+ * tables are undefined (rodent_instances.h): do not render before a sound rebuild. */
+int32_t rodent_hip_scene_transforms_status(int32_t dev, int32_t* info);
+/* DEVICE pointers and counts of an instanced scene's tables, for tests and tools; ray_slots is the per-ray slot array (ray_slot_capacity
+ * ints; it covers the device's stream slabs as they are when this is called).  No instanced scene loaded aborts. */
+struct RodentSceneInstances {
+    struct Node2* tlas_nodes; struct RodentInstance* instances; struct RodentInstanceDesc* descs; struct RodentObject* objects;
+    int32_t* slot_of; int32_t* bases /* int2 per instance */; int32_t* light_owner; struct RodentLight *lights, *object_lights;
+    int32_t* ray_slots; int32_t* tlas_info;
+    int32_t num_instances, num_objects, num_tlas_nodes, num_lights, num_object_lights, ray_slot_capacity;
+};
+void    rodent_hip_scene_instances(int32_t dev, struct RodentSceneInstances* out);
 void    rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len);   /* defaults 4 / 64 (converter.cpp:1007-1012) */
 /* 0 = streaming wavefront loop (src/render/mapping_gpu.impala:308-369), 1 = persistent-threads megakernel
  * (mapping_gpu.impala:371-474; the reference selects it at configure time with the converter target
@@ -172,6 +250,7 @@ void    rodent_hip_render_capacity(int32_t dev, int32_t rays);
  * every BSDF kind on neighbouring walls, a textured room) the unsorted loop is 5 ... 22 % faster, so it is the default; the sort
  * stays one call away.  Same paths, same ray counts; RODENT_HIP_SORT=0|1 sets the initial value, `rodent --sort` / `--no-sort`. */
 void    rodent_hip_render_sort(int32_t dev, int32_t enable);
+int32_t rodent_hip_render_sort_in_effect(int32_t dev);       /* 0 / 1: what the next frame does (0 for an instanced scene) */
 /* Hit records inside the library's own wavefront loop: 1 (default) = one 20-byte record per ray in the memory of the stream's geom_id /
  * prim_id / t / u / v arrays (one 16-byte + one 4-byte store per record instead of five scattered 4-byte stores: the traversal launches'
  * write traffic), 0 = the ABI's five arrays.  The stage-level entry points (hip_traverse_primary, hip_shade, ...) always use the five
@@ -215,6 +294,7 @@ void    rodent_hip_render_mega_joint(int32_t dev, int32_t enable);
  *    306 ... 142 444 nodes, profiles/r03_joint_sweep.txt), 0 for a tree of a few dozen nodes (Cornell box: 2 is 5 % slower).
  * Same film.  RODENT_HIP_TRACE_PERSISTENT=-1|0|1|2. */
 void    rodent_hip_render_trace_persistent(int32_t dev, int32_t enable);
+int32_t rodent_hip_render_trace_persistent_in_effect(int32_t dev);   /* 0 / 1 / 2 for the scene that is loaded (0 for an instanced one) */
 /* Lane refill in the persistent traversal launches (1 and 2 above).  Thresholds 1 .. 64: a wave whose idle lanes reach that count
  * retires their rays and draws as many new ones from its stripe's counter instead of waiting for the last ray of a 64-ray chunk
  * (k_trace_refill) -- idle_bounce while it draws from the rays the last bounce left, idle_shadow while it draws shadow rays (64 =

@@ -32,6 +32,7 @@
 #include "rodent_render.h"
 #include "shading.h"
 #include "traversal_device.h"
+#include "traversal_steps.h"
 
 namespace {
 
@@ -128,6 +129,7 @@ __global__ void k_copy_int(const int* src, int* dst) { *dst = *src; }
 #include "render_mega.h"
 #include "render_sort.h"
 #include "render_update.h"
+#include "render_instanced.h"
 
 // ---------------------------------------------------------------------------------------------
 // Host side: per-device state (interface.cpp:324-339), stream slabs, the streaming loop
@@ -145,6 +147,17 @@ struct DevScene {
     char* refit_scratch = nullptr; int32_t* refit_info = nullptr;
     int *light_tri = nullptr, *corner_first = nullptr, *corner_tri = nullptr;
     bool refit_enqueued = false;               // RenderDevice::ev_refit marks the end of the last device refit of THIS scene
+    // An instanced scene (rodent_hip_scene_create_instanced): dev.nodes / dev.tris are the packed object hierarchies and dev.lights the
+    // world lights; `inst` is what the two instanced kernels take beside `dev`.  Everything below is in `allocs` except the per-ray slot
+    // array, which grows with the stream slabs (ensure_ray_slots) and is freed with the scene.
+    bool instanced = false;
+    InstancedDev inst{};
+    RodentInstanceDesc* descs = nullptr; RodentObject* objects = nullptr;
+    Node2* tlas_nodes = nullptr; RodentInstance* instances = nullptr; char* tlas_scratch = nullptr; int32_t* tlas_info = nullptr;
+    int *slot_of = nullptr, *light_owner = nullptr; int2* bases = nullptr;
+    RodentLight *object_lights = nullptr, *world_lights = nullptr;
+    int num_instances = 0, num_objects = 0, num_object_lights = 0;
+    size_t ray_slot_cap = 0;
 };
 
 struct RenderDevice {
@@ -211,6 +224,7 @@ struct RenderDevice {
     bool counters_continue = false;
     unsigned long long call_iterations = 0, call_generated = 0;
     int* host_pinned = nullptr;
+    int32_t create_flags = 0;                  // device flags of the last rodent_hip_scene_create_instanced that failed on them
     // `buf`, about to be ensure()d for n elements: a buffer that has to grow allocates on the current device, so that is made this one
     template <typename T> DeviceBuffer<T>& growing(DeviceBuffer<T>& buf, size_t n) {
         if (buf.count < n) HIP_CHECK(hipSetDevice(dev));
@@ -255,6 +269,9 @@ void render_defaults(RenderDevice& r) {
     r.mapping = r.mapping_request == 1 ? 1 : 0;
     r.trace_persistent = std::max(0, r.trace_persistent_request);
 }
+
+// what the next frame does about the sort by material: the per-ray slot array of an instanced scene is not moved by the sort
+int sort_in_effect(const RenderDevice& r) { return r.scene.instanced ? 0 : r.sort; }
 
 RenderDevice& rdev(int dev) {
     if (dev < 0 || dev >= 16) { fprintf(stderr, "rodent_hip: invalid device index %d\n", dev); abort(); }
@@ -383,9 +400,35 @@ int shade_block() { static const int v = [] { const char* e = getenv("RODENT_HIP
 // b: threads per workgroup, 256 / 512 / 1024 (the renderer's own launches pass shade_block())
 template <typename... Args> void launch_k_shade(hipStream_t stream, int b, int rays, Args... args) {
     const int blocks = (rays + b - 1) / b;
-    if (b == 256) hipLaunchKernelGGL(k_shade<256>, dim3(blocks), dim3(256), 0, stream, args...);
-    else if (b == 512) hipLaunchKernelGGL(k_shade<512>, dim3(blocks), dim3(512), 0, stream, args...);
-    else hipLaunchKernelGGL(k_shade<1024>, dim3(blocks), dim3(1024), 0, stream, args...);
+    if (b == 256) hipLaunchKernelGGL((k_shade<256, false>), dim3(blocks), dim3(256), 0, stream, args...);
+    else if (b == 512) hipLaunchKernelGGL((k_shade<512, false>), dim3(blocks), dim3(512), 0, stream, args...);
+    else hipLaunchKernelGGL((k_shade<1024, false>), dim3(blocks), dim3(1024), 0, stream, args...);
+}
+template <typename... Args> void launch_k_shade_instanced(hipStream_t stream, int b, int rays, const InstancedDev& inst, Args... args) {
+    const int blocks = (rays + b - 1) / b;
+    if (b == 256) hipLaunchKernelGGL((k_shade<256, true, InstancedDev>), dim3(blocks), dim3(256), 0, stream, args..., inst);
+    else if (b == 512) hipLaunchKernelGGL((k_shade<512, true, InstancedDev>), dim3(blocks), dim3(512), 0, stream, args..., inst);
+    else hipLaunchKernelGGL((k_shade<1024, true, InstancedDev>), dim3(blocks), dim3(1024), 0, stream, args..., inst);
+}
+// the shader of the scene that is loaded
+template <typename... Args> void launch_shader(RenderDevice& r, hipStream_t stream, int b, int rays, Args... args) {
+    if (r.scene.instanced) launch_k_shade_instanced(stream, b, rays, r.scene.inst, args...);
+    else launch_k_shade(stream, b, rays, args...);
+}
+// The per-ray slot array of an instanced scene: at least n ints, and never fewer than the device's stream slabs hold rays, so that a
+// pointer handed out by rodent_hip_scene_instances stays valid while the streams do.  Growing it waits for the device.
+void ensure_ray_slots(RenderDevice& r, size_t n) {
+    DevScene& s = r.scene;
+    n = std::max(n, std::max(std::max(r.slab[0].count, r.slab[1].count) / 20, r.slab[2].count / 13));
+    n = std::max<size_t>(n, 64);
+    if (n <= s.ray_slot_cap) return;
+    HIP_CHECK(hipSetDevice(r.dev));
+    if (s.inst.ray_slots) { HIP_CHECK(hipDeviceSynchronize()); HIP_CHECK(hipFree(s.inst.ray_slots)); }
+    s.inst.ray_slots = nullptr; s.ray_slot_cap = 0;
+    HIP_CHECK(hipMalloc(&s.inst.ray_slots, sizeof(int32_t) * n));
+    HIP_CHECK(hipMemset(s.inst.ray_slots, 0, sizeof(int32_t) * n));
+    HIP_CHECK(hipStreamSynchronize(nullptr));               // (the fill does not wait for the host: DeviceBuffer::grow)
+    s.ray_slot_cap = n;
 }
 bool refill_indexable(long long n_primary, long long n_secondary) { return n_primary + kWave + n_secondary <= (long long)kIndexMask; }
 // One stream traversal launch -- the main kernel, then the one-wave kernel for the rays it abandoned -- over a closest-hit pass, a shadow
@@ -400,7 +443,23 @@ bool refill_indexable(long long n_primary, long long n_secondary) { return n_pri
 struct ClosestPass { const PrimaryStream* p = nullptr; int n = 0, coherent_from = 0; };
 // (size *size_ptr, or max_n; unoccluded rays add their colour x inv_spp to the film)
 struct ShadowPass { const SecondaryStream* s = nullptr; const int* size_ptr = nullptr; int max_n = 0; float inv_spp = 0.0f; };
+// An instanced scene: one launch per pass, no follow-up kernel (render_instanced.h).
+void launch_trace_instanced(RenderDevice& r, hipStream_t stream, const ClosestPass& c, const ShadowPass& sh) {
+    const DevScene& s = r.scene;
+    if (c.p) {
+        ensure_ray_slots(r, (size_t)c.n);
+        r.trace_kernel = "k_trace_instanced<false>";
+        hipLaunchKernelGGL(k_trace_instanced<false>, dim3((c.n + kWave - 1) / kWave), dim3(kWave), 0, stream, s.dev, s.inst, *c.p,
+            SecondaryStream{}, (const int*)nullptr, c.n, (float*)nullptr, 0.0f, r.counters, r.ctl + 2, r.ctl + 6);
+    }
+    if (sh.s) {
+        r.trace_kernel = "k_trace_instanced<true>";
+        hipLaunchKernelGGL(k_trace_instanced<true>, dim3((sh.max_n + kWave - 1) / kWave), dim3(kWave), 0, stream, s.dev, s.inst,
+            PrimaryStream{}, *sh.s, sh.size_ptr, sh.max_n, r.film, sh.inv_spp, r.counters, r.ctl + 2, (int*)nullptr);
+    }
+}
 void launch_trace(RenderDevice& r, hipStream_t stream, const ClosestPass& c, const ShadowPass& sh) {
+    if (r.scene.instanced) { launch_trace_instanced(r, stream, c, sh); return; }
     const bool joint = c.p && sh.s;
     const int which = c.p ? 0 : 1;         // ticket array and spill block: [1] = a lone shadow pass (it may run beside a closest-hit one)
     const PrimaryStream p = c.p ? *c.p : PrimaryStream{};
@@ -519,6 +578,7 @@ void frame_end(RenderDevice& r, hipStream_t stream, unsigned long long iteration
 void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, int y1, hipStream_t stream, int tile_rows = 0,
     int stride_rows = 0) {
     frame_begin(r, stream, 8);
+    const int sort = sort_in_effect(r);
     const int G = r.scene.dev.num_materials;
     if (G + 1 > kMaxBins) { fprintf(stderr, "rodent_hip: too many geometries (%d)\n", G); abort(); }
     PrimaryStream a, b; SecondaryStream sec;
@@ -540,7 +600,7 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
     carve_primary(b, ensure_slab(r, 1, kCapacity, 20), round_cap(kCapacity));
     // hit records as 20-byte records instead of five arrays (store_hit_record) -- unless the sort by material runs: its kernels move and
     // read the arrays
-    a.pad = b.pad = (r.hit_records_aos && !r.sort) ? kHitRecordsAoS : 0;
+    a.pad = b.pad = (r.hit_records_aos && !sort) ? kHitRecordsAoS : 0;
     carve_secondary(sec, ensure_slab(r, 2, kCapacity, 13), round_cap(kCapacity));
     PrimaryStream* primary = &a; PrimaryStream* other = &b;
     const CameraDev cam = to_cam(settings);
@@ -572,6 +632,7 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
     }
     ensure_deep(r, 0, kCapacity); ensure_deep(r, 1, kCapacity);       // before the loop: growing them synchronises the device
     r.perm.ensure(round_cap(kCapacity));
+    if (r.scene.instanced) ensure_ray_slots(r, (size_t)round_cap(kCapacity));
     const bool fused = r.fused_compact != 0;
     int* d_alive = r.ctl + 6;                            // fused compaction: the shader's last block leaves the new stream size here
     if (fused) r.scan.ensure((kCapacity + kBlock - 1) / kBlock);
@@ -582,7 +643,7 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
             if (r.fused_compact != 2) HIP_CHECK(hipMemsetAsync(r.scan.ptr, 0, sizeof(unsigned) * (size_t)blocks, stream));
             // (d_alive was zeroed by the primary pass's follow-up kernel, k_trace_deep<false>)
         }
-        launch_k_shade(stream, shade_block(), blocks * kBlock, r.scene.dev, from, to, perm, sec, size_ptr, n_value, r.film, inv_spp,
+        launch_shader(r, stream, shade_block(), blocks * kBlock, r.scene.dev, from, to, perm, sec, size_ptr, n_value, r.film, inv_spp,
             r.max_path_len, unsorted,
                        fused ? (r.fused_compact == 2 ? kScanAtomic : r.scan.ptr) : (unsigned*)nullptr, d_alive);
     };
@@ -604,9 +665,9 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
         pending = ShadowPass{};
         // Sort by material (:166-221) or shade in stream order (misses end in the shader); sorted, the stream's size is the count of rays
         // that hit something, on the device
-        const int* const size_ptr = r.sort ? d_valid : nullptr;
-        int* const perm = r.sort && r.fused_sort ? r.perm.ptr : nullptr;
-        if (r.sort) {
+        const int* const size_ptr = sort ? d_valid : nullptr;
+        int* const perm = sort && r.fused_sort ? r.perm.ptr : nullptr;
+        if (sort) {
             // the aux stream has its copy of the previous valid count
             if (overlap && iterations) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_copy, 0));
             // fused: WITHOUT moving the rays -- the binning kernels only compute the permutation, the shader gathers through it and writes
@@ -616,15 +677,15 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
         }
         // the previous shadow rays have been traced
         if (overlap && iterations) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_sec, 0));
-        if (perm || fused) { shade(*primary, *other, perm, size_ptr, r.sort ? 0 : size, !r.sort, blocks); std::swap(primary, other); }
-        else shade(*primary, *primary, nullptr, size_ptr, r.sort ? 0 : size, !r.sort, blocks);
+        if (perm || fused) { shade(*primary, *other, perm, size_ptr, sort ? 0 : size, !sort, blocks); std::swap(primary, other); }
+        else shade(*primary, *primary, nullptr, size_ptr, sort ? 0 : size, !sort, blocks);
         // the shadow pass of this iteration: on the second stream, behind the shader on this one, or (joint) inside the next closest-hit
         // launch
         const int* shadow_size_ptr = size_ptr;
         if (overlap) {
             HIP_CHECK(hipEventRecord(r.ev_shade, stream));
             HIP_CHECK(hipStreamWaitEvent(r.aux, r.ev_shade, 0));
-            if (r.sort) {
+            if (sort) {
                 hipLaunchKernelGGL(k_copy_int, dim3(1), dim3(1), 0, r.aux, d_valid, r.ctl + 5);
                 HIP_CHECK(hipEventRecord(r.ev_copy, r.aux));
                 shadow_size_ptr = r.ctl + 5;
@@ -685,6 +746,7 @@ int auto_mega_max_nodes() {
     return v;
 }
 int resolve_mapping(const RenderDevice& r) {
+    if (r.scene.instanced) return 0;                   // the instanced kernels are stream kernels
     if (r.mapping_request >= 0) return r.mapping_request;
     return r.scene.loaded && r.scene.num_nodes <= auto_mega_max_nodes() ? 1 : 0;
 }
@@ -692,6 +754,7 @@ int resolve_mapping(const RenderDevice& r) {
 // for every hierarchy above the megakernel's size class (+3 ... +9 % on the atrium at 306 ... 142 444 nodes, profiles/r03_joint_sweep.txt),
 // the 2-wave kernels with the shadow pass on a second stream for a tree of a few dozen nodes (Cornell box: joint -5 %).
 int resolve_trace(const RenderDevice& r) {
+    if (r.scene.instanced) return 0;
     if (r.trace_persistent_request >= 0) return r.trace_persistent_request;
     return r.scene.loaded && r.scene.num_nodes > auto_mega_max_nodes() ? 2 : 0;
 }
@@ -702,6 +765,7 @@ int resolve_trace(const RenderDevice& r) {
 // -4 ... -11 % from 4 951 nodes down.
 constexpr int kRefillMinNodes = 16384, kRefillIdleLanes = 40;
 void resolve_refill(RenderDevice& r) {
+    if (r.scene.instanced) { r.trace_refill = r.trace_refill_shadow = 0; return; }
     if (r.trace_refill_request[0] >= 0) { r.trace_refill = r.trace_refill_request[0]; r.trace_refill_shadow = r.trace_refill_request[1];
         return; }
     r.trace_refill = r.trace_refill_shadow = r.scene.loaded && r.scene.num_nodes >= kRefillMinNodes ? kRefillIdleLanes : 0;
@@ -731,6 +795,7 @@ void rodent_hip_scene_destroy(int32_t dev) {
     HIP_CHECK(hipSetDevice(dev));
     HIP_CHECK(hipDeviceSynchronize());
     for (void* p : r.scene.allocs) HIP_CHECK(hipFree(p));
+    if (r.scene.inst.ray_slots) HIP_CHECK(hipFree(r.scene.inst.ray_slots));
     r.scene = DevScene();
 }
 
@@ -770,6 +835,31 @@ std::vector<float> tri_shade(const float* face_normals, const float* normals, co
         }
     }
     return rec;
+}
+
+// SceneDev::tri_shade and ::tri_tex of the tables in `d` (host), uploaded into `s`
+void upload_shading_records(DevScene& s, const RodentSceneDesc* d, bool textured) {
+    // SceneDev::tri_shade: per triangle face normal + its three vertex normals, gathered (RODENT_HIP_TRI_SHADE=0: not built, the shader
+    // goes through indices -> normals)
+    {
+        static const bool on = [] { const char* e = getenv("RODENT_HIP_TRI_SHADE"); return !e || atoi(e) != 0; }();
+        s.dev.tri_shade = nullptr;
+        if (on && d->num_tris > 0) {
+            const std::vector<float> rec = tri_shade(d->face_normals, d->normals, d->indices, d->num_tris);
+            s.dev.tri_shade = reinterpret_cast<const float4*>(upload(s, rec.data(), rec.size()));
+        }
+        s.dev.tri_tex = nullptr;
+        // SceneDev::tri_tex: the corners' texture coordinates, for resolve_material
+        if (on && textured && d->num_tris > 0) {
+            std::vector<float> tc(6 * (size_t)d->num_tris);
+            for (int32_t t = 0; t < d->num_tris; t++)
+                for (int k = 0; k < 3; k++) {
+                    const float* c = d->texcoords + 4 * (size_t)d->indices[4 * (size_t)t + k];
+                    tc[6 * (size_t)t + 2 * k] = c[0]; tc[6 * (size_t)t + 2 * k + 1] = c[1];
+                }
+            s.dev.tri_tex = upload(s, tc.data(), tc.size());
+        }
+    }
 }
 
 // rodent_hip_scene_create and rodent_hip_scene_create_device_bvh(_opt / _split): build = NULL uploads the caller's hierarchy
@@ -895,27 +985,7 @@ void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOption
         (capacity == kSceneTopNodes ? s.dev.top_image : s.dev.top_image_large) =
             reinterpret_cast<const int4*>(upload(s, image.data(), image.size()));
     }
-    // SceneDev::tri_shade: per triangle face normal + its three vertex normals, gathered (RODENT_HIP_TRI_SHADE=0: not built, the shader
-    // goes through indices -> normals)
-    {
-        static const bool on = [] { const char* e = getenv("RODENT_HIP_TRI_SHADE"); return !e || atoi(e) != 0; }();
-        s.dev.tri_shade = nullptr;
-        if (on && d->num_tris > 0) {
-            const std::vector<float> rec = tri_shade(d->face_normals, d->normals, d->indices, d->num_tris);
-            s.dev.tri_shade = reinterpret_cast<const float4*>(upload(s, rec.data(), rec.size()));
-        }
-        s.dev.tri_tex = nullptr;
-        // SceneDev::tri_tex: the corners' texture coordinates, for resolve_material
-        if (on && textured && d->num_tris > 0) {
-            std::vector<float> tc(6 * (size_t)d->num_tris);
-            for (int32_t t = 0; t < d->num_tris; t++)
-                for (int k = 0; k < 3; k++) {
-                    const float* c = d->texcoords + 4 * (size_t)d->indices[4 * (size_t)t + k];
-                    tc[6 * (size_t)t + 2 * k] = c[0]; tc[6 * (size_t)t + 2 * k + 1] = c[1];
-                }
-            s.dev.tri_tex = upload(s, tc.data(), tc.size());
-        }
-    }
+    upload_shading_records(s, d, textured);
     s.num_nodes = d->num_nodes;
     s.num_bvh_tris = d->num_bvh_tris;
     s.num_vertices = d->num_vertices;
@@ -973,6 +1043,19 @@ DevScene& loaded_scene(int32_t dev, const char* entry) {
         fprintf(stderr, "rodent_hip: %s: no scene loaded on device %d (call rodent_hip_scene_create)\n", entry, dev); abort(); }
     return s;
 }
+// the refit entries: an instanced scene has no single hierarchy to refit (its instances move with rodent_hip_scene_set_transforms)
+DevScene& flat_scene(int32_t dev, const char* entry) {
+    DevScene& s = loaded_scene(dev, entry);
+    if (s.instanced) { fprintf(stderr, "rodent_hip: %s: the scene on device %d is instanced (move its instances with "
+        "rodent_hip_scene_set_transforms)\n", entry, dev); abort(); }
+    return s;
+}
+DevScene& instanced_scene(int32_t dev, const char* entry) {
+    DevScene& s = loaded_scene(dev, entry);
+    if (!s.instanced) { fprintf(stderr, "rodent_hip: %s: the scene on device %d is not instanced (rodent_hip_scene_create_instanced)\n",
+        entry, dev); abort(); }
+    return s;
+}
 
 } // namespace
 
@@ -1027,6 +1110,7 @@ void rodent_hip_scene_refit(int32_t dev, const float* vertices, const float* nor
     RenderDevice& r = rdev(dev);
     DevScene& s = r.scene;
     if (!s.loaded) { fprintf(stderr, "rodent_hip: no scene loaded on device %d (call rodent_hip_scene_create)\n", dev); abort(); }
+    flat_scene(dev, "rodent_hip_scene_refit");
     if (!vertices || !normals || !face_normals || (s.dev.num_lights > 0 && !lights)) {
         fprintf(stderr, "rodent_hip: rodent_hip_scene_refit: a NULL table\n"); abort(); }
     HIP_CHECK(hipSetDevice(dev));
@@ -1071,12 +1155,12 @@ void rodent_hip_scene_refit(int32_t dev, const float* vertices, const float* nor
 }
 
 void rodent_hip_scene_refit_prepare(int32_t dev, int32_t smooth_normals) {
-    loaded_scene(dev, "rodent_hip_scene_refit_prepare");
+    flat_scene(dev, "rodent_hip_scene_refit_prepare");
     refit_prepare(rdev(dev), smooth_normals != 0);
 }
 
 void rodent_hip_scene_refit_device(int32_t dev, const float* vertices_dev, const float* normals_dev, void* stream_) {
-    DevScene& s = loaded_scene(dev, "rodent_hip_scene_refit_device");
+    DevScene& s = flat_scene(dev, "rodent_hip_scene_refit_device");
     RenderDevice& r = rdev(dev);
     if (!vertices_dev) { fprintf(stderr, "rodent_hip: rodent_hip_scene_refit_device: NULL vertices\n"); abort(); }
     HIP_CHECK(hipSetDevice(dev));
@@ -1114,7 +1198,7 @@ void rodent_hip_scene_refit_device(int32_t dev, const float* vertices_dev, const
 }
 
 int32_t rodent_hip_scene_refit_status(int32_t dev, int32_t* info) {
-    DevScene& s = loaded_scene(dev, "rodent_hip_scene_refit_status");
+    DevScene& s = flat_scene(dev, "rodent_hip_scene_refit_status");
     int32_t words[RODENT_BUILD_INFO_WORDS] = {s.num_nodes, s.num_bvh_tris, 0, 0};      // before the first refit: a sound one's words
     if (s.refit_enqueued) {
         HIP_CHECK(hipSetDevice(dev));
@@ -1142,12 +1226,219 @@ void rodent_hip_scene_bvh(int32_t dev, const Node2** nodes, const Tri1** tris, i
     *num_nodes = r.scene.num_nodes; *num_tris = r.scene.num_bvh_tris;
 }
 
+// The tables an instanced scene derives from its matrices, enqueued on `stream`: the TLAS and the instance array, slot_of, the world
+// lights (rodent_hip_scene_create_instanced, rodent_hip_scene_set_transforms).  Returns rodent_hip_build_tlas's status.
+static int32_t derive_instanced(int32_t dev, DevScene& s, hipStream_t stream) {
+    const int32_t rc = rodent_hip_build_tlas(dev, s.dev.nodes, s.objects, s.num_objects, s.descs, s.num_instances, 1, s.tlas_nodes,
+                                             s.instances, s.tlas_scratch, s.tlas_info, stream);
+    if (rc != RODENT_BUILD_OK) return rc;
+    const auto blocks = [](int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
+    hipLaunchKernelGGL(k_slot_of, blocks(s.num_instances), dim3(kBlock), 0, stream, s.instances, s.num_instances, s.slot_of);
+    hipLaunchKernelGGL(k_world_lights, blocks(s.dev.num_lights), dim3(kBlock), 0, stream, s.descs, s.instances, s.slot_of, s.light_owner,
+                       s.bases, s.object_lights, s.dev.num_lights, s.world_lights);
+    HIP_CHECK(hipGetLastError());
+    return rc;
+}
+
+int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d, const RodentObjectRange* objects, int32_t num_objects,
+                                          const RodentInstanceDesc* instances, int32_t num_instances, const RodentBuildOptions* opt_) {
+    const RodentBuildOptions default_opt{2, 0, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
+    const RodentBuildOptions* opt = opt_ ? opt_ : &default_opt;
+    // ---- the refusals: all on the host tables, before anything is enqueued or the current scene touched ----
+    if (!d || !objects || !instances || num_objects < 1 || num_instances < 1 || num_instances > RODENT_TLAS_MAX_INSTANCES) return
+        RODENT_SCENE_ERR_COUNTS;
+    const bool textured = d->num_textures > 0;
+    if (d->nodes || d->tris || d->num_nodes || d->num_bvh_tris || !d->vertices || !d->normals || !d->face_normals || !d->indices
+        || !d->materials || !d->light_ids || d->num_vertices < 1 || d->num_tris < 1 || d->num_tris > RODENT_BUILD_MAX_TRIS
+        || d->num_materials < 1 || d->num_lights < 0 || (d->num_lights > 0 && !d->lights) || d->num_textures < 0
+        || (textured && (!d->texcoords || !d->textures || !d->texels))) return RODENT_SCENE_ERR_COUNTS;
+    if (rodent_hip_build_opt_scratch_bytes(1, opt) < 0) return RODENT_SCENE_ERR_OPTIONS;
+    {
+        int64_t tri = 0, light = 0;
+        for (int32_t o = 0; o < num_objects; o++) {
+            const RodentObjectRange& r = objects[o];
+            if (r.first_tri != tri || r.num_tris < 1 || r.first_light != light || r.num_lights < 0) return RODENT_SCENE_ERR_RANGES;
+            tri += r.num_tris; light += r.num_lights;
+            if (tri > d->num_tris || light > d->num_lights) return RODENT_SCENE_ERR_RANGES;
+        }
+        if (tri != d->num_tris || light != d->num_lights) return RODENT_SCENE_ERR_RANGES;
+    }
+    for (int32_t k = 0; k < d->num_materials; k++)
+        if (d->materials[k].tex_kd < 0 || d->materials[k].tex_kd > d->num_textures || d->materials[k].tex_ks < 0
+            || d->materials[k].tex_ks > d->num_textures) return RODENT_SCENE_ERR_TABLE;
+    for (int32_t k = 0; k < d->num_textures; k++)
+        if (d->textures[k].width <= 0 || d->textures[k].height <= 0
+            || (uint64_t)d->textures[k].offset + (uint64_t)d->textures[k].width * (uint64_t)d->textures[k].height > d->num_texels)
+            return RODENT_SCENE_ERR_TABLE;
+    for (int32_t o = 0; o < num_objects; o++) {
+        const RodentObjectRange& r = objects[o];
+        for (int32_t t = r.first_tri; t < r.first_tri + r.num_tris; t++) {
+            for (int k = 0; k < 3; k++)
+                if ((uint32_t)d->indices[4 * (size_t)t + k] >= (uint32_t)d->num_vertices) return RODENT_SCENE_ERR_TABLE;
+            if ((uint32_t)d->indices[4 * (size_t)t + 3] >= (uint32_t)d->num_materials) return RODENT_SCENE_ERR_TABLE;
+            // an emitter's triangles are looked up in the light table by the shader: the entry must exist, and be the object's own
+            if (d->materials[d->indices[4 * (size_t)t + 3]].emissive
+                && (d->light_ids[t] < r.first_light || d->light_ids[t] >= r.first_light + r.num_lights)) return RODENT_SCENE_ERR_LIGHT;
+        }
+    }
+    int64_t world_lights = 0;
+    for (int32_t k = 0; k < num_instances; k++) {
+        if (instances[k].object < 0 || instances[k].object >= num_objects) return RODENT_SCENE_ERR_OBJECT;
+        world_lights += objects[instances[k].object].num_lights;
+    }
+    if (world_lights < 1) return RODENT_SCENE_ERR_NO_LIGHT;
+    if (world_lights > 0x7FFFFFFF) return RODENT_SCENE_ERR_COUNTS;
+
+    // ---- from here on the device's scene is the new one, or none ----
+    RenderDevice& r = rdev(dev);
+    rodent_hip_scene_destroy(dev);
+    HIP_CHECK(hipSetDevice(dev));
+    r.create_flags = 0;
+    DevScene& s = r.scene;
+    s.dev.vertices = upload(s, d->vertices, 4 * (size_t)d->num_vertices);
+    s.dev.normals = upload(s, d->normals, 4 * (size_t)d->num_vertices);
+    s.dev.face_normals = upload(s, d->face_normals, 4 * (size_t)d->num_tris);
+    s.dev.indices = upload(s, d->indices, 4 * (size_t)d->num_tris);
+    s.dev.materials = upload(s, d->materials, (size_t)d->num_materials);
+    s.dev.light_ids = upload(s, d->light_ids, (size_t)d->num_tris);
+    s.dev.texcoords = upload(s, d->texcoords, textured ? 4 * (size_t)d->num_vertices : 0);
+    s.dev.textures = upload(s, d->textures, textured ? (size_t)d->num_textures : 0);
+    s.dev.texels = upload(s, d->texels, textured ? (size_t)d->num_texels : 0);
+    s.object_lights = upload(s, d->lights, (size_t)d->num_lights);
+    const auto fail = [&](int32_t flags) { rodent_hip_scene_destroy(dev); r.create_flags = flags; return RODENT_SCENE_ERR_DEVICE; };
+    // every object's hierarchy, built into a block of its own (its node count is known only afterwards), then packed
+    std::vector<RodentObject> table((size_t)num_objects);
+    std::vector<char*> built((size_t)num_objects, nullptr);
+    const auto free_built = [&] { for (char* b : built) if (b) HIP_CHECK(hipFree(b)); };
+    int64_t total_nodes = 0;
+    for (int32_t o = 0; o < num_objects; o++) {
+        const int32_t n = objects[o].num_tris;
+        const size_t node_bytes = sizeof(Node2) * (size_t)std::max(1, n - 1), tri_bytes = sizeof(Tri1) * (size_t)n;
+        const int64_t scratch_bytes = std::max<int64_t>(rodent_hip_build_opt_scratch_bytes(n, opt), 0);
+        char* scratch = nullptr;
+        HIP_CHECK(hipMalloc(&built[o], node_bytes + tri_bytes));
+        HIP_CHECK(hipMalloc(&scratch, (size_t)scratch_bytes + 4 * RODENT_BUILD_INFO_WORDS));
+        int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + scratch_bytes);
+        int32_t info[RODENT_BUILD_INFO_WORDS] = {};
+        const int32_t rc = rodent_hip_build_bvh2_tri1_opt(dev, s.dev.vertices, d->num_vertices,
+            s.dev.indices + 4 * (size_t)objects[o].first_tri, n, opt, reinterpret_cast<Node2*>(built[o]),
+            reinterpret_cast<Tri1*>(built[o] + node_bytes), scratch, info_dev, nullptr);
+        if (rc == RODENT_BUILD_OK) HIP_CHECK(hipMemcpy(info, info_dev, sizeof(info), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipFree(scratch));
+        if (rc != RODENT_BUILD_OK || info[2] || info[0] < 1 || info[0] > std::max(1, n - 1)) {
+            free_built();
+            return fail(rc != RODENT_BUILD_OK ? rc : info[2] ? info[2] : (int32_t)0x80000000u);
+        }
+        table[o] = RodentObject{(int32_t)total_nodes, objects[o].first_tri, info[0], n};
+        total_nodes += info[0];
+    }
+    {   // one allocation: all nodes, then, 256-byte aligned, all triangles (instances.pack_objects)
+        const size_t node_bytes = sizeof(Node2) * (size_t)total_nodes, tri_start = (node_bytes + 255) / 256 * 256;
+        char* bvh = nullptr;
+        HIP_CHECK(hipMalloc(&bvh, tri_start + sizeof(Tri1) * (size_t)d->num_tris));
+        s.allocs.push_back(bvh);
+        for (int32_t o = 0; o < num_objects; o++) {
+            const size_t from_tris = sizeof(Node2) * (size_t)std::max(1, objects[o].num_tris - 1);
+            HIP_CHECK(hipMemcpy(bvh + sizeof(Node2) * (size_t)table[o].node_offset, built[o], sizeof(Node2) * (size_t)table[o].num_nodes,
+                                hipMemcpyDeviceToDevice));
+            HIP_CHECK(hipMemcpy(bvh + tri_start + sizeof(Tri1) * (size_t)table[o].tri_offset, built[o] + from_tris,
+                                sizeof(Tri1) * (size_t)table[o].num_tris, hipMemcpyDeviceToDevice));
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+        free_built();
+        s.dev.nodes = reinterpret_cast<const Node2*>(bvh);
+        s.dev.tris = reinterpret_cast<const Tri1*>(bvh + tri_start);
+    }
+    s.objects = upload(s, table.data(), table.size());
+    // descriptors (ids = indices), bases and light owners: fixed for the scene's life
+    std::vector<RodentInstanceDesc> descs(instances, instances + num_instances);
+    std::vector<int2> bases((size_t)num_instances);
+    std::vector<int> owner((size_t)world_lights);
+    int32_t light_base = 0;
+    for (int32_t k = 0; k < num_instances; k++) {
+        descs[k].instance_id = k; descs[k].pad[0] = descs[k].pad[1] = 0;
+        const RodentObjectRange& o = objects[descs[k].object];
+        bases[k] = make_int2(o.first_tri, light_base - o.first_light);
+        for (int32_t j = 0; j < o.num_lights; j++) owner[(size_t)light_base + j] = k;
+        light_base += o.num_lights;
+    }
+    s.descs = upload(s, descs.data(), descs.size());
+    s.bases = upload(s, bases.data(), bases.size());
+    s.light_owner = upload(s, owner.data(), owner.size());
+    const auto device_block = [&](size_t bytes) { char* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+        HIP_CHECK(hipMemset(p, 0, std::max<size_t>(bytes, 16))); s.allocs.push_back(p); return p; };
+    s.tlas_nodes = reinterpret_cast<Node2*>(device_block(sizeof(Node2) * (size_t)std::max(1, num_instances - 1)));
+    s.instances = reinterpret_cast<RodentInstance*>(device_block(sizeof(RodentInstance) * (size_t)num_instances));
+    s.slot_of = reinterpret_cast<int*>(device_block(sizeof(int) * (size_t)num_instances));
+    s.world_lights = reinterpret_cast<RodentLight*>(device_block(sizeof(RodentLight) * (size_t)world_lights));
+    s.tlas_scratch = device_block((size_t)std::max<int64_t>(rodent_hip_tlas_scratch_bytes(num_instances), 0));
+    s.tlas_info = reinterpret_cast<int32_t*>(device_block(4 * RODENT_BUILD_INFO_WORDS));
+    s.num_instances = num_instances; s.num_objects = num_objects; s.num_object_lights = d->num_lights;
+    s.dev.lights = s.world_lights;
+    s.dev.num_tris = d->num_tris; s.dev.num_materials = d->num_materials; s.dev.num_lights = (int32_t)world_lights;
+    s.dev.top_image = s.dev.top_image_large = nullptr;         // the instanced kernels stage no image; no other kernel is launched
+    HIP_CHECK(hipDeviceSynchronize());
+    const int32_t rc = derive_instanced(dev, s, nullptr);
+    int32_t info[RODENT_BUILD_INFO_WORDS] = {};
+    HIP_CHECK(hipDeviceSynchronize());
+    if (rc == RODENT_BUILD_OK) HIP_CHECK(hipMemcpy(info, s.tlas_info, sizeof(info), hipMemcpyDeviceToHost));
+    if (rc != RODENT_BUILD_OK || info[2]) return fail(rc != RODENT_BUILD_OK ? rc : info[2]);
+    upload_shading_records(s, d, textured);
+    s.inst.tlas = s.tlas_nodes; s.inst.instances = s.instances; s.inst.bases = s.bases;
+    s.num_nodes = (int)total_nodes; s.num_bvh_tris = d->num_tris; s.num_vertices = d->num_vertices; s.tri_delta = 0;
+    s.loaded = true; s.instanced = true;
+    ensure_ray_slots(r, 0);
+    r.mapping = resolve_mapping(r); r.trace_persistent = resolve_trace(r); resolve_refill(r);
+    return RODENT_SCENE_OK;
+}
+
+int32_t rodent_hip_scene_create_flags(int32_t dev) { return rdev(dev).create_flags; }
+
+void rodent_hip_scene_set_transforms(int32_t dev, const float* object_to_world_dev, void* stream_) {
+    DevScene& s = instanced_scene(dev, "rodent_hip_scene_set_transforms");
+    RenderDevice& r = rdev(dev);
+    if (!object_to_world_dev) { fprintf(stderr, "rodent_hip: rodent_hip_scene_set_transforms: NULL matrices\n"); abort(); }
+    HIP_CHECK(hipSetDevice(dev));
+    if (!r.ev_refit) HIP_CHECK(hipEventCreateWithFlags(&r.ev_refit, hipEventDisableTiming));
+    hipStream_t stream = (hipStream_t)stream_;
+    // behind the last move, whichever stream it took; frames need no wait (rodent_hip_scene_refit_device says why)
+    if (s.refit_enqueued) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_refit, 0));
+    hipLaunchKernelGGL(k_instance_matrices, dim3((unsigned)((12 * s.num_instances + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                       object_to_world_dev, s.num_instances, s.descs);
+    const int32_t rc = derive_instanced(dev, s, stream);
+    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: top-level rebuild refused (%d)\n", rc); abort(); }
+    HIP_CHECK(hipEventRecord(r.ev_refit, stream));
+    s.refit_enqueued = true;
+}
+
+int32_t rodent_hip_scene_transforms_status(int32_t dev, int32_t* info) {
+    DevScene& s = instanced_scene(dev, "rodent_hip_scene_transforms_status");
+    int32_t words[RODENT_BUILD_INFO_WORDS] = {};
+    HIP_CHECK(hipSetDevice(dev));
+    if (s.refit_enqueued) HIP_CHECK(hipEventSynchronize(rdev(dev).ev_refit));
+    HIP_CHECK(hipMemcpy(words, s.tlas_info, sizeof(words), hipMemcpyDeviceToHost));
+    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
+    return words[2];
+}
+
+void rodent_hip_scene_instances(int32_t dev, RodentSceneInstances* out) {
+    DevScene& s = instanced_scene(dev, "rodent_hip_scene_instances");
+    if (!out) return;
+    ensure_ray_slots(rdev(dev), 0);
+    *out = RodentSceneInstances{s.tlas_nodes, s.instances, s.descs, s.objects, s.slot_of, reinterpret_cast<int32_t*>(s.bases),
+        s.light_owner, s.world_lights, s.object_lights, s.inst.ray_slots, s.tlas_info, s.num_instances, s.num_objects,
+        std::max(1, s.num_instances - 1), s.dev.num_lights, s.num_object_lights, (int32_t)s.ray_slot_cap};
+}
+
 void rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len) {
     if (spp < 1 || max_path_len < 0) { fprintf(stderr, "rodent_hip: invalid render configuration\n"); abort(); }
     RenderDevice& r = rdev(dev); r.spp = spp; r.max_path_len = max_path_len;
 }
 
 void rodent_hip_render_sort(int32_t dev, int32_t enable) { rdev(dev).sort = enable ? 1 : 0; }
+int32_t rodent_hip_render_sort_in_effect(int32_t dev) { return sort_in_effect(rdev(dev)); }
+int32_t rodent_hip_render_trace_persistent_in_effect(int32_t dev) { return rdev(dev).trace_persistent; }
 void rodent_hip_render_hit_records(int32_t dev, int32_t aos) { rdev(dev).hit_records_aos = aos ? 1 : 0; }
 void rodent_hip_render_overlap(int32_t dev, int32_t enable) { rdev(dev).overlap = enable ? 1 : 0; }
 void rodent_hip_render_fused_sort(int32_t dev, int32_t enable) { rdev(dev).fused_sort = enable ? 1 : 0; }
@@ -1334,7 +1625,8 @@ void hip_shade(int32_t dev, PrimaryStream* primary, SecondaryStream* secondary, 
     RenderDevice& r = open_scene(rdev(dev), (hipStream_t)stream);
     primary->size = num_rays; secondary->size = num_rays; primary->pad = 0;
     if (num_rays <= 0) return;
-    launch_k_shade((hipStream_t)stream, shade_block(), num_rays, r.scene.dev, *primary, *primary, (const int*)nullptr, *secondary,
+    if (r.scene.instanced) ensure_ray_slots(r, (size_t)num_rays);
+    launch_shader(r, (hipStream_t)stream, shade_block(), num_rays, r.scene.dev, *primary, *primary, (const int*)nullptr, *secondary,
         (const int*)nullptr, num_rays, r.film,
                    1.0f / (float)r.spp, r.max_path_len,
                        /* a ray that missed ends here instead of indexing the material table with the miss id: */ 1, (unsigned*)nullptr,
@@ -1351,13 +1643,14 @@ int32_t hip_shade_compact(int32_t dev, PrimaryStream* from, PrimaryStream* to, S
     from->size = num_rays; secondary->size = num_rays; from->pad = 0; to->pad = 0; to->size = 0;
     if (num_rays <= 0) return 0;
     const int b = block ? block : shade_block(), blocks = (num_rays + b - 1) / b;
+    if (r.scene.instanced) ensure_ray_slots(r, (size_t)num_rays);
     int* d_alive = r.ctl + 6;                            // as in render_rows: the slot counter / the last block's new size
     HIP_CHECK(hipMemsetAsync(d_alive, 0, sizeof(int), (hipStream_t)stream));
     if (mode == 1) {
         r.growing(r.scan, blocks).ensure(blocks);
         HIP_CHECK(hipMemsetAsync(r.scan.ptr, 0, sizeof(unsigned) * (size_t)blocks, (hipStream_t)stream));
     }
-    launch_k_shade((hipStream_t)stream, b, num_rays, r.scene.dev, *from, *to, (const int*)perm, *secondary, (const int*)nullptr, num_rays,
+    launch_shader(r, (hipStream_t)stream, b, num_rays, r.scene.dev, *from, *to, (const int*)perm, *secondary, (const int*)nullptr, num_rays,
         r.film, 1.0f / (float)r.spp, r.max_path_len, 1, mode == 2 ? kScanAtomic : r.scan.ptr, d_alive);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(r.host_pinned + 8, d_alive, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));

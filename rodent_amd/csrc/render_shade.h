@@ -28,7 +28,16 @@ constexpr float kRayOffset = 0.001f;           // renderer.impala:46
 #ifndef RODENT_SHADE_HOIST_LIGHT
 #define RODENT_SHADE_HOIST_LIGHT 2
 #endif
-__device__ __forceinline__ ShadeOut shade_vertex(const SceneDev& sc, const PathVertex& pv, int max_path_len) {
+// INST (instanced scenes, k_shade<.., true>): pv.prim indexes the concatenated tables and `frame` is the instance the hit lies in -- the
+// surface frame goes through its world_to_object rows (surface_element_instanced) and the emitter of a hit is a WORLD light, frame->
+// light_offset behind the object's own id; next-event estimation samples sc.lights, which are the world lights then.  Nothing else differs.
+template <bool INST> __device__ __forceinline__ Surf hit_surface(const SceneDev& sc, const PathVertex& pv, const InstanceFrame* frame) {
+    if constexpr (INST) return surface_element_instanced(&sc, frame, pv.org, pv.dir, pv.prim, pv.t, pv.u, pv.v);
+    else return surface_element(&sc, pv.org, pv.dir, pv.prim, pv.t, pv.u, pv.v);
+}
+template <bool INST = false>
+__device__ __forceinline__ ShadeOut shade_vertex(const SceneDev& sc, const PathVertex& pv, int max_path_len,
+    const InstanceFrame* frame = nullptr) {
     ShadeOut o;
     const float pdf_lightpick = 1.0f / (float)sc.num_lights;
     uint32_t rnd = pv.rnd;
@@ -49,14 +58,15 @@ __device__ __forceinline__ ShadeOut shade_vertex(const SceneDev& sc, const PathV
 #endif
     RodentMaterial textured;
     const RodentMaterial* m = resolve_material(&sc, sc.materials + pv.geom, &textured, pv.prim, pv.u, pv.v);
-    const Surf sf = surface_element(&sc, pv.org, pv.dir, pv.prim, pv.t, pv.u, pv.v);
+    const Surf sf = hit_surface<INST>(sc, pv, frame);
     const v3 out_dir = neg(pv.dir);
 
     // on_hit (renderer.impala:113-128)
     o.emitted = V(0, 0, 0);
     o.emits = m->emissive && sf.entering;
     if (o.emits) {
-        const RodentLight* L = sc.lights + sc.light_ids[pv.prim];
+        const RodentLight* L = sc.lights
+            + (INST ? sc.light_ids[pv.prim] + frame->light_offset : sc.light_ids[pv.prim]);
         const float pdf_dir = cosine_hemisphere_pdf(dot(LD3(L->n), out_dir));
         const v3 intensity = pdf_dir > 0.0f ? LD3(L->color) : V(0, 0, 0);
         const float pdf_area = pdf_dir > 0.0f ? L->inv_area : 1.0f;
@@ -164,10 +174,16 @@ __device__ __forceinline__ unsigned lookback_exclusive(unsigned* status, int blo
 // stable order the separate compaction produced, without reading and writing the 15-word stream once more per bounce (the
 // compaction's copy was 38 % of the summed kernel time of BASELINE config 4, profiles/r02_render_pmc_digest.txt); the
 // new stream size goes to *alive_total.
-template <int kBlock /* threads per workgroup = rays per compaction slot request (shade_block()) */>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_shade(SceneDev sc, PrimaryStream p, PrimaryStream q,
-    const int* __restrict__ perm, SecondaryStream s, const int* size_ptr, int n_value, float* film,
-                                                   float inv_spp, int max_path_len, int unsorted, unsigned* scan, int* alive_total) {
+// INST = true (launched for instanced scenes only, with ONE trailing InstancedDev argument; k_shade<kBlock, false> takes none and is the
+// kernel as it was): ray `src` lies in the instance at leaf-order slot ray_slots[src]; its record gives the world_to_object rows and the
+// instance id k, bases[k] the object's first triangle and the offset of its lights (rules: include/rodent_render.h).
+// Its register budget is that of 7 waves per SIMD: under the flat shader's 8 the frame's rows cost it two spilled VGPRs.
+template <int kBlock /* threads per workgroup = rays per compaction slot request (shade_block()) */, bool INST = false, typename... Inst>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(INST ? 7 : 8, 8))) void k_shade(SceneDev sc, PrimaryStream p,
+    PrimaryStream q, const int* __restrict__ perm, SecondaryStream s, const int* size_ptr, int n_value, float* film,
+                                                   float inv_spp, int max_path_len, int unsorted, unsigned* scan, int* alive_total,
+                                                   Inst... inst) {
+    static_assert(sizeof...(Inst) == (INST ? 1 : 0), "k_shade<.., true> takes one InstancedDev");
     __shared__ unsigned wave_total[kBlock / kWave + 1];
 #if RODENT_SHADE_HOIST_LIGHT == 2
     __shared__ int light_sink[kBlock];
@@ -204,6 +220,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 #endif
         pv.contrib = V(p.contrib_r[src], p.contrib_g[src], p.contrib_b[src]);
         pv.depth = p.depth[src];
+        if constexpr (INST) {
+            const InstancedDev& in = (inst, ...);
+            const float4* rec = reinterpret_cast<const float4*>(in.instances + in.ray_slots[src]);
+            InstanceFrame frame;
+            frame.w0 = rec[0]; frame.w1 = rec[1]; frame.w2 = rec[2];
+            const int2 base = in.bases[reinterpret_cast<const int4*>(rec + 3)->z & 0x7FFFFFFF];
+            pv.prim += base.x; frame.light_offset = base.y;
+            o = shade_vertex<true>(sc, pv, max_path_len, &frame);
+        } else
         o = shade_vertex(sc, pv, max_path_len);
     }
     film_add_wave(film, pv.pixel, live && o.emits, o.emitted.x * inv_spp, o.emitted.y * inv_spp, o.emitted.z * inv_spp);

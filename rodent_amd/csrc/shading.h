@@ -226,6 +226,43 @@ RD_FN Surf surface_element(const SceneDev* sc, v3 org, v3 dir, int32_t prim, flo
     s.face_normal = s.entering ? fn : neg(fn); s.local = orthonormal(dot(dir, nrm) <= 0.0f ? nrm : neg(nrm)); return s;
 }
 
+/* ---- instanced scenes (include/rodent_render.h, "instanced scenes") ----
+ * What the two kernels of an instanced scene take beside SceneDev (whose nodes / tris are the packed object arrays and whose lights are
+ * the world lights): a struct of its own, so that the argument lists of the kernels that existed before stay byte for byte what they
+ * were. */
+struct InstancedDev {
+    const Node2* tlas; const RodentInstance* instances;   /* the top level and the instances in leaf order */
+    const int2* bases;                                    /* per instance id: first triangle of its object, world light - object light id */
+    int32_t* ray_slots;                                   /* per stream index: the leaf-order slot of the instance that was hit */
+};
+/* The instance a hit lies in: rows of world_to_object, and what its object's light ids are offset by */
+typedef struct { float4 w0, w1, w2; int32_t light_offset; } InstanceFrame;
+/* N(n): n times the transpose of world_to_object = the inverse transpose of the placement */
+RD_FN v3 normal_to_world(const InstanceFrame* f, v3 n) {
+    return V((f->w0.x * n.x + f->w1.x * n.y) + f->w2.x * n.z, (f->w0.y * n.x + f->w1.y * n.y) + f->w2.y * n.z,
+             (f->w0.z * n.x + f->w1.z * n.y) + f->w2.z * n.z);
+}
+/* surface_element for a hit inside an instance: `prim` indexes the concatenated tables, the face normal is normalize(N(fn)), the corner
+ * normals are N(n_i) unnormalised, then lerp2 and normalize as above; org, dir, t are world quantities. */
+RD_FN Surf surface_element_instanced(const SceneDev* sc, const InstanceFrame* f, v3 org, v3 dir, int32_t prim, float t, float u,
+    float v) {
+    v3 fn, n0, n1, n2;
+    if (sc->tri_shade) {
+        const float4* rec = sc->tri_shade + 3 * (size_t)prim;
+        const float4 a = rec[0], b = rec[1], c = rec[2];       /* fn.xyz n0.x | n0.yz n1.xy | n1.z n2.xyz */
+        fn = V(a.x, a.y, a.z); n0 = V(a.w, b.x, b.y); n1 = V(b.z, b.w, c.x); n2 = V(c.y, c.z, c.w);
+    } else {
+        const int32_t* idx = sc->indices + 4 * prim;
+        fn = LD3(sc->face_normals + 4 * prim);
+        n0 = LD3(sc->normals + 4 * idx[0]); n1 = LD3(sc->normals + 4 * idx[1]); n2 = LD3(sc->normals + 4 * idx[2]);
+    }
+    fn = normalize(normal_to_world(f, fn));
+    n0 = normal_to_world(f, n0); n1 = normal_to_world(f, n1); n2 = normal_to_world(f, n2);
+    const v3 nrm = normalize(V(lerp2(n0.x, n1.x, n2.x, u, v), lerp2(n0.y, n1.y, n2.y, u, v), lerp2(n0.z, n1.z, n2.z, u, v)));
+    Surf s; s.entering = dot(dir, fn) <= 0.0f; s.point = add(org, mulf(dir, t));
+    s.face_normal = s.entering ? fn : neg(fn); s.local = orthonormal(dot(dir, nrm) <= 0.0f ? nrm : neg(nrm)); return s;
+}
+
 /* image.impala:24-38 (RGBA8 -> colour), :48-54 (repeat border), :64-86 (bilinear filter) */
 RD_FN v3 texel(const SceneDev* sc, const RodentTexture* t, int32_t x, int32_t y) {
     const uint32_t p = sc->texels[t->offset + (uint32_t)y * (uint32_t)t->width + (uint32_t)x];

@@ -19,27 +19,7 @@
 // that follows a TLAS step loads the ray and takes its three reciprocals again; what that costs has not been measured apart.
 #pragma once
 
-// The 64 entries of one lane: indices clamped as in DeepStack; an overflow shows in the caller's cursor (ptr >= kStackCap), not in a flag.
-struct InstanceStack {
-    lds_int* base;
-    __device__ __forceinline__ void put(int e, int v) { if (e < kStackCap) base[e * kWave] = v; }
-    __device__ __forceinline__ int  get(int e) const { return base[(e < kStackCap ? e : kStackCap - 1) * kWave]; }
-};
-
-// The ray in the object space of the instance whose world_to_object rows are w0 w1 w2; tmin and the current tmax are shared.
-__device__ __forceinline__ RayX object_ray(const RayX& r, const float4& w0, const float4& w1, const float4& w2) {
-    RayX o;
-    o.ox = ((w0.x * r.ox + w0.y * r.oy) + w0.z * r.oz) + w0.w;
-    o.oy = ((w1.x * r.ox + w1.y * r.oy) + w1.z * r.oz) + w1.w;
-    o.oz = ((w2.x * r.ox + w2.y * r.oy) + w2.z * r.oz) + w2.w;
-    o.dx = (w0.x * r.dx + w0.y * r.dy) + w0.z * r.dz;
-    o.dy = (w1.x * r.dx + w1.y * r.dy) + w1.z * r.dz;
-    o.dz = (w2.x * r.dx + w2.y * r.dy) + w2.z * r.dz;
-    o.idx = safe_rcp(o.dx); o.idy = safe_rcp(o.dy); o.idz = safe_rcp(o.dz);
-    o.iox = -(o.ox * o.idx); o.ioy = -(o.oy * o.idy); o.ioz = -(o.oz * o.idz);
-    o.tmin = r.tmin; o.tmax = r.tmax;
-    return o;
-}
+// InstanceStack (the 64 entries of one lane) and object_ray (the ray in an instance's object space): traversal_steps.h.
 
 template <bool ANY>
 __global__ __launch_bounds__(kWave) void k_instanced(const Node2* __restrict__ tlas, const RodentInstance* __restrict__ instances,

@@ -196,3 +196,49 @@ def download(tlas: Tlas):
     nodes = tlas.nodes[: tlas.num_nodes * F.NODE2.itemsize].cpu().numpy().view(F.NODE2).copy()
     instances = tlas.instances[: tlas.num_instances * F.INSTANCE.itemsize].cpu().numpy().view(F.INSTANCE).copy()
     return nodes, instances
+
+
+# ---- instanced scenes for the renderer (include/rodent_render.h: rodent_hip_scene_create_instanced; render.Renderer(instances=...)) ----
+class ObjectScene:
+    """The concatenated tables of several scene.Scene objects, in object space, duck-typed like scene.Scene (no hierarchy: the
+    renderer builds every object's on the device), and `ranges`: (num_objects, 4) int32 rows first_tri, num_tris, first_light,
+    num_lights."""
+
+    @property
+    def num_tris(self):
+        return len(self.indices)
+
+
+def concat_scenes(scenes) -> ObjectScene:
+    """Concatenates scene.Scene objects into the one description an instanced scene is created from: vertex ids, material ids, texture
+    ids, texel offsets and the light ids of emissive triangles are offset by what lies in front of them (a triangle that does not emit
+    keeps light id 0), so every object keeps its own materials, textures and lights."""
+    from .scene import LIGHT, MATERIAL, TEXTURE
+    if not len(scenes):
+        raise ValueError("concat_scenes: at least one object is needed")
+    out = ObjectScene()
+    parts = {n: [] for n in ("vertices", "normals", "face_normals", "indices", "materials", "lights", "light_ids", "texcoords",
+                             "textures", "texels")}
+    ranges = np.zeros((len(scenes), 4), np.int32)
+    nv = nt = nm = nl = ntex = ntexel = 0
+    for k, s in enumerate(scenes):
+        ind = np.array(s.indices, np.int32).reshape(-1, 4)
+        emissive = np.asarray(s.materials)["emissive"][ind[:, 3]] != 0
+        ranges[k] = (nt, len(ind), nl, len(s.lights))
+        ind[:, :3] += nv; ind[:, 3] += nm
+        mats = np.array(s.materials, MATERIAL)
+        for f in ("tex_kd", "tex_ks"):
+            mats[f] = np.where(mats[f] > 0, mats[f] + ntex, 0)
+        tex = np.array(s.textures, TEXTURE)
+        tex["offset"] += np.uint32(ntexel)
+        for n, a in (("vertices", s.vertices), ("normals", s.normals), ("face_normals", s.face_normals), ("indices", ind),
+                     ("materials", mats), ("lights", np.asarray(s.lights, LIGHT)),
+                     ("light_ids", np.where(emissive, np.asarray(s.light_ids, np.int32) + nl, 0).astype(np.int32)),
+                     ("texcoords", s.texcoords), ("textures", tex), ("texels", np.asarray(s.texels, np.uint32))):
+            parts[n].append(a)
+        nv += len(s.vertices); nt += len(ind); nm += len(mats); nl += len(s.lights); ntex += len(tex); ntexel += len(s.texels)
+    for n, p in parts.items():
+        setattr(out, n, np.ascontiguousarray(np.concatenate(p)))
+    out.nodes, out.tris = np.zeros(0, F.NODE2), np.zeros(0, F.TRI1)
+    out.ranges = ranges
+    return out

@@ -34,7 +34,36 @@ class SceneTables(C.Structure):
                [(n, i32) for n in ("num_vertices", "num_tris", "num_lights", "top_nodes", "top_nodes_large")]
 
 
-RENDER_EXPORTS = ["rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_create_device_bvh_opt",
+class ObjectRange(C.Structure):
+    """RodentObjectRange: the triangle and light range of one object of an instanced scene."""
+    _fields_ = [(n, i32) for n in ("first_tri", "num_tris", "first_light", "num_lights")]
+
+
+class SceneInstances(C.Structure):
+    """RodentSceneInstances: device pointers and counts of an instanced scene's tables."""
+    _fields_ = [(n, vp) for n in ("tlas_nodes", "instances", "descs", "objects", "slot_of", "bases", "light_owner", "lights",
+                                  "object_lights", "ray_slots", "tlas_info")] + \
+               [(n, i32) for n in ("num_instances", "num_objects", "num_tlas_nodes", "num_lights", "num_object_lights",
+                                   "ray_slot_capacity")]
+
+
+# rodent_hip_scene_create_instanced's refusals (RODENT_SCENE_ERR_*)
+SCENE_ERR_COUNTS, SCENE_ERR_RANGES, SCENE_ERR_LIGHT, SCENE_ERR_OBJECT, SCENE_ERR_NO_LIGHT, SCENE_ERR_OPTIONS, SCENE_ERR_TABLE, \
+    SCENE_ERR_DEVICE = range(-20, -28, -1)
+SCENE_ERRORS = {SCENE_ERR_COUNTS: "a missing table, a count below 1, more than 2^22 instances, or a hierarchy in the description",
+                SCENE_ERR_RANGES: "the objects' triangle or light ranges do not tile the tables in order",
+                SCENE_ERR_LIGHT: "an emissive triangle names a light outside its object's light range",
+                SCENE_ERR_OBJECT: "an instance names an object outside the table",
+                SCENE_ERR_NO_LIGHT: "no instance places an object that has a light",
+                SCENE_ERR_OPTIONS: "invalid build options",
+                SCENE_ERR_TABLE: "a vertex, material or texture index outside its table",
+                SCENE_ERR_DEVICE: "the device raised a flag while building"}
+
+
+RENDER_EXPORTS = ["rodent_hip_scene_create_instanced", "rodent_hip_scene_create_flags", "rodent_hip_scene_set_transforms",
+                  "rodent_hip_scene_transforms_status", "rodent_hip_scene_instances", "rodent_hip_render_sort_in_effect",
+                  "rodent_hip_render_trace_persistent_in_effect",
+                  "rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_create_device_bvh_opt",
                   "rodent_hip_scene_create_device_bvh_split", "rodent_hip_scene_create_device_bvh_ploc",
     "rodent_hip_scene_bvh", "rodent_hip_scene_refit", "rodent_hip_scene_destroy",
     "rodent_hip_scene_refit_prepare", "rodent_hip_scene_refit_device", "rodent_hip_scene_refit_status", "rodent_hip_scene_tables",
@@ -81,6 +110,15 @@ def lib():
         l.rodent_hip_scene_refit_device.argtypes = [i32, vp, vp, vp]; l.rodent_hip_scene_refit_device.restype = None
         l.rodent_hip_scene_refit_status.argtypes = [i32, C.POINTER(i32)]; l.rodent_hip_scene_refit_status.restype = i32
         l.rodent_hip_scene_tables.argtypes = [i32, C.POINTER(SceneTables)]; l.rodent_hip_scene_tables.restype = None
+        l.rodent_hip_scene_create_instanced.argtypes = [i32, C.POINTER(SceneDesc), C.POINTER(ObjectRange), i32, vp, i32,
+                                                        C.POINTER(abi.BuildOptions)]
+        l.rodent_hip_scene_create_instanced.restype = i32
+        l.rodent_hip_scene_create_flags.argtypes = [i32]; l.rodent_hip_scene_create_flags.restype = i32
+        l.rodent_hip_scene_set_transforms.argtypes = [i32, vp, vp]; l.rodent_hip_scene_set_transforms.restype = None
+        l.rodent_hip_scene_transforms_status.argtypes = [i32, C.POINTER(i32)]; l.rodent_hip_scene_transforms_status.restype = i32
+        l.rodent_hip_scene_instances.argtypes = [i32, C.POINTER(SceneInstances)]; l.rodent_hip_scene_instances.restype = None
+        l.rodent_hip_render_sort_in_effect.argtypes = [i32]; l.rodent_hip_render_sort_in_effect.restype = i32
+        l.rodent_hip_render_trace_persistent_in_effect.argtypes = [i32]; l.rodent_hip_render_trace_persistent_in_effect.restype = i32
         l.rodent_hip_render_config.argtypes = [i32, i32, i32]; l.rodent_hip_render_config.restype = None
         l.rodent_hip_render_mapping.argtypes = [i32, i32]; l.rodent_hip_render_mapping.restype = None
         l.rodent_hip_render_capacity.argtypes = [i32, i32]; l.rodent_hip_render_capacity.restype = None
@@ -122,6 +160,33 @@ def lib():
     return l
 
 
+def scene_desc(scene):
+    """(RodentSceneDesc of a scene.Scene-like object, the arrays it points into: keep them alive while the record is used)."""
+    keep = [np.ascontiguousarray(getattr(scene, n)) for n in ("vertices", "normals", "face_normals", "indices", "nodes", "tris",
+                                                                "materials", "lights", "light_ids", "texcoords", "textures", "texels")]
+    desc = SceneDesc(*[a.ctypes.data_as(vp) for a in keep[:9]], len(scene.vertices), scene.num_tris, len(scene.nodes), len(scene.tris),
+                     len(scene.materials), len(scene.lights), *[a.ctypes.data_as(vp) for a in keep[9:]], len(scene.textures),
+                     len(scene.texels))
+    return desc, keep
+
+
+def create_instanced(dev, scene, ranges, transforms, object_ids, opt=None):
+    """rodent_hip_scene_create_instanced as it stands: returns its status (RODENT_SCENE_OK = 0, SCENE_ERR_*) and raises nothing --
+    Renderer(instances=...) is the checked way in."""
+    from . import formats as F
+    desc, keep = scene_desc(scene)
+    if not len(scene.nodes):
+        desc.nodes = None                                  # (an empty array still has an address)
+    if not len(scene.tris):
+        desc.tris = None
+    ranges = np.ascontiguousarray(ranges, np.int32).reshape(-1, 4)
+    t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 12)
+    descs = np.zeros(len(t), F.INSTANCE_DESC)
+    descs["object_to_world"], descs["object"] = t, object_ids
+    return lib().rodent_hip_scene_create_instanced(dev, C.byref(desc), ranges.ctypes.data_as(C.POINTER(ObjectRange)), len(ranges),
+                                                   descs.ctypes.data_as(vp), len(t), C.byref(opt) if opt is not None else None)
+
+
 def make_settings(cam) -> Settings:
     v = lambda a: Vec3(float(a[0]), float(a[1]), float(a[2]))
     return Settings(v(cam["eye"]), v(cam["dir"]), v(cam["up"]), v(cam["right"]), float(cam["w"]), float(cam["h"]))
@@ -135,7 +200,8 @@ class Renderer:
     def __init__(self, scene, width, height, spp=4, max_path_len=64, dev=0, mapping="streaming", capacity=0, sort=None, overlap=None,
         fused_sort=None, lds_image=None,
                  trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None,
-                 gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64, gpu_bvh_ploc=0, persist_min_rays=None):
+                 gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64, gpu_bvh_ploc=0, persist_min_rays=None, instances=None,
+                 build=None):
         """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says.
         gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh_opt);
         gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it.
@@ -143,7 +209,15 @@ class Renderer:
         triangle (rodent_hip_scene_create_device_bvh_split).
         gpu_bvh_ploc = 1 ... 64: its topology by locally-ordered clustering over that many Morton neighbours to either side
         (rodent_hip_scene_create_device_bvh_ploc); the passes and the split options act on it.
-        persist_min_rays: rays from which a traversal launch takes the persistent kernels (rodent_hip_render_persist_min_rays)."""
+        persist_min_rays: rays from which a traversal launch takes the persistent kernels (rodent_hip_render_persist_min_rays).
+        instances = (object_ranges, transforms, object_ids): an INSTANCED scene (rodent_hip_scene_create_instanced) -- `scene` holds the
+        concatenated tables of all objects in object space (instances.concat_scenes makes them), object_ranges is (num_objects, 4) int32
+        rows first_tri, num_tris, first_light, num_lights, transforms (n, 12) or (n, 3, 4) object_to_world, object_ids n ints; the
+        objects' hierarchies are built on the device with build = (max_leaf, treelet_passes) or a gpubuild.options() record (None:
+        max_leaf 2, no passes).  A refusal raises gpubuild.BuildError.  Such a scene renders through the streaming loop without the
+        sort by material, whatever the options ask for; set_transforms() moves its instances."""
+        if instances is not None and gpu_bvh:
+            raise ValueError("instances: the objects' hierarchies are built on the device anyway (pass `build`, not gpu_bvh)")
         if gpu_bvh_passes and not gpu_bvh:
             raise ValueError("gpu_bvh_passes needs gpu_bvh (the treelet passes act on the device-built hierarchy)")
         if gpu_bvh_split and not gpu_bvh:
@@ -166,7 +240,10 @@ class Renderer:
         self._counts = (len(scene.vertices), len(scene.lights), len(scene.texels))
         l.rodent_hip_set_device(dev)
         l.rodent_hip_render_defaults(dev)                    # options of an earlier Renderer in this process do not leak into this one
-        if gpu_bvh:
+        self.num_instances = 0
+        if instances is not None:
+            self._create_instanced(desc, instances, build)
+        elif gpu_bvh:
             from . import gpubuild
             desc.nodes = desc.tris = None
             desc.num_nodes = desc.num_bvh_tris = 0
@@ -212,6 +289,109 @@ class Renderer:
             l.rodent_hip_render_trace_refill(dev, int(bounce), int(shadow))
         l.setup_interface(width, height)
         l.clear_pixels()
+
+    def _create_instanced(self, desc, instances, build):
+        from . import formats as F, gpubuild
+        ranges, transforms, object_ids = instances
+        ranges = np.ascontiguousarray(ranges, np.int32).reshape(-1, 4)
+        t = np.ascontiguousarray(transforms, np.float32)
+        n = len(t)
+        if t.size != 12 * n:
+            raise ValueError(f"instances: expected (n, 12) or (n, 3, 4) transforms, got shape {t.shape}")
+        ids = np.ascontiguousarray(object_ids).astype(np.int64).reshape(-1)
+        if len(ids) != n:
+            raise ValueError(f"instances: {n} transforms but {len(ids)} object ids")
+        descs = np.zeros(n, F.INSTANCE_DESC)
+        descs["object_to_world"] = t.reshape(n, 12)
+        descs["object"] = np.clip(ids, -1, (1 << 31) - 1)                 # (an id past int32 is outside every table too)
+        if build is None or isinstance(build, abi.BuildOptions):
+            opt = build
+        else:
+            opt = gpubuild.options(*build) if isinstance(build, (tuple, list)) else gpubuild.options(int(build))
+        desc.nodes = desc.tris = None
+        desc.num_nodes = desc.num_bvh_tris = 0
+        rc = lib().rodent_hip_scene_create_instanced(self.dev, C.byref(desc), ranges.ctypes.data_as(C.POINTER(ObjectRange)), len(ranges),
+                                                     descs.ctypes.data_as(vp), n, C.byref(opt) if opt is not None else None)
+        if rc:
+            what = SCENE_ERRORS.get(rc, f"status {rc}")
+            if rc == SCENE_ERR_DEVICE:
+                from .instances import _TLAS_FLAGS
+                flags = lib().rodent_hip_scene_create_flags(self.dev)
+                what += ": " + (", ".join(s for bit, s in _TLAS_FLAGS if flags > 0 and flags & bit) or f"flags {flags}")
+            raise gpubuild.BuildError(f"rodent_hip_scene_create_instanced: {what}")
+        self.num_instances = n
+
+    def set_transforms(self, transforms, stream=None, check=True):
+        """The instances moved (rodent_hip_scene_set_transforms): `transforms` is a contiguous float32 tensor of num_instances x 12
+        object_to_world entries ((n, 12) or (n, 3, 4)) on the renderer's device, or an integer device pointer.  The top-level hierarchy,
+        the instance array, slot_of and the world lights follow on `stream` (a torch stream; None: the current one) with no host copy
+        and no wait; the next frame, on any stream, sees the moved instances.  check=True waits for the rebuild
+        (rodent_hip_scene_transforms_status) and raises gpubuild.BuildError on a flag (a singular or non-finite matrix): the scene must
+        not be rendered before a sound rebuild.  The film is not cleared."""
+        import torch
+        stream = torch.cuda.current_stream(self.dev) if stream is None else stream
+        if isinstance(transforms, int):
+            pointer = transforms
+        else:
+            t = transforms
+            if (not t.is_cuda or t.device.index != self.dev or t.dtype != torch.float32 or t.numel() != 12 * self.num_instances
+                    or not t.is_contiguous()):
+                raise ValueError(f"set_transforms: a contiguous float32 tensor of {self.num_instances} x 12 entries on cuda:{self.dev} is "
+                                 "needed (or an integer device pointer)")
+            stream.wait_stream(torch.cuda.current_stream(self.dev))          # the tensor may come from there
+            pointer = t.data_ptr()
+        lib().rodent_hip_scene_set_transforms(self.dev, pointer, C.c_void_p(stream.cuda_stream))
+        if not isinstance(transforms, int):
+            transforms.record_stream(stream)
+        if check:
+            self.transforms_status(raise_on_flag=True)
+
+    def transforms_status(self, raise_on_flag=False):
+        """(flags, info words) of the last set_transforms, once it has finished (before the first: the creation's); flags 0 = sound."""
+        words = (i32 * 4)()
+        flags = lib().rodent_hip_scene_transforms_status(self.dev, words)
+        if flags and raise_on_flag:
+            from . import gpubuild
+            from .instances import _TLAS_FLAGS
+            raise gpubuild.BuildError("rodent_hip_scene_set_transforms: " + ", ".join(s for bit, s in _TLAS_FLAGS if flags & bit))
+        return flags, list(words)
+
+    def instance_pointers(self):
+        """Device pointers (integers) and counts of an instanced scene's tables (rodent_hip_scene_instances)."""
+        t = SceneInstances()
+        lib().rodent_hip_scene_instances(self.dev, C.byref(t))
+        return {n: (getattr(t, n) or 0) for n, _ in SceneInstances._fields_}
+
+    def instance_tables(self):
+        """Host copies (numpy) of what an instanced scene derives: tlas_nodes (NODE2), instances (INSTANCE, leaf order), descs
+        (INSTANCE_DESC), objects (OBJECT), slot_of, bases ((n, 2) int32), light_owner, lights (the world lights, scene.LIGHT),
+        object_lights and tlas_info (the last rebuild's info words).  Waits for the device."""
+        import torch
+        from . import formats as F
+        from .scene import LIGHT
+        p = self.instance_pointers()
+        torch.cuda.synchronize(self.dev)
+        hip = C.cdll.LoadLibrary("libamdhip64.so")
+
+        def fetch(name, dtype, count, shape=None):
+            nbytes = count * np.dtype(dtype).itemsize
+            t = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=f"cuda:{self.dev}")
+            hip.hipMemcpy(C.c_void_p(t.data_ptr()), C.c_void_p(p[name]), C.c_size_t(nbytes), 3)
+            a = t.cpu().numpy()[:nbytes].view(dtype).copy()
+            return a.reshape(shape) if shape else a
+        n = p["num_instances"]
+        info = fetch("tlas_info", "<i4", 4)
+        return {"tlas_nodes": fetch("tlas_nodes", F.NODE2, int(info[0])), "instances": fetch("instances", F.INSTANCE, n),
+                "descs": fetch("descs", F.INSTANCE_DESC, n), "objects": fetch("objects", F.OBJECT, p["num_objects"]),
+                "slot_of": fetch("slot_of", "<i4", n), "bases": fetch("bases", "<i4", 2 * n, (n, 2)),
+                "light_owner": fetch("light_owner", "<i4", p["num_lights"]), "lights": fetch("lights", LIGHT, p["num_lights"]),
+                "object_lights": fetch("object_lights", LIGHT, p["num_object_lights"]), "tlas_info": info}
+
+    def options_in_effect(self):
+        """What the next frame uses for the scene that is loaded: mapping name, trace_persistent, (refill thresholds), sort."""
+        l = lib()
+        return {"mapping": self.mapping_name(), "trace_persistent": l.rodent_hip_render_trace_persistent_in_effect(self.dev),
+                "trace_refill": self.trace_refill(), "sort": l.rodent_hip_render_sort_in_effect(self.dev)}
 
     def configure(self, spp, max_path_len):
         self.spp = spp
