@@ -97,7 +97,50 @@ int32_t rodent_hip_build_tlas_sync(int32_t dev, const struct Node2* nodes, const
                                    const struct RodentInstanceDesc* descs, int32_t num_instances, int32_t max_leaf,
                                    struct Node2* tlas_nodes, struct RodentInstance* instances, int32_t* info);
 
-/* Traces num_rays rays through the TLAS and the objects below it.  DEVICE pointers; hit_instances (one int32_t per ray) may be NULL.
+/* ---- refit of deforming objects: a chosen subset of the packed objects, in place, in one launch list ----
+ * One RodentRefitRange per listed object: `object` indexes the RodentObject table; first_tri / num_tris cut the object's rows out of
+ * the concatenated index table (the prim ids of the object's Tri1 records index these rows); node_start / rec_start are the exclusive
+ * prefix sums of the listed objects' num_nodes / num_tris (Tri1 records) in list order. */
+struct RodentRefitRange   { int32_t object, first_tri, num_tris, node_start, rec_start, pad[3]; }; /* 32 B */
+
+/* Fills ranges[0 .. num_listed) on the HOST from host arrays: the object table, the listed object ids (any order) and, per listed
+ * object, its first row and row count in the index table.  A listed id outside the table gets node and record counts of 0 (the device
+ * raises RODENT_TLAS_BAD_OBJECT for it).  totals[0] / totals[1]: the listed objects' nodes / Tri1 records.  Returns the bytes of device
+ * scratch rodent_hip_refit_objects needs for these totals (any 256-byte aligned buffer, its contents are ignored), or -1 for a NULL
+ * pointer, num_objects < 1, num_listed < 1 or totals beyond 2^31 - 1. */
+int64_t rodent_hip_refit_objects_plan(const struct RodentObject* objects, int32_t num_objects, const int32_t* listed,
+                                      const int32_t* first_tri, const int32_t* num_tris, int32_t num_listed,
+                                      struct RodentRefitRange* ranges, int32_t* totals);
+
+/* Refits the listed objects in place to moved vertices.  All pointers are DEVICE pointers: vertices (num_vertices float4 rows, the
+ * concatenated table), indices (num_rows int4 rows, the concatenated table), nodes / tris (the packed arrays the object table points
+ * into), objects (num_objects RodentObject), ranges (num_listed RodentRefitRange), scratch (rodent_hip_refit_objects_plan's bytes for
+ * total_nodes / total_recs), info_dev (RODENT_BUILD_INFO_WORDS ints, zeroed at the start of the call).  Asynchronous on `stream` like
+ * rodent_hip_refit_bvh2_tri1: nothing is allocated, nothing waits for the device; two memsets and three kernels whatever num_listed.
+ *
+ * For every listed object o the bytes of nodes[node_offset .. + num_nodes) and tris[tri_offset .. + num_tris) are those
+ * rodent_hip_refit_bvh2_tri1 writes for that object alone over indices + 4 * first_tri, num_tris rows (the refit rules of
+ * rodent_build.h); child ids, leaf starts and prim ids stay object-local; every record of an unlisted object keeps its bytes; the
+ * result does not depend on the list's order.  info: [0] nodes completed over all listed objects [1] records rewritten [2] flags [3] 0.
+ * A sound call leaves info[0] = total_nodes.
+ *
+ * Flags: a listed object id outside the table raises RODENT_TLAS_BAD_OBJECT and nothing of that range is touched.  Within an object,
+ * what rodent_hip_refit_bvh2_tri1 flags is flagged (RODENT_BUILD_BAD_TOPOLOGY: a child id beyond the object's nodes, the object's root
+ * as a child, a leaf start or walk beyond its records, a prim id beyond its rows, a node named twice; RODENT_BUILD_BAD_INDEX,
+ * RODENT_BUILD_NON_FINITE) and leaves that object incomplete; the other listed objects come out complete.  A range whose rows leave
+ * the index table or whose stretch [node_start, + num_nodes) / [rec_start, + num_tris) leaves the totals raises
+ * RODENT_BUILD_BAD_TOPOLOGY and has nothing touched; other faults of the range table (wrong prefix sums, an object listed twice) leave
+ * nodes incomplete or bytes undefined inside the listed objects, and nothing is read or written beyond the totals or the objects.
+ *
+ * Checks, in this order, each enqueuing nothing when it fails: RODENT_BUILD_ERR_NUM_TRIS (num_rows outside [1, 2^25]),
+ * RODENT_BUILD_ERR_NUM_VERTICES, RODENT_TLAS_ERR_NUM_OBJECTS, RODENT_BUILD_ERR_NUM_NODES (num_listed < 1, a negative total),
+ * RODENT_BUILD_ERR_NULL, RODENT_BUILD_ERR_DEVICE. */
+int32_t rodent_hip_refit_objects(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_rows,
+                                 struct Node2* nodes, struct Tri1* tris, const struct RodentObject* objects, int32_t num_objects,
+                                 const struct RodentRefitRange* ranges, int32_t num_listed, int32_t total_nodes, int32_t total_recs,
+                                 void* scratch, int32_t* info_dev, void* stream);
+
+/* Traces num_rays rays through the TLAS and the objects below it. DEVICE pointers; hit_instances (one int32_t per ray) may be NULL.
  * Enqueued on `stream` without synchronising, like hip_traverse_bvh2_tri1_async; a stack overflow is reported by
  * rodent_hip_check_errors(dev, stream). */
 void hip_traverse_instanced_bvh2_tri1_async(int32_t dev, const struct Node2* tlas_nodes, const struct RodentInstance* instances,

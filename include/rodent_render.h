@@ -225,6 +225,47 @@ struct RodentSceneInstances {
     int32_t num_instances, num_objects, num_tlas_nodes, num_lights, num_object_lights, ray_slot_capacity;
 };
 void    rodent_hip_scene_instances(int32_t dev, struct RodentSceneInstances* out);
+/* ---- geometry that deforms inside the objects of an instanced scene ----
+ * Objects of a declared set D get moved vertices; their hierarchies are refitted once, however many instances place them
+ * (rodent_instances.h: rodent_hip_refit_objects), and what hangs off the objects' boxes is rebuilt.  The rules are those of "moved
+ * geometry that is already on the device" above, restricted to D (CPU model: tests/instanced_deform_model.py):
+ *   face normals and tri_shade records   of the triangles in D's triangle ranges; every other triangle keeps its bytes.
+ *   smooth vertex normals                of the vertices a triangle of D names, over the corners of ALL the scene's triangles that name
+ *                                        the vertex, in ascending (t, k) order: a static triangle that shares the vertex contributes
+ *                                        its stored face normal.  A vertex no triangle of D names keeps its bytes.
+ *   object lights                        of D's light ranges: a light is bound to the lowest emissive triangle that names it (one of
+ *                                        its own object's) and gets that triangle's record; a light nobody names and every light
+ *                                        outside D's ranges keeps its bytes.
+ *   hierarchies                          the listed objects' nodes and Tri1 records as rodent_hip_refit_objects writes them; the others'
+ *                                        keep their bytes.  Topologies stay, so no ray's stack need changes.
+ *   TLAS, instance array, slot_of, world lights   rebuilt from the refitted root boxes, the object lights and the matrices, as by
+ *                                        rodent_hip_scene_set_transforms.
+ * Rows of vertices_dev (and of normals_dev) that no object of D names must equal the scene's: the caller's contract, not checked.
+ *
+ * rodent_hip_scene_deform_prepare: one-time, synchronous.  Declares D = objects[0 .. num_objects) (a HOST array, any order) and
+ * allocates, owned by the scene and freed with it: the range table, the refit's scratch and info words, D's bound lights and, with
+ * smooth_normals != 0, D's vertices with their incidence lists.  Calling it again replaces the set.  Returns RODENT_SCENE_OK, or, leaving
+ * the scene and an earlier set exactly as they are: RODENT_SCENE_ERR_NOT_INSTANCED (no instanced scene loaded), RODENT_SCENE_ERR_COUNTS
+ * (NULL or num_objects < 1), RODENT_SCENE_ERR_OBJECT (an id outside the object table, or one listed twice). */
+#define RODENT_SCENE_ERR_NOT_INSTANCED -28
+int32_t rodent_hip_scene_deform_prepare(int32_t dev, const int32_t* objects, int32_t num_objects, int32_t smooth_normals);
+/* D's geometry moved; all pointers are DEVICE pointers on `dev`.
+ *   vertices_dev:        the whole concatenated table, num_vertices x 4 floats, object space; may be the scene's own table
+ *                        (rodent_hip_scene_tables), then nothing is copied.
+ *   normals_dev:         the whole table, or NULL: smooth normals of D's vertices are recomputed (the set must have been prepared for it).
+ *   object_to_world_dev: NULL, or n x 12 floats as for rodent_hip_scene_set_transforms: the instances move too, with ONE TLAS rebuild.
+ * Enqueues on `stream`, in this order: the wait for the last update or move, the copies, the matrices, D's face normals, D's light
+ * records, D's vertex normals, rodent_hip_refit_objects over D in the scene's packed allocation, D's tri_shade records (when the scene
+ * has the table), rodent_hip_build_tlas, slot_of, the world lights, the event.  After the prepare call it allocates nothing, copies
+ * nothing to or from the host and does not wait for the device; later calls and frames are ordered behind it as behind
+ * rodent_hip_scene_set_transforms.  No instanced scene, no declared set or a NULL vertices_dev aborts with a message. */
+void    rodent_hip_scene_deform_device(int32_t dev, const float* vertices_dev, const float* normals_dev, const float* object_to_world_dev,
+                                       void* stream);
+/* Waits for the last rodent_hip_scene_deform_device and copies the refit's and the TLAS build's info words (RODENT_BUILD_INFO_WORDS ints
+ * each, may be NULL).  Returns 0 for a sound update, else the refit's flags | the TLAS flags, with bit 31 set when the refit completed
+ * fewer nodes than D holds.  Never aborts on a flag; with one raised the tables are undefined until a sound call.  Before the first
+ * call: 0, a sound refit's words and the last TLAS build's. */
+int32_t rodent_hip_scene_deform_status(int32_t dev, int32_t* refit_info, int32_t* tlas_info);
 void    rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len);   /* defaults 4 / 64 (converter.cpp:1007-1012) */
 /* 0 = streaming wavefront loop (src/render/mapping_gpu.impala:308-369), 1 = persistent-threads megakernel
  * (mapping_gpu.impala:371-474; the reference selects it at configure time with the converter target

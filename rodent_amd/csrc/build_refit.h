@@ -235,3 +235,166 @@ __global__ __launch_bounds__(kBlock) void k_refit_wide_climb(Node* nodes, int nu
     completed = wave_sum(completed);
     if (lane_id() == 0 && completed) atomicAdd(&info[kInfoRefitNodes], completed);
 }
+
+// ---- the refit of a chosen subset of the packed objects of an instanced scene (rules: include/rodent_instances.h) ------------------
+// The three launches of the refit over the listed objects' nodes and records laid end to end: element i of the node space belongs to
+// the range r with ranges[r].node_start <= i < ranges[r + 1].node_start (the record space likewise by rec_start), found by a bisection
+// of the range table, and works on its object's records at node_offset / tri_offset with object-local ids, in the object's own stretch
+// of the scratch arrays (parent and arrivals at node_start, tribox at rec_start).  What a range claims is checked against the totals
+// the call was given before anything of it is indexed (forest_span): a range that fails has nothing touched.
+struct ForestSpan {
+    int node_offset, tri_offset, num_nodes, num_recs;    // the object (RodentObject)
+    int first_tri, num_tris;                             // its rows of the index table
+    int node_start, rec_start;                           // its stretch of the node and record spaces
+    int flags;                                           // 0: sound
+};
+struct ForestArgs {
+    const RodentObject* objects; const RodentRefitRange* ranges;
+    int num_objects, num_listed, total_nodes, total_recs, num_rows;
+};
+
+__device__ __forceinline__ ForestSpan forest_span(const ForestArgs& a, int r) {
+    const RodentRefitRange g = a.ranges[r];
+    ForestSpan s{};
+    s.first_tri = g.first_tri; s.num_tris = g.num_tris; s.node_start = g.node_start; s.rec_start = g.rec_start;
+    if ((unsigned)g.object >= (unsigned)a.num_objects) { s.flags = RODENT_TLAS_BAD_OBJECT; return s; }
+    const RodentObject o = a.objects[g.object];
+    s.node_offset = o.node_offset; s.tri_offset = o.tri_offset; s.num_nodes = o.num_nodes; s.num_recs = o.num_tris;
+    const bool sound = o.num_nodes >= 1 && o.num_tris >= 1 && g.first_tri >= 0 && g.num_tris >= 1 && g.first_tri <= a.num_rows - g.num_tris
+        && g.node_start >= 0 && g.node_start <= a.total_nodes - o.num_nodes && g.rec_start >= 0 && g.rec_start <= a.total_recs - o.num_tris;
+    if (!sound) s.flags = RODENT_BUILD_BAD_TOPOLOGY;
+    return s;
+}
+
+// The last range whose start (Records: rec_start, else node_start) is <= i: at most 32 halvings.  An empty range in front of another
+// shares its start and loses to it.
+template <bool Records> __device__ __forceinline__ int forest_range(const ForestArgs& a, int i) {
+    int lo = 0, hi = a.num_listed;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((Records ? a.ranges[mid].rec_start : a.ranges[mid].node_start) <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// The first num_listed threads also judge one range each: its flag is raised once, whether or not an element falls into it.
+__global__ __launch_bounds__(kBlock) void k_forest_links(const Node2* __restrict__ nodes, ForestArgs a, int* parent,
+                                                         uint32_t* __restrict__ arrivals, int* info) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    int flags = i < a.num_listed ? forest_span(a, i).flags : 0;
+    if (i < a.total_nodes) {
+        arrivals[i] = 0u;
+        const ForestSpan s = forest_span(a, forest_range<false>(a, i));
+        const int local = i - s.node_start;
+        if (!s.flags && local >= 0 && local < s.num_nodes) {
+            for (int k = 0; k < 2; k++) {
+                const int c = nodes[s.node_offset + local].child[k];
+                if (c > 0) {
+                    // local node 0 is its object's root: nobody's child.  A child that already has a parent slot keeps it.
+                    if (c > s.num_nodes || c == 1 || atomicCAS(&parent[s.node_start + c - 1], -1, 2 * local + k) != -1)
+                        flags |= RODENT_BUILD_BAD_TOPOLOGY;
+                } else if (c < 0 && ~c >= s.num_recs) {
+                    flags |= RODENT_BUILD_BAD_TOPOLOGY;
+                }
+            }
+        }
+    }
+    if (flags) atomicOr(&info[kInfoFlags], flags);
+}
+
+__global__ __launch_bounds__(kBlock) void k_forest_tris(const float4* __restrict__ vertices, int nv, const int4* __restrict__ indices,
+                                                        Tri1* __restrict__ tris, ForestArgs a, float* __restrict__ tribox, int* info) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    bool done = false;
+    if (p < a.total_recs) {
+        float box[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+        const ForestSpan s = forest_span(a, forest_range<true>(a, p));
+        const int local = p - s.rec_start;
+        if (!s.flags && local >= 0 && local < s.num_recs) {
+            float4* rec = reinterpret_cast<float4*>(tris + s.tri_offset + local);
+            const float4 w2 = rec[2];
+            const int t = (int)((uint32_t)__float_as_int(w2.w) & ~kLastInLeaf);
+            if (t < s.num_tris) {
+                float3 v[3]; int geom;
+                load_triangle(vertices, nv, indices + s.first_tri, t, v, &geom, info);
+                const TriGeometry g = tri1_geometry(v);
+                rec[0] = make_float4(g.v0.x, g.v0.y, g.v0.z, rec[0].w);
+                rec[1] = make_float4(g.e1.x, g.e1.y, g.e1.z, rec[1].w);
+                rec[2] = make_float4(g.e2.x, g.e2.y, g.e2.z, w2.w);
+                triangle_box(v, box);
+                done = true;
+            } else {
+                atomicOr(&info[kInfoFlags], RODENT_BUILD_BAD_TOPOLOGY);  // the record stays as it is, its box is empty
+            }
+        }
+        for (int k = 0; k < 6; k++) tribox[6 * (size_t)p + k] = box[k];
+    }
+    const int count = __syncthreads_count(done);
+    if (threadIdx.x == 0 && count) atomicAdd(&info[kInfoRefitTris], count);
+}
+
+// k_refit_climb with a lane's node, parent slots and counters relative to its object.  A wave may hold nodes of several objects: the
+// loop's bound is total_nodes, which no sound range's node count exceeds, and a lane's climb ends at its own object's local node 0.
+__global__ __launch_bounds__(kBlock) void k_forest_climb(Node2* nodes, const Tri1* __restrict__ tris, ForestArgs a,
+                                                         const float* __restrict__ tribox, const int* __restrict__ parent,
+                                                         uint32_t* arrivals, int* info) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    int node = -1;
+    ForestSpan s{};
+    if (i < a.total_nodes) {
+        s = forest_span(a, forest_range<false>(a, i));
+        const int local = i - s.node_start;
+        if (!s.flags && local >= 0 && local < s.num_nodes) node = local;
+    }
+    Node2* const mine = nodes + s.node_offset;           // the object's nodes, parent slots and counters
+    const int* const up_of = parent + s.node_start;
+    uint32_t* const arrived = arrivals + s.node_start;
+    if (node >= 0) {
+        const Tri1* const recs = tris + s.tri_offset;
+        const float* const boxes = tribox + 6 * (size_t)s.rec_start;
+        for (int k = 0; k < 2; k++) {
+            const int c = mine[node].child[k];
+            if (c >= 0 || ~c >= s.num_recs) continue;            // empty, inner, or flagged by k_forest_links: the slot stays as stored
+            float b[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+            bool ended = false;
+            for (int p = ~c; p < s.num_recs && !ended; p++) {
+                unite(b, b, boxes + 6 * (size_t)p);
+                ended = recs[p].prim_id < 0;
+            }
+            if (ended) for (int j = 0; j < 6; j++) mine[node].bounds[6 * k + j] = b[j];
+            else atomicOr(&info[kInfoFlags], RODENT_BUILD_BAD_TOPOLOGY);       // a leaf without an end bit
+        }
+    }
+    bool active = node >= 0, strayed = false;
+    int completed = 0;
+    // the wave-uniform form of the hand-off (build_device.h), as in k_refit_climb
+    for (int step = 0; step <= a.total_nodes; step++) {
+        if (__ballot(active) == 0) break;
+        publish();
+        bool last = false;
+        if (active) {
+            const uint32_t needed = 1u + (mine[node].child[0] > 0) + (mine[node].child[1] > 0);
+            last = arrive(&arrived[node]) == needed - 1u;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        active = false;
+        if (last) {
+            completed++;
+            const int up = up_of[node];
+            // (a slot beyond the object's nodes: another range's, under a range table that lets two stretches overlap)
+            if (up >= 0 && (up >> 1) < s.num_nodes) {
+                const float* b = mine[node].bounds;
+                float u[6];
+                unite(u, b, b + 6);
+                node = up >> 1;
+                for (int j = 0; j < 6; j++) mine[node].bounds[6 * (up & 1) + j] = u[j];
+                active = true;
+            } else if (up >= 0) {
+                strayed = true;
+            }
+        }
+    }
+    if (strayed) atomicOr(&info[kInfoFlags], RODENT_BUILD_BAD_TOPOLOGY);
+    completed = wave_sum(completed);
+    if (lane_id() == 0 && completed) atomicAdd(&info[kInfoRefitNodes], completed);
+}

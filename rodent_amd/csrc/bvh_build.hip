@@ -37,6 +37,8 @@
 // Refit (build_refit.h, rodent_hip_refit_bvh2_tri1): k_refit_links, k_refit_tris, k_refit_climb rewrite the boxes and Tri1 records of an
 // existing hierarchy in place from moved vertices; the topology stays.  rodent_hip_refit_bvh4_tri4 / _bvh8_tri4 do the same for
 // Node4 / Node8 + Tri4 (k_refit_wide_links, k_refit_tri4, k_refit_wide_climb; CPU model: tests/refit_wide_model.py).
+// rodent_hip_refit_objects (include/rodent_instances.h) refits a listed subset of the packed objects of an instanced scene in the same
+// three launches, whatever their number (k_forest_links, k_forest_tris, k_forest_climb).
 // Collapse (build_collapse.h, rodent_hip_collapse_bvh2_tri1): any BVH2 / Tri1 becomes Node4 / Node8 + Tri4 by bounded walks per node,
 // no thread waiting for another (CPU model: tests/collapse_model.py); rodent_hip_collapse_bvh2_tri1_bounded: the same under a stack limit
 // (tests/collapse_bounded_model.py).
@@ -465,6 +467,27 @@ int32_t launch_refit(const float* vertices, int nv, const int32_t* indices, int 
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
 
+// The refit of the listed objects of a packed set after its argument checks: launch_refit's list over the listed objects' nodes and
+// records laid end to end, whatever their number.  The links launch also covers one thread per range (the ranges' own flags).
+int32_t launch_refit_objects(const float* vertices, int nv, const int32_t* indices, Node2* nodes, Tri1* tris, const ForestArgs& a,
+                             void* scratch, int32_t* info_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const RefitScratch s = carve_refit(static_cast<char*>(scratch), a.total_nodes, a.total_recs);
+    if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess
+        || (a.total_nodes > 0 && hipMemsetAsync(s.parent, 0xFF, 4 * (size_t)a.total_nodes, stream) != hipSuccess))
+        return RODENT_BUILD_ERR_LAUNCH;
+    hipLaunchKernelGGL(k_forest_links, dim3(blocks_for(std::max(a.total_nodes, a.num_listed))), dim3(kBlock), 0, stream, nodes, a,
+                       s.parent, s.arrivals, info_dev);
+    if (a.total_recs > 0)
+        hipLaunchKernelGGL(k_forest_tris, dim3(blocks_for(a.total_recs)), dim3(kBlock), 0, stream,
+                           reinterpret_cast<const float4*>(vertices), nv, reinterpret_cast<const int4*>(indices), tris, a, s.tribox,
+                           info_dev);
+    if (a.total_nodes > 0)
+        hipLaunchKernelGGL(k_forest_climb, dim3(blocks_for(a.total_nodes)), dim3(kBlock), 0, stream, nodes, tris, a, s.tribox, s.parent,
+                           s.arrivals, info_dev);
+    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
 // The same for Node4 / Node8 + Tri4: one launcher for both widths.
 template <class Node>
 int32_t launch_refit_wide(const float* vertices, int nv, const int32_t* indices, int n, Node* nodes, int num_nodes, Tri4* tris,
@@ -854,6 +877,36 @@ int32_t rodent_hip_build_tlas_sync(int32_t dev, const struct Node2* nodes, const
         return rodent_hip_build_tlas(dev, nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch,
                                      info_dev, nullptr);
     });
+}
+
+int64_t rodent_hip_refit_objects_plan(const struct RodentObject* objects, int32_t num_objects, const int32_t* listed,
+                                      const int32_t* first_tri, const int32_t* num_tris, int32_t num_listed,
+                                      struct RodentRefitRange* ranges, int32_t* totals) {
+    if (!objects || !listed || !first_tri || !num_tris || !ranges || !totals || num_objects < 1 || num_listed < 1) return -1;
+    int64_t nodes = 0, recs = 0;
+    for (int32_t k = 0; k < num_listed; k++) {
+        const bool known = listed[k] >= 0 && listed[k] < num_objects;
+        ranges[k] = RodentRefitRange{listed[k], first_tri[k], num_tris[k], (int32_t)nodes, (int32_t)recs, {0, 0, 0}};
+        nodes += known ? std::max(objects[listed[k]].num_nodes, 0) : 0;
+        recs += known ? std::max(objects[listed[k]].num_tris, 0) : 0;
+        if (nodes > INT32_MAX || recs > INT32_MAX) return -1;
+    }
+    totals[0] = (int32_t)nodes; totals[1] = (int32_t)recs;
+    return (int64_t)std::max<size_t>(carve_refit(nullptr, (int)nodes, (int)recs).bytes, 256);
+}
+
+int32_t rodent_hip_refit_objects(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_rows,
+                                 struct Node2* nodes, struct Tri1* tris, const struct RodentObject* objects, int32_t num_objects,
+                                 const struct RodentRefitRange* ranges, int32_t num_listed, int32_t total_nodes, int32_t total_recs,
+                                 void* scratch, int32_t* info_dev, void* stream) {
+    if (bad_num_tris(num_rows)) return RODENT_BUILD_ERR_NUM_TRIS;
+    if (num_vertices < 1) return RODENT_BUILD_ERR_NUM_VERTICES;
+    if (num_objects < 1) return RODENT_TLAS_ERR_NUM_OBJECTS;
+    if (num_listed < 1 || total_nodes < 0 || total_recs < 0) return RODENT_BUILD_ERR_NUM_NODES;
+    if (!vertices || !indices || !nodes || !tris || !objects || !ranges || !scratch || !info_dev) return RODENT_BUILD_ERR_NULL;
+    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
+    const ForestArgs a{objects, ranges, num_objects, num_listed, total_nodes, total_recs, num_rows};
+    return launch_refit_objects(vertices, num_vertices, indices, nodes, tris, a, scratch, info_dev, stream);
 }
 
 } // extern "C"

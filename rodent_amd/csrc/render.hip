@@ -158,6 +158,19 @@ struct DevScene {
     RodentLight *object_lights = nullptr, *world_lights = nullptr;
     int num_instances = 0, num_objects = 0, num_object_lights = 0;
     size_t ray_slot_cap = 0;
+    // Host copies of the objects' ranges and of the RodentObject table, and the deforming set D of rodent_hip_scene_deform_prepare: its
+    // range table, the forest refit's scratch with its info words behind it, the vertices D's triangles name with their incidence
+    // lists (vertex verts[j]: corner_tri[corner_first[j] .. corner_first[j + 1])), its bound lights {object light, triangle}.  In
+    // `deform.allocs`, freed with the scene or when the set is replaced.
+    std::vector<RodentObjectRange> object_ranges;
+    std::vector<RodentObject> object_table;
+    struct DeformSet {
+        std::vector<void*> allocs;
+        RodentRefitRange* ranges = nullptr; char* scratch = nullptr; int32_t* info = nullptr;
+        int *verts = nullptr, *corner_first = nullptr, *corner_tri = nullptr; int2* lights = nullptr;
+        int num_listed = 0, num_nodes = 0, num_tris = 0, num_verts = 0, num_lights = 0;
+        bool smooth = false, enqueued = false;
+    } deform;
 };
 
 struct RenderDevice {
@@ -795,6 +808,7 @@ void rodent_hip_scene_destroy(int32_t dev) {
     HIP_CHECK(hipSetDevice(dev));
     HIP_CHECK(hipDeviceSynchronize());
     for (void* p : r.scene.allocs) HIP_CHECK(hipFree(p));
+    for (void* p : r.scene.deform.allocs) HIP_CHECK(hipFree(p));
     if (r.scene.inst.ray_slots) HIP_CHECK(hipFree(r.scene.inst.ray_slots));
     r.scene = DevScene();
 }
@@ -1351,6 +1365,8 @@ int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d,
         s.dev.tris = reinterpret_cast<const Tri1*>(bvh + tri_start);
     }
     s.objects = upload(s, table.data(), table.size());
+    s.object_table = table;
+    s.object_ranges.assign(objects, objects + num_objects);
     // descriptors (ids = indices), bases and light owners: fixed for the scene's life
     std::vector<RodentInstanceDesc> descs(instances, instances + num_instances);
     std::vector<int2> bases((size_t)num_instances);
@@ -1420,6 +1436,146 @@ int32_t rodent_hip_scene_transforms_status(int32_t dev, int32_t* info) {
     HIP_CHECK(hipMemcpy(words, s.tlas_info, sizeof(words), hipMemcpyDeviceToHost));
     if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
     return words[2];
+}
+
+int32_t rodent_hip_scene_deform_prepare(int32_t dev, const int32_t* objects, int32_t num_objects, int32_t smooth_normals) {
+    RenderDevice& r = rdev(dev);
+    DevScene& s = r.scene;
+    // ---- the refusals: on the host, the scene and an earlier set stay as they are ----
+    if (!s.loaded || !s.instanced) return RODENT_SCENE_ERR_NOT_INSTANCED;
+    if (!objects || num_objects < 1) return RODENT_SCENE_ERR_COUNTS;
+    std::vector<char> listed((size_t)s.num_objects, 0);
+    for (int32_t k = 0; k < num_objects; k++) {
+        if (objects[k] < 0 || objects[k] >= s.num_objects || listed[objects[k]]) return RODENT_SCENE_ERR_OBJECT;
+        listed[objects[k]] = 1;
+    }
+    std::vector<int32_t> first_tri((size_t)num_objects), num_tris((size_t)num_objects);
+    for (int32_t k = 0; k < num_objects; k++) {
+        first_tri[k] = s.object_ranges[objects[k]].first_tri; num_tris[k] = s.object_ranges[objects[k]].num_tris; }
+    std::vector<RodentRefitRange> ranges((size_t)num_objects);
+    int32_t totals[2] = {};
+    const int64_t scratch_bytes = rodent_hip_refit_objects_plan(s.object_table.data(), s.num_objects, objects, first_tri.data(),
+                                                                num_tris.data(), num_objects, ranges.data(), totals);
+    if (scratch_bytes < 0) return RODENT_SCENE_ERR_COUNTS;
+    // ---- from here on the set is the new one ----
+    HIP_CHECK(hipSetDevice(dev));
+    HIP_CHECK(hipDeviceSynchronize());                   // no update still works in the lists that are replaced
+    if (!r.ev_refit) HIP_CHECK(hipEventCreateWithFlags(&r.ev_refit, hipEventDisableTiming));
+    for (void* p : s.deform.allocs) HIP_CHECK(hipFree(p));
+    s.deform = DevScene::DeformSet();
+    DevScene::DeformSet& d = s.deform;
+    const auto put = [&](const auto* host, size_t count) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(host)>>;
+        T* p = nullptr;
+        HIP_CHECK(hipMalloc(&p, std::max<size_t>(sizeof(T) * count, 16)));
+        if (count) HIP_CHECK(hipMemcpy(p, host, sizeof(T) * count, hipMemcpyHostToDevice));
+        d.allocs.push_back(p);
+        return p;
+    };
+    d.ranges = put(ranges.data(), ranges.size());
+    HIP_CHECK(hipMalloc(&d.scratch, (size_t)scratch_bytes + 4 * RODENT_BUILD_INFO_WORDS));
+    d.allocs.push_back(d.scratch);
+    d.info = reinterpret_cast<int32_t*>(d.scratch + scratch_bytes);
+    HIP_CHECK(hipMemset(d.info, 0, 4 * RODENT_BUILD_INFO_WORDS));
+    d.num_listed = num_objects; d.num_nodes = totals[0]; d.num_tris = totals[1]; d.smooth = smooth_normals != 0;
+    // The tables the lists are made from never change under an update: indices, light ids, materials.
+    const size_t nv = (size_t)s.num_vertices, nt = (size_t)s.dev.num_tris;
+    std::vector<int32_t> indices(4 * nt), light_ids(nt);
+    std::vector<RodentMaterial> materials((size_t)s.dev.num_materials);
+    HIP_CHECK(hipMemcpy(indices.data(), s.dev.indices, sizeof(int32_t) * indices.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(light_ids.data(), s.dev.light_ids, sizeof(int32_t) * nt, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(materials.data(), s.dev.materials, sizeof(RodentMaterial) * materials.size(), hipMemcpyDeviceToHost));
+    // light k of D's light ranges: bound to the lowest emissive triangle that names it (one of its own object's: the creation checked)
+    std::vector<int2> bound;
+    for (int32_t o = 0; o < s.num_objects; o++) {
+        if (!listed[o]) continue;
+        const RodentObjectRange& g = s.object_ranges[o];
+        std::vector<int> tri((size_t)g.num_lights, -1);
+        for (int32_t t = g.first_tri; t < g.first_tri + g.num_tris; t++) {
+            const int32_t k = light_ids[t] - g.first_light;
+            if (materials[indices[4 * (size_t)t + 3]].emissive && k >= 0 && k < g.num_lights && tri[k] < 0) tri[k] = t;
+        }
+        for (int32_t k = 0; k < g.num_lights; k++) if (tri[k] >= 0) bound.push_back(make_int2(g.first_light + k, tri[k]));
+    }
+    d.lights = put(bound.data(), bound.size()); d.num_lights = (int)bound.size();
+    if (d.smooth) {
+        // the vertices D's triangles name, ascending, and for each the corners of ALL triangles that name it, ascending (triangle, corner)
+        std::vector<int> slot(nv, -1), verts;
+        for (int32_t o = 0; o < s.num_objects; o++) {
+            if (!listed[o]) continue;
+            const RodentObjectRange& g = s.object_ranges[o];
+            for (size_t c = 4 * (size_t)g.first_tri; c < 4 * (size_t)(g.first_tri + g.num_tris); c++) if (c % 4 != 3) slot[indices[c]] = 0;
+        }
+        for (size_t v = 0; v < nv; v++) if (slot[v] == 0) { slot[v] = (int)verts.size(); verts.push_back((int)v); }
+        std::vector<int> first(verts.size() + 1, 0);
+        for (size_t t = 0; t < nt; t++) for (int k = 0; k < 3; k++) { const int j = slot[indices[4 * t + k]]; if (j >= 0) first[(size_t)j + 1]++; }
+        for (size_t j = 0; j < verts.size(); j++) first[j + 1] += first[j];
+        std::vector<int> next(first.begin(), first.end() - 1), tri((size_t)first.back());
+        for (size_t t = 0; t < nt; t++) for (int k = 0; k < 3; k++) { const int j = slot[indices[4 * t + k]]; if (j >= 0) tri[next[j]++] = (int)t; }
+        d.verts = put(verts.data(), verts.size()); d.num_verts = (int)verts.size();
+        d.corner_first = put(first.data(), first.size());
+        d.corner_tri = put(tri.data(), tri.size());
+    }
+    return RODENT_SCENE_OK;
+}
+
+void rodent_hip_scene_deform_device(int32_t dev, const float* vertices_dev, const float* normals_dev, const float* object_to_world_dev,
+                                    void* stream_) {
+    DevScene& s = instanced_scene(dev, "rodent_hip_scene_deform_device");
+    RenderDevice& r = rdev(dev);
+    DevScene::DeformSet& d = s.deform;
+    if (!vertices_dev) { fprintf(stderr, "rodent_hip: rodent_hip_scene_deform_device: NULL vertices\n"); abort(); }
+    if (!d.ranges || (!normals_dev && !d.smooth)) {
+        fprintf(stderr, "rodent_hip: rodent_hip_scene_deform_device: no deforming set declared (rodent_hip_scene_deform_prepare%s)\n",
+                d.ranges ? " with smooth_normals, or pass normals" : ""); abort(); }
+    HIP_CHECK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)stream_;
+    // behind the last update or move, whichever stream it took; frames need no wait (rodent_hip_scene_refit_device says why)
+    if (s.refit_enqueued) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_refit, 0));
+    const int nv = s.num_vertices;
+    float4* const vertices = reinterpret_cast<float4*>(const_cast<float*>(s.dev.vertices));
+    float4* const normals = reinterpret_cast<float4*>(const_cast<float*>(s.dev.normals));
+    float4* const face_normals = reinterpret_cast<float4*>(const_cast<float*>(s.dev.face_normals));
+    const int4* const indices = reinterpret_cast<const int4*>(s.dev.indices);
+    if (vertices_dev != s.dev.vertices)
+        HIP_CHECK(hipMemcpyAsync(vertices, vertices_dev, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToDevice, stream));
+    if (normals_dev && normals_dev != s.dev.normals)
+        HIP_CHECK(hipMemcpyAsync(normals, normals_dev, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToDevice, stream));
+    const auto blocks = [](int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
+    if (object_to_world_dev)
+        hipLaunchKernelGGL(k_instance_matrices, blocks(12 * s.num_instances), dim3(kBlock), 0, stream, object_to_world_dev,
+                           s.num_instances, s.descs);
+    const DeformTris tris{d.ranges, d.num_listed, d.num_tris};
+    hipLaunchKernelGGL(k_deform_face_normals, blocks(d.num_tris), dim3(kBlock), 0, stream, vertices, indices, tris, face_normals);
+    if (d.num_lights > 0) hipLaunchKernelGGL(k_deform_light_records, blocks(d.num_lights), dim3(kBlock), 0, stream, vertices, indices,
+                                             d.lights, d.num_lights, s.object_lights);
+    if (!normals_dev) hipLaunchKernelGGL(k_deform_smooth_normals, blocks(d.num_verts), dim3(kBlock), 0, stream, face_normals, d.verts,
+                                         d.corner_first, d.corner_tri, d.num_verts, normals);
+    // the listed objects' hierarchies, in the packed allocation: rodent_hip_scene_bvh's pointers stay valid
+    int32_t rc = rodent_hip_refit_objects(dev, s.dev.vertices, nv, s.dev.indices, s.dev.num_tris, const_cast<Node2*>(s.dev.nodes),
+                                          const_cast<Tri1*>(s.dev.tris), s.objects, s.num_objects, d.ranges, d.num_listed, d.num_nodes,
+                                          d.num_tris, d.scratch, d.info, stream);
+    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: refit of the deforming objects refused (%d)\n", rc); abort(); }
+    if (s.dev.tri_shade) hipLaunchKernelGGL(k_deform_tri_shade, blocks(d.num_tris), dim3(kBlock), 0, stream, face_normals, normals,
+                                            indices, tris, const_cast<float4*>(s.dev.tri_shade));
+    // the objects' boxes changed: the TLAS, slot_of and the world lights, as after a move
+    rc = derive_instanced(dev, s, stream);
+    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: top-level rebuild refused (%d)\n", rc); abort(); }
+    HIP_CHECK(hipEventRecord(r.ev_refit, stream));
+    s.refit_enqueued = true; d.enqueued = true;
+}
+
+int32_t rodent_hip_scene_deform_status(int32_t dev, int32_t* refit_info, int32_t* tlas_info) {
+    DevScene& s = instanced_scene(dev, "rodent_hip_scene_deform_status");
+    const DevScene::DeformSet& d = s.deform;
+    int32_t refit[RODENT_BUILD_INFO_WORDS] = {d.num_nodes, d.num_tris, 0, 0}, tlas[RODENT_BUILD_INFO_WORDS] = {};
+    HIP_CHECK(hipSetDevice(dev));
+    if (s.refit_enqueued) HIP_CHECK(hipEventSynchronize(rdev(dev).ev_refit));
+    if (d.enqueued) HIP_CHECK(hipMemcpy(refit, d.info, sizeof(refit), hipMemcpyDeviceToHost));    // before the first: a sound one's words
+    HIP_CHECK(hipMemcpy(tlas, s.tlas_info, sizeof(tlas), hipMemcpyDeviceToHost));
+    if (refit_info) std::copy(refit, refit + RODENT_BUILD_INFO_WORDS, refit_info);
+    if (tlas_info) std::copy(tlas, tlas + RODENT_BUILD_INFO_WORDS, tlas_info);
+    return refit[2] | tlas[2] | (refit[0] < d.num_nodes ? (int32_t)0x80000000u : 0);
 }
 
 void rodent_hip_scene_instances(int32_t dev, RodentSceneInstances* out) {

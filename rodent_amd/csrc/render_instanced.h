@@ -1,6 +1,7 @@
 // render_instanced.h -- instanced scenes in the renderer (include/rodent_render.h, "instanced scenes"; included by render.hip after
 // render_update.h): the stream traversal kernels over the two-level hierarchy and the kernels that derive the scene's tables from the
-// instances' matrices.  CPU model: tests/instanced_scene_model.py.
+// instances' matrices, and the kernels that rederive the tables of deforming objects.  CPU models: tests/instanced_scene_model.py,
+// tests/instanced_deform_model.py.
 #pragma once
 
 // k_trace_instanced<false>: the closest-hit pass over a PrimaryStream; <true>: the shadow pass over a SecondaryStream.  The loop is
@@ -147,4 +148,56 @@ __global__ __launch_bounds__(kBlock) void k_world_lights(const RodentInstanceDes
     const float inv = __fdiv_rn(1.0f, sqrtf(length2(nw[0], nw[1], nw[2])));
     for (int a = 0; a < 3; a++) out.n[a] = __fmul_rn(nw[a], inv);
     lights[l] = out;
+}
+
+// ---- the tables of the deforming objects D (rodent_hip_scene_deform_device): the steps of render_update.h over D's elements alone ------
+// D's triangles are the rows the scene's range table cuts out of the index table (RodentRefitRange: rec_start is the exclusive prefix
+// sum of the listed objects' triangle counts, one Tri1 record per triangle); its vertices and lights come as lists the prepare call
+// built.  Every thread owns what it writes; whatever lies outside D is not written.
+struct DeformTris { const RodentRefitRange* ranges; int num_listed, num_tris; };
+
+// Triangle p of D (p < num_tris) in the index table: the last range whose rec_start is <= p, at most 32 halvings.  The table is the
+// scene's own, checked on the host when it was made.
+__device__ __forceinline__ int deform_tri(const DeformTris& d, int p) {
+    int lo = 0, hi = d.num_listed;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (d.ranges[mid].rec_start <= p) lo = mid; else hi = mid;
+    }
+    return d.ranges[lo].first_tri + (p - d.ranges[lo].rec_start);
+}
+
+__global__ __launch_bounds__(kBlock) void k_deform_face_normals(const float4* __restrict__ vertices, const int4* __restrict__ indices,
+                                                                DeformTris d, float4* __restrict__ face_normals) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= d.num_tris) return;
+    store_face_normal(vertices, indices, deform_tri(d, p), face_normals);
+}
+
+// One thread per bound light of D: bound[j] = {object light, the triangle it is bound to}.
+__global__ __launch_bounds__(kBlock) void k_deform_light_records(const float4* __restrict__ vertices, const int4* __restrict__ indices,
+                                                                 const int2* __restrict__ bound, int num_bound,
+                                                                 RodentLight* object_lights) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= num_bound) return;
+    store_light_record(vertices, indices, bound[j].y, object_lights[bound[j].x]);
+}
+
+// One thread per vertex a triangle of D names: vertex verts[j], its list corner_tri[first[j] .. first[j + 1]) over ALL the scene's
+// triangles (a static triangle that shares the vertex contributes its stored face normal).
+__global__ __launch_bounds__(kBlock) void k_deform_smooth_normals(const float4* __restrict__ face_normals, const int* __restrict__ verts,
+                                                                  const int* __restrict__ first, const int* __restrict__ corner_tri,
+                                                                  int num_verts, float4* __restrict__ normals) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= num_verts) return;
+    const int end = first[j + 1];
+    normals[verts[j]] = smooth_normal(face_normals, corner_tri, first[j], end);
+}
+
+__global__ __launch_bounds__(kBlock) void k_deform_tri_shade(const float4* __restrict__ face_normals, const float4* __restrict__ normals,
+                                                             const int4* __restrict__ indices, DeformTris d,
+                                                             float4* __restrict__ tri_shade) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= d.num_tris) return;
+    store_tri_shade(face_normals, normals, indices, deform_tri(d, p), tri_shade);
 }

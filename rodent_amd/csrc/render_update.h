@@ -23,29 +23,30 @@ __device__ __forceinline__ float length2(float x, float y, float z) {
     return __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
 }
 
-// One thread per triangle: c * (1 / |c|), w = 0.  A degenerate triangle gives NaN, as on the host.
-__global__ __launch_bounds__(kBlock) void k_face_normals(const float4* __restrict__ vertices, const int4* __restrict__ indices,
-                                                         int num_tris, float4* __restrict__ face_normals) {
-    const int t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= num_tris) return;
+// Triangle t's face normal: c * (1 / |c|), w = 0.  A degenerate triangle gives NaN, as on the host.
+__device__ __forceinline__ void store_face_normal(const float4* __restrict__ vertices, const int4* __restrict__ indices, int t,
+                                                  float4* __restrict__ face_normals) {
     float4 v[3];
     const UpdateV3 c = corner_cross(vertices, indices[t], v);
     const float inv = __fdiv_rn(1.0f, sqrtf(length2(c.x, c.y, c.z)));
     face_normals[t] = make_float4(__fmul_rn(c.x, inv), __fmul_rn(c.y, inv), __fmul_rn(c.z, inv), 0.0f);
 }
 
-// One thread per light: corners, normal and 1 / area of the triangle it is bound to (light_tri[k], -1: the light keeps its bytes).  The
-// fourth word of every corner and the colour stay as stored.
-__global__ __launch_bounds__(kBlock) void k_light_records(const float4* __restrict__ vertices, const int4* __restrict__ indices,
-                                                          const int* __restrict__ light_tri, int num_lights, RodentLight* lights) {
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    if (k >= num_lights) return;
-    const int t = light_tri[k];
-    if (t < 0) return;
+// One thread per triangle.
+__global__ __launch_bounds__(kBlock) void k_face_normals(const float4* __restrict__ vertices, const int4* __restrict__ indices,
+                                                         int num_tris, float4* __restrict__ face_normals) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= num_tris) return;
+    store_face_normal(vertices, indices, t, face_normals);
+}
+
+// Light L from the triangle t it is bound to: corners, normal and 1 / area.  The fourth word of every corner and the colour stay as
+// stored.
+__device__ __forceinline__ void store_light_record(const float4* __restrict__ vertices, const int4* __restrict__ indices, int t,
+                                                   RodentLight& L) {
     float4 v[3];
     const UpdateV3 c = corner_cross(vertices, indices[t], v);
     const float l = sqrtf(length2(c.x, c.y, c.z)), inv = __fdiv_rn(1.0f, l);
-    RodentLight& L = lights[k];
     L.v0[0] = v[0].x; L.v0[1] = v[0].y; L.v0[2] = v[0].z;
     L.v1[0] = v[1].x; L.v1[1] = v[1].y; L.v1[2] = v[1].z;
     L.v2[0] = v[2].x; L.v2[1] = v[2].y; L.v2[2] = v[2].z;
@@ -53,16 +54,22 @@ __global__ __launch_bounds__(kBlock) void k_light_records(const float4* __restri
                                                   __fdiv_rn(1.0f, __fmul_rn(0.5f, l)));
 }
 
-// One thread per vertex: the face normals of its corners summed in list order (ascending (triangle, corner)), then the loader's
-// normalisation.  The list of vertex v is corner_tri[first[v] .. first[v + 1]); a triangle that names v twice is in it twice.
-__global__ __launch_bounds__(kBlock) void k_smooth_normals(const float4* __restrict__ face_normals, const int* __restrict__ first,
-                                                           const int* __restrict__ corner_tri, int num_vertices,
-                                                           float4* __restrict__ normals) {
-    const int v = blockIdx.x * kBlock + threadIdx.x;
-    if (v >= num_vertices) return;
+// One thread per light: the record of the triangle it is bound to (light_tri[k], -1: the light keeps its bytes).
+__global__ __launch_bounds__(kBlock) void k_light_records(const float4* __restrict__ vertices, const int4* __restrict__ indices,
+                                                          const int* __restrict__ light_tri, int num_lights, RodentLight* lights) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= num_lights) return;
+    const int t = light_tri[k];
+    if (t < 0) return;
+    store_light_record(vertices, indices, t, lights[k]);
+}
+
+// A vertex's normal from its incidence list corner_tri[begin .. end): the face normals of its corners summed in list order (ascending
+// (triangle, corner)), then the loader's normalisation.  A triangle that names the vertex twice is in the list twice.
+__device__ __forceinline__ float4 smooth_normal(const float4* __restrict__ face_normals, const int* __restrict__ corner_tri, int begin,
+                                                int end) {
     float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-    const int end = first[v + 1];
-    for (int j = first[v]; j < end; j++) {
+    for (int j = begin; j < end; j++) {
         const float4 n = face_normals[corner_tri[j]];
         sx = __fadd_rn(sx, n.x); sy = __fadd_rn(sy, n.y); sz = __fadd_rn(sz, n.z);
     }
@@ -72,20 +79,36 @@ __global__ __launch_bounds__(kBlock) void k_smooth_normals(const float4* __restr
         const float inv = __fdiv_rn(1.0f, sqrtf(l2));
         out = make_float4(__fmul_rn(sx, inv), __fmul_rn(sy, inv), __fmul_rn(sz, inv), 0.0f);
     }
-    normals[v] = out;
+    return out;
 }
 
-// One thread per triangle: the SceneDev::tri_shade record (face normal, then the three corners' vertex normals) as three 16-byte stores.
-__global__ __launch_bounds__(kBlock) void k_tri_shade(const float4* __restrict__ face_normals, const float4* __restrict__ normals,
-                                                      const int4* __restrict__ indices, int num_tris, float4* __restrict__ tri_shade) {
-    const int t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= num_tris) return;
+// One thread per vertex; the list of vertex v is corner_tri[first[v] .. first[v + 1]).
+__global__ __launch_bounds__(kBlock) void k_smooth_normals(const float4* __restrict__ face_normals, const int* __restrict__ first,
+                                                           const int* __restrict__ corner_tri, int num_vertices,
+                                                           float4* __restrict__ normals) {
+    const int v = blockIdx.x * kBlock + threadIdx.x;
+    if (v >= num_vertices) return;
+    const int end = first[v + 1];
+    normals[v] = smooth_normal(face_normals, corner_tri, first[v], end);
+}
+
+// The SceneDev::tri_shade record of triangle t (face normal, then the three corners' vertex normals) as three 16-byte stores.
+__device__ __forceinline__ void store_tri_shade(const float4* __restrict__ face_normals, const float4* __restrict__ normals,
+                                                const int4* __restrict__ indices, int t, float4* __restrict__ tri_shade) {
     const int4 ix = indices[t];
     const float4 f = face_normals[t], a = normals[ix.x], b = normals[ix.y], c = normals[ix.z];
     float4* o = tri_shade + 3 * (size_t)t;
     o[0] = make_float4(f.x, f.y, f.z, a.x);
     o[1] = make_float4(a.y, a.z, b.x, b.y);
     o[2] = make_float4(b.z, c.x, c.y, c.z);
+}
+
+// One thread per triangle.
+__global__ __launch_bounds__(kBlock) void k_tri_shade(const float4* __restrict__ face_normals, const float4* __restrict__ normals,
+                                                      const int4* __restrict__ indices, int num_tris, float4* __restrict__ tri_shade) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= num_tris) return;
+    store_tri_shade(face_normals, normals, indices, t, tri_shade);
 }
 
 // One wave per image (block 0: kSceneTopNodes records, block 1: kPersistTopNodes), the slots' node ids in LDS: the bytes of the host's

@@ -31,6 +31,9 @@ OBJECT = np.dtype([("node_offset", "<i4"), ("tri_offset", "<i4"), ("num_nodes", 
 INSTANCE_DESC = np.dtype([("object_to_world", "<f4", (12,)), ("object", "<i4"), ("instance_id", "<i4"), ("pad", "<i4", (2,))])
 INSTANCE = np.dtype([("world_to_object", "<f4", (12,)), ("node_offset", "<i4"), ("tri_offset", "<i4"), ("instance_id", "<i4"),
                      ("pad", "<i4")])
+REFIT_RANGE = np.dtype([("object", "<i4"), ("first_tri", "<i4"), ("num_tris", "<i4"), ("node_start", "<i4"), ("rec_start", "<i4"),
+                        ("pad", "<i4", (3,))])
+assert REFIT_RANGE.itemsize == 32
 
 assert (NODE2.itemsize, TRI1.itemsize, NODE4.itemsize, NODE8.itemsize, TRI4.itemsize,
         RAY1.itemsize, HIT1.itemsize) == (64, 48, 128, 256, 224, 32, 16)

@@ -5,6 +5,7 @@ include/rodent_instances.h; kernels: csrc/build_tlas.h, csrc/traversal_instanced
     tlas = build_tlas(objects, transforms, object_ids)        # transforms: (n, 12) or (n, 3, 4), row-major object_to_world
     hits, ids = trace(objects, tlas, rays)                    # Hit1 records (tri_id: the object's own prim id) + instance ids
     build_tlas(objects, moved_transforms, object_ids, out=tlas)   # the per-frame path: the objects' hierarchies stay as they are
+    refit_objects(objects, [2, 0], moved_vertices, indices, rows) # geometry moved inside objects 2 and 0: refitted in one launch list
 
 The top-level hierarchy is a pure function of the objects' root boxes, the transforms and max_leaf, byte for byte.
 """
@@ -196,6 +197,62 @@ def download(tlas: Tlas):
     nodes = tlas.nodes[: tlas.num_nodes * F.NODE2.itemsize].cpu().numpy().view(F.NODE2).copy()
     instances = tlas.instances[: tlas.num_instances * F.INSTANCE.itemsize].cpu().numpy().view(F.INSTANCE).copy()
     return nodes, instances
+
+
+# ---- deforming objects: the listed objects of an ObjectSet refitted in place, in one launch list (rodent_hip_refit_objects) ----------
+class RefitPlan:
+    """What refit_objects needs of a list of objects, prepared once: the RodentRefitRange table on the host (`table`,
+    formats.REFIT_RANGE) and on the device (`table_dev`), the listed objects' node and record totals and the scratch bytes."""
+
+    def __init__(self, table, table_dev, num_nodes, num_recs, scratch_bytes):
+        self.table, self.table_dev, self.num_listed = table, table_dev, len(table)
+        self.num_nodes, self.num_recs, self.scratch_bytes = int(num_nodes), int(num_recs), int(scratch_bytes)
+
+
+def plan_refit(objects: ObjectSet, object_ids, ranges) -> RefitPlan:
+    """The plan of refit_objects for the objects `object_ids` (any order) of `objects`; `ranges`: one (first_tri, num_tris) row per
+    listed object, its rows of the concatenated index table (rodent_hip_refit_objects_plan).  An id outside the table is kept: the
+    device flags it."""
+    ids = np.ascontiguousarray(np.clip(np.asarray(object_ids, np.int64).reshape(-1), -1, (1 << 31) - 1).astype(np.int32))
+    rows = np.asarray(ranges, np.int32).reshape(-1, 2)
+    if len(ids) < 1 or len(rows) != len(ids):
+        raise ValueError(f"plan_refit: {len(ids)} object ids and {len(rows)} (first_tri, num_tris) rows")
+    first, count = np.ascontiguousarray(rows[:, 0]), np.ascontiguousarray(rows[:, 1])
+    table, totals = np.zeros(len(ids), F.REFIT_RANGE), np.zeros(2, np.int32)
+    host = np.ascontiguousarray(objects.table)
+    need = abi.lib().rodent_hip_refit_objects_plan(host.ctypes.data, len(host), ids.ctypes.data, first.ctypes.data, count.ctypes.data,
+                                                   len(ids), table.ctypes.data, totals.ctypes.data)
+    if need < 0:
+        raise BuildError("rodent_hip_refit_objects_plan: the listed objects hold more than 2^31 - 1 nodes or records")
+    return RefitPlan(table, abi.to_device(table, objects.dev), totals[0], totals[1], need)
+
+
+def refit_objects(objects: ObjectSet, object_ids, vertices, indices, ranges, stream=None, scratch=None, check=True):
+    """Refits the objects `object_ids` of `objects` in place to moved `vertices` (rodent_hip_refit_objects): new boxes and Tri1 records
+    for the listed objects, the same topologies, every other object's bytes as they are.  `vertices` and `indices` are the concatenated
+    tables of all objects ((n, 3) or (n, 4); tensors on the device are not copied); `ranges` is one (first_tri, num_tris) row per listed
+    object, or a RefitPlan of plan_refit (then `object_ids` is not read and nothing is uploaded).  The launch list does not grow with
+    the list.  Returns the info words ([0] nodes completed over the listed objects, [1] records rewritten, [2] flags); with `check` it
+    raises BuildError on a flag and when a node stayed incomplete.  scratch: a uint8 tensor to reuse, large enough."""
+    _need_gpu()
+    from .gpubuild import _columns4
+    dev, cuda = objects.dev, f"cuda:{objects.dev}"
+    plan = ranges if isinstance(ranges, RefitPlan) else plan_refit(objects, object_ids, ranges)
+    v, ix = _columns4(vertices, torch.float32, dev), _columns4(indices, torch.int32, dev)
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    if scratch is None or scratch.numel() * scratch.element_size() < plan.scratch_bytes:
+        scratch = torch.empty(plan.scratch_bytes, dtype=torch.uint8, device=cuda)
+    info = torch.empty(INFO_WORDS, dtype=torch.int32, device=cuda)
+    entry = "rodent_hip_refit_objects"
+    words = _enqueue(entry, dev, stream, info, (v, ix, scratch, objects.buffer, objects.table_dev, plan.table_dev), v.data_ptr(),
+                     v.shape[0], ix.data_ptr(), ix.shape[0], objects.nodes.data_ptr(), objects.tris.data_ptr(),
+                     objects.table_dev.data_ptr(), objects.num_objects, plan.table_dev.data_ptr(), plan.num_listed, plan.num_nodes,
+                     plan.num_recs, scratch.data_ptr()).copy()
+    if check and words[2]:
+        raise BuildError(f"{entry}: " + ", ".join(s for bit, s in _TLAS_FLAGS if words[2] & bit))
+    if check and words[0] != plan.num_nodes:
+        raise BuildError(f"{entry}: malformed hierarchy ({words[0]} of {plan.num_nodes} nodes completed)")
+    return words
 
 
 # ---- instanced scenes for the renderer (include/rodent_render.h: rodent_hip_scene_create_instanced; render.Renderer(instances=...)) ----

@@ -50,6 +50,7 @@ class SceneInstances(C.Structure):
 # rodent_hip_scene_create_instanced's refusals (RODENT_SCENE_ERR_*)
 SCENE_ERR_COUNTS, SCENE_ERR_RANGES, SCENE_ERR_LIGHT, SCENE_ERR_OBJECT, SCENE_ERR_NO_LIGHT, SCENE_ERR_OPTIONS, SCENE_ERR_TABLE, \
     SCENE_ERR_DEVICE = range(-20, -28, -1)
+SCENE_ERR_NOT_INSTANCED = -28                              # rodent_hip_scene_deform_prepare's own
 SCENE_ERRORS = {SCENE_ERR_COUNTS: "a missing table, a count below 1, more than 2^22 instances, or a hierarchy in the description",
                 SCENE_ERR_RANGES: "the objects' triangle or light ranges do not tile the tables in order",
                 SCENE_ERR_LIGHT: "an emissive triangle names a light outside its object's light range",
@@ -63,7 +64,8 @@ SCENE_ERRORS = {SCENE_ERR_COUNTS: "a missing table, a count below 1, more than 2
 RENDER_EXPORTS = ["rodent_hip_scene_create_instanced", "rodent_hip_scene_create_flags", "rodent_hip_scene_set_transforms",
                   "rodent_hip_scene_transforms_status", "rodent_hip_scene_instances", "rodent_hip_render_sort_in_effect",
                   "rodent_hip_render_trace_persistent_in_effect",
-                  "rodent_hip_scene_create", "rodent_hip_scene_create_device_bvh", "rodent_hip_scene_create_device_bvh_opt",
+                  "rodent_hip_scene_deform_prepare", "rodent_hip_scene_deform_device", "rodent_hip_scene_deform_status",
+                  "rodent_hip_scene_create","rodent_hip_scene_create_device_bvh", "rodent_hip_scene_create_device_bvh_opt",
                   "rodent_hip_scene_create_device_bvh_split", "rodent_hip_scene_create_device_bvh_ploc",
     "rodent_hip_scene_bvh", "rodent_hip_scene_refit", "rodent_hip_scene_destroy",
     "rodent_hip_scene_refit_prepare", "rodent_hip_scene_refit_device", "rodent_hip_scene_refit_status", "rodent_hip_scene_tables",
@@ -117,6 +119,10 @@ def lib():
         l.rodent_hip_scene_set_transforms.argtypes = [i32, vp, vp]; l.rodent_hip_scene_set_transforms.restype = None
         l.rodent_hip_scene_transforms_status.argtypes = [i32, C.POINTER(i32)]; l.rodent_hip_scene_transforms_status.restype = i32
         l.rodent_hip_scene_instances.argtypes = [i32, C.POINTER(SceneInstances)]; l.rodent_hip_scene_instances.restype = None
+        l.rodent_hip_scene_deform_prepare.argtypes = [i32, C.POINTER(i32), i32, i32]; l.rodent_hip_scene_deform_prepare.restype = i32
+        l.rodent_hip_scene_deform_device.argtypes = [i32, vp, vp, vp, vp]; l.rodent_hip_scene_deform_device.restype = None
+        l.rodent_hip_scene_deform_status.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
+        l.rodent_hip_scene_deform_status.restype = i32
         l.rodent_hip_render_sort_in_effect.argtypes = [i32]; l.rodent_hip_render_sort_in_effect.restype = i32
         l.rodent_hip_render_trace_persistent_in_effect.argtypes = [i32]; l.rodent_hip_render_trace_persistent_in_effect.restype = i32
         l.rodent_hip_render_config.argtypes = [i32, i32, i32]; l.rodent_hip_render_config.restype = None
@@ -355,6 +361,62 @@ class Renderer:
             from .instances import _TLAS_FLAGS
             raise gpubuild.BuildError("rodent_hip_scene_set_transforms: " + ", ".join(s for bit, s in _TLAS_FLAGS if flags & bit))
         return flags, list(words)
+
+    def prepare_deform(self, objects, smooth_normals=True):
+        """Declares the deforming set of an instanced scene (rodent_hip_scene_deform_prepare): `objects` are object ids, any order,
+        none twice.  One-time and synchronous: allocates what deform_objects needs (smooth_normals: also what a call without `normals`
+        needs); calling it again replaces the set.  A refusal raises gpubuild.BuildError and leaves the scene as it is."""
+        ids = np.ascontiguousarray(np.clip(np.asarray(objects, np.int64).reshape(-1), -1, (1 << 31) - 1).astype(np.int32))
+        rc = lib().rodent_hip_scene_deform_prepare(self.dev, ids.ctypes.data_as(C.POINTER(i32)), len(ids), int(bool(smooth_normals)))
+        if rc:
+            from . import gpubuild
+            what = {SCENE_ERR_NOT_INSTANCED: "no instanced scene is loaded", SCENE_ERR_COUNTS: "no objects listed",
+                    SCENE_ERR_OBJECT: "an object id outside the table, or one listed twice"}.get(rc, f"status {rc}")
+            raise gpubuild.BuildError(f"rodent_hip_scene_deform_prepare: {what}")
+
+    def deform_objects(self, vertices, normals=None, transforms=None, stream=None, check=True):
+        """The vertices of the deforming objects moved (rodent_hip_scene_deform_device): `vertices` -- and `normals`, or None for smooth
+        normals recomputed for the set's vertices -- are the whole concatenated (num_vertices, 4) float32 tables as tensors on the
+        renderer's device or integer device pointers (the scene's own vertex table, scene_vertices_tensor(), written in place, is
+        copied nowhere); rows no listed object names must equal the scene's.  transforms: None, or the instances' new matrices as for
+        set_transforms -- they move in the same call, with one rebuild of the top-level hierarchy.  The listed objects' face normals,
+        light records, vertex normals, hierarchies and shading records, then the top-level hierarchy, slot_of and the world lights
+        follow on `stream` (a torch stream; None: the current one) with no host copy and no wait; the next frame, on any stream, sees
+        the deformed scene.  check=True waits (deform_status) and raises gpubuild.BuildError on a flag.  The film is not cleared."""
+        import torch
+        stream = torch.cuda.current_stream(self.dev) if stream is None else stream
+        tensors = [t for t in (vertices, normals, transforms) if isinstance(t, torch.Tensor)]
+        pointers = [self._table_pointer(vertices, "vertices"), self._table_pointer(normals, "normals")]
+        if pointers[0] is None:
+            raise ValueError("deform_objects: `vertices` is None")
+        if isinstance(transforms, torch.Tensor):
+            t = transforms
+            if (not t.is_cuda or t.device.index != self.dev or t.dtype != torch.float32 or t.numel() != 12 * self.num_instances
+                    or not t.is_contiguous()):
+                raise ValueError(f"deform_objects: `transforms` must be a contiguous float32 tensor of {self.num_instances} x 12 entries "
+                                 f"on cuda:{self.dev} (or an integer device pointer)")
+            pointers.append(t.data_ptr())
+        else:
+            pointers.append(transforms)
+        if tensors:
+            stream.wait_stream(torch.cuda.current_stream(self.dev))          # the tensors may come from there
+        lib().rodent_hip_scene_deform_device(self.dev, *pointers, C.c_void_p(stream.cuda_stream))
+        for t in tensors:
+            t.record_stream(stream)
+        if check:
+            self.deform_status(raise_on_flag=True)
+
+    def deform_status(self, raise_on_flag=False):
+        """(flags, refit info words, TLAS info words) of the last deform_objects, once it has finished: flags 0 = sound (the refit's
+        flags | the top-level build's; bit 31: nodes the refit could not complete)."""
+        refit, tlas = (i32 * 4)(), (i32 * 4)()
+        flags = lib().rodent_hip_scene_deform_status(self.dev, refit, tlas)
+        if flags and raise_on_flag:
+            from . import gpubuild
+            from .instances import _TLAS_FLAGS
+            raise gpubuild.BuildError("rodent_hip_scene_deform_device: " + (", ".join(s for bit, s in _TLAS_FLAGS if flags & bit)
+                                      or f"malformed hierarchy ({refit[0]} nodes completed)"))
+        return flags, list(refit), list(tlas)
 
     def instance_pointers(self):
         """Device pointers (integers) and counts of an instanced scene's tables (rodent_hip_scene_instances)."""
