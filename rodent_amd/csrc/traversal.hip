@@ -300,18 +300,21 @@ __device__ __forceinline__ void bvh2_step(Lane& L, const Bases& base, Hit1* __re
         const bool h0 = slab_canonical<OCT>(L.ray, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, te0, splat) && ch.x != 0;
         const bool h1 = slab_canonical<OCT>(L.ray, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, te1, splat) && ch.y != 0;
         const bool c0first = te0 < te1, both = h0 && h1;
+        // (Five v_cndmask_b32 for the push and the new top.  ONE lane mask, first0 = h0 && (!h1 || c0first), gives the same values with
+        // three -- push first0 ? ch.y : ch.x, top (h0 || h1) ? (first0 ? ch.x : ch.y) : popped -- once the masks are combined on the scalar
+        // unit (ballots of the five compares, s_and / s_orn2 / s_or, inverse ballots): node-only iteration 37 -> 35 VALU.  Measured, it
+        // LOSES 1 % on the benchmark launch, alone and beside the two changes below: the selects then wait for a chain of three dependent
+        // scalar instructions behind the last compare.  LAB_NOTES 18.)
         L.sp[kWave] = c0first ? ch.y : ch.x;
         L.top = both ? (c0first ? ch.x : ch.y) : (h0 ? ch.x : (h1 ? ch.y : popped));
         L.sp += (both ? kWave : 0) - ((h0 || h1) ? 0 : kWave);
-        if (both && L.sp >= sp_limit) {                                 // (`both`: popping the sentinel moves sp below col, which wraps)
-            // deeper than the LDS window: the oldest entries move out
-            if constexpr (SPILL > 0) stack_spill<SPILL>(L.sp, L.top, sp_limit, spill, WPG, &ctl->err, &ctl->stats[7]);
-            else {                                                      // ... or k_bvh2_finish redoes this ray
-                deep_list[atomicAdd(&ctl->deep_count, 1)] = L.ray_id;
-                L.top = 0;
-                if (LAZY) L.found = true;                               // its record is the follow-up pass's business
-                if (FENCE) __threadfence();
-            }
+        // deeper than the LDS window?  (`both`: popping the sentinel moves sp below col, which wraps)  SPILL > 0: the oldest entries move
+        // out, in the cold block below ...
+        if constexpr (SPILL == 0) if (both && L.sp >= sp_limit) {       // ... or k_bvh2_finish redoes this ray
+            deep_list[atomicAdd(&ctl->deep_count, 1)] = L.ray_id;
+            L.top = 0;
+            if (LAZY) L.found = true;                                   // its record is the follow-up pass's business
+            if (FENCE) __threadfence();
         }
     } else {
         const int prim_id = __float_as_int(q2.w);
@@ -333,8 +336,23 @@ __device__ __forceinline__ void bvh2_step(Lane& L, const Bases& base, Hit1* __re
         L.top = (ANY && found) ? 0 : (leave ? popped : L.top - 1);    // top - 1 == ~(j + 1)
         L.sp -= (leave && !(ANY && found)) ? kWave : 0;
     }
-    // popped row 0 while entries are out: they come back
-    if constexpr (SPILL > 0) if (L.top >= kSpillMark) stack_reload<SPILL>(L.sp, L.top, sp_limit, spill, WPG);
+    if constexpr (SPILL > 0) {
+        // The two rare stack events behind ONE wave-uniform branch: a lane whose push filled row SPILL of its window (sp == sp_limit), and
+        // a lane that popped row 0 while entries are out, which come back (its new top is the mark).  No lane meets both in one step -- the
+        // one has pushed a child and goes on with the other, the other has popped -- and a lane that has spilled holds a child id or 0,
+        // never the mark.  (Tested one after the other, each paid a compare, an exec save, a taken branch and an exec restore in every
+        // iteration.)  The cursor is compared as a SIGNED LDS address: a lane that popped the sentinel stands one row below its column,
+        // which wraps below zero for the first wave's window, and nothing but a push moves a cursor up to the limit -- so the compare
+        // needs no `both`, holds for a triangle lane as well, and is one plain compare whose wave mask the scalar unit can OR and test
+        // (the ballot of anything but a compare goes through a 0 / 1 VGPR).
+        const unsigned long long spills = __builtin_amdgcn_ballot_w64((int)(size_t)L.sp >= (int)(size_t)sp_limit);
+        const unsigned long long reloads = __builtin_amdgcn_ballot_w64(L.top >= kSpillMark);
+        if (__builtin_expect((spills | reloads) != 0ull, 0)) {
+            if (__builtin_amdgcn_inverse_ballot_w64(spills))
+                stack_spill<SPILL, true>(L.sp, L.top, sp_limit, spill, WPG, &ctl->err, &ctl->stats[7]);
+            else if (__builtin_amdgcn_inverse_ballot_w64(reloads)) stack_reload<SPILL, true>(L.sp, L.top, sp_limit, spill, WPG);
+        }
+    }
 }
 
 // A fresh ray: loads it, stores the miss record, empty stack (col[0] = the 0 that ends the traversal when popped).

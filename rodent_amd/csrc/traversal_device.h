@@ -177,8 +177,13 @@ constexpr int kSpillWaveInts = kSpillRows * kSpillBlocks * kWave;       // 12 54
 // + WINDOW rows, which the step compares against anyway), the launch's spill buffer and the workgroup's wave count -- and derive the rest
 // behind an opaque barrier: computed outside, the column base and the 64-bit address of the lane's spill words would be three more VGPRs
 // carried around a loop that is compiled under a 64-VGPR budget (measured: +2 ... 3 % on the benchmark launches).
+// HERE (bvh2_step's cold block): the lane id is computed on the rare path, from an opaque mask -- loop-invariant, it is hoisted in front of the
+// caller's loops, where k_bvh2_top_auto's any-hit kernel has no register left for it and reloaded it from scratch inside the block.
+template <bool HERE = false>
 __device__ __forceinline__ int* spill_words(int* __restrict__ spill, int waves_per_group) {
-    unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    unsigned all = ~0u;
+    if (HERE) asm volatile("" : "+s"(all));
+    unsigned lane = __builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
     // the wave's slot in the resident grid
     int slot = (int)blockIdx.x * waves_per_group + __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
     asm volatile("" : "+v"(lane), "+s"(slot));
@@ -192,7 +197,7 @@ __device__ __forceinline__ lds_int* window_base(lds_int* limit) {
 }
 // Called by a lane whose push filled row WINDOW (sp == limit).  `events` (may be null): a counter of blocks moved out, for the tests and
 // the per-scene reports (one atomic per block).
-template <int WINDOW>
+template <int WINDOW, bool HERE = false>
 __device__ __forceinline__ void stack_spill(lds_int*& sp, int& top, lds_int* limit, int* __restrict__ spill, int waves_per_group, int* err,
     unsigned long long* events = nullptr) {
     static_assert(WINDOW > kSpillRows + 1, "something must stay in the window");
@@ -201,7 +206,7 @@ __device__ __forceinline__ void stack_spill(lds_int*& sp, int& top, lds_int* lim
     // more than the reference's 64 slots: the host reports it
     if (blocks >= kSpillBlocks) { __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); top = 0; return; }
     if (events) atomicAdd(events, 1ull);
-    int* g = spill_words(spill, waves_per_group) + blocks * kSpillRows * kWave;
+    int* g = spill_words<HERE>(spill, waves_per_group) + blocks * kSpillRows * kWave;
 #pragma unroll 1
     for (int j = 0; j < kSpillRows; j++) g[j * kWave] = col[(1 + j) * kWave];
 #pragma unroll 1
@@ -213,11 +218,11 @@ __device__ __forceinline__ void stack_spill(lds_int*& sp, int& top, lds_int* lim
 // comes back into rows 1..kSpillRows - 1, its newest entry is the new top.  (Measured beside the alternative -- testing the word UNDER the
 // cursor at the start of the step, off the dependency chain: 0.1857 against 0.1872 ms on the benchmark launch,
 // profiles/r05_spill_experiment.txt.)
-template <int WINDOW>
+template <int WINDOW, bool HERE = false>
 __device__ __forceinline__ void stack_reload(lds_int*& sp, int& top, lds_int* limit, int* __restrict__ spill, int waves_per_group) {
     lds_int* const col = window_base<WINDOW>(limit);
     const int blocks = top - kSpillMark;                                // >= 1
-    const int* g = spill_words(spill, waves_per_group) + (blocks - 1) * kSpillRows * kWave;
+    const int* g = spill_words<HERE>(spill, waves_per_group) + (blocks - 1) * kSpillRows * kWave;
 #pragma unroll 1
     for (int j = 0; j < kSpillRows - 1; j++) col[(1 + j) * kWave] = g[j * kWave];
     top = g[(kSpillRows - 1) * kWave];

@@ -443,10 +443,10 @@ __device__ __forceinline__ int chunk_octant(const Lane& L) {
 template <bool ANY, bool LAZY, int LDS_N, int WAVES, int OCT, bool OFFS>
 __device__ __forceinline__ void trace_chunk(Lane& L, const Bases& base, Hit1* __restrict__ hits, lds_int* sp_limit, Ctl* ctl,
     int* __restrict__ deep_list, lds_int* image, int* __restrict__ spill, const RaySplat* splat, const RecordOffsets* offs) {
-    while (__ballot(L.top != 0)) {
-        if (L.top != 0) bvh2_step<ANY, false, true, LAZY, false, false, LDS_N, WAVES, OCT, OFFS>(L, base, hits, sp_limit, ctl, deep_list,
-            false, nullptr, image, nullptr, spill, splat, offs);
-    }
+    // Per lane: a lane that has finished leaves exec until the chunk's last lane has (the step's ballots are relative to exec).  As
+    // `while (__ballot(top != 0)) if (top != 0) step` the same loop carried two copies of `top` and three branches per iteration.
+    while (L.top != 0) bvh2_step<ANY, false, true, LAZY, false, false, LDS_N, WAVES, OCT, OFFS>(L, base, hits, sp_limit, ctl, deep_list,
+        false, nullptr, image, nullptr, spill, splat, offs);
 }
 
 // The default from round 4 on: ONE persistent kernel that chooses per wave between the two loop forms above (compaction
