@@ -28,7 +28,13 @@
  *   fminf / fmaxf over the corners, as v + 0 (one bit pattern for a zero).  Each bound is then moved outward by
  *   e = 2^-21 * (((|m0|*X + |m1|*Y) + |m2|*Z) + |m3|), X = fmaxf(|lo_x|, |hi_x|) and so on: lo - e, hi + e.  The rounding error of the
  *   four-term sum is at most gamma_4 ~ 2^-22 times the sum of magnitudes and the factor 2 covers computing e itself in fp32, so the
- *   widened box contains the exact image of the object box.
+ *   widened box contains the exact image of the object box -- on this domain: no product m_k * c and no partial sum of the four-term
+ *   row sum is a non-zero value below 2^-126 in magnitude (none is rounded as a denormal), and nothing overflows.  The bound is a
+ *   relative one and has no room for the absolute rounding error of a denormal (up to 2^-150 per operation): outside the domain the
+ *   box may miss a corner by that much.  (Observed in exact arithmetic on random matrices and boxes: with entries and coordinates
+ *   around 1e-22 and no translation nearly every box misses a corner; at scales from 1e-18 to 1e15 no failure was found, which is
+ *   an observation, not membership of the domain -- a coordinate near 0 can underflow a product at any scale.
+ *   tests/test_instance_edge_fixtures.py pins one case on each side.)
  * TLAS build: the sort point of an instance is lo + hi of its world box per axis; from there the LBVH stages of rodent_build.h as they
  *   stand: frame, 30-bit Morton codes, stable radix sort (code, then instance index), Karras, renumbering, bottom-up boxes, emission;
  *   the single-leaf root for num_instances <= max_leaf.  RodentInstance k is the k-th instance in that order: world_to_object, the

@@ -199,6 +199,20 @@ def _object_rays(inst, rays):
     return org.astype(F32), direction.astype(F32)
 
 
+# Three decisions of the walk, as functions of their own so that a test can replace one and see the expectations change
+# (tests/test_instance_edge_fixtures.py).
+def _child0_first(entry0, entry1):
+    return entry0 < entry1                                              # strict <: a tie goes into child 1 (mapping_gpu.impala:128-129)
+
+
+def _instance_tmax(tmax, hit_inst):
+    return F32(tmax)                                                    # the current tmax as it is: acceptance stays <= across instances
+
+
+def _miss_t(tmax):
+    return tmax                                                         # the ray's tmax bit for bit, a signalling NaN included
+
+
 def _walk(oracle, tlas, inst, nodes, tris, rays, any_hit, want_peak):
     rays = np.ascontiguousarray(rays)
     hits = np.zeros(len(rays), F.HIT1)
@@ -214,7 +228,7 @@ def _walk(oracle, tlas, inst, nodes, tris, rays, any_hit, want_peak):
         o_org, o_dir = _object_rays(inst, part)
         entry, far = entry.tolist(), far.tolist()
         for k in range(len(part)):
-            tmax, hit, hit_inst, peak = float(part[k]["tmax"]), (-1, part[k]["tmax"], F32(0), F32(0)), -1, 0
+            tmax, hit, hit_inst, peak = float(part[k]["tmax"]), (-1, _miss_t(part[k]["tmax"]), F32(0), F32(0)), -1, 0
             mem, ptr, top, done = {0: 0}, 0, 1, False
             while top != 0 and not done:
                 n = top - 1
@@ -222,7 +236,7 @@ def _walk(oracle, tlas, inst, nodes, tris, rays, any_hit, want_peak):
                 if not h[0] and not h[1]:
                     top = mem[ptr]; ptr -= 1
                 elif h[0] and h[1]:
-                    c0first = entry[k][n][0] < entry[k][n][1]
+                    c0first = _child0_first(entry[k][n][0], entry[k][n][1])
                     top = child[n][0 if c0first else 1]
                     ptr += 1; mem[ptr] = child[n][1 if c0first else 0]
                 else:
@@ -230,7 +244,7 @@ def _walk(oracle, tlas, inst, nodes, tris, rays, any_hit, want_peak):
                 while top < 0:                                       # a leaf: its continuation stays on the stack (ptr entries held)
                     j = ~top
                     while True:
-                        one["org"], one["dir"], one["tmin"], one["tmax"] = o_org[k, j], o_dir[k, j], part[k]["tmin"], F32(tmax)
+                        one["org"], one["dir"], one["tmin"], one["tmax"] = o_org[k, j], o_dir[k, j], part[k]["tmin"], _instance_tmax(tmax, hit_inst)
                         on, ot = nodes[inst["node_offset"][j]:], tris[inst["tri_offset"][j]:]
                         if want_peak:
                             peak = max(peak, ptr + int(oracle.ray_depths(on, ot, one, any_hit=any_hit)[0]))
