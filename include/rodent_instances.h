@@ -146,6 +146,60 @@ int32_t rodent_hip_refit_objects(int32_t dev, const float* vertices, int32_t num
                                  const struct RodentRefitRange* ranges, int32_t num_listed, int32_t total_nodes, int32_t total_recs,
                                  void* scratch, int32_t* info_dev, void* stream);
 
+/* ---- build of the objects' hierarchies: all objects of a new set, or a chosen subset of a packed one, in one launch list ----
+ * The forest form of rodent_hip_build_bvh2_tri1 (rodent_build.h): for every listed object the Node2 / Tri1 records are, byte for byte,
+ * those rodent_hip_build_bvh2_tri1 writes for that object alone over indices + 4 * first_tri, num_tris rows and max_leaf -- the object's
+ * own frame, the order (code, row), Karras' ties by the object's own sorted positions, child ids, leaf starts and prim ids object-local.
+ * One RodentRefitRange per listed object, with node_start == rec_start == the exclusive prefix sum of the listed objects' num_tris in list
+ * order (rodent_hip_build_objects_plan writes them).  No treelet passes, no pre-splitting, no PLOC.
+ *
+ * mode RODENT_BUILD_OBJECTS_PACK: the device writes the whole RodentObject of every listed object: node_offset = the sum of num_nodes of
+ *   the objects listed before it, tri_offset = rec_start, num_nodes, num_tris.  `nodes` needs room for the sum of max(1, num_tris - 1),
+ *   `tris` for total_tris.  With the list 0 .. K - 1 the table and the records are a tight packed set (instances.pack_objects).
+ * mode RODENT_BUILD_OBJECTS_IN_PLACE: the device reads node_offset, tri_offset and num_tris of each listed object from the table and
+ *   writes only num_nodes; the caller guarantees a node slot of max(1, num_tris - 1) records at node_offset.  Bytes of a slot beyond
+ *   num_nodes and every record of an unlisted object keep their contents; the result does not depend on the list's order.
+ * object_info[4 j ..] = {Node2 count, depth, flags, 0} of listed object j; info_dev = {total nodes, largest depth, OR of the flags, 0}.
+ *
+ * Flags: a range with an object id outside the table raises RODENT_TLAS_BAD_OBJECT; a range whose rows leave the index table, whose
+ * stretch [rec_start, + num_tris) leaves total_tris, whose node_start differs from its rec_start or (in place) whose num_tris differs
+ * from the table's (or whose table offsets are negative) raises RODENT_BUILD_BAD_TOPOLOGY; nothing of a refused range is touched, its
+ * node count is 0.  RODENT_BUILD_BAD_INDEX / RODENT_BUILD_NON_FINITE inside one object land in that object's info words (and in
+ * info_dev[2]); the other objects come out complete and correct.  Other faults of the range table (wrong prefix sums, an object listed
+ * twice) leave bytes undefined inside the listed objects and may raise RODENT_BUILD_BAD_TOPOLOGY; nothing is read or written beyond the
+ * totals, the node room or the objects. */
+#define RODENT_BUILD_OBJECTS_IN_PLACE    0
+#define RODENT_BUILD_OBJECTS_PACK        1
+#define RODENT_BUILD_OBJECTS_MAX_LISTED  (1 << 20)
+
+/* Fills ranges[0 .. num_listed) on the HOST from host arrays: the listed object ids (any order) and, per listed object, its first row and
+ * row count in the index table.  totals[0]: the listed triangles.  Returns the bytes of device scratch rodent_hip_build_objects needs (any
+ * 256-byte aligned buffer, its contents are ignored), or -1 for a NULL pointer, num_listed outside [1, 2^20], a row count < 1 or more than
+ * 2^25 listed triangles. */
+int64_t rodent_hip_build_objects_plan(const int32_t* listed, const int32_t* first_tri, const int32_t* num_tris, int32_t num_listed,
+                                      struct RodentRefitRange* ranges, int32_t* totals);
+
+/* All pointers are DEVICE pointers: vertices (num_vertices float4 rows), indices (num_rows int4 rows; the concatenated tables),
+ * nodes / tris (the packed arrays), objects (num_objects RodentObject), ranges (num_listed RodentRefitRange), scratch (the plan's bytes), object_info
+ * (4 ints per listed object), info_dev (RODENT_BUILD_INFO_WORDS ints); both info arrays are written by the call.  Asynchronous on `stream`
+ * like every builder: nothing is allocated, nothing waits for the device, and the launch list depends on num_listed only through the
+ * ceil(log2(num_listed) / 8) extra sort passes.  Checks, in this order, each enqueuing nothing when it fails: RODENT_BUILD_ERR_NUM_TRIS
+ * (num_rows outside [1, 2^25]), RODENT_BUILD_ERR_NUM_VERTICES, RODENT_TLAS_ERR_NUM_OBJECTS, RODENT_BUILD_ERR_NUM_NODES (num_listed outside
+ * [1, 2^20], total_tris outside [1, 2^25]), RODENT_BUILD_ERR_MAX_LEAF, RODENT_BUILD_ERR_INPUT (an unknown mode), RODENT_BUILD_ERR_NULL,
+ * RODENT_BUILD_ERR_DEVICE. */
+int32_t rodent_hip_build_objects(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_rows,
+                                 int32_t max_leaf, int32_t mode, struct Node2* nodes, struct Tri1* tris, struct RodentObject* objects,
+                                 int32_t num_objects, const struct RodentRefitRange* ranges, int32_t num_listed, int32_t total_tris,
+                                 void* scratch, int32_t* object_info, int32_t* info_dev, void* stream);
+
+/* Synchronous form on the null stream with its own scratch: copies both info arrays to the host (object_info: 4 ints per listed object,
+ * info: RODENT_BUILD_INFO_WORDS ints; either may be NULL) and returns RODENT_BUILD_ERR_INPUT when the device raised a flag.  It checks
+ * RODENT_BUILD_ERR_NUM_NODES and RODENT_BUILD_ERR_DEVICE first (it sizes and allocates the scratch), then as above. */
+int32_t rodent_hip_build_objects_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_rows,
+                                      int32_t max_leaf, int32_t mode, struct Node2* nodes, struct Tri1* tris,
+                                      struct RodentObject* objects, int32_t num_objects, const struct RodentRefitRange* ranges,
+                                      int32_t num_listed, int32_t total_tris, int32_t* object_info, int32_t* info);
+
 /* Traces num_rays rays through the TLAS and the objects below it. DEVICE pointers; hit_instances (one int32_t per ray) may be NULL.
  * Enqueued on `stream` without synchronising, like hip_traverse_bvh2_tri1_async; a stack overflow is reported by
  * rodent_hip_check_errors(dev, stream). */

@@ -54,6 +54,7 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "rodent_hip_tlas_scratch_bytes", "rodent_hip_build_tlas", "rodent_hip_build_tlas_sync",
     "hip_traverse_instanced_bvh2_tri1_async", "hip_intersect_instanced_bvh2_tri1", "hip_occluded_instanced_bvh2_tri1",
     "rodent_hip_refit_objects_plan", "rodent_hip_refit_objects",
+    "rodent_hip_build_objects_plan", "rodent_hip_build_objects", "rodent_hip_build_objects_sync",
 ]
 BLOCK_OF_WIDTH = {2: F.BVH2_TRI1, 4: F.BVH4_TRI4, 8: F.BVH8_TRI4}
 
@@ -172,6 +173,12 @@ def lib():
         l.rodent_hip_refit_objects_plan.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp]
         l.rodent_hip_refit_objects.restype = i32
         l.rodent_hip_refit_objects.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]
+        l.rodent_hip_build_objects_plan.restype = C.c_int64
+        l.rodent_hip_build_objects_plan.argtypes = [vp, vp, vp, i32, vp, vp]
+        l.rodent_hip_build_objects.restype = i32
+        l.rodent_hip_build_objects.argtypes = [i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
+        l.rodent_hip_build_objects_sync.restype = i32
+        l.rodent_hip_build_objects_sync.argtypes = [i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp]
         _lib = l
     return _lib
 

@@ -39,6 +39,9 @@
 // Node4 / Node8 + Tri4 (k_refit_wide_links, k_refit_tri4, k_refit_wide_climb; CPU model: tests/refit_wide_model.py).
 // rodent_hip_refit_objects (include/rodent_instances.h) refits a listed subset of the packed objects of an instanced scene in the same
 // three launches, whatever their number (k_forest_links, k_forest_tris, k_forest_climb).
+// rodent_hip_build_objects (build_forest.h; CPU model: tests/forest_build_model.py) BUILDS a listed subset of the packed objects, or all
+// objects of a new set, in one launch list whatever their number: the LBVH's stages over the objects' triangles laid end to end
+// (k_bf_*), each object in its own frame, sorted by (list rank, code, row), every Karras position object-local.
 // Collapse (build_collapse.h, rodent_hip_collapse_bvh2_tri1): any BVH2 / Tri1 becomes Node4 / Node8 + Tri4 by bounded walks per node,
 // no thread waiting for another (CPU model: tests/collapse_model.py); rodent_hip_collapse_bvh2_tri1_bounded: the same under a stack limit
 // (tests/collapse_bounded_model.py).
@@ -182,6 +185,36 @@ TlasScratch carve_tlas(char* base, int n) {
     return t;
 }
 
+struct ForestBuildScratch {
+    uint32_t *keys[2], *vals[2];
+    uint32_t* hist;               // 256 x radix tiles (digit-major), scanned in place
+    uint32_t *code0, *codes;      // per unsorted / per sorted position: its Morton code
+    float4* cent;                 // per unsorted position: centroid sum (w unused)
+    float* leafbox;               // per sorted position
+    int *first, *last, *split, *parent, *leaf_parent, *height;    // per position: the object's Karras node of that local index
+    uint32_t* gidx;               // per position: kept nodes in front of it, over all objects
+    float* box;                   // per position, as leafbox
+    uint32_t* arrivals;           // per position (zeroed for every call)
+    uint32_t* blockcount;         // kept nodes per block of k_bf_karras, scanned in place
+    uint32_t* fbounds;            // 6 per listed object
+    uint32_t* objnodes;           // per listed object
+    size_t bytes;
+};
+
+ForestBuildScratch carve_forest_build(char* base, int total_tris, int num_listed) {
+    ForestBuildScratch s{};
+    Carver c{base};
+    const size_t N = (size_t)total_tris, K = (size_t)num_listed;
+    for (int k = 0; k < 2; k++) { c.take(s.keys[k], N); c.take(s.vals[k], N); }
+    c.take(s.hist, 256 * (size_t)radix_tiles(total_tris)); c.take(s.code0, N); c.take(s.codes, N); c.take(s.cent, N);
+    c.take(s.leafbox, 6 * N);
+    c.take(s.first, N); c.take(s.last, N); c.take(s.split, N); c.take(s.parent, N); c.take(s.leaf_parent, N); c.take(s.height, N);
+    c.take(s.gidx, N); c.take(s.box, 6 * N); c.take(s.arrivals, N); c.take(s.blockcount, (N + kBlock - 1) / kBlock);
+    c.take(s.fbounds, 6 * K); c.take(s.objnodes, K);
+    s.bytes = c.bytes;
+    return s;
+}
+
 struct PlocScratch {
     float4* clusters[2];          // per position, the two cluster buffers: a 32-byte record (build_ploc.h: PlocCluster)
     int* nn;                      // per position
@@ -206,6 +239,7 @@ PlocScratch carve_ploc(char* base, int max_refs) {
 #include "build_split.h"
 #include "build_ploc.h"
 #include "build_refit.h"
+#include "build_forest.h"
 #include "build_collapse.h"
 
 inline int blocks_for(long long items) { return (int)((items + kBlock - 1) / kBlock); }
@@ -485,6 +519,49 @@ int32_t launch_refit_objects(const float* vertices, int nv, const int32_t* indic
     if (a.total_nodes > 0)
         hipLaunchKernelGGL(k_forest_climb, dim3(blocks_for(a.total_nodes)), dim3(kBlock), 0, stream, nodes, tris, a, s.tribox, s.parent,
                            s.arrivals, info_dev);
+    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
+// The build of the listed objects after its argument checks (build_forest.h): the info words and the arrival counters zeroed, then the
+// LBVH's list over the listed objects' triangles laid end to end.  The list depends on the number of listed objects only through the
+// rank passes of the sort: ceil(log2(num_listed) / 8) of them, none for one object.
+int32_t launch_build_objects(const float* vertices, int nv, const int32_t* indices, Node2* nodes, Tri1* tris, BuildForest a, void* scratch,
+                             void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int T = a.total_tris, K = a.num_listed, tb = blocks_for(T), kb = blocks_for(K), tiles = radix_tiles(T);
+    const ForestBuildScratch s = carve_forest_build(static_cast<char*>(scratch), T, K);
+    a.fbounds = s.fbounds; a.objnodes = s.objnodes;
+    const float4* v4 = reinterpret_cast<const float4*>(vertices);
+    const int4* i4 = reinterpret_cast<const int4*>(indices);
+    if (hipMemsetAsync(a.info, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess
+        || hipMemsetAsync(s.arrivals, 0, 4 * (size_t)T, stream) != hipSuccess)
+        return RODENT_BUILD_ERR_LAUNCH;
+    hipLaunchKernelGGL(k_bf_begin, dim3(kb), dim3(kBlock), 0, stream, a);
+    hipLaunchKernelGGL(k_bf_centroids, dim3(tb), dim3(kBlock), 0, stream, v4, nv, i4, a, s.cent);
+    hipLaunchKernelGGL(k_bf_morton, dim3(tb), dim3(kBlock), 0, stream, a, s.cent, s.code0, s.keys[0], s.vals[0]);
+    int cur = 0;
+    const auto radix_pass = [&](int shift) {
+        hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(kBlock), 0, stream, s.keys[cur], T, shift, s.hist, (const int*)nullptr);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.hist, 256 * tiles, (int*)nullptr);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(kBlock), 0, stream, s.keys[cur], s.vals[cur], s.keys[cur ^ 1],
+                           s.vals[cur ^ 1], s.hist, T, shift, (const int*)nullptr);
+        cur ^= 1;
+    };
+    for (int pass = 0; pass < 4; pass++) radix_pass(8 * pass);           // by code: ties stay in (rank, row) order
+    const int rank_passes = (host_clog2(K) + 7) / 8;
+    if (rank_passes > 0) hipLaunchKernelGGL(k_bf_rank_keys, dim3(tb), dim3(kBlock), 0, stream, a, s.vals[cur], s.keys[cur]);
+    for (int pass = 0; pass < rank_passes; pass++) radix_pass(8 * pass); // then, stably, by list rank
+    hipLaunchKernelGGL(k_bf_leaves, dim3(tb), dim3(kBlock), 0, stream, v4, nv, i4, a, s.vals[cur], s.code0, tris, s.leafbox, s.codes);
+    hipLaunchKernelGGL(k_bf_karras, dim3(tb), dim3(kBlock), 0, stream, a, s.codes, s.first, s.last, s.split, s.parent, s.leaf_parent,
+                       s.blockcount);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.blockcount, tb, (int*)nullptr);
+    hipLaunchKernelGGL(k_bf_renumber, dim3(tb), dim3(kBlock), 0, stream, a, s.first, s.last, s.blockcount, s.gidx);
+    hipLaunchKernelGGL(k_bf_counts, dim3(kb), dim3(kBlock), 0, stream, a, s.gidx);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, stream, s.objnodes, K, a.info + kInfoNodes);
+    hipLaunchKernelGGL(k_bf_bottom_up, dim3(tb), dim3(kBlock), 0, stream, a, s.first, s.last, s.split, s.parent, s.leaf_parent,
+                       s.leafbox, s.box, s.height, s.arrivals);
+    hipLaunchKernelGGL(k_bf_emit, dim3(tb), dim3(kBlock), 0, stream, a, s.first, s.last, s.split, s.gidx, s.leafbox, s.box, nodes, tris);
+    hipLaunchKernelGGL(k_bf_objects, dim3(kb), dim3(kBlock), 0, stream, a, s.leafbox, s.box, nodes, tris);
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
 }
 
@@ -907,6 +984,64 @@ int32_t rodent_hip_refit_objects(int32_t dev, const float* vertices, int32_t num
     if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
     const ForestArgs a{objects, ranges, num_objects, num_listed, total_nodes, total_recs, num_rows};
     return launch_refit_objects(vertices, num_vertices, indices, nodes, tris, a, scratch, info_dev, stream);
+}
+
+int64_t rodent_hip_build_objects_plan(const int32_t* listed, const int32_t* first_tri, const int32_t* num_tris, int32_t num_listed,
+                                      struct RodentRefitRange* ranges, int32_t* totals) {
+    if (!listed || !first_tri || !num_tris || !ranges || !totals || num_listed < 1 || num_listed > RODENT_BUILD_OBJECTS_MAX_LISTED)
+        return -1;
+    int64_t tris = 0;
+    for (int32_t k = 0; k < num_listed; k++) {
+        if (num_tris[k] < 1) return -1;
+        ranges[k] = RodentRefitRange{listed[k], first_tri[k], num_tris[k], (int32_t)tris, (int32_t)tris, {0, 0, 0}};
+        tris += num_tris[k];
+        if (tris > kMaxTris) return -1;
+    }
+    totals[0] = (int32_t)tris;
+    return (int64_t)carve_forest_build(nullptr, (int)tris, num_listed).bytes;
+}
+
+int32_t rodent_hip_build_objects(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_rows,
+                                 int32_t max_leaf, int32_t mode, struct Node2* nodes, struct Tri1* tris, struct RodentObject* objects,
+                                 int32_t num_objects, const struct RodentRefitRange* ranges, int32_t num_listed, int32_t total_tris,
+                                 void* scratch, int32_t* object_info, int32_t* info_dev, void* stream) {
+    if (bad_num_tris(num_rows)) return RODENT_BUILD_ERR_NUM_TRIS;
+    if (num_vertices < 1) return RODENT_BUILD_ERR_NUM_VERTICES;
+    if (num_objects < 1) return RODENT_TLAS_ERR_NUM_OBJECTS;
+    if (num_listed < 1 || num_listed > RODENT_BUILD_OBJECTS_MAX_LISTED || bad_num_tris(total_tris)) return RODENT_BUILD_ERR_NUM_NODES;
+    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) return RODENT_BUILD_ERR_MAX_LEAF;
+    if (mode != RODENT_BUILD_OBJECTS_IN_PLACE && mode != RODENT_BUILD_OBJECTS_PACK) return RODENT_BUILD_ERR_INPUT;
+    if (!vertices || !indices || !nodes || !tris || !objects || !ranges || !scratch || !object_info || !info_dev)
+        return RODENT_BUILD_ERR_NULL;
+    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
+    BuildForest a{};
+    a.objects = objects; a.ranges = ranges; a.num_objects = num_objects; a.num_listed = num_listed; a.total_tris = total_tris;
+    a.num_rows = num_rows; a.max_leaf = max_leaf; a.pack = mode == RODENT_BUILD_OBJECTS_PACK; a.object_info = object_info;
+    a.info = info_dev;
+    return launch_build_objects(vertices, num_vertices, indices, nodes, tris, a, scratch, stream);
+}
+
+int32_t rodent_hip_build_objects_sync(int32_t dev, const float* vertices, int32_t num_vertices, const int32_t* indices, int32_t num_rows,
+                                      int32_t max_leaf, int32_t mode, struct Node2* nodes, struct Tri1* tris,
+                                      struct RodentObject* objects, int32_t num_objects, const struct RodentRefitRange* ranges,
+                                      int32_t num_listed, int32_t total_tris, int32_t* object_info, int32_t* info) {
+    if (num_listed < 1 || num_listed > RODENT_BUILD_OBJECTS_MAX_LISTED || bad_num_tris(total_tris)) return RODENT_BUILD_ERR_NUM_NODES;
+    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
+    const size_t scratch_bytes = carve_forest_build(nullptr, total_tris, num_listed).bytes, words = 4 * (size_t)num_listed;
+    char* scratch = nullptr;
+    if (hipMalloc(&scratch, scratch_bytes + 4 * (words + RODENT_BUILD_INFO_WORDS)) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
+    int32_t* object_info_dev = reinterpret_cast<int32_t*>(scratch + scratch_bytes);
+    int32_t* info_dev = object_info_dev + words;
+    int32_t rc = rodent_hip_build_objects(dev, vertices, num_vertices, indices, num_rows, max_leaf, mode, nodes, tris, objects,
+                                          num_objects, ranges, num_listed, total_tris, scratch, object_info_dev, info_dev, nullptr);
+    int32_t host[RODENT_BUILD_INFO_WORDS] = {};
+    if (rc == RODENT_BUILD_OK && (hipMemcpy(host, info_dev, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess
+                                  || (object_info && hipMemcpy(object_info, object_info_dev, 4 * words, hipMemcpyDeviceToHost) != hipSuccess)))
+        rc = RODENT_BUILD_ERR_LAUNCH;
+    (void)hipFree(scratch);
+    if (info) std::copy(host, host + RODENT_BUILD_INFO_WORDS, info);
+    if (rc == RODENT_BUILD_OK && host[kInfoFlags]) rc = RODENT_BUILD_ERR_INPUT;
+    return rc;
 }
 
 } // extern "C"

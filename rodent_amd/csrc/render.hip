@@ -1325,7 +1325,54 @@ int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d,
     std::vector<char*> built((size_t)num_objects, nullptr);
     const auto free_built = [&] { for (char* b : built) if (b) HIP_CHECK(hipFree(b)); };
     int64_t total_nodes = 0;
-    for (int32_t o = 0; o < num_objects; o++) {
+    // Without treelet passes: ALL objects by one rodent_hip_build_objects call in pack mode (one launch list whatever their number)
+    // into a temporary block; the table, the per-object info words and the call's come back in one copy.
+    std::vector<RodentRefitRange> plan((size_t)num_objects);
+    char* forest = nullptr;                              // nodes (room for max(1, n - 1) each), then, 256-byte aligned, the triangles
+    size_t forest_tris = 0;
+    int64_t forest_scratch = -1;
+    if (opt->treelet_passes == 0) {
+        std::vector<int32_t> ids((size_t)num_objects), first((size_t)num_objects), count((size_t)num_objects);
+        for (int32_t o = 0; o < num_objects; o++) { ids[o] = o; first[o] = objects[o].first_tri; count[o] = objects[o].num_tris; }
+        int32_t totals[2] = {};
+        forest_scratch = rodent_hip_build_objects_plan(ids.data(), first.data(), count.data(), num_objects, plan.data(), totals);
+    }
+    if (forest_scratch >= 0) {
+        size_t room = 0;
+        for (int32_t o = 0; o < num_objects; o++) room += (size_t)std::max(1, objects[o].num_tris - 1);
+        forest_tris = (sizeof(Node2) * room + 255) / 256 * 256;
+        const size_t range_bytes = (sizeof(RodentRefitRange) * (size_t)num_objects + 255) / 256 * 256;
+        const size_t result_words = 8 * (size_t)num_objects + RODENT_BUILD_INFO_WORDS;    // table, object info, info
+        char* work = nullptr;                            // scratch, the range table, the results
+        HIP_CHECK(hipMalloc(&forest, forest_tris + sizeof(Tri1) * (size_t)d->num_tris));
+        HIP_CHECK(hipMalloc(&work, (size_t)forest_scratch + range_bytes + 4 * result_words));
+        RodentRefitRange* ranges_dev = reinterpret_cast<RodentRefitRange*>(work + forest_scratch);
+        RodentObject* table_dev = reinterpret_cast<RodentObject*>(work + forest_scratch + range_bytes);
+        int32_t* object_info_dev = reinterpret_cast<int32_t*>(table_dev + num_objects);
+        int32_t* info_dev = object_info_dev + 4 * (size_t)num_objects;
+        HIP_CHECK(hipMemcpy(ranges_dev, plan.data(), sizeof(RodentRefitRange) * (size_t)num_objects, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(table_dev, 0, 4 * result_words));
+        const int32_t rc = rodent_hip_build_objects(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, opt->max_leaf,
+            RODENT_BUILD_OBJECTS_PACK, reinterpret_cast<Node2*>(forest), reinterpret_cast<Tri1*>(forest + forest_tris), table_dev,
+            num_objects, ranges_dev, num_objects, d->num_tris, work, object_info_dev, info_dev, nullptr);
+        std::vector<int32_t> result(result_words, 0);
+        if (rc == RODENT_BUILD_OK) HIP_CHECK(hipMemcpy(result.data(), table_dev, 4 * result_words, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipFree(work));
+        const int32_t* object_info = result.data() + 4 * (size_t)num_objects;
+        int32_t bad = rc;
+        for (int32_t o = 0; o < num_objects && !bad; o++) {      // the first flagged object in object order, as the loop reports it
+            const int32_t nodes_o = object_info[4 * o], n = objects[o].num_tris;
+            bad = object_info[4 * o + 2] ? object_info[4 * o + 2] : nodes_o < 1 || nodes_o > std::max(1, n - 1) ? (int32_t)0x80000000u : 0;
+        }
+        if (!bad) bad = object_info[4 * (size_t)num_objects + 2];
+        if (bad) { HIP_CHECK(hipFree(forest)); return fail(bad); }
+        for (int32_t o = 0; o < num_objects; o++) {
+            std::memcpy(&table[o], result.data() + 4 * (size_t)o, sizeof(RodentObject));
+            total_nodes += table[o].num_nodes;
+        }
+    }
+    for (int32_t o = 0; o < num_objects && !forest; o++) {
         const int32_t n = objects[o].num_tris;
         const size_t node_bytes = sizeof(Node2) * (size_t)std::max(1, n - 1), tri_bytes = sizeof(Tri1) * (size_t)n;
         const int64_t scratch_bytes = std::max<int64_t>(rodent_hip_build_opt_scratch_bytes(n, opt), 0);
@@ -1352,7 +1399,11 @@ int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d,
         char* bvh = nullptr;
         HIP_CHECK(hipMalloc(&bvh, tri_start + sizeof(Tri1) * (size_t)d->num_tris));
         s.allocs.push_back(bvh);
-        for (int32_t o = 0; o < num_objects; o++) {
+        if (forest) {                                            // packed tight already: the nodes, then the triangles
+            HIP_CHECK(hipMemcpy(bvh, forest, node_bytes, hipMemcpyDeviceToDevice));
+            HIP_CHECK(hipMemcpy(bvh + tri_start, forest + forest_tris, sizeof(Tri1) * (size_t)d->num_tris, hipMemcpyDeviceToDevice));
+        }
+        for (int32_t o = 0; o < num_objects && !forest; o++) {
             const size_t from_tris = sizeof(Node2) * (size_t)std::max(1, objects[o].num_tris - 1);
             HIP_CHECK(hipMemcpy(bvh + sizeof(Node2) * (size_t)table[o].node_offset, built[o], sizeof(Node2) * (size_t)table[o].num_nodes,
                                 hipMemcpyDeviceToDevice));
@@ -1361,6 +1412,7 @@ int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d,
         }
         HIP_CHECK(hipDeviceSynchronize());
         free_built();
+        if (forest) HIP_CHECK(hipFree(forest));
         s.dev.nodes = reinterpret_cast<const Node2*>(bvh);
         s.dev.tris = reinterpret_cast<const Tri1*>(bvh + tri_start);
     }

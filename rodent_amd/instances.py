@@ -6,6 +6,10 @@ include/rodent_instances.h; kernels: csrc/build_tlas.h, csrc/traversal_instanced
     hits, ids = trace(objects, tlas, rays)                    # Hit1 records (tri_id: the object's own prim id) + instance ids
     build_tlas(objects, moved_transforms, object_ids, out=tlas)   # the per-frame path: the objects' hierarchies stay as they are
     refit_objects(objects, [2, 0], moved_vertices, indices, rows) # geometry moved inside objects 2 and 0: refitted in one launch list
+    objects = build_objects(vertices, indices, rows)              # ALL objects built on the device in one launch list: pack_objects of
+                                                                  # per-object gpubuild.build_bvh2, byte for byte
+    slotted = build_objects(vertices, indices, rows, slots=True)  # ... each in a node slot of its own, so that
+    rebuild_objects(slotted, [2, 0], moved_vertices, indices, rows[[2, 0]])   # rebuilds objects 2 and 0 where they lie (new topologies)
 
 The top-level hierarchy is a pure function of the objects' root boxes, the transforms and max_leaf, byte for byte.
 """
@@ -36,9 +40,12 @@ class ObjectSet:
     `buffer`, the triangles 256-byte aligned behind the nodes, as in abi.DeviceBvh), and the RodentObject table on the host (`table`,
     formats.OBJECT) and on the device (`table_dev`)."""
 
-    def __init__(self, buffer, nodes, tris, table, table_dev, dev):
+    def __init__(self, buffer, nodes, tris, table, table_dev, dev, capacities=None, depths=None):
         self.buffer, self.nodes, self.tris, self.table, self.table_dev, self.dev = buffer, nodes, tris, table, table_dev, dev
         self.num_objects, self.num_nodes, self.num_tris = len(table), int(table["num_nodes"].sum()), int(table["num_tris"].sum())
+        # capacities: per object the Node2 records of its slot (build_objects(slots=True): rebuild_objects works in such a set); None
+        # for a tight set.  depths: per object its hierarchy's depth, where the builder reported it (build_objects).
+        self.capacities, self.depths = capacities, depths
 
     @property
     def device_bytes(self):
@@ -253,6 +260,111 @@ def refit_objects(objects: ObjectSet, object_ids, vertices, indices, ranges, str
     if check and words[0] != plan.num_nodes:
         raise BuildError(f"{entry}: malformed hierarchy ({words[0]} of {plan.num_nodes} nodes completed)")
     return words
+
+
+# ---- the objects' hierarchies built in one launch list (rodent_hip_build_objects: csrc/build_forest.h) ----------------------------
+def _build_plan(object_ids, ranges, dev):
+    """(RodentRefitRange table on the host, on the device, listed triangles, scratch bytes) of rodent_hip_build_objects_plan."""
+    ids = np.ascontiguousarray(np.clip(np.asarray(object_ids, np.int64).reshape(-1), -1, (1 << 31) - 1).astype(np.int32))
+    rows = np.asarray(ranges, np.int32).reshape(-1, 2)
+    if len(ids) < 1 or len(rows) != len(ids):
+        raise ValueError(f"{len(ids)} object ids and {len(rows)} (first_tri, num_tris) rows")
+    first, count = np.ascontiguousarray(rows[:, 0]), np.ascontiguousarray(rows[:, 1])
+    table, totals = np.zeros(len(ids), F.REFIT_RANGE), np.zeros(2, np.int32)
+    need = abi.lib().rodent_hip_build_objects_plan(ids.ctypes.data, first.ctypes.data, count.ctypes.data, len(ids), table.ctypes.data,
+                                                   totals.ctypes.data)
+    if need < 0:
+        raise BuildError("rodent_hip_build_objects_plan: more than 2^20 objects, an object without triangles or more than 2^25 triangles")
+    return table, abi.to_device(table, dev), int(totals[0]), int(need)
+
+
+def _build_objects(mode, plan, vertices, indices, max_leaf, dev, stream, scratch, nodes, tris, table_dev, num_objects, keep):
+    """rodent_hip_build_objects on `stream`: (info words, (K, 4) per-object info words) on the host."""
+    if not 1 <= max_leaf <= MAX_LEAF:
+        raise BuildError(f"max_leaf = {max_leaf}: outside [1, 8]")
+    from .gpubuild import _columns4
+    ranges, ranges_dev, total, need = plan
+    cuda = f"cuda:{dev}"
+    v, ix = _columns4(vertices, torch.float32, dev), _columns4(indices, torch.int32, dev)
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    if scratch is None or scratch.numel() * scratch.element_size() < need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=cuda)
+    info = torch.empty(INFO_WORDS, dtype=torch.int32, device=cuda)
+    object_info = torch.empty((len(ranges), 4), dtype=torch.int32, device=cuda)
+    words = _enqueue("rodent_hip_build_objects", dev, stream, info, (v, ix, scratch, ranges_dev, object_info, table_dev, *keep),
+                     v.data_ptr(), v.shape[0], ix.data_ptr(), ix.shape[0], int(max_leaf), int(mode), nodes.data_ptr(), tris.data_ptr(),
+                     table_dev.data_ptr(), int(num_objects), ranges_dev.data_ptr(), len(ranges), total, scratch.data_ptr(),
+                     object_info.data_ptr()).copy()
+    return words, object_info.cpu().numpy()
+
+
+def _raise_object_flags(entry, words, per_object, ids):
+    if words[2]:
+        bad = np.nonzero(per_object[:, 2])[0]
+        k = int(bad[0]) if len(bad) else 0
+        flags = int(per_object[k, 2]) if len(bad) else int(words[2])
+        raise BuildError(f"{entry}: object {int(ids[k])}: " + ", ".join(s for bit, s in _TLAS_FLAGS if flags & bit))
+
+
+def build_objects(vertices, indices, ranges, max_leaf=2, dev=0, stream=None, slots=False, check=True) -> ObjectSet:
+    """Builds the BVH2 / Tri1 hierarchies of ALL objects of a new set in one launch list (rodent_hip_build_objects), whatever their
+    number: `vertices` and `indices` are the concatenated tables ((n, 3) or (n, 4); tensors on the device are not copied), `ranges` one
+    (first_tri, num_tris) row per object.  Every object's records are those build_bvh2(vertices, indices[first: first + n], max_leaf)
+    writes for it alone.  slots=False: the tight set, equal to pack_objects of the per-object builds.  slots=True: every object keeps a
+    node slot of max(1, n - 1) records (`capacities`), so rebuild_objects can rebuild any of them where it lies.  `depths` holds every
+    object's depth.  With `check` a device flag raises BuildError naming the first flagged object."""
+    _need_gpu()
+    rows = np.asarray(ranges, np.int32).reshape(-1, 2)
+    ids = np.arange(len(rows), dtype=np.int32)
+    plan = _build_plan(ids, rows, dev)
+    total, cuda = plan[2], f"cuda:{dev}"
+    room = np.maximum(rows[:, 1].astype(np.int64) - 1, 1)
+    node_bytes = int(room.sum()) * F.NODE2.itemsize
+    start = (node_bytes + 255) // 256 * 256
+    buffer = torch.zeros(start + total * F.TRI1.itemsize, dtype=torch.uint8, device=cuda)
+    table = np.zeros(len(rows), F.OBJECT)
+    if slots:
+        table["node_offset"], table["tri_offset"], table["num_tris"] = np.cumsum(room) - room, plan[0]["rec_start"], rows[:, 1]
+    table_dev = abi.to_device(table, dev)
+    entry = "rodent_hip_build_objects"
+    words, per_object = _build_objects(0 if slots else 1, plan, vertices, indices, max_leaf, dev, stream, None, buffer[:node_bytes],
+                                       buffer[start:], table_dev, len(rows), (buffer,))
+    if check:
+        _raise_object_flags(entry, words, per_object, ids)
+    table = abi.from_device(table_dev, F.OBJECT).copy()
+    if not slots:                                                # the nodes lie tight at the front of their room
+        node_bytes = int(table["num_nodes"].sum()) * F.NODE2.itemsize
+    return ObjectSet(buffer, buffer[:node_bytes], buffer[start:], table, table_dev, dev, room.astype(np.int32) if slots else None,
+                     per_object[:, 1].copy())
+
+
+def rebuild_objects(objects: ObjectSet, object_ids, vertices, indices, ranges, max_leaf=2, stream=None, scratch=None, check=True):
+    """Rebuilds the hierarchies of the objects `object_ids` (any order) of a slotted set (build_objects(slots=True)) where they lie,
+    from moved `vertices`: new topologies, not a refit.  `ranges`: one (first_tri, num_tris) row per listed object; its triangle count
+    must be its slot's.  One launch list whatever the list's length; every other object keeps its bytes.  Returns (info words, per-object
+    info words); with `check` the host table is refreshed (one K x 16-byte copy), `depths` updated and a flag raises BuildError naming
+    the first flagged object.  Raises ValueError on a tight set or a triangle count that differs from the slot's."""
+    _need_gpu()
+    if objects.capacities is None:
+        raise ValueError("rebuild_objects: a slotted set is needed (build_objects(slots=True))")
+    ids = np.asarray(object_ids, np.int64).reshape(-1)
+    rows = np.asarray(ranges, np.int32).reshape(-1, 2)
+    if len(rows) != len(ids):
+        raise ValueError(f"rebuild_objects: {len(ids)} object ids and {len(rows)} (first_tri, num_tris) rows")
+    known = (ids >= 0) & (ids < objects.num_objects)
+    if (objects.table["num_tris"][ids[known]] != rows[known, 1]).any():
+        raise ValueError("rebuild_objects: a listed object's triangle count differs from its slot's")
+    plan = _build_plan(ids, rows, objects.dev)
+    entry = "rodent_hip_build_objects"
+    words, per_object = _build_objects(0, plan, vertices, indices, max_leaf, objects.dev, stream, scratch, objects.nodes, objects.tris,
+                                       objects.table_dev, objects.num_objects, (objects.buffer,))
+    if check:
+        objects.table = abi.from_device(objects.table_dev, F.OBJECT).copy()
+        objects.num_nodes = int(objects.table["num_nodes"].sum())
+        if objects.depths is not None:
+            objects.depths[ids[known]] = per_object[known, 1]
+        _raise_object_flags(entry, words, per_object, ids)
+    return words, per_object
 
 
 # ---- instanced scenes for the renderer (include/rodent_render.h: rodent_hip_scene_create_instanced; render.Renderer(instances=...)) ----
