@@ -56,6 +56,33 @@
  *   entries for the ray, a ray whose P + 2 never exceeds 64 is traced without a flag; any other ray raises the overflow flag
  *   (rodent_hip_check_errors; the synchronous entries abort() on it), stops where it stands and stores an undefined hit: it never reads
  *   an entry that was not pushed.  A wrong hit without a flag does not occur.
+ *
+ * ---- moving instances: a time per ray over two-key instance motion (tests/motion_instance_model.py restates this section) ----
+ * Motion instance: one object placed by TWO object_to_world matrices, M0 at time 0 and M1 at time 1.
+ * Placement at time t: every ray carries a time t (a float, used as given: it is not clamped).  Entry by entry s = 1 - t; m = s*m0 + t*m1:
+ *   two products and one sum, each rounded, no fused multiply-add.  So t = 0 gives M0 and t = 1 gives M1, bit for bit -- with one
+ *   exception the three operations cannot avoid: an entry -0 whose partner is positive comes out as 1 * -0 + 0 * m1 = +0.  The value is
+ *   the same, and the inverse differs at most in the sign of a zero of its own.
+ * Per-ray inverse: the fp64 cofactor inverse above of the interpolated fp32 matrix, in the order above, each of the 12 entries rounded to
+ *   fp32 once -- one function (csrc/instance_inverse.h) for the build stage and for the kernel.  At t = 0 it is bit-equal to what
+ *   rodent_hip_build_tlas stores for M0 (but for the zeros just named).
+ * Skipped instances: an instance is skipped for a ray iff det is 0 or non-finite or one of the 12 rounded entries is non-finite (a
+ *   non-finite entry of the interpolated matrix always makes one of the two so).  It is skipped with no flag: its object is not entered,
+ *   tmax and the hit stay as they are.  An interpolation between two sound placements can pass through a singular matrix (a half turn at
+ *   t = 0.5): that is the scene's property, not an error.  A NaN time makes every entry NaN, so every instance is skipped for that ray.
+ * Object ray: formed from the per-ray inverse exactly as from a stored world_to_object above; everything inside the object is unchanged,
+ *   and so are the TLAS walk, the <= rule across instances, the miss record and the stack contract (P + 2 <= 64; a skipped instance
+ *   pushes nothing).
+ * Motion box of an instance: B0 and B1 are the widened world boxes above under M0 and M1, e0 and e1 their per-axis widenings.  Per axis
+ *   lo = fminf(lo0, lo1) - (e0 + e1), hi = fmaxf(hi0, hi1) + (e0 + e1).  Under exact interpolation a corner's image is linear in t, so for
+ *   t in [0, 1] it lies in the hull of the two endpoint images, which B0 and B1 contain; the fp32 interpolation moves an entry by at most
+ *   about 3 * 2^-24 * max(|m0|, |m1|), which moves a corner's image by less than e0 + e1.  Containment is promised for t in [0, 1] only,
+ *   on the domain of the static rule for both matrices.  tests/test_motion_instance_model.py checks it in exact rational arithmetic
+ *   (seeded pairs, the edge matrices paired with each other, a half turn; t in {0, 1, 0.5, 2^-24, 1 - 2^-24, a denormal, 33 seeded}):
+ *   no counterexample was found, so the widening stands as derived.
+ * Sort point: lo + hi of the motion box; from there the LBVH stages as for rodent_hip_build_tlas.  RodentMotionInstance k is the k-th
+ *   instance in that order: both matrices as given, the object's offsets, instance_id (bit 31: the last of its leaf), pads = 0.
+ * Flags: RODENT_TLAS_BAD_TRANSFORM if either endpoint matrix fails the static checks; RODENT_TLAS_BAD_OBJECT as above.
  */
 #ifndef RODENT_INSTANCES_H
 #define RODENT_INSTANCES_H
@@ -71,6 +98,10 @@ struct RodentObject       { int32_t node_offset, tri_offset, num_nodes, num_tris
 struct RodentInstanceDesc { float object_to_world[12]; int32_t object, instance_id, pad[2]; };    /* 64 B, the caller's input */
 struct RodentInstance     { float world_to_object[12]; int32_t node_offset, tri_offset,
                             instance_id /* bit 31 = last in leaf */, pad; };                      /* 64 B, what the kernel reads */
+struct RodentMotionInstanceDesc { float object_to_world0[12]; float object_to_world1[12];
+                                  int32_t object, instance_id, pad[6]; };                         /* 128 B, the caller's input */
+struct RodentMotionInstance     { float object_to_world0[12]; float object_to_world1[12]; int32_t node_offset, tri_offset,
+                                  instance_id /* bit 31 = last in leaf */, pad; int32_t pad2[4]; }; /* 128 B, one cache line */
 
 #define RODENT_TLAS_MAX_INSTANCES        (1 << 22)
 
@@ -102,6 +133,19 @@ int32_t rodent_hip_build_tlas(int32_t dev, const struct Node2* nodes, const stru
 int32_t rodent_hip_build_tlas_sync(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
                                    const struct RodentInstanceDesc* descs, int32_t num_instances, int32_t max_leaf,
                                    struct Node2* tlas_nodes, struct RodentInstance* instances, int32_t* info);
+
+/* The three above for moving instances (the section "moving instances" at the top): the same argument shape with
+ * RodentMotionInstanceDesc in and RodentMotionInstance out, the same host-side refusals in the same order, the same asynchronous
+ * contract (nothing is allocated, nothing waits for the device, the info words are zeroed at the start), the same launch list with the
+ * motion instance stage in the place of the instance stage. */
+int64_t rodent_hip_motion_tlas_scratch_bytes(int32_t num_instances);
+int32_t rodent_hip_build_motion_tlas(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
+                                     const struct RodentMotionInstanceDesc* descs, int32_t num_instances, int32_t max_leaf,
+                                     struct Node2* tlas_nodes, struct RodentMotionInstance* instances, void* scratch, int32_t* info_dev,
+                                     void* stream);
+int32_t rodent_hip_build_motion_tlas_sync(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
+                                          const struct RodentMotionInstanceDesc* descs, int32_t num_instances, int32_t max_leaf,
+                                          struct Node2* tlas_nodes, struct RodentMotionInstance* instances, int32_t* info);
 
 /* ---- refit of deforming objects: a chosen subset of the packed objects, in place, in one launch list ----
  * One RodentRefitRange per listed object: `object` indexes the RodentObject table; first_tri / num_tris cut the object's rows out of
@@ -215,6 +259,23 @@ void hip_intersect_instanced_bvh2_tri1(int32_t dev, const struct Node2* tlas_nod
 void hip_occluded_instanced_bvh2_tri1(int32_t dev, const struct Node2* tlas_nodes, const struct RodentInstance* instances,
                                       const struct Node2* nodes, const struct Tri1* tris, const struct Ray1* rays, struct Hit1* hits,
                                       int32_t* hit_instances, int32_t num_rays);
+
+/* The three above through a motion TLAS (rodent_hip_build_motion_tlas): `times` (DEVICE, one float per ray, required) holds every ray's
+ * time; each instance a ray meets is placed, inverted and possibly skipped for that ray by the rules of "moving instances" at the top.
+ * The overflow flag is reported as above. */
+void hip_traverse_motion_instanced_bvh2_tri1_async(int32_t dev, const struct Node2* tlas_nodes,
+                                                   const struct RodentMotionInstance* motion_instances, const struct Node2* nodes,
+                                                   const struct Tri1* tris, const struct Ray1* rays, const float* times,
+                                                   struct Hit1* hits, int32_t* hit_instances, int32_t num_rays, int32_t any_hit,
+                                                   void* stream);
+void hip_intersect_motion_instanced_bvh2_tri1(int32_t dev, const struct Node2* tlas_nodes,
+                                              const struct RodentMotionInstance* motion_instances, const struct Node2* nodes,
+                                              const struct Tri1* tris, const struct Ray1* rays, const float* times, struct Hit1* hits,
+                                              int32_t* hit_instances, int32_t num_rays);
+void hip_occluded_motion_instanced_bvh2_tri1(int32_t dev, const struct Node2* tlas_nodes,
+                                             const struct RodentMotionInstance* motion_instances, const struct Node2* nodes,
+                                             const struct Tri1* tris, const struct Ray1* rays, const float* times, struct Hit1* hits,
+                                             int32_t* hit_instances, int32_t num_rays);
 
 #ifdef __cplusplus
 }

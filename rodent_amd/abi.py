@@ -53,6 +53,9 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "rodent_hip_collapse_bounded_scratch_bytes", "rodent_hip_collapse_bvh2_tri1_bounded", "rodent_hip_collapse_bvh2_tri1_bounded_sync",
     "rodent_hip_tlas_scratch_bytes", "rodent_hip_build_tlas", "rodent_hip_build_tlas_sync",
     "hip_traverse_instanced_bvh2_tri1_async", "hip_intersect_instanced_bvh2_tri1", "hip_occluded_instanced_bvh2_tri1",
+    "rodent_hip_motion_tlas_scratch_bytes", "rodent_hip_build_motion_tlas", "rodent_hip_build_motion_tlas_sync",
+    "hip_traverse_motion_instanced_bvh2_tri1_async", "hip_intersect_motion_instanced_bvh2_tri1",
+    "hip_occluded_motion_instanced_bvh2_tri1",
     "rodent_hip_refit_objects_plan", "rodent_hip_refit_objects",
     "rodent_hip_build_objects_plan", "rodent_hip_build_objects", "rodent_hip_build_objects_sync",
 ]
@@ -169,6 +172,16 @@ def lib():
         l.hip_traverse_instanced_bvh2_tri1_async.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
         for name in ("hip_intersect_instanced_bvh2_tri1", "hip_occluded_instanced_bvh2_tri1"):
             fn = getattr(l, name); fn.restype = None; fn.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i32]
+        # moving instances: the static entries' shapes, `times` behind `rays`
+        l.rodent_hip_motion_tlas_scratch_bytes.restype = C.c_int64; l.rodent_hip_motion_tlas_scratch_bytes.argtypes = [i32]
+        l.rodent_hip_build_motion_tlas.restype = i32
+        l.rodent_hip_build_motion_tlas.argtypes = [i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+        l.rodent_hip_build_motion_tlas_sync.restype = i32
+        l.rodent_hip_build_motion_tlas_sync.argtypes = [i32, vp, vp, i32, vp, i32, i32, vp, vp, C.POINTER(i32)]
+        l.hip_traverse_motion_instanced_bvh2_tri1_async.restype = None
+        l.hip_traverse_motion_instanced_bvh2_tri1_async.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
+        for name in ("hip_intersect_motion_instanced_bvh2_tri1", "hip_occluded_motion_instanced_bvh2_tri1"):
+            fn = getattr(l, name); fn.restype = None; fn.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]
         l.rodent_hip_refit_objects_plan.restype = C.c_int64
         l.rodent_hip_refit_objects_plan.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp]
         l.rodent_hip_refit_objects.restype = i32

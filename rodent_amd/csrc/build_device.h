@@ -122,9 +122,12 @@ __device__ __forceinline__ void store_tri1(Tri1* rec, const TriGeometry& g, int 
     out[2] = make_float4(g.e2.x, g.e2.y, g.e2.z, __int_as_float(prim));
 }
 
-// The end-of-leaf bit of a leaf record: bit 31 of a Tri1's prim_id, of a RodentInstance's instance_id (k_emit, k_emit_root).
+// The end-of-leaf bit of a leaf record: bit 31 of a Tri1's prim_id, of a Rodent(Motion)Instance's instance_id (k_emit, k_emit_root).
 __device__ __forceinline__ void mark_last_in_leaf(Tri1* rec) { rec->prim_id = (int32_t)((uint32_t)rec->prim_id | kLastInLeaf); }
 __device__ __forceinline__ void mark_last_in_leaf(RodentInstance* rec) {
+    rec->instance_id = (int32_t)((uint32_t)rec->instance_id | kLastInLeaf);
+}
+__device__ __forceinline__ void mark_last_in_leaf(RodentMotionInstance* rec) {
     rec->instance_id = (int32_t)((uint32_t)rec->instance_id | kLastInLeaf);
 }
 

@@ -1,28 +1,8 @@
 // build_tlas.h -- the top level of an instanced scene (include/rodent_instances.h; included by bvh_build.hip after build_lbvh.h): the
-// instance stage in front of the LBVH's stages 2, 3, 5, 6 and 7 and the leaf stage in the place of stage 4.  CPU model:
-// tests/instance_model.py.
+// instance stage (k_instances; k_motion_instances for moving instances) in front of the LBVH's stages 2, 3, 5, 6 and 7 and the leaf stage
+// in the place of stage 4.  CPU models: tests/instance_model.py, tests/motion_instance_model.py.
 #pragma once
-// world_to_object of object_to_world `m` (rows of 4): the cofactor inverse in fp64 in the header's order, each entry rounded to fp32
-// once.  Returns RODENT_TLAS_BAD_TRANSFORM or 0.
-__device__ __forceinline__ int invert_affine(const float m[12], float w[12]) {
-    bool ok = true;
-    for (int k = 0; k < 12; k++) ok = ok && isfinite(m[k]);
-    const double a = m[0], b = m[1], c = m[2], tx = m[3], d = m[4], e = m[5], f = m[6], ty = m[7], g = m[8], h = m[9], i = m[10],
-                 tz = m[11];
-    const double c0 = e * i - f * h, c1 = f * g - d * i, c2 = d * h - e * g;
-    const double det = (a * c0 + b * c1) + c * c2;
-    const double r = 1.0 / det;
-    const double q[9] = {c0 * r, (c * h - b * i) * r, (b * f - c * e) * r,
-                         c1 * r, (a * i - c * g) * r, (c * d - a * f) * r,
-                         c2 * r, (b * g - a * h) * r, (a * e - b * d) * r};
-    for (int k = 0; k < 3; k++) {
-        for (int j = 0; j < 3; j++) w[4 * k + j] = (float)q[3 * k + j];
-        w[4 * k + 3] = (float)-((q[3 * k] * tx + q[3 * k + 1] * ty) + q[3 * k + 2] * tz);
-    }
-    ok = ok && det != 0.0 && isfinite(det);
-    for (int k = 0; k < 12; k++) ok = ok && isfinite(w[k]);
-    return ok ? 0 : RODENT_TLAS_BAD_TRANSFORM;
-}
+// invert_affine, the one inverse of the build stage and of k_instanced_motion: instance_inverse.h.
 
 // The widened world box (lo_x hi_x lo_y hi_y lo_z hi_z) of the object box olo / ohi under `m`.
 __device__ __forceinline__ void instance_world_box(const float m[12], const float olo[3], const float ohi[3], float box[6]) {
@@ -77,15 +57,71 @@ __global__ __launch_bounds__(kBlock) void k_instances(const Node2* __restrict__ 
     block_bounds(lo, hi, partial + 6 * blockIdx.x);
 }
 
-// ---- the leaf stage: RodentInstance records and leaf boxes in sorted order (in the place of k_leaves) ---------------------------------
-__global__ __launch_bounds__(kBlock) void k_tlas_leaves(const RodentInstance* __restrict__ staged, const float* __restrict__ wbox,
+// ---- the motion instance stage (in the place of k_instances): both matrices checked, the motion box, its sort point ------------------
+// The per-axis widening e of instance_world_box under `m`, restated: the motion box is widened by both endpoints'.
+__device__ __forceinline__ void instance_widening(const float m[12], const float olo[3], const float ohi[3], float e[3]) {
+    const float X = fmaxf(fabsf(olo[0]), fabsf(ohi[0])), Y = fmaxf(fabsf(olo[1]), fabsf(ohi[1])), Z = fmaxf(fabsf(olo[2]), fabsf(ohi[2]));
+    for (int a = 0; a < 3; a++) {
+        const float* r = m + 4 * a;
+        e[a] = 0x1p-21f * (((fabsf(r[0]) * X + fabsf(r[1]) * Y) + fabsf(r[2]) * Z) + fabsf(r[3]));
+    }
+}
+
+// staged[t]: the RodentMotionInstance record of descriptor t without its end-of-leaf bit; wbox[6 t]: its motion box; cent[t]: its sort
+// point.
+__global__ __launch_bounds__(kBlock) void k_motion_instances(const Node2* __restrict__ nodes, const RodentObject* __restrict__ objects,
+                                                             int num_objects, const RodentMotionInstanceDesc* __restrict__ descs, int n,
+                                                             RodentMotionInstance* __restrict__ staged, float* __restrict__ wbox,
+                                                             float4* __restrict__ cent, float* __restrict__ partial, int* info) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int t = blockIdx.x * kBlock + threadIdx.x; t < n; t += gridDim.x * kBlock) {
+        const float4* dp = reinterpret_cast<const float4*>(descs + t);
+        float4 r[6];
+        for (int k = 0; k < 6; k++) r[k] = dp[k];
+        const int4 id = *reinterpret_cast<const int4*>(dp + 6);          // object, instance_id, pad, pad
+        const float m0[12] = {r[0].x, r[0].y, r[0].z, r[0].w, r[1].x, r[1].y, r[1].z, r[1].w, r[2].x, r[2].y, r[2].z, r[2].w};
+        const float m1[12] = {r[3].x, r[3].y, r[3].z, r[3].w, r[4].x, r[4].y, r[4].z, r[4].w, r[5].x, r[5].y, r[5].z, r[5].w};
+        int flags = 0, object = id.x;
+        if ((unsigned)object >= (unsigned)num_objects) { flags |= RODENT_TLAS_BAD_OBJECT; object = 0; }
+        const int4 ob = reinterpret_cast<const int4*>(objects)[object];  // node_offset, tri_offset, num_nodes, num_tris
+        float w[12];                                                     // only the verdicts are kept: the kernel inverts per ray
+        flags |= invert_affine(m0, w);
+        flags |= invert_affine(m1, w);
+        const float4* np = reinterpret_cast<const float4*>(nodes + ob.x);
+        const float4 b0 = np[0], b1 = np[1], b2 = np[2];                 // child 0: b0.x .. b1.y, child 1: b1.z .. b2.w
+        const float olo[3] = {fminf(b0.x, b1.z), fminf(b0.z, b2.x), fminf(b1.x, b2.z)};
+        const float ohi[3] = {fmaxf(b0.y, b1.w), fmaxf(b0.w, b2.y), fmaxf(b1.y, b2.w)};
+        float box0[6], box1[6], e0[3], e1[3], box[6];
+        instance_world_box(m0, olo, ohi, box0); instance_widening(m0, olo, ohi, e0);
+        instance_world_box(m1, olo, ohi, box1); instance_widening(m1, olo, ohi, e1);
+        for (int a = 0; a < 3; a++) {
+            const float e = e0[a] + e1[a];
+            box[2 * a] = fminf(box0[2 * a], box1[2 * a]) - e;
+            box[2 * a + 1] = fmaxf(box0[2 * a + 1], box1[2 * a + 1]) + e;
+        }
+        const float s[3] = {box[0] + box[1], box[2] + box[3], box[4] + box[5]};
+        float4* out = reinterpret_cast<float4*>(staged + t);
+        for (int k = 0; k < 6; k++) out[k] = r[k];
+        out[6] = make_float4(__int_as_float(ob.x), __int_as_float(ob.y), __int_as_float(id.y & 0x7FFFFFFF), 0.0f);
+        out[7] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        for (int k = 0; k < 6; k++) wbox[6 * (size_t)t + k] = box[k];
+        cent[t] = make_float4(s[0], s[1], s[2], 0.0f);
+        for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], s[a]); hi[a] = fmaxf(hi[a], s[a]); }
+        if (flags) atomicOr(&info[kInfoFlags], flags);
+    }
+    block_bounds(lo, hi, partial + 6 * blockIdx.x);
+}
+
+// ---- the leaf stage: RodentInstance / RodentMotionInstance records and leaf boxes in sorted order (in the place of k_leaves) ---------
+template <class Rec>
+__global__ __launch_bounds__(kBlock) void k_tlas_leaves(const Rec* __restrict__ staged, const float* __restrict__ wbox,
                                                         const uint32_t* __restrict__ order, int n,
-                                                        RodentInstance* __restrict__ instances, float* __restrict__ leafbox) {
+                                                        Rec* __restrict__ instances, float* __restrict__ leafbox) {
     const int p = blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
     const size_t r = order[p];
     const float4* in = reinterpret_cast<const float4*>(staged + r);
     float4* out = reinterpret_cast<float4*>(instances + p);
-    for (int k = 0; k < 4; k++) out[k] = in[k];
+    for (int k = 0; k < (int)(sizeof(Rec) / 16); k++) out[k] = in[k];
     for (int k = 0; k < 6; k++) leafbox[6 * (size_t)p + k] = wbox[6 * r + k];
 }

@@ -171,14 +171,16 @@ CollapseScratch carve_collapse(char* base, int num_nodes, int num_bvh_tris, bool
     return s;
 }
 
+template <class Rec>               // RodentInstance or RodentMotionInstance
 struct TlasScratch {
-    RodentInstance* staged;       // per descriptor: its RodentInstance record, before the sort
-    float* wbox;                  // per descriptor: its world box
+    Rec* staged;                  // per descriptor: its record, before the sort
+    float* wbox;                  // per descriptor: its world box (its motion box)
     size_t bytes;
 };
 
-TlasScratch carve_tlas(char* base, int n) {
-    TlasScratch t{};
+template <class Rec>
+TlasScratch<Rec> carve_tlas(char* base, int n) {
+    TlasScratch<Rec> t{};
     Carver c{base};
     c.take(t.staged, (size_t)n); c.take(t.wbox, 6 * (size_t)n);
     t.bytes = c.bytes;
@@ -234,6 +236,7 @@ PlocScratch carve_ploc(char* base, int max_refs) {
 }
 
 #include "build_lbvh.h"
+#include "instance_inverse.h"
 #include "build_tlas.h"
 #include "build_treelet.h"
 #include "build_split.h"
@@ -464,21 +467,26 @@ int32_t launch_build(const float* vertices, int nv, const int32_t* indices, int 
 }
 
 // The TLAS build after its argument checks: info words and arrival counters zeroed, the instance stage and the frame of its sort points,
-// the sort, the leaf stage, Karras and the LBVH tail over RodentInstance records.
-int32_t launch_tlas(const Node2* nodes, const RodentObject* objects, int num_objects, const RodentInstanceDesc* descs, int n, int max_leaf,
-                    Node2* tlas_nodes, RodentInstance* instances, void* scratch, int32_t* info_dev, void* stream_) {
+// the sort, the leaf stage, Karras and the LBVH tail over RodentInstance records -- or, with motion descriptors, the motion instance
+// stage and RodentMotionInstance records.
+inline auto instance_stage(const RodentInstanceDesc*) { return k_instances; }
+inline auto instance_stage(const RodentMotionInstanceDesc*) { return k_motion_instances; }
+
+template <class Desc, class Rec>
+int32_t launch_tlas(const Node2* nodes, const RodentObject* objects, int num_objects, const Desc* descs, int n, int max_leaf,
+                    Node2* tlas_nodes, Rec* instances, void* scratch, int32_t* info_dev, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const Scratch s = carve(static_cast<char*>(scratch), n);
-    const TlasScratch t = carve_tlas(static_cast<char*>(scratch) + s.bytes, n);
+    const TlasScratch<Rec> t = carve_tlas<Rec>(static_cast<char*>(scratch) + s.bytes, n);
     if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess
         || (n > 1 && hipMemsetAsync(s.arrivals, 0, 4 * (size_t)(n - 1), stream) != hipSuccess))
         return RODENT_BUILD_ERR_LAUNCH;
     const int cblocks = std::min(kBoundsBlocks, blocks_for(n));
-    hipLaunchKernelGGL(k_instances, dim3(cblocks), dim3(kBlock), 0, stream, nodes, objects, num_objects, descs, n, t.staged, t.wbox,
-                       s.cent, s.partial, info_dev);
+    hipLaunchKernelGGL(instance_stage(descs), dim3(cblocks), dim3(kBlock), 0, stream, nodes, objects, num_objects, descs, n, t.staged,
+                       t.wbox, s.cent, s.partial, info_dev);
     hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, s.partial, cblocks, s.frame);
     launch_sort(s, n, nullptr, stream);
-    hipLaunchKernelGGL(k_tlas_leaves, dim3(blocks_for(n)), dim3(kBlock), 0, stream, t.staged, t.wbox, s.vals[0], n, instances, s.leafbox);
+    hipLaunchKernelGGL(k_tlas_leaves<Rec>, dim3(blocks_for(n)), dim3(kBlock), 0, stream, t.staged, t.wbox, s.vals[0], n, instances, s.leafbox);
     launch_karras(s, n, max_leaf, nullptr, stream);
     launch_lbvh_tail(s, n, max_leaf, tlas_nodes, instances, info_dev, nullptr, stream);
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
@@ -686,6 +694,30 @@ int32_t refit_sync(int32_t dev, int64_t scratch_bytes, int32_t num_nodes, int32_
     if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
     if (rc == RODENT_BUILD_OK && words[kInfoRefitNodes] != num_nodes) rc = RODENT_BUILD_ERR_INPUT;    // a malformed topology
     return rc;
+}
+
+// The TLAS entries, static and motion: the argument checks in the header's order, then the launch list.
+template <class Desc, class Rec>
+int32_t build_tlas(int32_t dev, const Node2* nodes, const RodentObject* objects, int32_t num_objects, const Desc* descs,
+                   int32_t num_instances, int32_t max_leaf, Node2* tlas_nodes, Rec* instances, void* scratch, int32_t* info_dev,
+                   void* stream) {
+    if (num_instances < 1 || num_instances > RODENT_TLAS_MAX_INSTANCES) return RODENT_TLAS_ERR_NUM_INSTANCES;
+    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) return RODENT_BUILD_ERR_MAX_LEAF;
+    if (num_objects < 1) return RODENT_TLAS_ERR_NUM_OBJECTS;
+    if (!nodes || !objects || !descs || !tlas_nodes || !instances || !scratch || !info_dev) return RODENT_BUILD_ERR_NULL;
+    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
+    return launch_tlas(nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch, info_dev, stream);
+}
+
+template <class Desc, class Rec>
+int32_t build_tlas_sync(int32_t dev, int64_t bytes, const Node2* nodes, const RodentObject* objects, int32_t num_objects,
+                        const Desc* descs, int32_t num_instances, int32_t max_leaf, Node2* tlas_nodes, Rec* instances, int32_t* info) {
+    if (bytes < 0) return RODENT_TLAS_ERR_NUM_INSTANCES;
+    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) return RODENT_BUILD_ERR_MAX_LEAF;
+    return build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
+        return build_tlas(dev, nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch, info_dev,
+                          nullptr);
+    });
 }
 
 } // namespace
@@ -930,30 +962,39 @@ int32_t rodent_hip_collapse_bvh2_tri1_bounded_sync(int32_t dev, int32_t width, i
 
 int64_t rodent_hip_tlas_scratch_bytes(int32_t num_instances) {
     if (num_instances < 1 || num_instances > RODENT_TLAS_MAX_INSTANCES) return -1;
-    return (int64_t)(carve(nullptr, num_instances).bytes + carve_tlas(nullptr, num_instances).bytes);
+    return (int64_t)(carve(nullptr, num_instances).bytes + carve_tlas<RodentInstance>(nullptr, num_instances).bytes);
+}
+
+int64_t rodent_hip_motion_tlas_scratch_bytes(int32_t num_instances) {
+    if (num_instances < 1 || num_instances > RODENT_TLAS_MAX_INSTANCES) return -1;
+    return (int64_t)(carve(nullptr, num_instances).bytes + carve_tlas<RodentMotionInstance>(nullptr, num_instances).bytes);
 }
 
 int32_t rodent_hip_build_tlas(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
                               const struct RodentInstanceDesc* descs, int32_t num_instances, int32_t max_leaf, struct Node2* tlas_nodes,
                               struct RodentInstance* instances, void* scratch, int32_t* info_dev, void* stream) {
-    if (num_instances < 1 || num_instances > RODENT_TLAS_MAX_INSTANCES) return RODENT_TLAS_ERR_NUM_INSTANCES;
-    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) return RODENT_BUILD_ERR_MAX_LEAF;
-    if (num_objects < 1) return RODENT_TLAS_ERR_NUM_OBJECTS;
-    if (!nodes || !objects || !descs || !tlas_nodes || !instances || !scratch || !info_dev) return RODENT_BUILD_ERR_NULL;
-    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
-    return launch_tlas(nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch, info_dev, stream);
+    return build_tlas(dev, nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch, info_dev, stream);
 }
 
 int32_t rodent_hip_build_tlas_sync(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
                                    const struct RodentInstanceDesc* descs, int32_t num_instances, int32_t max_leaf,
                                    struct Node2* tlas_nodes, struct RodentInstance* instances, int32_t* info) {
-    const int64_t bytes = rodent_hip_tlas_scratch_bytes(num_instances);
-    if (bytes < 0) return RODENT_TLAS_ERR_NUM_INSTANCES;
-    if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) return RODENT_BUILD_ERR_MAX_LEAF;
-    return build_sync(dev, bytes, RODENT_BUILD_INFO_WORDS, info, [&](void* scratch, int32_t* info_dev) {
-        return rodent_hip_build_tlas(dev, nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch,
-                                     info_dev, nullptr);
-    });
+    return build_tlas_sync(dev, rodent_hip_tlas_scratch_bytes(num_instances), nodes, objects, num_objects, descs, num_instances, max_leaf,
+                           tlas_nodes, instances, info);
+}
+
+int32_t rodent_hip_build_motion_tlas(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
+                                     const struct RodentMotionInstanceDesc* descs, int32_t num_instances, int32_t max_leaf,
+                                     struct Node2* tlas_nodes, struct RodentMotionInstance* instances, void* scratch, int32_t* info_dev,
+                                     void* stream) {
+    return build_tlas(dev, nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_build_motion_tlas_sync(int32_t dev, const struct Node2* nodes, const struct RodentObject* objects, int32_t num_objects,
+                                          const struct RodentMotionInstanceDesc* descs, int32_t num_instances, int32_t max_leaf,
+                                          struct Node2* tlas_nodes, struct RodentMotionInstance* instances, int32_t* info) {
+    return build_tlas_sync(dev, rodent_hip_motion_tlas_scratch_bytes(num_instances), nodes, objects, num_objects, descs, num_instances,
+                           max_leaf, tlas_nodes, instances, info);
 }
 
 int64_t rodent_hip_refit_objects_plan(const struct RodentObject* objects, int32_t num_objects, const int32_t* listed,

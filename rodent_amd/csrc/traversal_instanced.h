@@ -1,5 +1,8 @@
 // traversal_instanced.h -- instanced scenes (include/rodent_instances.h; included by traversal.hip inside its namespace): a TLAS of Node2
 // records over RodentInstance records, each naming one object's BVH2 / Tri1 inside the packed arrays.  CPU model: tests/instance_model.py.
+// k_instanced_motion<ANY> is the same loop over RodentMotionInstance records (two placements each) with a time per ray: the loop is stated
+// once, instanced_loop, and the two kernels differ in how a record yields the object ray (StaticEnter, MotionEnter).  CPU model:
+// tests/motion_instance_model.py.
 //
 // k_instanced<ANY>: one ray per lane, one 64-ray chunk per one-wave workgroup; the while-while loop of the follow-up kernel (finish_launch)
 // on both levels, built from node2_step and leaf_tri1 as they stand.  One stack of the reference's 64 entries serves both levels,
@@ -21,12 +24,46 @@
 
 // InstanceStack (the 64 entries of one lane) and object_ray (the ray in an instance's object space): traversal_steps.h.
 
-template <bool ANY>
-__global__ __launch_bounds__(kWave) void k_instanced(const Node2* __restrict__ tlas, const RodentInstance* __restrict__ instances,
-                                                     const Node2* __restrict__ nodes, const Tri1* __restrict__ tris,
-                                                     const Ray1* __restrict__ rays, Hit1* __restrict__ hits,
-                                                     int* __restrict__ hit_instances, int n, Ctl* ctl) {
-    __shared__ int stack_lds[kStackCap * kWave];
+// How an instance record yields the object ray: the one difference between k_instanced and k_instanced_motion.  enter(j, i, ray, o, id)
+// reads record j for ray i, fills the object ray and id = {node_offset, tri_offset, instance_id, pad}, and returns whether the instance
+// is entered at all.
+struct StaticEnter {
+    const RodentInstance* instances;
+    __device__ __forceinline__ bool enter(int j, int, const RayX& ray, RayX& o, int4& id) const {
+        const float4* p = reinterpret_cast<const float4*>(instances + j);
+        const float4 w0 = p[0], w1 = p[1], w2 = p[2];
+        id = *reinterpret_cast<const int4*>(p + 3);                     // node_offset, tri_offset, instance_id, pad
+        o = object_ray(ray, w0, w1, w2);
+        return true;
+    }
+};
+
+// Seven 16-byte loads of the record's one cache line (its last 16 bytes are padding), the ray's time loaded again behind the same opaque index as the ray, 12 interpolations, the fp64
+// inverse of the build stage (instance_inverse.h), the skip test, object_ray.
+struct MotionEnter {
+    const RodentMotionInstance* instances;
+    const float* times;
+    __device__ __forceinline__ bool enter(int j, int i, const RayX& ray, RayX& o, int4& id) const {
+        const float4* p = reinterpret_cast<const float4*>(instances + j);
+        float4 r[6];
+        for (int k = 0; k < 6; k++) r[k] = p[k];
+        id = *reinterpret_cast<const int4*>(p + 6);                     // node_offset, tri_offset, instance_id, pad
+        const float m0[12] = {r[0].x, r[0].y, r[0].z, r[0].w, r[1].x, r[1].y, r[1].z, r[1].w, r[2].x, r[2].y, r[2].z, r[2].w};
+        const float m1[12] = {r[3].x, r[3].y, r[3].z, r[3].w, r[4].x, r[4].y, r[4].z, r[4].w, r[5].x, r[5].y, r[5].z, r[5].w};
+        float m[12], w[12];
+        lerp_affine(m0, m1, times[i], m);
+        if (invert_affine(m, w)) return false;                          // singular or non-finite at this ray's time: skipped, no flag
+        o = object_ray(ray, make_float4(w[0], w[1], w[2], w[3]), make_float4(w[4], w[5], w[6], w[7]),
+                       make_float4(w[8], w[9], w[10], w[11]));
+        return true;
+    }
+};
+
+// The loop of both kernels, stated once.
+template <bool ANY, class Enter>
+__device__ __forceinline__ void instanced_loop(const Node2* __restrict__ tlas, const Enter& in, const Node2* __restrict__ nodes,
+                                               const Tri1* __restrict__ tris, const Ray1* __restrict__ rays, Hit1* __restrict__ hits,
+                                               int* __restrict__ hit_instances, int n, Ctl* ctl, int* stack_lds) {
     const int i = blockIdx.x * kWave + threadIdx.x;
     if (i >= n) return;
     InstanceStack st{(lds_int*)stack_lds + threadIdx.x};
@@ -49,27 +86,27 @@ __global__ __launch_bounds__(kWave) void k_instanced(const Node2* __restrict__ t
             if (top < 0) j = ~top;                                      // a TLAS leaf: its continuation stays in slot ptr
             continue;
         }
-        const float4* p = reinterpret_cast<const float4*>(instances + j);
-        const float4 w0 = p[0], w1 = p[1], w2 = p[2];
-        const int4 id = *reinterpret_cast<const int4*>(p + 3);          // node_offset, tri_offset, instance_id, pad
-        RayX o = object_ray(ray, w0, w1, w2);
-        const Node2* onodes = nodes + id.x;
-        const Tri1* otris = tris + id.y;
-        HitAcc h{-1, 0.0f, 0.0f, 0.0f};
-        bool done = false;
-        int otop = 1; st.put(++ptr, 0);
-        if (ptr >= kStackCap) { overflow = true; break; }
-        while (otop != 0) {
-            otop = node2_step(onodes, otop, o, st, ptr);
+        RayX o;
+        int4 id;
+        if (in.enter(j, again, ray, o, id)) {
+            const Node2* onodes = nodes + id.x;
+            const Tri1* otris = tris + id.y;
+            HitAcc h{-1, 0.0f, 0.0f, 0.0f};
+            bool done = false;
+            int otop = 1; st.put(++ptr, 0);
             if (ptr >= kStackCap) { overflow = true; break; }
-            while (otop < 0) {
-                const int first = ~otop; otop = st.get(ptr); ptr--;
-                if (leaf_tri1<ANY>(otris, first, o, h)) { done = true; otop = 0; break; }
+            while (otop != 0) {
+                otop = node2_step(onodes, otop, o, st, ptr);
+                if (ptr >= kStackCap) { overflow = true; break; }
+                while (otop < 0) {
+                    const int first = ~otop; otop = st.get(ptr); ptr--;
+                    if (leaf_tri1<ANY>(otris, first, o, h)) { done = true; otop = 0; break; }
+                }
             }
+            if (h.id >= 0) { hit = h; hit_instance = id.z & 0x7FFFFFFF; }
+            if (overflow || (ANY && done)) break;
+            tmax = o.tmax;
         }
-        if (h.id >= 0) { hit = h; hit_instance = id.z & 0x7FFFFFFF; }
-        if (overflow || (ANY && done)) break;
-        tmax = o.tmax;
         j++;
         if (id.z < 0) {                                                 // the last instance of the leaf: on with its continuation
             top = st.get(ptr); ptr--;
@@ -79,4 +116,23 @@ __global__ __launch_bounds__(kWave) void k_instanced(const Node2* __restrict__ t
     if (overflow) __hip_atomic_store(ctl->host_err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     store_hit(hits, i, hit.id, hit.t, hit.u, hit.v);
     if (hit_instances) hit_instances[i] = hit_instance;
+}
+
+template <bool ANY>
+__global__ __launch_bounds__(kWave) void k_instanced(const Node2* __restrict__ tlas, const RodentInstance* __restrict__ instances,
+                                                     const Node2* __restrict__ nodes, const Tri1* __restrict__ tris,
+                                                     const Ray1* __restrict__ rays, Hit1* __restrict__ hits,
+                                                     int* __restrict__ hit_instances, int n, Ctl* ctl) {
+    __shared__ int stack_lds[kStackCap * kWave];
+    instanced_loop<ANY>(tlas, StaticEnter{instances}, nodes, tris, rays, hits, hit_instances, n, ctl, stack_lds);
+}
+
+template <bool ANY>
+__global__ __launch_bounds__(kWave) void k_instanced_motion(const Node2* __restrict__ tlas,
+                                                            const RodentMotionInstance* __restrict__ instances,
+                                                            const float* __restrict__ times, const Node2* __restrict__ nodes,
+                                                            const Tri1* __restrict__ tris, const Ray1* __restrict__ rays,
+                                                            Hit1* __restrict__ hits, int* __restrict__ hit_instances, int n, Ctl* ctl) {
+    __shared__ int stack_lds[kStackCap * kWave];
+    instanced_loop<ANY>(tlas, MotionEnter{instances, times}, nodes, tris, rays, hits, hit_instances, n, ctl, stack_lds);
 }

@@ -38,6 +38,12 @@ assert REFIT_RANGE.itemsize == 32
 assert (NODE2.itemsize, TRI1.itemsize, NODE4.itemsize, NODE8.itemsize, TRI4.itemsize,
         RAY1.itemsize, HIT1.itemsize) == (64, 48, 128, 256, 224, 32, 16)
 assert (OBJECT.itemsize, INSTANCE_DESC.itemsize, INSTANCE.itemsize) == (16, 64, 64)
+# moving instances: the placements at time 0 and at time 1
+MOTION_INSTANCE_DESC = np.dtype([("object_to_world0", "<f4", (12,)), ("object_to_world1", "<f4", (12,)), ("object", "<i4"),
+                                 ("instance_id", "<i4"), ("pad", "<i4", (6,))])
+MOTION_INSTANCE = np.dtype([("object_to_world0", "<f4", (12,)), ("object_to_world1", "<f4", (12,)), ("node_offset", "<i4"),
+                            ("tri_offset", "<i4"), ("instance_id", "<i4"), ("pad", "<i4"), ("pad2", "<i4", (4,))])
+assert (MOTION_INSTANCE_DESC.itemsize, MOTION_INSTANCE.itemsize) == (128, 128)
 
 _BLOCK_DTYPES = {BVH2_TRI1: (NODE2, TRI1), BVH4_TRI4: (NODE4, TRI4), BVH8_TRI4: (NODE8, TRI4)}
 

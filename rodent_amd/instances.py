@@ -10,6 +10,8 @@ include/rodent_instances.h; kernels: csrc/build_tlas.h, csrc/traversal_instanced
                                                                   # per-object gpubuild.build_bvh2, byte for byte
     slotted = build_objects(vertices, indices, rows, slots=True)  # ... each in a node slot of its own, so that
     rebuild_objects(slotted, [2, 0], moved_vertices, indices, rows[[2, 0]])   # rebuilds objects 2 and 0 where they lie (new topologies)
+    moving = build_motion_tlas(objects, transforms0, transforms1, object_ids)     # every copy placed at time 0 and at time 1 ...
+    hits, ids = trace_motion(objects, moving, rays, times)                        # ... and every ray traced at its own time
 
 The top-level hierarchy is a pure function of the objects' root boxes, the transforms and max_leaf, byte for byte.
 """
@@ -203,6 +205,99 @@ def download(tlas: Tlas):
     """(nodes NODE2, instances INSTANCE) host copies of a Tlas."""
     nodes = tlas.nodes[: tlas.num_nodes * F.NODE2.itemsize].cpu().numpy().view(F.NODE2).copy()
     instances = tlas.instances[: tlas.num_instances * F.INSTANCE.itemsize].cpu().numpy().view(F.INSTANCE).copy()
+    return nodes, instances
+
+
+# ---- moving instances: two placements per instance, a time per ray (the section "moving instances" of rodent_instances.h) -------------
+class MotionTlas(Tlas):
+    """A Tlas over moving instances: `instances` holds RodentMotionInstance records (both placements, in leaf order), the nodes bound
+    every placement with a time in [0, 1]."""
+
+    @property
+    def device_bytes(self):
+        return self.num_nodes * F.NODE2.itemsize + self.num_instances * F.MOTION_INSTANCE.itemsize
+
+
+def build_motion_tlas(objects: ObjectSet, transforms0, transforms1, object_ids, instance_ids=None, max_leaf=1, stream=None, scratch=None,
+                      out=None) -> MotionTlas:
+    """build_tlas for instances that move: object_ids[k] is placed by transforms0[k] at time 0 and by transforms1[k] at time 1 (both
+    object_to_world, 3 x 4 row-major; tensors on the device are taken without a host copy), and linearly between them, entry by entry.
+    Raises BuildError on invalid arguments and on the device's flags (an object index outside the table, a singular or non-finite
+    transform at either end).  scratch / out: as in build_tlas; `out` (a MotionTlas) is rebuilt in place and returned."""
+    _need_gpu()
+    dev, cuda = objects.dev, f"cuda:{objects.dev}"
+    if not 1 <= max_leaf <= MAX_LEAF:
+        raise BuildError(f"max_leaf = {max_leaf}: outside [1, 8]")
+    first = _descriptors(transforms0, object_ids, instance_ids, cuda)
+    n = first.shape[0]
+    t1 = transforms1 if isinstance(transforms1, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(transforms1, np.float32))
+    if t1.numel() != 12 * n:
+        raise ValueError(f"expected {n} (12,) or (3, 4) transforms at time 1, got shape {tuple(t1.shape)}")
+    desc = torch.zeros((n, 32), dtype=torch.int32, device=cuda)
+    desc[:, :12] = first[:, :12]
+    desc[:, 12:24] = t1.to(device=cuda, dtype=torch.float32).reshape(n, 12).contiguous().view(torch.int32)
+    desc[:, 24:26] = first[:, 12:14]
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    need = abi.lib().rodent_hip_motion_tlas_scratch_bytes(n)
+    if scratch is None and out is not None:
+        scratch = out.scratch
+    if scratch is None or scratch.numel() * scratch.element_size() < need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=cuda)
+    node_bytes, inst_bytes = max(1, n - 1) * F.NODE2.itemsize, n * F.MOTION_INSTANCE.itemsize
+    if out is None:
+        nodes = torch.empty(node_bytes, dtype=torch.uint8, device=cuda)
+        instances = torch.empty(inst_bytes, dtype=torch.uint8, device=cuda)
+    else:
+        nodes, instances = out.nodes, out.instances
+        if nodes.numel() < node_bytes or instances.numel() < inst_bytes:
+            raise ValueError("build_motion_tlas: the buffers of `out` are too small for these instances")
+    info = torch.empty(INFO_WORDS, dtype=torch.int32, device=cuda)
+    entry = "rodent_hip_build_motion_tlas"
+    words = _enqueue(entry, dev, stream, info, (objects.buffer, objects.table_dev, desc, scratch, nodes, instances),
+                     objects.nodes.data_ptr(), objects.table_dev.data_ptr(), objects.num_objects, desc.data_ptr(), n, int(max_leaf),
+                     nodes.data_ptr(), instances.data_ptr(), scratch.data_ptr())
+    if words[2]:
+        raise BuildError(f"{entry}: " + ", ".join(s for bit, s in _TLAS_FLAGS if words[2] & bit))
+    if out is None:
+        return MotionTlas(nodes, instances, n, words.copy(), scratch, dev)
+    out.num_instances, out.scratch = n, scratch
+    out.info, out.num_nodes, out.depth = words.copy(), int(words[0]), int(words[1])
+    return out
+
+
+def trace_motion_async(objects: ObjectSet, tlas: MotionTlas, rays_dev, times_dev, hits_dev, instances_dev, num_rays, any_hit=False,
+                       stream=None):
+    """trace_async through a MotionTlas: `times_dev` holds one float32 per ray, the time at which that ray sees every instance."""
+    if stream is None:
+        stream = torch.cuda.current_stream(objects.dev)
+    abi.lib().hip_traverse_motion_instanced_bvh2_tri1_async(
+        objects.dev, tlas.nodes.data_ptr(), tlas.instances.data_ptr(), objects.nodes.data_ptr(), objects.tris.data_ptr(),
+        rays_dev.data_ptr(), times_dev.data_ptr(), hits_dev.data_ptr(), None if instances_dev is None else instances_dev.data_ptr(),
+        int(num_rays), int(any_hit), C.c_void_p(stream.cuda_stream))
+
+
+def trace_motion(objects: ObjectSet, tlas: MotionTlas, rays: np.ndarray, times, any_hit=False):
+    """Synchronous convenience wrapper: host rays and their times (one float32 each) in, (Hit1 array, int32 instance ids) out."""
+    _need_gpu()
+    dev, n = objects.dev, len(rays)
+    times = np.ascontiguousarray(times, np.float32)
+    if times.shape != (n,):
+        raise ValueError(f"trace_motion: expected {n} times, got shape {times.shape}")
+    rays_dev = abi.to_device(rays, dev)
+    times_dev = torch.from_numpy(times if n else np.zeros(1, np.float32)).to(f"cuda:{dev}")
+    hits_dev = torch.zeros(max(n, 1) * F.HIT1.itemsize, dtype=torch.uint8, device=f"cuda:{dev}")
+    ids_dev = torch.zeros(max(n, 1), dtype=torch.int32, device=f"cuda:{dev}")
+    torch.cuda.synchronize(dev)
+    fn = abi.lib().hip_occluded_motion_instanced_bvh2_tri1 if any_hit else abi.lib().hip_intersect_motion_instanced_bvh2_tri1
+    fn(dev, tlas.nodes.data_ptr(), tlas.instances.data_ptr(), objects.nodes.data_ptr(), objects.tris.data_ptr(), rays_dev.data_ptr(),
+       times_dev.data_ptr(), hits_dev.data_ptr(), ids_dev.data_ptr(), n)
+    return abi.from_device(hits_dev, F.HIT1)[:n], ids_dev.cpu().numpy()[:n]
+
+
+def download_motion(tlas: MotionTlas):
+    """(nodes NODE2, instances MOTION_INSTANCE) host copies of a MotionTlas."""
+    nodes = tlas.nodes[: tlas.num_nodes * F.NODE2.itemsize].cpu().numpy().view(F.NODE2).copy()
+    instances = tlas.instances[: tlas.num_instances * F.MOTION_INSTANCE.itemsize].cpu().numpy().view(F.MOTION_INSTANCE).copy()
     return nodes, instances
 
 
