@@ -266,6 +266,76 @@ void    rodent_hip_scene_deform_device(int32_t dev, const float* vertices_dev, c
  * fewer nodes than D holds.  Never aborts on a flag; with one raised the tables are undefined until a sound call.  Before the first
  * call: 0, a sound refit's words and the last TLAS build's. */
 int32_t rodent_hip_scene_deform_status(int32_t dev, int32_t* refit_info, int32_t* tlas_info);
+/* ---- moving instances in the renderer: a time per path through the motion TLAS of rodent_instances.h ----
+ * CPU model of everything below: tests/motion_scene_model.py (over tests/motion_instance_model.py, tests/instanced_scene_model.py and the
+ * flat oracle).  A moving scene is an instanced scene whose instances carry TWO placements, M0 at time 0 and M1 at time 1
+ * (RodentMotionInstanceDesc); every path draws one time in the shutter interval and sees every instance where that time puts it.
+ *
+ * The time costs no stream word.  With a moving scene loaded,
+ *   PrimaryStream::depth[i]    holds depth | ubits << RODENT_MOTION_DEPTH_BITS: bits 0 .. 7 the depth, bits 8 .. 30 the 23 mantissa bits of
+ *                              the path's shutter sample u = randf(&rnd) = ubits * 2^-23 (exactly), bit 31 zero.  Every kernel that
+ *                              copies a primary ray (the sort's and the compaction's k_scatter, the shader's fused compaction) carries
+ *                              the word as it stands.
+ *   SecondaryStream::prim_id[i] holds the shadow ray's time as float bits (no other kernel of the library reads or writes that array).
+ * Shutter: t = fminf(close, open + (close - open) * u), the difference, the product and the sum each rounded in fp32, no fma; so
+ * open <= t <= close, inside [0, 1], where rodent_instances.h's motion boxes contain; (0, 1), the default, gives t == u bit for bit.
+ * Every kernel that needs t recomputes it from ubits and the pair.
+ * Generation: after the two draws of the pixel sample a THIRD randf(&rnd) is u; the stored rnd is the state behind that draw and the
+ * stored depth word is ubits << 8.  Pixel, origin, direction, tmin, tmax are the flat generation's.
+ * Path length: the length in effect is min(requested, RODENT_MOTION_DEPTH_MASK) while a moving scene is loaded (depth never exceeds it,
+ * so depth + 1 never carries into the time bits); a flat or static instanced scene loaded afterwards gets what was requested again.
+ * Traversal (k_trace_instanced_motion<false|true>): k_trace_instanced's loop and stream I/O; for record j and a ray at time t (from
+ * depth[i] >> 8 by the shutter rule in the closest-hit pass, prim_id[i] as float bits in the shadow pass) m = lerp(M0, M1, t) and
+ * w = invert(m) by rodent_instances.h's rules; an instance whose interpolated matrix the inverse refuses is skipped for that ray: nothing
+ * is pushed, tmax and the hit stay.
+ * Shading a moving hit: the slot j from the per-ray slot array, the RodentMotionInstance at j, t from the depth word,
+ * w = invert(lerp(M0, M1, t)) -- the function and the inputs of the traversal, hence its 12 floats --, then the instanced shading rules
+ * with w and bases[k].  The depth test uses word & 0xFF; the ray that goes on gets (depth + 1) | ubits << 8, the shadow ray the bits of
+ * t in prim_id.
+ * Lights stay static: an instance whose object has num_lights > 0 must have object_to_world0 == object_to_world1 byte for byte
+ * (RODENT_SCENE_ERR_MOVING_LIGHT otherwise).  The world light table is the static one derived from M0: the corners by the world-box rule
+ * under M0, n = normalize(N(n_obj)) with w = invert(M0) computed where the lights are derived (a motion record stores no inverse),
+ * inv_area and colour as before.  The TRAVERSAL reaches such an emitter through lerp(M0, M0, t) = s * m + t * m, which equals M0 only up
+ * to the rounding of that sum (at t = 0 and t = 1 exactly): an emitter's surface as rays hit it and its light record as next-event
+ * estimation samples it may differ in the last bits.  The model restates exactly this.
+ * Derived tables: slot_of, bases, light_owner as for an instanced scene; the per-ray slot array is the same one.
+ * Options in effect are those of an instanced scene (streaming mapping, no persistent kernels, no refill, no sort); overlap and all three
+ * fused_compact modes work.  The stage-level entries (hip_generate_rays, hip_traverse_primary / _secondary / _streams, hip_shade,
+ * hip_shade_compact, hip_compact_primary) work on a moving scene through the same branches, on streams that hold these words.
+ * rodent_hip_scene_set_transforms, _scene_instances, _scene_deform_* and _scene_refit* treat a moving scene
+ * as they treat "no instanced scene" (abort, or RODENT_SCENE_ERR_NOT_INSTANCED): geometry that deforms under motion is not built.
+ *
+ * rodent_hip_scene_create_motion: rodent_hip_scene_create_instanced with RodentMotionInstanceDesc records and rodent_hip_build_motion_tlas
+ * (max_leaf 1): the same refusals in the same order, then RODENT_SCENE_ERR_MOVING_LIGHT, all on the host, leaving the loaded scene alone;
+ * a device flag (either endpoint singular: RODENT_TLAS_BAD_TRANSFORM) returns RODENT_SCENE_ERR_DEVICE, the flags through
+ * rodent_hip_scene_create_flags. */
+#define RODENT_MOTION_DEPTH_BITS       8
+#define RODENT_MOTION_DEPTH_MASK       0xFF
+#define RODENT_SCENE_ERR_MOVING_LIGHT -29   /* an instance of an object with lights has object_to_world0 != object_to_world1 */
+#define RODENT_SCENE_ERR_SHUTTER      -30   /* not 0 <= open <= close <= 1 (a NaN included) */
+int32_t rodent_hip_scene_create_motion(int32_t dev, const struct RodentSceneDesc* desc, const struct RodentObjectRange* objects,
+                                       int32_t num_objects, const struct RodentMotionInstanceDesc* instances, int32_t num_instances,
+                                       const struct RodentBuildOptions* opt);
+/* Both placements moved: m0_dev / m1_dev hold n x 12 floats each on the DEVICE (they may be the same pointer).  The launch list and the
+ * promises of rodent_hip_scene_set_transforms: the matrices into the descriptor array, rodent_hip_build_motion_tlas into the scene's
+ * buffers, slot_of, the world lights (from M0), the event; nothing allocated, no host copy, no wait.  rodent_hip_scene_transforms_status
+ * serves it too.  The static-light rule cannot be checked without a host copy: the CALLER keeps the two keys of every emitter equal.  No
+ * moving scene loaded or a NULL pointer aborts with a message. */
+void    rodent_hip_scene_set_motion_transforms(int32_t dev, const float* m0_dev, const float* m1_dev, void* stream);
+/* DEVICE pointers and counts of a moving scene's tables, for tests and tools (as rodent_hip_scene_instances).  No moving scene aborts. */
+struct RodentSceneMotionInstances {
+    struct Node2* tlas_nodes; struct RodentMotionInstance* instances; struct RodentMotionInstanceDesc* descs; struct RodentObject* objects;
+    int32_t* slot_of; int32_t* bases /* int2 per instance */; int32_t* light_owner; struct RodentLight *lights, *object_lights;
+    int32_t* ray_slots; int32_t* tlas_info;
+    int32_t num_instances, num_objects, num_tlas_nodes, num_lights, num_object_lights, ray_slot_capacity;
+};
+void    rodent_hip_scene_motion_instances(int32_t dev, struct RodentSceneMotionInstances* out);
+/* The shutter of device `dev` (default (0, 1); rodent_hip_render_defaults restores it).  Anything but 0 <= open <= close <= 1 returns
+ * RODENT_SCENE_ERR_SHUTTER and changes nothing.  Without a moving scene it has no effect. */
+int32_t rodent_hip_render_shutter(int32_t dev, float open, float close);
+void    rodent_hip_render_shutter_in_effect(int32_t dev, float out[2]);
+/* The path length the next frame uses: min(requested, 255) with a moving scene loaded, else what rodent_hip_render_config was given. */
+int32_t rodent_hip_render_max_path_len_in_effect(int32_t dev);
 void    rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len);   /* defaults 4 / 64 (converter.cpp:1007-1012) */
 /* 0 = streaming wavefront loop (src/render/mapping_gpu.impala:308-369), 1 = persistent-threads megakernel
  * (mapping_gpu.impala:371-474; the reference selects it at configure time with the converter target

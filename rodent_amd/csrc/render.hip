@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "device_buffer.h"
@@ -92,6 +93,9 @@ __device__ __forceinline__ v3 emit_sample(const CameraDev& cam, int iter, int fi
 // Pixels of a call: [first_pixel, ...) contiguous (tile_pixels == 0: a row band), or interleaved row tiles -- local pixel q is pixel
 // first_pixel + (q / tile_pixels) * stride_pixels + q % tile_pixels (rodent_hip_render_tiles: the film's row tiles dealt round-robin to the
 // GPUs).
+// MOTION (a moving scene, rodent_render.h): a third draw behind the pixel sample's two is the path's shutter sample u; the stored rnd is
+// the state behind it and the depth word holds u's 23 mantissa bits above the depth 0.  k_generate<false> is the kernel as it was.
+template <bool MOTION = false>
 __global__ __launch_bounds__(kBlock) void k_generate(PrimaryStream p, int first_dst, int first_ray_id, int num_rays, CameraDev cam,
                                                       int iter, int film_w, int film_h, int first_pixel, int spp, int tile_pixels,
                                                           int stride_pixels,
@@ -117,10 +121,14 @@ __global__ __launch_bounds__(kBlock) void k_generate(PrimaryStream p, int first_
     p.rays.org_x[dst] = cam.eye[0]; p.rays.org_y[dst] = cam.eye[1]; p.rays.org_z[dst] = cam.eye[2];
     p.rays.dir_x[dst] = d.x; p.rays.dir_y[dst] = d.y; p.rays.dir_z[dst] = d.z;
     p.rays.tmin[dst] = 0.0f; p.rays.tmax[dst] = FLT_MAX_REF;
-    p.rnd[dst] = rnd; p.mis[dst] = 0.0f; p.contrib_r[dst] = 1.0f; p.contrib_g[dst] = 1.0f; p.contrib_b[dst] = 1.0f; p.depth[dst] = 0;
+    int depth_word = 0;
+    if constexpr (MOTION) depth_word = (int)(xorshift(&rnd) & 0x7FFFFFu) << RODENT_MOTION_DEPTH_BITS;       // randf's mantissa bits
+    p.rnd[dst] = rnd; p.mis[dst] = 0.0f; p.contrib_r[dst] = 1.0f; p.contrib_g[dst] = 1.0f; p.contrib_b[dst] = 1.0f;
+    p.depth[dst] = depth_word;
 }
 
 // The other stages' device code, one header each, in the order the kernels are emitted.
+#include "instance_inverse.h"        // the fp64 inverse and the interpolation a moving scene's kernels take per ray (render_motion.h)
 #include "render_trace.h"
 
 __global__ void k_copy_int(const int* src, int* dst) { *dst = *src; }
@@ -130,6 +138,7 @@ __global__ void k_copy_int(const int* src, int* dst) { *dst = *src; }
 #include "render_sort.h"
 #include "render_update.h"
 #include "render_instanced.h"
+#include "render_motion.h"
 
 // ---------------------------------------------------------------------------------------------
 // Host side: per-device state (interface.cpp:324-339), stream slabs, the streaming loop
@@ -158,6 +167,11 @@ struct DevScene {
     RodentLight *object_lights = nullptr, *world_lights = nullptr;
     int num_instances = 0, num_objects = 0, num_object_lights = 0;
     size_t ray_slot_cap = 0;
+    // A MOVING scene (rodent_hip_scene_create_motion) is an instanced one (`instanced` is set: the options in effect, the per-ray slot
+    // array and the launchers' branch are shared) whose records are motion records: `motion_descs` / `motion_instances` stand in for
+    // `descs` / `instances`, which stay null, and the kernels take motion_dev() instead of `inst`.
+    bool motion = false;
+    RodentMotionInstanceDesc* motion_descs = nullptr; RodentMotionInstance* motion_instances = nullptr;
     // Host copies of the objects' ranges and of the RodentObject table, and the deforming set D of rodent_hip_scene_deform_prepare: its
     // range table, the forest refit's scratch with its info words behind it, the vertices D's triangles name with their incidence
     // lists (vertex verts[j]: corner_tri[corner_first[j] .. corner_first[j + 1])), its bound lights {object light, triangle}.  In
@@ -178,6 +192,7 @@ struct RenderDevice {
     int dev = 0;
     DevScene scene;
     int spp = 4, max_path_len = 64;
+    float shutter[2] = {0.0f, 1.0f};           // a moving scene's paths draw their times in [open, close] (rodent_hip_render_shutter)
     int capacity = 0;                          // rays per stream; 0 = default (env_capacity())
     // 1 = sort hit rays by material before shading (mapping_gpu.impala:166-221), 0 = shade in stream order (default: the shader is ONE
     // table-driven kernel, not a kernel per material, and the sort costs more than the divergence it removes -- 5 ... 22 % of the frame on
@@ -259,6 +274,7 @@ void render_defaults(RenderDevice& r) {
     r.sort = 0; r.overlap = 1; r.fused_sort = 0; r.fused_compact = 2; r.mega_joint = 0; r.lds_image = 1; r.trace_persistent_request = -1;
     r.mapping_request = -1; r.capacity = 0; r.trace_refill_request[0] = r.trace_refill_request[1] = -1;
     r.persist_min_rays = kPersistMinRays;
+    r.shutter[0] = 0.0f; r.shutter[1] = 1.0f;
     env_int("RODENT_HIP_HIT_AOS", 0, 1, r.hit_records_aos); env_int("RODENT_HIP_SORT", 0, 1, r.sort);
     env_int("RODENT_HIP_OVERLAP", 0, 1, r.overlap); env_int("RODENT_HIP_FUSED_SORT", 0, 1, r.fused_sort);
     env_int("RODENT_HIP_FUSED_COMPACT", 0, 2, r.fused_compact); env_int("RODENT_HIP_LDS_IMAGE", 0, 1, r.lds_image);
@@ -285,6 +301,17 @@ void render_defaults(RenderDevice& r) {
 
 // what the next frame does about the sort by material: the per-ray slot array of an instanced scene is not moved by the sort
 int sort_in_effect(const RenderDevice& r) { return r.scene.instanced ? 0 : r.sort; }
+// ... and about the path length: a moving scene's depth word keeps eight bits for the depth
+int path_len_in_effect(const RenderDevice& r) {
+    return r.scene.motion ? std::min(r.max_path_len, RODENT_MOTION_DEPTH_MASK) : r.max_path_len;
+}
+// the ray generation of the scene that is loaded
+decltype(&k_generate<false>) generate_kernel(const RenderDevice& r) { return r.scene.motion ? k_generate<true> : k_generate<false>; }
+// what the kernels of a moving scene take beside SceneDev: the scene's tables and the shutter as it is now
+MotionDev motion_dev(const RenderDevice& r) {
+    const DevScene& s = r.scene;
+    return MotionDev{s.tlas_nodes, s.motion_instances, s.bases, s.inst.ray_slots, r.shutter[0], r.shutter[1]};
+}
 
 RenderDevice& rdev(int dev) {
     if (dev < 0 || dev >= 16) { fprintf(stderr, "rodent_hip: invalid device index %d\n", dev); abort(); }
@@ -417,15 +444,18 @@ template <typename... Args> void launch_k_shade(hipStream_t stream, int b, int r
     else if (b == 512) hipLaunchKernelGGL((k_shade<512, false>), dim3(blocks), dim3(512), 0, stream, args...);
     else hipLaunchKernelGGL((k_shade<1024, false>), dim3(blocks), dim3(1024), 0, stream, args...);
 }
-template <typename... Args> void launch_k_shade_instanced(hipStream_t stream, int b, int rays, const InstancedDev& inst, Args... args) {
+// (Dev: InstancedDev, or MotionDev for a moving scene)
+template <typename Dev, typename... Args> void launch_k_shade_instanced(hipStream_t stream, int b, int rays, const Dev& inst,
+                                                                        Args... args) {
     const int blocks = (rays + b - 1) / b;
-    if (b == 256) hipLaunchKernelGGL((k_shade<256, true, InstancedDev>), dim3(blocks), dim3(256), 0, stream, args..., inst);
-    else if (b == 512) hipLaunchKernelGGL((k_shade<512, true, InstancedDev>), dim3(blocks), dim3(512), 0, stream, args..., inst);
-    else hipLaunchKernelGGL((k_shade<1024, true, InstancedDev>), dim3(blocks), dim3(1024), 0, stream, args..., inst);
+    if (b == 256) hipLaunchKernelGGL((k_shade<256, true, Dev>), dim3(blocks), dim3(256), 0, stream, args..., inst);
+    else if (b == 512) hipLaunchKernelGGL((k_shade<512, true, Dev>), dim3(blocks), dim3(512), 0, stream, args..., inst);
+    else hipLaunchKernelGGL((k_shade<1024, true, Dev>), dim3(blocks), dim3(1024), 0, stream, args..., inst);
 }
 // the shader of the scene that is loaded
 template <typename... Args> void launch_shader(RenderDevice& r, hipStream_t stream, int b, int rays, Args... args) {
-    if (r.scene.instanced) launch_k_shade_instanced(stream, b, rays, r.scene.inst, args...);
+    if (r.scene.motion) launch_k_shade_instanced(stream, b, rays, motion_dev(r), args...);
+    else if (r.scene.instanced) launch_k_shade_instanced(stream, b, rays, r.scene.inst, args...);
     else launch_k_shade(stream, b, rays, args...);
 }
 // The per-ray slot array of an instanced scene: at least n ints, and never fewer than the device's stream slabs hold rays, so that a
@@ -459,6 +489,20 @@ struct ShadowPass { const SecondaryStream* s = nullptr; const int* size_ptr = nu
 // An instanced scene: one launch per pass, no follow-up kernel (render_instanced.h).
 void launch_trace_instanced(RenderDevice& r, hipStream_t stream, const ClosestPass& c, const ShadowPass& sh) {
     const DevScene& s = r.scene;
+    if (s.motion) {                                      // a moving scene: the same two launches over the motion records
+        if (c.p) {
+            ensure_ray_slots(r, (size_t)c.n);
+            r.trace_kernel = "k_trace_instanced_motion<false>";
+            hipLaunchKernelGGL(k_trace_instanced_motion<false>, dim3((c.n + kWave - 1) / kWave), dim3(kWave), 0, stream, s.dev,
+                motion_dev(r), *c.p, SecondaryStream{}, (const int*)nullptr, c.n, (float*)nullptr, 0.0f, r.counters, r.ctl + 2, r.ctl + 6);
+        }
+        if (sh.s) {
+            r.trace_kernel = "k_trace_instanced_motion<true>";
+            hipLaunchKernelGGL(k_trace_instanced_motion<true>, dim3((sh.max_n + kWave - 1) / kWave), dim3(kWave), 0, stream, s.dev,
+                motion_dev(r), PrimaryStream{}, *sh.s, sh.size_ptr, sh.max_n, r.film, sh.inv_spp, r.counters, r.ctl + 2, (int*)nullptr);
+        }
+        return;
+    }
     if (c.p) {
         ensure_ray_slots(r, (size_t)c.n);
         r.trace_kernel = "k_trace_instanced<false>";
@@ -657,7 +701,7 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
             // (d_alive was zeroed by the primary pass's follow-up kernel, k_trace_deep<false>)
         }
         launch_shader(r, stream, shade_block(), blocks * kBlock, r.scene.dev, from, to, perm, sec, size_ptr, n_value, r.film, inv_spp,
-            r.max_path_len, unsorted,
+            path_len_in_effect(r), unsorted,
                        fused ? (r.fused_compact == 2 ? kScanAtomic : r.scan.ptr) : (unsigned*)nullptr, d_alive);
     };
     while (id < num_rays || size > 0) {
@@ -665,7 +709,7 @@ void render_rows(RenderDevice& r, const Settings* settings, int iter, int y0, in
         const int survivors = size;
         if (size < kCapacity && id < num_rays) {                                         // regenerate (mapping_gpu.impala:332-336)
             const int n = (int)std::min<long long>(num_rays - id, kCapacity - size);
-            hipLaunchKernelGGL(k_generate, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, *primary, size, (int)id, n, cam, iter,
+            hipLaunchKernelGGL(generate_kernel(r), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, *primary, size, (int)id, n, cam, iter,
                                r.film_w, r.film_h, first_pixel, r.spp, tile_rows * r.film_w, stride_rows * r.film_w, block,
                                    tile_rows > 0 ? tile_rows : y1 - y0);
             id += n; size += n; generated += n;
@@ -1064,9 +1108,17 @@ DevScene& flat_scene(int32_t dev, const char* entry) {
         "rodent_hip_scene_set_transforms)\n", entry, dev); abort(); }
     return s;
 }
+// (the static-instance entries: a moving scene is "no instanced scene" to them)
 DevScene& instanced_scene(int32_t dev, const char* entry) {
     DevScene& s = loaded_scene(dev, entry);
-    if (!s.instanced) { fprintf(stderr, "rodent_hip: %s: the scene on device %d is not instanced (rodent_hip_scene_create_instanced)\n",
+    if (!s.instanced || s.motion) {
+        fprintf(stderr, "rodent_hip: %s: the scene on device %d is not instanced (rodent_hip_scene_create_instanced)\n", entry, dev);
+        abort(); }
+    return s;
+}
+DevScene& motion_scene(int32_t dev, const char* entry) {
+    DevScene& s = loaded_scene(dev, entry);
+    if (!s.motion) { fprintf(stderr, "rodent_hip: %s: the scene on device %d has no moving instances (rodent_hip_scene_create_motion)\n",
         entry, dev); abort(); }
     return s;
 }
@@ -1242,11 +1294,23 @@ void rodent_hip_scene_bvh(int32_t dev, const Node2** nodes, const Tri1** tris, i
 
 // The tables an instanced scene derives from its matrices, enqueued on `stream`: the TLAS and the instance array, slot_of, the world
 // lights (rodent_hip_scene_create_instanced, rodent_hip_scene_set_transforms).  Returns rodent_hip_build_tlas's status.
+// A moving scene: rodent_hip_build_motion_tlas and the motion forms of the two kernels (the world lights from M0).
 static int32_t derive_instanced(int32_t dev, DevScene& s, hipStream_t stream) {
+    const auto blocks = [](int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
+    if (s.motion) {
+        const int32_t rc = rodent_hip_build_motion_tlas(dev, s.dev.nodes, s.objects, s.num_objects, s.motion_descs, s.num_instances, 1,
+                                                        s.tlas_nodes, s.motion_instances, s.tlas_scratch, s.tlas_info, stream);
+        if (rc != RODENT_BUILD_OK) return rc;
+        hipLaunchKernelGGL(k_motion_slot_of, blocks(s.num_instances), dim3(kBlock), 0, stream, s.motion_instances, s.num_instances,
+                           s.slot_of);
+        hipLaunchKernelGGL(k_motion_world_lights, blocks(s.dev.num_lights), dim3(kBlock), 0, stream, s.motion_descs, s.light_owner,
+                           s.bases, s.object_lights, s.dev.num_lights, s.world_lights);
+        HIP_CHECK(hipGetLastError());
+        return rc;
+    }
     const int32_t rc = rodent_hip_build_tlas(dev, s.dev.nodes, s.objects, s.num_objects, s.descs, s.num_instances, 1, s.tlas_nodes,
                                              s.instances, s.tlas_scratch, s.tlas_info, stream);
     if (rc != RODENT_BUILD_OK) return rc;
-    const auto blocks = [](int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
     hipLaunchKernelGGL(k_slot_of, blocks(s.num_instances), dim3(kBlock), 0, stream, s.instances, s.num_instances, s.slot_of);
     hipLaunchKernelGGL(k_world_lights, blocks(s.dev.num_lights), dim3(kBlock), 0, stream, s.descs, s.instances, s.slot_of, s.light_owner,
                        s.bases, s.object_lights, s.dev.num_lights, s.world_lights);
@@ -1254,8 +1318,14 @@ static int32_t derive_instanced(int32_t dev, DevScene& s, hipStream_t stream) {
     return rc;
 }
 
-int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d, const RodentObjectRange* objects, int32_t num_objects,
-                                          const RodentInstanceDesc* instances, int32_t num_instances, const RodentBuildOptions* opt_) {
+} // extern "C"
+
+// rodent_hip_scene_create_instanced (Desc = RodentInstanceDesc) and rodent_hip_scene_create_motion (RodentMotionInstanceDesc): one
+// creation; what differs is the record types, the top-level builder behind derive_instanced and the moving scene's one more refusal.
+template <typename Desc>
+static int32_t create_instanced_scene(int32_t dev, const RodentSceneDesc* d, const RodentObjectRange* objects, int32_t num_objects,
+                                      const Desc* instances, int32_t num_instances, const RodentBuildOptions* opt_) {
+    constexpr bool kMotion = std::is_same<Desc, RodentMotionInstanceDesc>::value;
     const RodentBuildOptions default_opt{2, 0, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
     const RodentBuildOptions* opt = opt_ ? opt_ : &default_opt;
     // ---- the refusals: all on the host tables, before anything is enqueued or the current scene touched ----
@@ -1302,6 +1372,11 @@ int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d,
     }
     if (world_lights < 1) return RODENT_SCENE_ERR_NO_LIGHT;
     if (world_lights > 0x7FFFFFFF) return RODENT_SCENE_ERR_COUNTS;
+    if constexpr (kMotion)                               // lights stay static: an emitter's two keys are equal byte for byte
+        for (int32_t k = 0; k < num_instances; k++)
+            if (objects[instances[k].object].num_lights > 0
+                && std::memcmp(instances[k].object_to_world0, instances[k].object_to_world1, sizeof(float) * 12) != 0)
+                return RODENT_SCENE_ERR_MOVING_LIGHT;
 
     // ---- from here on the device's scene is the new one, or none ----
     RenderDevice& r = rdev(dev);
@@ -1420,27 +1495,33 @@ int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d,
     s.object_table = table;
     s.object_ranges.assign(objects, objects + num_objects);
     // descriptors (ids = indices), bases and light owners: fixed for the scene's life
-    std::vector<RodentInstanceDesc> descs(instances, instances + num_instances);
+    std::vector<Desc> descs(instances, instances + num_instances);
     std::vector<int2> bases((size_t)num_instances);
     std::vector<int> owner((size_t)world_lights);
     int32_t light_base = 0;
     for (int32_t k = 0; k < num_instances; k++) {
-        descs[k].instance_id = k; descs[k].pad[0] = descs[k].pad[1] = 0;
+        descs[k].instance_id = k;
+        for (int32_t& word : descs[k].pad) word = 0;
         const RodentObjectRange& o = objects[descs[k].object];
         bases[k] = make_int2(o.first_tri, light_base - o.first_light);
         for (int32_t j = 0; j < o.num_lights; j++) owner[(size_t)light_base + j] = k;
         light_base += o.num_lights;
     }
-    s.descs = upload(s, descs.data(), descs.size());
+    s.motion = kMotion;
+    if constexpr (kMotion) s.motion_descs = upload(s, descs.data(), descs.size());
+    else s.descs = upload(s, descs.data(), descs.size());
     s.bases = upload(s, bases.data(), bases.size());
     s.light_owner = upload(s, owner.data(), owner.size());
     const auto device_block = [&](size_t bytes) { char* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
         HIP_CHECK(hipMemset(p, 0, std::max<size_t>(bytes, 16))); s.allocs.push_back(p); return p; };
     s.tlas_nodes = reinterpret_cast<Node2*>(device_block(sizeof(Node2) * (size_t)std::max(1, num_instances - 1)));
-    s.instances = reinterpret_cast<RodentInstance*>(device_block(sizeof(RodentInstance) * (size_t)num_instances));
+    if constexpr (kMotion)
+        s.motion_instances = reinterpret_cast<RodentMotionInstance*>(device_block(sizeof(RodentMotionInstance) * (size_t)num_instances));
+    else s.instances = reinterpret_cast<RodentInstance*>(device_block(sizeof(RodentInstance) * (size_t)num_instances));
     s.slot_of = reinterpret_cast<int*>(device_block(sizeof(int) * (size_t)num_instances));
     s.world_lights = reinterpret_cast<RodentLight*>(device_block(sizeof(RodentLight) * (size_t)world_lights));
-    s.tlas_scratch = device_block((size_t)std::max<int64_t>(rodent_hip_tlas_scratch_bytes(num_instances), 0));
+    s.tlas_scratch = device_block((size_t)std::max<int64_t>(
+        kMotion ? rodent_hip_motion_tlas_scratch_bytes(num_instances) : rodent_hip_tlas_scratch_bytes(num_instances), 0));
     s.tlas_info = reinterpret_cast<int32_t*>(device_block(4 * RODENT_BUILD_INFO_WORDS));
     s.num_instances = num_instances; s.num_objects = num_objects; s.num_object_lights = d->num_lights;
     s.dev.lights = s.world_lights;
@@ -1461,7 +1542,55 @@ int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d,
     return RODENT_SCENE_OK;
 }
 
+extern "C" {
+
+int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d, const RodentObjectRange* objects, int32_t num_objects,
+                                          const RodentInstanceDesc* instances, int32_t num_instances, const RodentBuildOptions* opt) {
+    return create_instanced_scene(dev, d, objects, num_objects, instances, num_instances, opt);
+}
+
+int32_t rodent_hip_scene_create_motion(int32_t dev, const RodentSceneDesc* d, const RodentObjectRange* objects, int32_t num_objects,
+                                       const RodentMotionInstanceDesc* instances, int32_t num_instances, const RodentBuildOptions* opt) {
+    return create_instanced_scene(dev, d, objects, num_objects, instances, num_instances, opt);
+}
+
 int32_t rodent_hip_scene_create_flags(int32_t dev) { return rdev(dev).create_flags; }
+
+void rodent_hip_scene_set_motion_transforms(int32_t dev, const float* m0_dev, const float* m1_dev, void* stream_) {
+    DevScene& s = motion_scene(dev, "rodent_hip_scene_set_motion_transforms");
+    RenderDevice& r = rdev(dev);
+    if (!m0_dev || !m1_dev) { fprintf(stderr, "rodent_hip: rodent_hip_scene_set_motion_transforms: NULL matrices\n"); abort(); }
+    HIP_CHECK(hipSetDevice(dev));
+    if (!r.ev_refit) HIP_CHECK(hipEventCreateWithFlags(&r.ev_refit, hipEventDisableTiming));
+    hipStream_t stream = (hipStream_t)stream_;
+    // behind the last move, whichever stream it took; frames need no wait (rodent_hip_scene_refit_device says why)
+    if (s.refit_enqueued) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_refit, 0));
+    hipLaunchKernelGGL(k_motion_instance_matrices, dim3((unsigned)((24 * s.num_instances + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                       m0_dev, m1_dev, s.num_instances, s.motion_descs);
+    const int32_t rc = derive_instanced(dev, s, stream);
+    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: top-level rebuild refused (%d)\n", rc); abort(); }
+    HIP_CHECK(hipEventRecord(r.ev_refit, stream));
+    s.refit_enqueued = true;
+}
+
+void rodent_hip_scene_motion_instances(int32_t dev, RodentSceneMotionInstances* out) {
+    DevScene& s = motion_scene(dev, "rodent_hip_scene_motion_instances");
+    if (!out) return;
+    ensure_ray_slots(rdev(dev), 0);
+    *out = RodentSceneMotionInstances{s.tlas_nodes, s.motion_instances, s.motion_descs, s.objects, s.slot_of,
+        reinterpret_cast<int32_t*>(s.bases), s.light_owner, s.world_lights, s.object_lights, s.inst.ray_slots, s.tlas_info, s.num_instances,
+        s.num_objects, std::max(1, s.num_instances - 1), s.dev.num_lights, s.num_object_lights, (int32_t)s.ray_slot_cap};
+}
+
+int32_t rodent_hip_render_shutter(int32_t dev, float open, float close) {
+    RenderDevice& r = rdev(dev);
+    if (!(0.0f <= open && open <= close && close <= 1.0f)) return RODENT_SCENE_ERR_SHUTTER;      // (a NaN fails a comparison)
+    r.shutter[0] = open + 0.0f; r.shutter[1] = close + 0.0f;                                     // (a -0 becomes +0)
+    return RODENT_SCENE_OK;
+}
+void rodent_hip_render_shutter_in_effect(int32_t dev, float out[2]) { const RenderDevice& r = rdev(dev);
+    out[0] = r.shutter[0]; out[1] = r.shutter[1]; }
+int32_t rodent_hip_render_max_path_len_in_effect(int32_t dev) { return path_len_in_effect(rdev(dev)); }
 
 void rodent_hip_scene_set_transforms(int32_t dev, const float* object_to_world_dev, void* stream_) {
     DevScene& s = instanced_scene(dev, "rodent_hip_scene_set_transforms");
@@ -1481,7 +1610,8 @@ void rodent_hip_scene_set_transforms(int32_t dev, const float* object_to_world_d
 }
 
 int32_t rodent_hip_scene_transforms_status(int32_t dev, int32_t* info) {
-    DevScene& s = instanced_scene(dev, "rodent_hip_scene_transforms_status");
+    DevScene& s = loaded_scene(dev, "rodent_hip_scene_transforms_status");
+    if (!s.motion) instanced_scene(dev, "rodent_hip_scene_transforms_status");       // (it serves a moving scene's moves too)
     int32_t words[RODENT_BUILD_INFO_WORDS] = {};
     HIP_CHECK(hipSetDevice(dev));
     if (s.refit_enqueued) HIP_CHECK(hipEventSynchronize(rdev(dev).ev_refit));
@@ -1494,7 +1624,7 @@ int32_t rodent_hip_scene_deform_prepare(int32_t dev, const int32_t* objects, int
     RenderDevice& r = rdev(dev);
     DevScene& s = r.scene;
     // ---- the refusals: on the host, the scene and an earlier set stay as they are ----
-    if (!s.loaded || !s.instanced) return RODENT_SCENE_ERR_NOT_INSTANCED;
+    if (!s.loaded || !s.instanced || s.motion) return RODENT_SCENE_ERR_NOT_INSTANCED;
     if (!objects || num_objects < 1) return RODENT_SCENE_ERR_COUNTS;
     std::vector<char> listed((size_t)s.num_objects, 0);
     for (int32_t k = 0; k < num_objects; k++) {
@@ -1802,9 +1932,9 @@ void hip_generate_rays(int32_t dev, PrimaryStream* primary, int32_t capacity, in
     rdev(dev); HIP_CHECK(hipSetDevice(dev));
     if (primary->size + num_rays > capacity) { fprintf(stderr, "rodent_hip: hip_generate_rays exceeds the stream capacity\n"); abort(); }
     if (num_rays > 0)
-        hipLaunchKernelGGL(k_generate, dim3((num_rays + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, *primary,
+        hipLaunchKernelGGL(generate_kernel(rdev(dev)), dim3((num_rays + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, *primary,
             primary->size, first_ray_id,
-                           num_rays, to_cam(settings), iter, film_width, film_height, first_pixel, spp, 0, 0);
+                           num_rays, to_cam(settings), iter, film_width, film_height, first_pixel, spp, 0, 0, 0, 0);
     primary->size += num_rays;
     HIP_CHECK(hipGetLastError());
 }
@@ -1836,7 +1966,7 @@ void hip_shade(int32_t dev, PrimaryStream* primary, SecondaryStream* secondary, 
     if (r.scene.instanced) ensure_ray_slots(r, (size_t)num_rays);
     launch_shader(r, (hipStream_t)stream, shade_block(), num_rays, r.scene.dev, *primary, *primary, (const int*)nullptr, *secondary,
         (const int*)nullptr, num_rays, r.film,
-                   1.0f / (float)r.spp, r.max_path_len,
+                   1.0f / (float)r.spp, path_len_in_effect(r),
                        /* a ray that missed ends here instead of indexing the material table with the miss id: */ 1, (unsigned*)nullptr,
                        (int*)nullptr);
     HIP_CHECK(hipGetLastError());
@@ -1859,7 +1989,7 @@ int32_t hip_shade_compact(int32_t dev, PrimaryStream* from, PrimaryStream* to, S
         HIP_CHECK(hipMemsetAsync(r.scan.ptr, 0, sizeof(unsigned) * (size_t)blocks, (hipStream_t)stream));
     }
     launch_shader(r, (hipStream_t)stream, b, num_rays, r.scene.dev, *from, *to, (const int*)perm, *secondary, (const int*)nullptr, num_rays,
-        r.film, 1.0f / (float)r.spp, r.max_path_len, 1, mode == 2 ? kScanAtomic : r.scan.ptr, d_alive);
+        r.film, 1.0f / (float)r.spp, path_len_in_effect(r), 1, mode == 2 ? kScanAtomic : r.scan.ptr, d_alive);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(r.host_pinned + 8, d_alive, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));

@@ -14,12 +14,29 @@
 // counters, film_add_wave for the shadow rays nothing occludes.  A stack overflow raises *err (the flag frame_end reads) and the ray
 // stops where it stands: there is no deep list and no follow-up kernel, so block 0 of the closest-hit pass does that kernel's
 // housekeeping for the loop: it zeroes the shader's slot counter.  (The ticket counters are the persistent kernels', which an instanced
-// scene never launches: they stay zero.)
-template <bool ANY>
-__global__ __launch_bounds__(kWave) void k_trace_instanced(SceneDev sc, InstancedDev in, PrimaryStream p, SecondaryStream s,
-                                                           const int* size_ptr, int n_value, float* film, float inv_spp,
-                                                           unsigned long long* counters, int* err, int* zero_word) {
-    __shared__ int stack_lds[kStackCap * kWave];
+// scene never launches: they stay zero.)  The pass is stated once, trace_instanced_pass, for this kernel and k_trace_instanced_motion
+// (render_motion.h); they differ in how a record yields the object ray.
+
+// How an instance record yields the object ray, as in traversal_instanced.h: enter(j, i, ray, o, id) reads record j for stream index i
+// (the opaque copy), fills the object ray and id = {node_offset, tri_offset, instance_id, pad}, and returns whether the instance is
+// entered at all.  The static form; the moving one is StreamMotionEnter (render_motion.h).
+struct StreamStaticEnter {
+    const RodentInstance* instances;
+    __device__ __forceinline__ bool enter(int j, int, const RayX& ray, RayX& o, int4& id) const {
+        const float4* rec = reinterpret_cast<const float4*>(instances + j);
+        const float4 w0 = rec[0], w1 = rec[1], w2 = rec[2];
+        id = *reinterpret_cast<const int4*>(rec + 3);                   // node_offset, tri_offset, instance_id, pad
+        o = object_ray(ray, w0, w1, w2);
+        return true;
+    }
+};
+
+// The pass of both kernels (k_trace_instanced, k_trace_instanced_motion), stated once.
+template <bool ANY, class Enter>
+__device__ __forceinline__ void trace_instanced_pass(const SceneDev& sc, const Node2* __restrict__ tlas, const Enter& in,
+                                                     int32_t* ray_slots, const PrimaryStream& p, const SecondaryStream& s,
+                                                     const int* size_ptr, int n_value, float* film, float inv_spp,
+                                                     unsigned long long* counters, int* err, int* zero_word, int* stack_lds) {
     const int lane = threadIdx.x, chunk = blockIdx.x, i = chunk * kWave + lane;
     // (the grid covers n_value rays: a shadow pass's size may live on the device)
     const int n = ANY ? stream_size(size_ptr, n_value) : n_value;
@@ -50,33 +67,33 @@ __global__ __launch_bounds__(kWave) void k_trace_instanced(SceneDev sc, Instance
             RayX ray = load_stream_ray(rays, again);
             ray.tmax = tmax;
             if (j < 0) {
-                top = node2_step(in.tlas, top, ray, st, ptr);
+                top = node2_step(tlas, top, ray, st, ptr);
                 if (ptr >= kStackCap) { overflow = true; break; }
                 if (top < 0) j = ~top;                                      // a TLAS leaf: its continuation stays in slot ptr
                 continue;
             }
-            const float4* rec = reinterpret_cast<const float4*>(in.instances + j);
-            const float4 w0 = rec[0], w1 = rec[1], w2 = rec[2];
-            const int4 id = *reinterpret_cast<const int4*>(rec + 3);        // node_offset, tri_offset, instance_id, pad
-            RayX o = object_ray(ray, w0, w1, w2);
-            const Node2* onodes = sc.nodes + id.x;
-            const Tri1* otris = sc.tris + id.y;
-            HitAccGeom h; h.id = -1; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.geom = 0;
-            bool done = false;
-            int otop = 1; st.put(++ptr, 0);
-            if (ptr >= kStackCap) { overflow = true; break; }
-            while (otop != 0) {
-                otop = node2_step(onodes, otop, o, st, ptr);
+            RayX o;
+            int4 id;
+            if (in.enter(j, again, ray, o, id)) {
+                const Node2* onodes = sc.nodes + id.x;
+                const Tri1* otris = sc.tris + id.y;
+                HitAccGeom h; h.id = -1; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.geom = 0;
+                bool done = false;
+                int otop = 1; st.put(++ptr, 0);
                 if (ptr >= kStackCap) { overflow = true; break; }
-                while (otop < 0) {
-                    const int first = ~otop; otop = st.get(ptr); ptr--;
-                    if (leaf_tri1<ANY>(otris, first, o, h)) { done = true; otop = 0; break; }
+                while (otop != 0) {
+                    otop = node2_step(onodes, otop, o, st, ptr);
+                    if (ptr >= kStackCap) { overflow = true; break; }
+                    while (otop < 0) {
+                        const int first = ~otop; otop = st.get(ptr); ptr--;
+                        if (leaf_tri1<ANY>(otris, first, o, h)) { done = true; otop = 0; break; }
+                    }
                 }
+                if (h.id >= 0) { hit = h; slot = j; }
+                if (ANY && done) occluded = true;
+                if (overflow || (ANY && done)) break;
+                tmax = o.tmax;
             }
-            if (h.id >= 0) { hit = h; slot = j; }
-            if (ANY && done) occluded = true;
-            if (overflow || (ANY && done)) break;
-            tmax = o.tmax;
             j++;
             if (id.z < 0) {                                                 // the last instance of the leaf: on with its continuation
                 top = st.get(ptr); ptr--;
@@ -87,11 +104,20 @@ __global__ __launch_bounds__(kWave) void k_trace_instanced(SceneDev sc, Instance
         if (ANY) lit = !occluded && !overflow;
         else {
             store_hit_record(p, (unsigned)i, hit.geom, hit.id, hit.t, hit.u, hit.v);
-            in.ray_slots[i] = slot;
+            ray_slots[i] = slot;
         }
     }
     if (ANY) film_add_wave(film, pixel, lit, lit ? s.color_r[i] * inv_spp : 0.0f, lit ? s.color_g[i] * inv_spp : 0.0f,
         lit ? s.color_b[i] * inv_spp : 0.0f);
+}
+
+template <bool ANY>
+__global__ __launch_bounds__(kWave) void k_trace_instanced(SceneDev sc, InstancedDev in, PrimaryStream p, SecondaryStream s,
+                                                           const int* size_ptr, int n_value, float* film, float inv_spp,
+                                                           unsigned long long* counters, int* err, int* zero_word) {
+    __shared__ int stack_lds[kStackCap * kWave];
+    trace_instanced_pass<ANY>(sc, in.tlas, StreamStaticEnter{in.instances}, in.ray_slots, p, s, size_ptr, n_value, film, inv_spp,
+                              counters, err, zero_word, stack_lds);
 }
 
 // ---- the tables an instanced scene derives from its matrices (rodent_hip_scene_create_instanced, rodent_hip_scene_set_transforms) ----
@@ -120,7 +146,8 @@ __device__ __forceinline__ float row_point(const float* m, float x, float y, flo
     return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[0], x), __fmul_rn(m[1], y)), __fmul_rn(m[2], z)), m[3]);
 }
 // One thread per world light l, owned by instance k = light_owner[l]: object light l - bases[k].y under k's matrices (rules:
-// include/rodent_render.h).
+// include/rodent_render.h).  k_motion_world_lights (render_motion.h) states the same statements again -- shared through a function this
+// kernel lost a register of its row --: a change here is a change there.
 __global__ __launch_bounds__(kBlock) void k_world_lights(const RodentInstanceDesc* __restrict__ descs,
                                                          const RodentInstance* __restrict__ instances, const int* __restrict__ slot_of,
                                                          const int* __restrict__ light_owner, const int2* __restrict__ bases,

@@ -178,12 +178,43 @@ __device__ __forceinline__ unsigned lookback_exclusive(unsigned* status, int blo
 // kernel as it was): ray `src` lies in the instance at leaf-order slot ray_slots[src]; its record gives the world_to_object rows and the
 // instance id k, bases[k] the object's first triangle and the offset of its lights (rules: include/rodent_render.h).
 // Its register budget is that of 7 waves per SIMD: under the flat shader's 8 the frame's rows cost it two spilled VGPRs.
+// A MOVING scene (k_shade<kBlock, true, MotionDev>): the depth word holds depth | ubits << 8 (rodent_render.h); the record at the ray's
+// slot is a RodentMotionInstance, t comes from the word by the shutter rule and the frame is invert(lerp(M0, M1, t)) through
+// motion_frame, the function the traversal entered the instance with.  The ray that goes on carries (depth + 1) | ubits << 8, the
+// shadow ray t's bits in s.prim_id.  Its register budget: kShadeMotionWaves.
+
+// The frame of a motion record at time t: the seven 16-byte loads of traversal_instanced.h's MotionEnter, lerp_affine, invert_affine
+// (instance_inverse.h).  The traversal (render_motion.h) and the shader both call THIS, with the same record and the same t, so the
+// shader's 12 floats are the traversal's.  Returns false when the inverse refuses the interpolated matrix.
+__device__ __forceinline__ bool motion_frame(const RodentMotionInstance* instances, int j, float t, float w[12], int4& id) {
+    const float4* p = reinterpret_cast<const float4*>(instances + j);
+    float4 r[6];
+    for (int k = 0; k < 6; k++) r[k] = p[k];
+    id = *reinterpret_cast<const int4*>(p + 6);                         // node_offset, tri_offset, instance_id, pad
+    const float m0[12] = {r[0].x, r[0].y, r[0].z, r[0].w, r[1].x, r[1].y, r[1].z, r[1].w, r[2].x, r[2].y, r[2].z, r[2].w};
+    const float m1[12] = {r[3].x, r[3].y, r[3].z, r[3].w, r[4].x, r[4].y, r[4].z, r[4].w, r[5].x, r[5].y, r[5].z, r[5].w};
+    float m[12];
+    lerp_affine(m0, m1, t, m);
+    return invert_affine(m, w) == 0;
+}
+#ifndef RODENT_SHADE_MOTION_WAVES
+#define RODENT_SHADE_MOTION_WAVES 5      // (compile time) 7: 20 ... 26 spilled VGPRs, 6: 9 ... 13, 5: none beyond the flat shader's 68 bytes
+#endif
+constexpr int kShadeMotionWaves = RODENT_SHADE_MOTION_WAVES;
+template <bool INST, typename... Inst> constexpr bool shade_motion() { return (std::is_same<Inst, MotionDev>::value || ...); }
+template <bool INST, typename... Inst> constexpr int shade_waves() {
+    return shade_motion<INST, Inst...>() ? kShadeMotionWaves : INST ? 7 : 8;
+}
 template <int kBlock /* threads per workgroup = rays per compaction slot request (shade_block()) */, bool INST = false, typename... Inst>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(INST ? 7 : 8, 8))) void k_shade(SceneDev sc, PrimaryStream p,
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(shade_waves<INST, Inst...>(), 8))) void k_shade(SceneDev sc,
+    PrimaryStream p,
     PrimaryStream q, const int* __restrict__ perm, SecondaryStream s, const int* size_ptr, int n_value, float* film,
                                                    float inv_spp, int max_path_len, int unsorted, unsigned* scan, int* alive_total,
                                                    Inst... inst) {
-    static_assert(sizeof...(Inst) == (INST ? 1 : 0), "k_shade<.., true> takes one InstancedDev");
+    static_assert(sizeof...(Inst) == (INST ? 1 : 0), "k_shade<.., true> takes one InstancedDev or MotionDev");
+    constexpr bool MOTION = shade_motion<INST, Inst...>();
+    int time_bits = 0;                                                  // MOTION: the depth word's bits above the depth
+    float time = 0.0f;
     __shared__ unsigned wave_total[kBlock / kWave + 1];
 #if RODENT_SHADE_HOIST_LIGHT == 2
     __shared__ int light_sink[kBlock];
@@ -220,7 +251,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(INST ? 7
 #endif
         pv.contrib = V(p.contrib_r[src], p.contrib_g[src], p.contrib_b[src]);
         pv.depth = p.depth[src];
-        if constexpr (INST) {
+        if constexpr (MOTION) {
+            const MotionDev& in = (inst, ...);
+            time_bits = pv.depth & ~RODENT_MOTION_DEPTH_MASK; pv.depth &= RODENT_MOTION_DEPTH_MASK;
+            time = shutter_time((uint32_t)time_bits >> RODENT_MOTION_DEPTH_BITS, in.open, in.close);
+            float w[12];
+            int4 id;
+            (void)motion_frame(in.instances, in.ray_slots[src], time, w, id);      // (a hit lies in an instance that was not skipped)
+            InstanceFrame frame;
+            frame.w0 = make_float4(w[0], w[1], w[2], w[3]); frame.w1 = make_float4(w[4], w[5], w[6], w[7]);
+            frame.w2 = make_float4(w[8], w[9], w[10], w[11]);
+            const int2 base = in.bases[id.z & 0x7FFFFFFF];
+            pv.prim += base.x; frame.light_offset = base.y;
+            o = shade_vertex<true>(sc, pv, max_path_len, &frame);
+        } else if constexpr (INST) {
             const InstancedDev& in = (inst, ...);
             const float4* rec = reinterpret_cast<const float4*>(in.instances + in.ray_slots[src]);
             InstanceFrame frame;
@@ -240,6 +284,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(INST ? 7
             s.rays.dir_x[i] = o.s_dir.x; s.rays.dir_y[i] = o.s_dir.y; s.rays.dir_z[i] = o.s_dir.z;
             s.rays.tmin[i] = kRayOffset; s.rays.tmax[i] = 1.0f - kRayOffset;
             s.color_r[i] = o.s_color.x; s.color_g[i] = o.s_color.y; s.color_b[i] = o.s_color.z;
+            if constexpr (MOTION) s.prim_id[i] = __float_as_int(time);
         }
         s.rays.id[i] = o.shadow ? pv.pixel : -1;
     }
@@ -274,5 +319,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(INST ? 7
     q.rays.dir_x[d] = o.b_dir.x; q.rays.dir_y[d] = o.b_dir.y; q.rays.dir_z[d] = o.b_dir.z;
     q.rays.tmin[d] = kRayOffset; q.rays.tmax[d] = FLT_MAX_REF;
     q.rnd[d] = o.rnd; q.mis[d] = o.mis;
-    q.contrib_r[d] = o.contrib.x; q.contrib_g[d] = o.contrib.y; q.contrib_b[d] = o.contrib.z; q.depth[d] = pv.depth + 1;
+    q.contrib_r[d] = o.contrib.x; q.contrib_g[d] = o.contrib.y; q.contrib_b[d] = o.contrib.z;
+    q.depth[d] = MOTION ? (pv.depth + 1) | time_bits : pv.depth + 1;
 }

@@ -263,6 +263,20 @@ RD_FN Surf surface_element_instanced(const SceneDev* sc, const InstanceFrame* f,
     s.face_normal = s.entering ? fn : neg(fn); s.local = orthonormal(dot(dir, nrm) <= 0.0f ? nrm : neg(nrm)); return s;
 }
 
+/* ---- moving instances (include/rodent_render.h, "moving instances in the renderer") ----
+ * What the kernels of a moving scene take beside SceneDev: InstancedDev's members over RodentMotionInstance records, and the shutter. */
+struct MotionDev {
+    const Node2* tlas; const RodentMotionInstance* instances;   /* the motion TLAS and the two-key instances in leaf order */
+    const int2* bases; int32_t* ray_slots;                      /* as in InstancedDev */
+    float open, close;                                          /* the shutter: 0 <= open <= close <= 1 */
+};
+/* A path's time from the 23 bits of its shutter sample u = ubits * 2^-23: fminf(close, open + (close - open) * u), every operation rounded
+ * on its own, so open <= t <= close and (0, 1) gives u bit for bit. */
+RD_FN float shutter_time(uint32_t ubits, float open, float close) {
+    const float u = (float)ubits * 1.1920928955078125e-7f;
+    return fminf(close, __fadd_rn(open, __fmul_rn(__fsub_rn(close, open), u)));
+}
+
 /* image.impala:24-38 (RGBA8 -> colour), :48-54 (repeat border), :64-86 (bilinear filter) */
 RD_FN v3 texel(const SceneDev* sc, const RodentTexture* t, int32_t x, int32_t y) {
     const uint32_t p = sc->texels[t->offset + (uint32_t)y * (uint32_t)t->width + (uint32_t)x];

@@ -51,6 +51,8 @@ class SceneInstances(C.Structure):
 SCENE_ERR_COUNTS, SCENE_ERR_RANGES, SCENE_ERR_LIGHT, SCENE_ERR_OBJECT, SCENE_ERR_NO_LIGHT, SCENE_ERR_OPTIONS, SCENE_ERR_TABLE, \
     SCENE_ERR_DEVICE = range(-20, -28, -1)
 SCENE_ERR_NOT_INSTANCED = -28                              # rodent_hip_scene_deform_prepare's own
+SCENE_ERR_MOVING_LIGHT, SCENE_ERR_SHUTTER = -29, -30       # rodent_hip_scene_create_motion's own, rodent_hip_render_shutter's
+MOTION_DEPTH_BITS, MOTION_DEPTH_MASK = 8, 0xFF             # a moving scene's depth word: depth | ubits << 8
 SCENE_ERRORS = {SCENE_ERR_COUNTS: "a missing table, a count below 1, more than 2^22 instances, or a hierarchy in the description",
                 SCENE_ERR_RANGES: "the objects' triangle or light ranges do not tile the tables in order",
                 SCENE_ERR_LIGHT: "an emissive triangle names a light outside its object's light range",
@@ -58,10 +60,35 @@ SCENE_ERRORS = {SCENE_ERR_COUNTS: "a missing table, a count below 1, more than 2
                 SCENE_ERR_NO_LIGHT: "no instance places an object that has a light",
                 SCENE_ERR_OPTIONS: "invalid build options",
                 SCENE_ERR_TABLE: "a vertex, material or texture index outside its table",
-                SCENE_ERR_DEVICE: "the device raised a flag while building"}
+                SCENE_ERR_DEVICE: "the device raised a flag while building",
+                SCENE_ERR_MOVING_LIGHT: "an instance of an object with lights has two different placements (lights stay static)"}
 
 
-RENDER_EXPORTS = ["rodent_hip_scene_create_instanced", "rodent_hip_scene_create_flags", "rodent_hip_scene_set_transforms",
+class SceneMotionInstances(C.Structure):
+    """RodentSceneMotionInstances: device pointers and counts of a moving scene's tables."""
+    _fields_ = [(n, vp) for n in ("tlas_nodes", "instances", "descs", "objects", "slot_of", "bases", "light_owner", "lights",
+                                  "object_lights", "ray_slots", "tlas_info")] + \
+               [(n, i32) for n in ("num_instances", "num_objects", "num_tlas_nodes", "num_lights", "num_object_lights",
+                                   "ray_slot_capacity")]
+
+
+def pack_depth_time(depth, ubits):
+    """The depth words (int32) of a moving scene's primary stream: depth (0 ... 255) | ubits (23 bits) << 8; bit 31 stays 0."""
+    depth, ubits = np.asarray(depth, np.int64), np.asarray(ubits, np.int64)
+    if ((depth < 0) | (depth > MOTION_DEPTH_MASK)).any() or ((ubits < 0) | (ubits >= 1 << 23)).any():
+        raise ValueError("pack_depth_time: depth must lie in [0, 255] and ubits in [0, 2^23)")
+    return (depth | ubits << MOTION_DEPTH_BITS).astype(np.int32)
+
+
+def unpack_depth_time(words):
+    """(depth, ubits) of depth words as pack_depth_time makes them."""
+    w = np.asarray(words).astype(np.int64) & 0xFFFFFFFF
+    return (w & MOTION_DEPTH_MASK).astype(np.int32), (w >> MOTION_DEPTH_BITS).astype(np.int32)
+
+
+RENDER_EXPORTS = ["rodent_hip_scene_create_motion", "rodent_hip_scene_set_motion_transforms", "rodent_hip_scene_motion_instances",
+                  "rodent_hip_render_shutter", "rodent_hip_render_shutter_in_effect", "rodent_hip_render_max_path_len_in_effect",
+                  "rodent_hip_scene_create_instanced", "rodent_hip_scene_create_flags", "rodent_hip_scene_set_transforms",
                   "rodent_hip_scene_transforms_status", "rodent_hip_scene_instances", "rodent_hip_render_sort_in_effect",
                   "rodent_hip_render_trace_persistent_in_effect",
                   "rodent_hip_scene_deform_prepare", "rodent_hip_scene_deform_device", "rodent_hip_scene_deform_status",
@@ -123,6 +150,15 @@ def lib():
         l.rodent_hip_scene_deform_device.argtypes = [i32, vp, vp, vp, vp]; l.rodent_hip_scene_deform_device.restype = None
         l.rodent_hip_scene_deform_status.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
         l.rodent_hip_scene_deform_status.restype = i32
+        l.rodent_hip_scene_create_motion.argtypes = [i32, C.POINTER(SceneDesc), C.POINTER(ObjectRange), i32, vp, i32,
+                                                     C.POINTER(abi.BuildOptions)]
+        l.rodent_hip_scene_create_motion.restype = i32
+        l.rodent_hip_scene_set_motion_transforms.argtypes = [i32, vp, vp, vp]; l.rodent_hip_scene_set_motion_transforms.restype = None
+        l.rodent_hip_scene_motion_instances.argtypes = [i32, C.POINTER(SceneMotionInstances)]
+        l.rodent_hip_scene_motion_instances.restype = None
+        l.rodent_hip_render_shutter.argtypes = [i32, C.c_float, C.c_float]; l.rodent_hip_render_shutter.restype = i32
+        l.rodent_hip_render_shutter_in_effect.argtypes = [i32, C.POINTER(C.c_float)]; l.rodent_hip_render_shutter_in_effect.restype = None
+        l.rodent_hip_render_max_path_len_in_effect.argtypes = [i32]; l.rodent_hip_render_max_path_len_in_effect.restype = i32
         l.rodent_hip_render_sort_in_effect.argtypes = [i32]; l.rodent_hip_render_sort_in_effect.restype = i32
         l.rodent_hip_render_trace_persistent_in_effect.argtypes = [i32]; l.rodent_hip_render_trace_persistent_in_effect.restype = i32
         l.rodent_hip_render_config.argtypes = [i32, i32, i32]; l.rodent_hip_render_config.restype = None
@@ -193,6 +229,23 @@ def create_instanced(dev, scene, ranges, transforms, object_ids, opt=None):
                                                    descs.ctypes.data_as(vp), len(t), C.byref(opt) if opt is not None else None)
 
 
+def create_motion(dev, scene, ranges, transforms0, transforms1, object_ids, opt=None):
+    """rodent_hip_scene_create_motion as it stands: returns its status and raises nothing -- Renderer(motion=...) is the checked way in."""
+    from . import formats as F
+    desc, keep = scene_desc(scene)
+    if not len(scene.nodes):
+        desc.nodes = None
+    if not len(scene.tris):
+        desc.tris = None
+    ranges = np.ascontiguousarray(ranges, np.int32).reshape(-1, 4)
+    t0 = np.ascontiguousarray(transforms0, np.float32).reshape(-1, 12)
+    descs = np.zeros(len(t0), F.MOTION_INSTANCE_DESC)
+    descs["object_to_world0"], descs["object_to_world1"] = t0, np.ascontiguousarray(transforms1, np.float32).reshape(-1, 12)
+    descs["object"] = object_ids
+    return lib().rodent_hip_scene_create_motion(dev, C.byref(desc), ranges.ctypes.data_as(C.POINTER(ObjectRange)), len(ranges),
+                                                descs.ctypes.data_as(vp), len(t0), C.byref(opt) if opt is not None else None)
+
+
 def make_settings(cam) -> Settings:
     v = lambda a: Vec3(float(a[0]), float(a[1]), float(a[2]))
     return Settings(v(cam["eye"]), v(cam["dir"]), v(cam["up"]), v(cam["right"]), float(cam["w"]), float(cam["h"]))
@@ -207,7 +260,7 @@ class Renderer:
         fused_sort=None, lds_image=None,
                  trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None,
                  gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64, gpu_bvh_ploc=0, persist_min_rays=None, instances=None,
-                 build=None):
+                 build=None, motion=None, shutter=(0.0, 1.0)):
         """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says.
         gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh_opt);
         gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it.
@@ -221,7 +274,20 @@ class Renderer:
         rows first_tri, num_tris, first_light, num_lights, transforms (n, 12) or (n, 3, 4) object_to_world, object_ids n ints; the
         objects' hierarchies are built on the device with build = (max_leaf, treelet_passes) or a gpubuild.options() record (None:
         max_leaf 2, no passes).  A refusal raises gpubuild.BuildError.  Such a scene renders through the streaming loop without the
-        sort by material, whatever the options ask for; set_transforms() moves its instances."""
+        sort by material, whatever the options ask for; set_transforms() moves its instances.
+        motion = (object_ranges, transforms0, transforms1, object_ids): a MOVING scene (rodent_hip_scene_create_motion) -- an instanced
+        scene whose instances carry two placements, at time 0 and at time 1; every path draws a time in `shutter` = (open, close),
+        0 <= open <= close <= 1, and sees every instance where that time puts it (entry-wise interpolation of the matrices).  Excludes
+        `instances`.  Instances of objects with lights must have equal placements.  Paths are at most 255 vertices long.
+        set_motion_transforms() moves both placements, set_shutter() changes the interval.  `shutter` is checked whatever the scene
+        (a pair outside 0 <= open <= close <= 1 raises ValueError) but only a moving scene uses it: without `motion` the device keeps
+        its default (0, 1)."""
+        if motion is not None and instances is not None:
+            raise ValueError("motion: a moving scene carries its own placements (pass `motion` or `instances`, not both)")
+        if not 0.0 <= float(shutter[0]) <= float(shutter[1]) <= 1.0:       # (with or without `motion`, before the device is touched)
+            raise ValueError(f"shutter: 0 <= open <= close <= 1 is needed, got {tuple(shutter)}")
+        if motion is not None and gpu_bvh:
+            raise ValueError("motion: the objects' hierarchies are built on the device anyway (pass `build`, not gpu_bvh)")
         if instances is not None and gpu_bvh:
             raise ValueError("instances: the objects' hierarchies are built on the device anyway (pass `build`, not gpu_bvh)")
         if gpu_bvh_passes and not gpu_bvh:
@@ -247,7 +313,12 @@ class Renderer:
         l.rodent_hip_set_device(dev)
         l.rodent_hip_render_defaults(dev)                    # options of an earlier Renderer in this process do not leak into this one
         self.num_instances = 0
-        if instances is not None:
+        self.moving = motion is not None
+        if self.moving:
+            ranges, t0, t1, ids = motion
+            self._create_instanced(desc, (ranges, t0, ids), build, transforms1=t1)
+            self.set_shutter(*shutter)
+        elif instances is not None:
             self._create_instanced(desc, instances, build)
         elif gpu_bvh:
             from . import gpubuild
@@ -296,7 +367,8 @@ class Renderer:
         l.setup_interface(width, height)
         l.clear_pixels()
 
-    def _create_instanced(self, desc, instances, build):
+    def _create_instanced(self, desc, instances, build, transforms1=None):
+        """transforms1 given: a moving scene (rodent_hip_scene_create_motion), `instances` holding the placements at time 0."""
         from . import formats as F, gpubuild
         ranges, transforms, object_ids = instances
         ranges = np.ascontiguousarray(ranges, np.int32).reshape(-1, 4)
@@ -307,8 +379,17 @@ class Renderer:
         ids = np.ascontiguousarray(object_ids).astype(np.int64).reshape(-1)
         if len(ids) != n:
             raise ValueError(f"instances: {n} transforms but {len(ids)} object ids")
-        descs = np.zeros(n, F.INSTANCE_DESC)
-        descs["object_to_world"] = t.reshape(n, 12)
+        if transforms1 is None:
+            entry = "rodent_hip_scene_create_instanced"
+            descs = np.zeros(n, F.INSTANCE_DESC)
+            descs["object_to_world"] = t.reshape(n, 12)
+        else:
+            entry = "rodent_hip_scene_create_motion"
+            t1 = np.ascontiguousarray(transforms1, np.float32)
+            if t1.size != 12 * n:
+                raise ValueError(f"motion: {n} placements at time 0, but transforms1 has shape {t1.shape}")
+            descs = np.zeros(n, F.MOTION_INSTANCE_DESC)
+            descs["object_to_world0"], descs["object_to_world1"] = t.reshape(n, 12), t1.reshape(n, 12)
         descs["object"] = np.clip(ids, -1, (1 << 31) - 1)                 # (an id past int32 is outside every table too)
         if build is None or isinstance(build, abi.BuildOptions):
             opt = build
@@ -316,16 +397,71 @@ class Renderer:
             opt = gpubuild.options(*build) if isinstance(build, (tuple, list)) else gpubuild.options(int(build))
         desc.nodes = desc.tris = None
         desc.num_nodes = desc.num_bvh_tris = 0
-        rc = lib().rodent_hip_scene_create_instanced(self.dev, C.byref(desc), ranges.ctypes.data_as(C.POINTER(ObjectRange)), len(ranges),
-                                                     descs.ctypes.data_as(vp), n, C.byref(opt) if opt is not None else None)
+        rc = getattr(lib(), entry)(self.dev, C.byref(desc), ranges.ctypes.data_as(C.POINTER(ObjectRange)), len(ranges),
+                                   descs.ctypes.data_as(vp), n, C.byref(opt) if opt is not None else None)
         if rc:
             what = SCENE_ERRORS.get(rc, f"status {rc}")
             if rc == SCENE_ERR_DEVICE:
                 from .instances import _TLAS_FLAGS
                 flags = lib().rodent_hip_scene_create_flags(self.dev)
                 what += ": " + (", ".join(s for bit, s in _TLAS_FLAGS if flags > 0 and flags & bit) or f"flags {flags}")
-            raise gpubuild.BuildError(f"rodent_hip_scene_create_instanced: {what}")
+            raise gpubuild.BuildError(f"{entry}: {what}")
         self.num_instances = n
+
+    def _matrices_pointer(self, t, what):
+        """Device pointer of num_instances x 12 float32 entries given as a tensor on the renderer's device, or as an integer pointer."""
+        import torch
+        if isinstance(t, int):
+            return t
+        if (not t.is_cuda or t.device.index != self.dev or t.dtype != torch.float32 or t.numel() != 12 * self.num_instances
+                or not t.is_contiguous()):
+            raise ValueError(f"{what}: a contiguous float32 tensor of {self.num_instances} x 12 entries on cuda:{self.dev} is needed (or "
+                             "an integer device pointer)")
+        return t.data_ptr()
+
+    def set_motion_transforms(self, transforms0, transforms1, stream=None, check=True):
+        """Both placements of a moving scene's instances moved (rodent_hip_scene_set_motion_transforms): two tensors as for
+        set_transforms (they may be the same one), the placements at time 0 and at time 1.  The motion TLAS, the instance array, slot_of
+        and the world lights (from the placements at time 0) follow on `stream` with no host copy and no wait.  The caller keeps the two
+        placements of every instance of an object with lights equal: this call cannot check it.  check=True waits
+        (transforms_status) and raises gpubuild.BuildError on a flag (a singular or non-finite endpoint).  The film is not cleared."""
+        import torch
+        stream = torch.cuda.current_stream(self.dev) if stream is None else stream
+        pointers = [self._matrices_pointer(t, "set_motion_transforms") for t in (transforms0, transforms1)]
+        tensors = [t for t in (transforms0, transforms1) if not isinstance(t, int)]
+        if tensors:
+            stream.wait_stream(torch.cuda.current_stream(self.dev))          # the tensors may come from there
+        lib().rodent_hip_scene_set_motion_transforms(self.dev, *pointers, C.c_void_p(stream.cuda_stream))
+        for t in tensors:
+            t.record_stream(stream)
+        if check:
+            self.transforms_status(raise_on_flag=True)
+
+    def set_shutter(self, open_, close):
+        """The interval a moving scene's paths draw their times in (rodent_hip_render_shutter): 0 <= open <= close <= 1, else ValueError
+        and nothing changes.  A path's time is min(close, open + (close - open) * u) in float32, u its shutter sample."""
+        if lib().rodent_hip_render_shutter(self.dev, float(open_), float(close)) != 0:
+            raise ValueError(f"shutter: 0 <= open <= close <= 1 is needed, got ({open_}, {close})")
+
+    def shutter(self):
+        out = (C.c_float * 2)()
+        lib().rodent_hip_render_shutter_in_effect(self.dev, out)
+        return float(out[0]), float(out[1])
+
+    def max_path_len(self):
+        """The path length the next frame uses (rodent_hip_render_max_path_len_in_effect): at most 255 with a moving scene loaded."""
+        return lib().rodent_hip_render_max_path_len_in_effect(self.dev)
+
+    def motion_pointers(self):
+        """Device pointers (integers) and counts of a moving scene's tables (rodent_hip_scene_motion_instances)."""
+        t = SceneMotionInstances()
+        lib().rodent_hip_scene_motion_instances(self.dev, C.byref(t))
+        return {n: (getattr(t, n) or 0) for n, _ in SceneMotionInstances._fields_}
+
+    def motion_tables(self):
+        """instance_tables() of a moving scene: `instances` are MOTION_INSTANCE records, `descs` MOTION_INSTANCE_DESC records."""
+        from . import formats as F
+        return self._derived_tables(self.motion_pointers(), F.MOTION_INSTANCE, F.MOTION_INSTANCE_DESC)
 
     def set_transforms(self, transforms, stream=None, check=True):
         """The instances moved (rodent_hip_scene_set_transforms): `transforms` is a contiguous float32 tensor of num_instances x 12
@@ -428,10 +564,13 @@ class Renderer:
         """Host copies (numpy) of what an instanced scene derives: tlas_nodes (NODE2), instances (INSTANCE, leaf order), descs
         (INSTANCE_DESC), objects (OBJECT), slot_of, bases ((n, 2) int32), light_owner, lights (the world lights, scene.LIGHT),
         object_lights and tlas_info (the last rebuild's info words).  Waits for the device."""
+        from . import formats as F
+        return self._derived_tables(self.instance_pointers(), F.INSTANCE, F.INSTANCE_DESC)
+
+    def _derived_tables(self, p, instance_dtype, desc_dtype):
         import torch
         from . import formats as F
         from .scene import LIGHT
-        p = self.instance_pointers()
         torch.cuda.synchronize(self.dev)
         hip = C.cdll.LoadLibrary("libamdhip64.so")
 
@@ -443,17 +582,23 @@ class Renderer:
             return a.reshape(shape) if shape else a
         n = p["num_instances"]
         info = fetch("tlas_info", "<i4", 4)
-        return {"tlas_nodes": fetch("tlas_nodes", F.NODE2, int(info[0])), "instances": fetch("instances", F.INSTANCE, n),
-                "descs": fetch("descs", F.INSTANCE_DESC, n), "objects": fetch("objects", F.OBJECT, p["num_objects"]),
+        return {"tlas_nodes": fetch("tlas_nodes", F.NODE2, int(info[0])), "instances": fetch("instances", instance_dtype, n),
+                "descs": fetch("descs", desc_dtype, n), "objects": fetch("objects", F.OBJECT, p["num_objects"]),
                 "slot_of": fetch("slot_of", "<i4", n), "bases": fetch("bases", "<i4", 2 * n, (n, 2)),
                 "light_owner": fetch("light_owner", "<i4", p["num_lights"]), "lights": fetch("lights", LIGHT, p["num_lights"]),
                 "object_lights": fetch("object_lights", LIGHT, p["num_object_lights"]), "tlas_info": info}
 
     def options_in_effect(self):
-        """What the next frame uses for the scene that is loaded: mapping name, trace_persistent, (refill thresholds), sort."""
+        """What the next frame uses for the scene that is loaded: mapping name, trace_persistent, (refill thresholds), sort.
+        The keys depend on how the renderer was made: one made with `motion=` ALSO returns max_path_len and shutter; every other
+        renderer returns exactly the four keys above (callers compare that dictionary for equality), and max_path_len() and
+        shutter() read the two values for any renderer."""
         l = lib()
-        return {"mapping": self.mapping_name(), "trace_persistent": l.rodent_hip_render_trace_persistent_in_effect(self.dev),
-                "trace_refill": self.trace_refill(), "sort": l.rodent_hip_render_sort_in_effect(self.dev)}
+        out = {"mapping": self.mapping_name(), "trace_persistent": l.rodent_hip_render_trace_persistent_in_effect(self.dev),
+               "trace_refill": self.trace_refill(), "sort": l.rodent_hip_render_sort_in_effect(self.dev)}
+        if self.moving:
+            out.update(max_path_len=self.max_path_len(), shutter=self.shutter())
+        return out
 
     def configure(self, spp, max_path_len):
         self.spp = spp
