@@ -143,6 +143,7 @@ __global__ void k_copy_int(const int* src, int* dst) { *dst = *src; }
 // ---------------------------------------------------------------------------------------------
 // Host side: per-device state (interface.cpp:324-339), stream slabs, the streaming loop
 // ---------------------------------------------------------------------------------------------
+// The scene of a device: RenderDevice holds it by value, so it is declared here; all the code that works on it is render_scene.h's.
 struct DevScene {
     bool loaded = false;
     int num_nodes = 0, num_bvh_tris = 0, num_vertices = 0;
@@ -828,14 +829,6 @@ void resolve_refill(RenderDevice& r) {
     r.trace_refill = r.trace_refill_shadow = r.scene.loaded && r.scene.num_nodes >= kRefillMinNodes ? kRefillIdleLanes : 0;
 }
 
-template <typename T> T* upload(DevScene& s, const T* host, size_t count) {
-    T* d = nullptr;
-    HIP_CHECK(hipMalloc(&d, std::max<size_t>(sizeof(T) * count, 16)));
-    if (count) HIP_CHECK(hipMemcpy(d, host, sizeof(T) * count, hipMemcpyHostToDevice));
-    s.allocs.push_back(d);
-    return d;
-}
-
 // host-side stream slabs of rodent_cpu_get_*_stream: per thread, like the reference's (interface.cpp:341-342,507-508)
 thread_local std::vector<float> t_cpu_primary, t_cpu_secondary;
 
@@ -843,744 +836,12 @@ thread_local std::vector<float> t_cpu_primary, t_cpu_secondary;
 
 void rodent_services_cleanup();                                              // services.hip
 
+// The scene: everything that creates, checks, updates, reports on or destroys a DevScene, and its entry points.
+#include "render_scene.h"
+
 extern "C" {
 
 void rodent_hip_set_device(int32_t dev) { rdev(dev); g_current_dev = dev; }
-
-void rodent_hip_scene_destroy(int32_t dev) {
-    RenderDevice& r = rdev(dev);
-    HIP_CHECK(hipSetDevice(dev));
-    HIP_CHECK(hipDeviceSynchronize());
-    for (void* p : r.scene.allocs) HIP_CHECK(hipFree(p));
-    for (void* p : r.scene.deform.allocs) HIP_CHECK(hipFree(p));
-    if (r.scene.inst.ray_slots) HIP_CHECK(hipFree(r.scene.inst.ray_slots));
-    r.scene = DevScene();
-}
-
-} // extern "C"
-
-namespace {
-
-// Top-of-tree image of the stream traversal kernels (record layout: traversal_device.h build_top_image), `capacity` records of 16 words:
-// breadth first from the root; a child that got a slot is a link (kLdsTag + byte offset of its record), the others keep their ids.
-std::vector<int32_t> build_image(const Node2* nodes, int capacity) {
-    std::vector<int32_t> image((size_t)capacity * 16, 0), slots{1};
-    for (size_t k = 0; k < slots.size(); k++) {
-        const Node2& nd = nodes[slots[k] - 1];
-        int32_t* rec = image.data() + 16 * k;
-        memcpy(rec, nd.bounds, 12 * sizeof(float));
-        for (int j = 0; j < 2; j++) {
-            const int32_t c = nd.child[j];
-            rec[12 + j] = c;
-            if (c > 0 && (int)slots.size() < capacity) { rec[12 + j] = kLdsTag + (int32_t)slots.size() * (int32_t)sizeof(Node2);
-                slots.push_back(c); }
-        }
-        rec[14] = slots[k];
-    }
-    return image;
-}
-
-// SceneDev::tri_shade records (12 floats per triangle): the face normal, then the three corners' vertex normals, gathered.
-std::vector<float> tri_shade(const float* face_normals, const float* normals, const int32_t* indices, int32_t num_tris) {
-    std::vector<float> rec(12 * (size_t)num_tris);
-    for (int32_t t = 0; t < num_tris; t++) {
-        float* o = rec.data() + 12 * (size_t)t;
-        const float* fn = face_normals + 4 * (size_t)t;
-        o[0] = fn[0]; o[1] = fn[1]; o[2] = fn[2];
-        for (int k = 0; k < 3; k++) {
-            const float* n = normals + 4 * (size_t)indices[4 * (size_t)t + k];
-            o[3 + 3 * k] = n[0]; o[4 + 3 * k] = n[1]; o[5 + 3 * k] = n[2];
-        }
-    }
-    return rec;
-}
-
-// SceneDev::tri_shade and ::tri_tex of the tables in `d` (host), uploaded into `s`
-void upload_shading_records(DevScene& s, const RodentSceneDesc* d, bool textured) {
-    // SceneDev::tri_shade: per triangle face normal + its three vertex normals, gathered (RODENT_HIP_TRI_SHADE=0: not built, the shader
-    // goes through indices -> normals)
-    {
-        static const bool on = [] { const char* e = getenv("RODENT_HIP_TRI_SHADE"); return !e || atoi(e) != 0; }();
-        s.dev.tri_shade = nullptr;
-        if (on && d->num_tris > 0) {
-            const std::vector<float> rec = tri_shade(d->face_normals, d->normals, d->indices, d->num_tris);
-            s.dev.tri_shade = reinterpret_cast<const float4*>(upload(s, rec.data(), rec.size()));
-        }
-        s.dev.tri_tex = nullptr;
-        // SceneDev::tri_tex: the corners' texture coordinates, for resolve_material
-        if (on && textured && d->num_tris > 0) {
-            std::vector<float> tc(6 * (size_t)d->num_tris);
-            for (int32_t t = 0; t < d->num_tris; t++)
-                for (int k = 0; k < 3; k++) {
-                    const float* c = d->texcoords + 4 * (size_t)d->indices[4 * (size_t)t + k];
-                    tc[6 * (size_t)t + 2 * k] = c[0]; tc[6 * (size_t)t + 2 * k + 1] = c[1];
-                }
-            s.dev.tri_tex = upload(s, tc.data(), tc.size());
-        }
-    }
-}
-
-// rodent_hip_scene_create and rodent_hip_scene_create_device_bvh(_opt / _split): build = NULL uploads the caller's hierarchy
-// (desc->nodes / tris), build options build one on the device from the vertices and indices just uploaded (bvh_build.hip; with
-// `split`, over pre-split references) and takes a host copy of it; from there on both are the same code: checks, LDS images, per-scene
-// rules.
-void scene_create(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* build, const RodentSplitOptions* split = nullptr,
-                  const RodentPlocOptions* ploc = nullptr) {
-    RenderDevice& r = rdev(dev);
-    rodent_hip_scene_destroy(dev);
-    HIP_CHECK(hipSetDevice(dev));
-    DevScene& s = r.scene;
-    s.dev.vertices = upload(s, d->vertices, 4 * (size_t)d->num_vertices);
-    s.dev.normals = upload(s, d->normals, 4 * (size_t)d->num_vertices);
-    s.dev.face_normals = upload(s, d->face_normals, 4 * (size_t)d->num_tris);
-    s.dev.indices = upload(s, d->indices, 4 * (size_t)d->num_tris);
-    RodentSceneDesc built_desc;                 // d with the device-built hierarchy (host copy) in place of the caller's
-    std::vector<Node2> built_nodes;
-    std::vector<Tri1> built_tris;
-    {   // nodes and triangles in ONE allocation: k_trace_refill addresses both from one base with 32-bit offsets (joint_fetch_off)
-        // (a device-built hierarchy: room for the builder's max(1, refs - 1) nodes, then its refs triangles; the builder's scratch and
-        // info words.  Unsplit: refs = n, 4 info words, info[4] keeps n)
-        int32_t refs = d->num_tris, info_words = RODENT_BUILD_INFO_WORDS;
-        int64_t scratch_bytes = build ? rodent_hip_build_opt_scratch_bytes(d->num_tris, build) : 0;
-        if (split) {
-            refs = (int32_t)rodent_hip_build_split_max_refs(d->num_tris, split);
-            scratch_bytes = rodent_hip_build_split_scratch_bytes(d->num_tris, build, split);
-            info_words = RODENT_BUILD_SPLIT_INFO_WORDS;
-        }
-        if (ploc) {                                      // the PLOC topology stage, with or without the split front: 8 info words
-            scratch_bytes = rodent_hip_build_ploc_scratch_bytes(d->num_tris, build, split, ploc);
-            info_words = RODENT_BUILD_SPLIT_INFO_WORDS;
-        }
-        const size_t node_bytes = sizeof(Node2) * (size_t)(build ? std::max(1, refs - 1) : d->num_nodes);
-        const size_t tri_bytes = sizeof(Tri1) * (size_t)(build ? refs : d->num_bvh_tris);
-        char* bvh = nullptr;
-        HIP_CHECK(hipMalloc(&bvh, std::max<size_t>(node_bytes + tri_bytes, 16)));
-        s.allocs.push_back(bvh);
-        s.dev.nodes = reinterpret_cast<const Node2*>(bvh);
-        s.dev.tris = reinterpret_cast<const Tri1*>(bvh + node_bytes);
-        if (build) {
-            char* scratch = nullptr;
-            int32_t info[RODENT_BUILD_SPLIT_INFO_WORDS] = {0, 0, 0, 0, d->num_tris, 0, 0, 0};
-            const size_t info_bytes = 4 * (size_t)info_words;
-            HIP_CHECK(hipMalloc(&scratch, (size_t)std::max<int64_t>(scratch_bytes, 0) + info_bytes));
-            int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + std::max<int64_t>(scratch_bytes, 0));
-            Node2* out_nodes = reinterpret_cast<Node2*>(bvh);
-            Tri1* out_tris = reinterpret_cast<Tri1*>(bvh + node_bytes);
-            const int32_t rc = ploc
-                ? rodent_hip_build_bvh2_tri1_ploc(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build, split, ploc,
-                                                  out_nodes, out_tris, scratch, info_dev, nullptr)
-                : split
-                ? rodent_hip_build_bvh2_tri1_split(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build, split,
-                                                   out_nodes, out_tris, scratch, info_dev, nullptr)
-                : rodent_hip_build_bvh2_tri1_opt(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, build, out_nodes,
-                                                 out_tris, scratch, info_dev, nullptr);
-            if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: device BVH build refused (%d)\n", rc); abort(); }
-            HIP_CHECK(hipMemcpy(info, info_dev, info_bytes, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipFree(scratch));
-            if (info[2]) { fprintf(stderr, "rodent_hip: invalid scene: device BVH build flagged the mesh (%d)\n", info[2]); abort(); }
-            built_nodes.resize(info[0]);
-            built_tris.resize(info[4]);                  // the references (= num_tris unsplit)
-            HIP_CHECK(hipMemcpy(built_nodes.data(), bvh, sizeof(Node2) * built_nodes.size(), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(built_tris.data(), bvh + node_bytes, sizeof(Tri1) * built_tris.size(), hipMemcpyDeviceToHost));
-            built_desc = *d;
-            built_desc.nodes = built_nodes.data(); built_desc.num_nodes = info[0];
-            built_desc.tris = built_tris.data(); built_desc.num_bvh_tris = info[4];
-            d = &built_desc;
-        } else {
-            if (node_bytes) HIP_CHECK(hipMemcpy(bvh, d->nodes, node_bytes, hipMemcpyHostToDevice));
-            if (tri_bytes) HIP_CHECK(hipMemcpy(bvh + node_bytes, d->tris, tri_bytes, hipMemcpyHostToDevice));
-        }
-        // tri_delta: bytes from the record a node id of 0 would have to triangle 0; 0 = not addressable this way (offsets beyond 32 bits,
-        // or an index beyond the 24-bit multiply)
-        const unsigned long long delta = sizeof(Node2) + node_bytes, end = delta + tri_bytes;
-        s.tri_delta = (end < (1ull << 32) && d->num_nodes < (1 << 24) - 1 && d->num_bvh_tris < (1 << 24)) ? (unsigned)delta : 0u;
-    }
-    s.dev.materials = upload(s, d->materials, (size_t)d->num_materials);
-    s.dev.lights = upload(s, d->lights, (size_t)d->num_lights);
-    s.dev.light_ids = upload(s, d->light_ids, (size_t)d->num_tris);
-    const bool textured = d->num_textures > 0;
-    if (textured && (!d->texcoords || !d->textures || !d->texels)) {
-        fprintf(stderr, "rodent_hip: scene with textures but without texture data\n"); abort(); }
-    s.dev.texcoords = upload(s, d->texcoords, textured ? 4 * (size_t)d->num_vertices : 0);
-    s.dev.textures = upload(s, d->textures, textured ? (size_t)d->num_textures : 0);
-    s.dev.texels = upload(s, d->texels, textured ? (size_t)d->num_texels : 0);
-    for (int32_t k = 0; k < d->num_materials; k++)
-        if (d->materials[k].tex_kd < 0 || d->materials[k].tex_kd > d->num_textures || d->materials[k].tex_ks < 0
-            || d->materials[k].tex_ks > d->num_textures) {
-            fprintf(stderr, "rodent_hip: material %d refers to a texture that does not exist\n", k); abort();
-        }
-    // every index the kernels follow, checked once on the host tables (a corrupt scene must not become an out-of-bounds read in k_shade /
-    // trace_one)
-    auto invalid = [](const char* what) { fprintf(stderr, "rodent_hip: invalid scene: %s\n", what); abort(); };
-    if (d->num_vertices <= 0 || d->num_tris <= 0 || d->num_nodes <= 0 || d->num_bvh_tris <= 0 || d->num_materials <= 0
-        || d->num_lights < 0) invalid("empty table");
-    for (int32_t t = 0; t < d->num_tris; t++) {
-        for (int k = 0; k < 3; k++) if ((uint32_t)d->indices[4 * t + k] >= (uint32_t)d->num_vertices) invalid("vertex index out of range");
-        if ((uint32_t)d->indices[4 * t + 3] >= (uint32_t)d->num_materials) invalid("material index out of range");
-        if (d->light_ids[t] < 0 || (d->light_ids[t] > 0 && d->light_ids[t] >= d->num_lights)) invalid("light id out of range");
-        // an emitter's triangles are looked up in the light table by the shader (on_hit: sc.lights[light_ids[prim]]): the entry must exist
-        if (d->materials[d->indices[4 * t + 3]].emissive
-            && d->light_ids[t] >= d->num_lights) invalid("emissive triangle without an entry in the light table");
-    }
-    for (int32_t k = 0; k < d->num_nodes; k++)
-        for (int j = 0; j < 2; j++) {
-            const int32_t c = d->nodes[k].child[j];
-            if ((c > 0 && c > d->num_nodes) || (c < 0 && ~c >= d->num_bvh_tris)) invalid("BVH child id out of range");
-        }
-    if (d->tris[d->num_bvh_tris - 1].prim_id >= 0) invalid("the last BVH triangle lacks the end-of-leaf bit");
-    for (int32_t k = 0; k < d->num_bvh_tris; k++)
-        if ((d->tris[k].prim_id & 0x7FFFFFFF) >= d->num_tris
-            || (uint32_t)d->tris[k].geom_id
-            >= (uint32_t)d->num_materials) invalid("BVH triangle refers to a primitive or material that does not exist");
-    for (int32_t k = 0; k < d->num_textures; k++)
-        if (d->textures[k].width <= 0 || d->textures[k].height <= 0
-            || (uint64_t)d->textures[k].offset + (uint64_t)d->textures[k].width * (uint64_t)d->textures[k].height
-            > d->num_texels) invalid("texture outside the texel pool");
-    s.dev.num_tris = d->num_tris; s.dev.num_materials = d->num_materials; s.dev.num_lights = d->num_lights;
-    // top-of-tree images of the stream traversal kernels (build_image)
-    for (const int capacity : {kSceneTopNodes, kPersistTopNodes}) {
-        const std::vector<int32_t> image = build_image(d->nodes, capacity);
-        (capacity == kSceneTopNodes ? s.dev.top_image : s.dev.top_image_large) =
-            reinterpret_cast<const int4*>(upload(s, image.data(), image.size()));
-    }
-    upload_shading_records(s, d, textured);
-    s.num_nodes = d->num_nodes;
-    s.num_bvh_tris = d->num_bvh_tris;
-    s.num_vertices = d->num_vertices;
-    s.loaded = true;
-    r.mapping = resolve_mapping(r);
-    r.trace_persistent = resolve_trace(r);
-    resolve_refill(r);
-}
-
-// rodent_hip_scene_refit_prepare: one-time and synchronous.  The tables it reads back (indices, light ids, materials) never change under
-// a refit, so the lists it builds on the host hold for the scene's life.
-void refit_prepare(RenderDevice& r, bool smooth_normals) {
-    DevScene& s = r.scene;
-    HIP_CHECK(hipSetDevice(r.dev));
-    if (!r.ev_refit) HIP_CHECK(hipEventCreateWithFlags(&r.ev_refit, hipEventDisableTiming));
-    const size_t nv = (size_t)s.num_vertices, nt = (size_t)s.dev.num_tris;
-    std::vector<int32_t> indices;
-    if (!s.refit_info || (smooth_normals && !s.corner_first)) {
-        indices.resize(4 * nt);
-        HIP_CHECK(hipMemcpy(indices.data(), s.dev.indices, sizeof(int32_t) * indices.size(), hipMemcpyDeviceToHost));
-    }
-    if (!s.refit_info) {
-        const int64_t scratch_bytes = std::max<int64_t>(rodent_hip_refit_scratch_bytes(s.num_nodes, s.num_bvh_tris), 0);
-        HIP_CHECK(hipMalloc(&s.refit_scratch, (size_t)scratch_bytes + 4 * RODENT_BUILD_INFO_WORDS));
-        s.allocs.push_back(s.refit_scratch);
-        int32_t* const info = reinterpret_cast<int32_t*>(s.refit_scratch + scratch_bytes);
-        HIP_CHECK(hipMemset(info, 0, 4 * RODENT_BUILD_INFO_WORDS));
-        // light k: the lowest emissive triangle whose light id is k
-        std::vector<int32_t> light_ids(nt);
-        std::vector<RodentMaterial> materials((size_t)s.dev.num_materials);
-        HIP_CHECK(hipMemcpy(light_ids.data(), s.dev.light_ids, sizeof(int32_t) * nt, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(materials.data(), s.dev.materials, sizeof(RodentMaterial) * materials.size(), hipMemcpyDeviceToHost));
-        std::vector<int> light_tri((size_t)s.dev.num_lights, -1);
-        for (size_t t = 0; t < nt; t++) {
-            const int32_t k = light_ids[t];
-            if (materials[indices[4 * t + 3]].emissive && k >= 0 && k < s.dev.num_lights && light_tri[k] < 0) light_tri[k] = (int)t;
-        }
-        s.light_tri = upload(s, light_tri.data(), light_tri.size());
-        s.refit_info = info;
-    }
-    if (smooth_normals && !s.corner_first) {
-        std::vector<int> first(nv + 1, 0), tri(3 * nt);
-        for (size_t t = 0; t < nt; t++) for (int k = 0; k < 3; k++) first[(size_t)indices[4 * t + k] + 1]++;
-        for (size_t v = 0; v < nv; v++) first[v + 1] += first[v];
-        std::vector<int> next(first.begin(), first.end() - 1);
-        for (size_t t = 0; t < nt; t++) for (int k = 0; k < 3; k++) tri[next[indices[4 * t + k]]++] = (int)t;
-        s.corner_tri = upload(s, tri.data(), tri.size());
-        s.corner_first = upload(s, first.data(), first.size());
-    }
-}
-
-DevScene& loaded_scene(int32_t dev, const char* entry) {
-    DevScene& s = rdev(dev).scene;
-    if (!s.loaded) {
-        fprintf(stderr, "rodent_hip: %s: no scene loaded on device %d (call rodent_hip_scene_create)\n", entry, dev); abort(); }
-    return s;
-}
-// the refit entries: an instanced scene has no single hierarchy to refit (its instances move with rodent_hip_scene_set_transforms)
-DevScene& flat_scene(int32_t dev, const char* entry) {
-    DevScene& s = loaded_scene(dev, entry);
-    if (s.instanced) { fprintf(stderr, "rodent_hip: %s: the scene on device %d is instanced (move its instances with "
-        "rodent_hip_scene_set_transforms)\n", entry, dev); abort(); }
-    return s;
-}
-// (the static-instance entries: a moving scene is "no instanced scene" to them)
-DevScene& instanced_scene(int32_t dev, const char* entry) {
-    DevScene& s = loaded_scene(dev, entry);
-    if (!s.instanced || s.motion) {
-        fprintf(stderr, "rodent_hip: %s: the scene on device %d is not instanced (rodent_hip_scene_create_instanced)\n", entry, dev);
-        abort(); }
-    return s;
-}
-DevScene& motion_scene(int32_t dev, const char* entry) {
-    DevScene& s = loaded_scene(dev, entry);
-    if (!s.motion) { fprintf(stderr, "rodent_hip: %s: the scene on device %d has no moving instances (rodent_hip_scene_create_motion)\n",
-        entry, dev); abort(); }
-    return s;
-}
-
-} // namespace
-
-extern "C" {
-
-void rodent_hip_scene_create(int32_t dev, const RodentSceneDesc* d) { scene_create(dev, d, nullptr); }
-
-void rodent_hip_scene_create_device_bvh(int32_t dev, const RodentSceneDesc* d, int32_t max_leaf) {
-    const RodentBuildOptions opt{max_leaf, 0, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
-    rodent_hip_scene_create_device_bvh_opt(dev, d, &opt);
-}
-
-void rodent_hip_scene_create_device_bvh_opt(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* opt) {
-    if (!opt || rodent_hip_build_opt_scratch_bytes(1, opt) < 0 || d->num_tris < 1 || d->num_tris > RODENT_BUILD_MAX_TRIS
-        || d->num_vertices < 1 || d->nodes || d->tris || d->num_nodes || d->num_bvh_tris) {
-        fprintf(stderr, "rodent_hip: rodent_hip_scene_create_device_bvh: invalid arguments (max_leaf 1 ... 8, treelet passes 0 ... 3, "
-                        "costs in (0, 1e6], 1 ... 2^25 triangles, "
-                        "no hierarchy in the description)\n");
-        abort();
-    }
-    scene_create(dev, d, opt);
-}
-
-void rodent_hip_scene_create_device_bvh_split(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* opt,
-                                              const RodentSplitOptions* split) {
-    if (!opt || !split || rodent_hip_build_split_scratch_bytes(1, opt, split) < 0 || d->num_tris < 1
-        || d->num_tris > RODENT_BUILD_MAX_TRIS || d->num_vertices < 1 || d->nodes || d->tris || d->num_nodes || d->num_bvh_tris) {
-        fprintf(stderr, "rodent_hip: rodent_hip_scene_create_device_bvh_split: invalid arguments (max_leaf 1 ... 8, treelet passes "
-                        "0 ... 3, costs in (0, 1e6], split budget 0 ... 4, max_pieces 1 ... 64, 1 ... 2^25 triangles, "
-                        "no hierarchy in the description)\n");
-        abort();
-    }
-    scene_create(dev, d, opt, split);
-}
-
-void rodent_hip_scene_create_device_bvh_ploc(int32_t dev, const RodentSceneDesc* d, const RodentBuildOptions* opt,
-                                             const RodentSplitOptions* split, const RodentPlocOptions* ploc) {
-    if (!opt || !ploc || d->num_tris < 1 || d->num_tris > RODENT_BUILD_MAX_TRIS
-        || rodent_hip_build_ploc_scratch_bytes(d->num_tris, opt, split, ploc) < 0 || d->num_vertices < 1 || d->nodes || d->tris
-        || d->num_nodes || d->num_bvh_tris) {
-        fprintf(stderr, "rodent_hip: rodent_hip_scene_create_device_bvh_ploc: invalid arguments (max_leaf 1 ... 8, treelet passes "
-                        "0 ... 3, costs in (0, 1e6], split budget 0 ... 4, max_pieces 1 ... 64, PLOC radius 1 ... 64, depth limit 0 or "
-                        "ceil(log2 references) ... 56 and 56 with treelet passes, wide iterations -1 ... 255, 1 ... 2^25 triangles, "
-                        "no hierarchy in the description)\n");
-        abort();
-    }
-    scene_create(dev, d, opt, split, ploc);
-}
-
-void rodent_hip_scene_refit(int32_t dev, const float* vertices, const float* normals, const float* face_normals,
-                            const RodentLight* lights) {
-    RenderDevice& r = rdev(dev);
-    DevScene& s = r.scene;
-    if (!s.loaded) { fprintf(stderr, "rodent_hip: no scene loaded on device %d (call rodent_hip_scene_create)\n", dev); abort(); }
-    flat_scene(dev, "rodent_hip_scene_refit");
-    if (!vertices || !normals || !face_normals || (s.dev.num_lights > 0 && !lights)) {
-        fprintf(stderr, "rodent_hip: rodent_hip_scene_refit: a NULL table\n"); abort(); }
-    HIP_CHECK(hipSetDevice(dev));
-    HIP_CHECK(hipDeviceSynchronize());                   // no frame still reads the tables that are overwritten
-    const size_t nv = (size_t)s.num_vertices, nt = (size_t)s.dev.num_tris;
-    HIP_CHECK(hipMemcpy(const_cast<float*>(s.dev.vertices), vertices, sizeof(float) * 4 * nv, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(const_cast<float*>(s.dev.normals), normals, sizeof(float) * 4 * nv, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(const_cast<float*>(s.dev.face_normals), face_normals, sizeof(float) * 4 * nt, hipMemcpyHostToDevice));
-    if (s.dev.num_lights > 0)
-        HIP_CHECK(hipMemcpy(const_cast<RodentLight*>(s.dev.lights), lights, sizeof(RodentLight) * (size_t)s.dev.num_lights,
-                            hipMemcpyHostToDevice));
-    // the hierarchy, in place: rodent_hip_scene_bvh's pointers stay valid
-    Node2* nodes = const_cast<Node2*>(s.dev.nodes);
-    Tri1* tris = const_cast<Tri1*>(s.dev.tris);
-    const int64_t scratch_bytes = rodent_hip_refit_scratch_bytes(s.num_nodes, s.num_bvh_tris);
-    char* scratch = nullptr;
-    int32_t info[RODENT_BUILD_INFO_WORDS] = {};
-    HIP_CHECK(hipMalloc(&scratch, (size_t)std::max<int64_t>(scratch_bytes, 0) + sizeof(info)));
-    int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + std::max<int64_t>(scratch_bytes, 0));
-    const int32_t rc = rodent_hip_refit_bvh2_tri1(dev, s.dev.vertices, s.num_vertices, s.dev.indices, s.dev.num_tris, nodes, s.num_nodes,
-                                                  tris, s.num_bvh_tris, scratch, info_dev, nullptr);
-    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: device BVH refit refused (%d)\n", rc); abort(); }
-    HIP_CHECK(hipMemcpy(info, info_dev, sizeof(info), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipFree(scratch));
-    if (info[2] || info[0] != s.num_nodes) {
-        fprintf(stderr, "rodent_hip: invalid scene: device BVH refit flagged the mesh or the hierarchy (flags %d, %d of %d nodes)\n",
-                info[2], info[0], s.num_nodes); abort(); }
-    // what scene_create derives from positions or bounds, into its existing allocations: both LDS images and the tri_shade records
-    std::vector<Node2> host_nodes((size_t)s.num_nodes);
-    HIP_CHECK(hipMemcpy(host_nodes.data(), nodes, sizeof(Node2) * host_nodes.size(), hipMemcpyDeviceToHost));
-    for (const int capacity : {kSceneTopNodes, kPersistTopNodes}) {
-        const std::vector<int32_t> image = build_image(host_nodes.data(), capacity);
-        const int4* dst = capacity == kSceneTopNodes ? s.dev.top_image : s.dev.top_image_large;
-        HIP_CHECK(hipMemcpy(const_cast<int4*>(dst), image.data(), sizeof(int32_t) * image.size(), hipMemcpyHostToDevice));
-    }
-    if (s.dev.tri_shade) {
-        std::vector<int32_t> indices(4 * nt);
-        HIP_CHECK(hipMemcpy(indices.data(), s.dev.indices, sizeof(int32_t) * indices.size(), hipMemcpyDeviceToHost));
-        const std::vector<float> rec = tri_shade(face_normals, normals, indices.data(), s.dev.num_tris);
-        HIP_CHECK(hipMemcpy(const_cast<float4*>(s.dev.tri_shade), rec.data(), sizeof(float) * rec.size(), hipMemcpyHostToDevice));
-    }
-}
-
-void rodent_hip_scene_refit_prepare(int32_t dev, int32_t smooth_normals) {
-    flat_scene(dev, "rodent_hip_scene_refit_prepare");
-    refit_prepare(rdev(dev), smooth_normals != 0);
-}
-
-void rodent_hip_scene_refit_device(int32_t dev, const float* vertices_dev, const float* normals_dev, void* stream_) {
-    DevScene& s = flat_scene(dev, "rodent_hip_scene_refit_device");
-    RenderDevice& r = rdev(dev);
-    if (!vertices_dev) { fprintf(stderr, "rodent_hip: rodent_hip_scene_refit_device: NULL vertices\n"); abort(); }
-    HIP_CHECK(hipSetDevice(dev));
-    if (!s.refit_info || (!normals_dev && !s.corner_first)) refit_prepare(r, !normals_dev);
-    hipStream_t stream = (hipStream_t)stream_;
-    // Behind the last device refit, whichever stream it took.  Frames need no such wait: a frame call returns when its rows are in the
-    // film (frame_end), so none is in flight; the next one waits for ev_refit (open_scene).
-    if (s.refit_enqueued) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_refit, 0));
-    const int nv = s.num_vertices, nt = s.dev.num_tris, nl = s.dev.num_lights;
-    float4* const vertices = reinterpret_cast<float4*>(const_cast<float*>(s.dev.vertices));
-    float4* const normals = reinterpret_cast<float4*>(const_cast<float*>(s.dev.normals));
-    float4* const face_normals = reinterpret_cast<float4*>(const_cast<float*>(s.dev.face_normals));
-    const int4* const indices = reinterpret_cast<const int4*>(s.dev.indices);
-    if (vertices_dev != s.dev.vertices)
-        HIP_CHECK(hipMemcpyAsync(vertices, vertices_dev, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToDevice, stream));
-    if (normals_dev && normals_dev != s.dev.normals)
-        HIP_CHECK(hipMemcpyAsync(normals, normals_dev, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToDevice, stream));
-    const auto blocks = [](int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
-    hipLaunchKernelGGL(k_face_normals, blocks(nt), dim3(kBlock), 0, stream, vertices, indices, nt, face_normals);
-    if (nl > 0) hipLaunchKernelGGL(k_light_records, blocks(nl), dim3(kBlock), 0, stream, vertices, indices, s.light_tri, nl,
-                                   const_cast<RodentLight*>(s.dev.lights));
-    if (!normals_dev) hipLaunchKernelGGL(k_smooth_normals, blocks(nv), dim3(kBlock), 0, stream, face_normals, s.corner_first,
-                                         s.corner_tri, nv, normals);
-    // the hierarchy, in place: rodent_hip_scene_bvh's pointers stay valid
-    const int32_t rc = rodent_hip_refit_bvh2_tri1(dev, s.dev.vertices, nv, s.dev.indices, nt, const_cast<Node2*>(s.dev.nodes), s.num_nodes,
-                                                  const_cast<Tri1*>(s.dev.tris), s.num_bvh_tris, s.refit_scratch, s.refit_info, stream);
-    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: device BVH refit refused (%d)\n", rc); abort(); }
-    hipLaunchKernelGGL(k_scene_images, dim3(2), dim3(kWave), 0, stream, s.dev.nodes, const_cast<int4*>(s.dev.top_image),
-                       const_cast<int4*>(s.dev.top_image_large));
-    if (s.dev.tri_shade) hipLaunchKernelGGL(k_tri_shade, blocks(nt), dim3(kBlock), 0, stream, face_normals, normals, indices, nt,
-                                            const_cast<float4*>(s.dev.tri_shade));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(r.ev_refit, stream));
-    s.refit_enqueued = true;
-}
-
-int32_t rodent_hip_scene_refit_status(int32_t dev, int32_t* info) {
-    DevScene& s = flat_scene(dev, "rodent_hip_scene_refit_status");
-    int32_t words[RODENT_BUILD_INFO_WORDS] = {s.num_nodes, s.num_bvh_tris, 0, 0};      // before the first refit: a sound one's words
-    if (s.refit_enqueued) {
-        HIP_CHECK(hipSetDevice(dev));
-        HIP_CHECK(hipEventSynchronize(rdev(dev).ev_refit));
-        HIP_CHECK(hipMemcpy(words, s.refit_info, sizeof(words), hipMemcpyDeviceToHost));
-    }
-    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
-    return words[2] | (words[0] != s.num_nodes ? (int32_t)0x80000000u : 0);
-}
-
-void rodent_hip_scene_tables(int32_t dev, RodentSceneTables* out) {
-    const DevScene& s = loaded_scene(dev, "rodent_hip_scene_tables");
-    if (!out) return;
-    *out = RodentSceneTables{const_cast<float*>(s.dev.vertices), const_cast<float*>(s.dev.normals), const_cast<float*>(s.dev.face_normals),
-        const_cast<RodentLight*>(s.dev.lights), reinterpret_cast<float*>(const_cast<float4*>(s.dev.tri_shade)),
-        reinterpret_cast<int32_t*>(const_cast<int4*>(s.dev.top_image)),
-        reinterpret_cast<int32_t*>(const_cast<int4*>(s.dev.top_image_large)),
-        s.num_vertices, s.dev.num_tris, s.dev.num_lights, kSceneTopNodes, kPersistTopNodes};
-}
-
-void rodent_hip_scene_bvh(int32_t dev, const Node2** nodes, const Tri1** tris, int32_t* num_nodes, int32_t* num_tris) {
-    RenderDevice& r = rdev(dev);
-    if (!r.scene.loaded) { fprintf(stderr, "rodent_hip: no scene loaded on device %d (call rodent_hip_scene_create)\n", dev); abort(); }
-    *nodes = r.scene.dev.nodes; *tris = r.scene.dev.tris;
-    *num_nodes = r.scene.num_nodes; *num_tris = r.scene.num_bvh_tris;
-}
-
-// The tables an instanced scene derives from its matrices, enqueued on `stream`: the TLAS and the instance array, slot_of, the world
-// lights (rodent_hip_scene_create_instanced, rodent_hip_scene_set_transforms).  Returns rodent_hip_build_tlas's status.
-// A moving scene: rodent_hip_build_motion_tlas and the motion forms of the two kernels (the world lights from M0).
-static int32_t derive_instanced(int32_t dev, DevScene& s, hipStream_t stream) {
-    const auto blocks = [](int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
-    if (s.motion) {
-        const int32_t rc = rodent_hip_build_motion_tlas(dev, s.dev.nodes, s.objects, s.num_objects, s.motion_descs, s.num_instances, 1,
-                                                        s.tlas_nodes, s.motion_instances, s.tlas_scratch, s.tlas_info, stream);
-        if (rc != RODENT_BUILD_OK) return rc;
-        hipLaunchKernelGGL(k_motion_slot_of, blocks(s.num_instances), dim3(kBlock), 0, stream, s.motion_instances, s.num_instances,
-                           s.slot_of);
-        hipLaunchKernelGGL(k_motion_world_lights, blocks(s.dev.num_lights), dim3(kBlock), 0, stream, s.motion_descs, s.light_owner,
-                           s.bases, s.object_lights, s.dev.num_lights, s.world_lights);
-        HIP_CHECK(hipGetLastError());
-        return rc;
-    }
-    const int32_t rc = rodent_hip_build_tlas(dev, s.dev.nodes, s.objects, s.num_objects, s.descs, s.num_instances, 1, s.tlas_nodes,
-                                             s.instances, s.tlas_scratch, s.tlas_info, stream);
-    if (rc != RODENT_BUILD_OK) return rc;
-    hipLaunchKernelGGL(k_slot_of, blocks(s.num_instances), dim3(kBlock), 0, stream, s.instances, s.num_instances, s.slot_of);
-    hipLaunchKernelGGL(k_world_lights, blocks(s.dev.num_lights), dim3(kBlock), 0, stream, s.descs, s.instances, s.slot_of, s.light_owner,
-                       s.bases, s.object_lights, s.dev.num_lights, s.world_lights);
-    HIP_CHECK(hipGetLastError());
-    return rc;
-}
-
-} // extern "C"
-
-// rodent_hip_scene_create_instanced (Desc = RodentInstanceDesc) and rodent_hip_scene_create_motion (RodentMotionInstanceDesc): one
-// creation; what differs is the record types, the top-level builder behind derive_instanced and the moving scene's one more refusal.
-template <typename Desc>
-static int32_t create_instanced_scene(int32_t dev, const RodentSceneDesc* d, const RodentObjectRange* objects, int32_t num_objects,
-                                      const Desc* instances, int32_t num_instances, const RodentBuildOptions* opt_) {
-    constexpr bool kMotion = std::is_same<Desc, RodentMotionInstanceDesc>::value;
-    const RodentBuildOptions default_opt{2, 0, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
-    const RodentBuildOptions* opt = opt_ ? opt_ : &default_opt;
-    // ---- the refusals: all on the host tables, before anything is enqueued or the current scene touched ----
-    if (!d || !objects || !instances || num_objects < 1 || num_instances < 1 || num_instances > RODENT_TLAS_MAX_INSTANCES) return
-        RODENT_SCENE_ERR_COUNTS;
-    const bool textured = d->num_textures > 0;
-    if (d->nodes || d->tris || d->num_nodes || d->num_bvh_tris || !d->vertices || !d->normals || !d->face_normals || !d->indices
-        || !d->materials || !d->light_ids || d->num_vertices < 1 || d->num_tris < 1 || d->num_tris > RODENT_BUILD_MAX_TRIS
-        || d->num_materials < 1 || d->num_lights < 0 || (d->num_lights > 0 && !d->lights) || d->num_textures < 0
-        || (textured && (!d->texcoords || !d->textures || !d->texels))) return RODENT_SCENE_ERR_COUNTS;
-    if (rodent_hip_build_opt_scratch_bytes(1, opt) < 0) return RODENT_SCENE_ERR_OPTIONS;
-    {
-        int64_t tri = 0, light = 0;
-        for (int32_t o = 0; o < num_objects; o++) {
-            const RodentObjectRange& r = objects[o];
-            if (r.first_tri != tri || r.num_tris < 1 || r.first_light != light || r.num_lights < 0) return RODENT_SCENE_ERR_RANGES;
-            tri += r.num_tris; light += r.num_lights;
-            if (tri > d->num_tris || light > d->num_lights) return RODENT_SCENE_ERR_RANGES;
-        }
-        if (tri != d->num_tris || light != d->num_lights) return RODENT_SCENE_ERR_RANGES;
-    }
-    for (int32_t k = 0; k < d->num_materials; k++)
-        if (d->materials[k].tex_kd < 0 || d->materials[k].tex_kd > d->num_textures || d->materials[k].tex_ks < 0
-            || d->materials[k].tex_ks > d->num_textures) return RODENT_SCENE_ERR_TABLE;
-    for (int32_t k = 0; k < d->num_textures; k++)
-        if (d->textures[k].width <= 0 || d->textures[k].height <= 0
-            || (uint64_t)d->textures[k].offset + (uint64_t)d->textures[k].width * (uint64_t)d->textures[k].height > d->num_texels)
-            return RODENT_SCENE_ERR_TABLE;
-    for (int32_t o = 0; o < num_objects; o++) {
-        const RodentObjectRange& r = objects[o];
-        for (int32_t t = r.first_tri; t < r.first_tri + r.num_tris; t++) {
-            for (int k = 0; k < 3; k++)
-                if ((uint32_t)d->indices[4 * (size_t)t + k] >= (uint32_t)d->num_vertices) return RODENT_SCENE_ERR_TABLE;
-            if ((uint32_t)d->indices[4 * (size_t)t + 3] >= (uint32_t)d->num_materials) return RODENT_SCENE_ERR_TABLE;
-            // an emitter's triangles are looked up in the light table by the shader: the entry must exist, and be the object's own
-            if (d->materials[d->indices[4 * (size_t)t + 3]].emissive
-                && (d->light_ids[t] < r.first_light || d->light_ids[t] >= r.first_light + r.num_lights)) return RODENT_SCENE_ERR_LIGHT;
-        }
-    }
-    int64_t world_lights = 0;
-    for (int32_t k = 0; k < num_instances; k++) {
-        if (instances[k].object < 0 || instances[k].object >= num_objects) return RODENT_SCENE_ERR_OBJECT;
-        world_lights += objects[instances[k].object].num_lights;
-    }
-    if (world_lights < 1) return RODENT_SCENE_ERR_NO_LIGHT;
-    if (world_lights > 0x7FFFFFFF) return RODENT_SCENE_ERR_COUNTS;
-    if constexpr (kMotion)                               // lights stay static: an emitter's two keys are equal byte for byte
-        for (int32_t k = 0; k < num_instances; k++)
-            if (objects[instances[k].object].num_lights > 0
-                && std::memcmp(instances[k].object_to_world0, instances[k].object_to_world1, sizeof(float) * 12) != 0)
-                return RODENT_SCENE_ERR_MOVING_LIGHT;
-
-    // ---- from here on the device's scene is the new one, or none ----
-    RenderDevice& r = rdev(dev);
-    rodent_hip_scene_destroy(dev);
-    HIP_CHECK(hipSetDevice(dev));
-    r.create_flags = 0;
-    DevScene& s = r.scene;
-    s.dev.vertices = upload(s, d->vertices, 4 * (size_t)d->num_vertices);
-    s.dev.normals = upload(s, d->normals, 4 * (size_t)d->num_vertices);
-    s.dev.face_normals = upload(s, d->face_normals, 4 * (size_t)d->num_tris);
-    s.dev.indices = upload(s, d->indices, 4 * (size_t)d->num_tris);
-    s.dev.materials = upload(s, d->materials, (size_t)d->num_materials);
-    s.dev.light_ids = upload(s, d->light_ids, (size_t)d->num_tris);
-    s.dev.texcoords = upload(s, d->texcoords, textured ? 4 * (size_t)d->num_vertices : 0);
-    s.dev.textures = upload(s, d->textures, textured ? (size_t)d->num_textures : 0);
-    s.dev.texels = upload(s, d->texels, textured ? (size_t)d->num_texels : 0);
-    s.object_lights = upload(s, d->lights, (size_t)d->num_lights);
-    const auto fail = [&](int32_t flags) { rodent_hip_scene_destroy(dev); r.create_flags = flags; return RODENT_SCENE_ERR_DEVICE; };
-    // every object's hierarchy, built into a block of its own (its node count is known only afterwards), then packed
-    std::vector<RodentObject> table((size_t)num_objects);
-    std::vector<char*> built((size_t)num_objects, nullptr);
-    const auto free_built = [&] { for (char* b : built) if (b) HIP_CHECK(hipFree(b)); };
-    int64_t total_nodes = 0;
-    // Without treelet passes: ALL objects by one rodent_hip_build_objects call in pack mode (one launch list whatever their number)
-    // into a temporary block; the table, the per-object info words and the call's come back in one copy.
-    std::vector<RodentRefitRange> plan((size_t)num_objects);
-    char* forest = nullptr;                              // nodes (room for max(1, n - 1) each), then, 256-byte aligned, the triangles
-    size_t forest_tris = 0;
-    int64_t forest_scratch = -1;
-    if (opt->treelet_passes == 0) {
-        std::vector<int32_t> ids((size_t)num_objects), first((size_t)num_objects), count((size_t)num_objects);
-        for (int32_t o = 0; o < num_objects; o++) { ids[o] = o; first[o] = objects[o].first_tri; count[o] = objects[o].num_tris; }
-        int32_t totals[2] = {};
-        forest_scratch = rodent_hip_build_objects_plan(ids.data(), first.data(), count.data(), num_objects, plan.data(), totals);
-    }
-    if (forest_scratch >= 0) {
-        size_t room = 0;
-        for (int32_t o = 0; o < num_objects; o++) room += (size_t)std::max(1, objects[o].num_tris - 1);
-        forest_tris = (sizeof(Node2) * room + 255) / 256 * 256;
-        const size_t range_bytes = (sizeof(RodentRefitRange) * (size_t)num_objects + 255) / 256 * 256;
-        const size_t result_words = 8 * (size_t)num_objects + RODENT_BUILD_INFO_WORDS;    // table, object info, info
-        char* work = nullptr;                            // scratch, the range table, the results
-        HIP_CHECK(hipMalloc(&forest, forest_tris + sizeof(Tri1) * (size_t)d->num_tris));
-        HIP_CHECK(hipMalloc(&work, (size_t)forest_scratch + range_bytes + 4 * result_words));
-        RodentRefitRange* ranges_dev = reinterpret_cast<RodentRefitRange*>(work + forest_scratch);
-        RodentObject* table_dev = reinterpret_cast<RodentObject*>(work + forest_scratch + range_bytes);
-        int32_t* object_info_dev = reinterpret_cast<int32_t*>(table_dev + num_objects);
-        int32_t* info_dev = object_info_dev + 4 * (size_t)num_objects;
-        HIP_CHECK(hipMemcpy(ranges_dev, plan.data(), sizeof(RodentRefitRange) * (size_t)num_objects, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(table_dev, 0, 4 * result_words));
-        const int32_t rc = rodent_hip_build_objects(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, opt->max_leaf,
-            RODENT_BUILD_OBJECTS_PACK, reinterpret_cast<Node2*>(forest), reinterpret_cast<Tri1*>(forest + forest_tris), table_dev,
-            num_objects, ranges_dev, num_objects, d->num_tris, work, object_info_dev, info_dev, nullptr);
-        std::vector<int32_t> result(result_words, 0);
-        if (rc == RODENT_BUILD_OK) HIP_CHECK(hipMemcpy(result.data(), table_dev, 4 * result_words, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipFree(work));
-        const int32_t* object_info = result.data() + 4 * (size_t)num_objects;
-        int32_t bad = rc;
-        for (int32_t o = 0; o < num_objects && !bad; o++) {      // the first flagged object in object order, as the loop reports it
-            const int32_t nodes_o = object_info[4 * o], n = objects[o].num_tris;
-            bad = object_info[4 * o + 2] ? object_info[4 * o + 2] : nodes_o < 1 || nodes_o > std::max(1, n - 1) ? (int32_t)0x80000000u : 0;
-        }
-        if (!bad) bad = object_info[4 * (size_t)num_objects + 2];
-        if (bad) { HIP_CHECK(hipFree(forest)); return fail(bad); }
-        for (int32_t o = 0; o < num_objects; o++) {
-            std::memcpy(&table[o], result.data() + 4 * (size_t)o, sizeof(RodentObject));
-            total_nodes += table[o].num_nodes;
-        }
-    }
-    for (int32_t o = 0; o < num_objects && !forest; o++) {
-        const int32_t n = objects[o].num_tris;
-        const size_t node_bytes = sizeof(Node2) * (size_t)std::max(1, n - 1), tri_bytes = sizeof(Tri1) * (size_t)n;
-        const int64_t scratch_bytes = std::max<int64_t>(rodent_hip_build_opt_scratch_bytes(n, opt), 0);
-        char* scratch = nullptr;
-        HIP_CHECK(hipMalloc(&built[o], node_bytes + tri_bytes));
-        HIP_CHECK(hipMalloc(&scratch, (size_t)scratch_bytes + 4 * RODENT_BUILD_INFO_WORDS));
-        int32_t* info_dev = reinterpret_cast<int32_t*>(scratch + scratch_bytes);
-        int32_t info[RODENT_BUILD_INFO_WORDS] = {};
-        const int32_t rc = rodent_hip_build_bvh2_tri1_opt(dev, s.dev.vertices, d->num_vertices,
-            s.dev.indices + 4 * (size_t)objects[o].first_tri, n, opt, reinterpret_cast<Node2*>(built[o]),
-            reinterpret_cast<Tri1*>(built[o] + node_bytes), scratch, info_dev, nullptr);
-        if (rc == RODENT_BUILD_OK) HIP_CHECK(hipMemcpy(info, info_dev, sizeof(info), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipFree(scratch));
-        if (rc != RODENT_BUILD_OK || info[2] || info[0] < 1 || info[0] > std::max(1, n - 1)) {
-            free_built();
-            return fail(rc != RODENT_BUILD_OK ? rc : info[2] ? info[2] : (int32_t)0x80000000u);
-        }
-        table[o] = RodentObject{(int32_t)total_nodes, objects[o].first_tri, info[0], n};
-        total_nodes += info[0];
-    }
-    {   // one allocation: all nodes, then, 256-byte aligned, all triangles (instances.pack_objects)
-        const size_t node_bytes = sizeof(Node2) * (size_t)total_nodes, tri_start = (node_bytes + 255) / 256 * 256;
-        char* bvh = nullptr;
-        HIP_CHECK(hipMalloc(&bvh, tri_start + sizeof(Tri1) * (size_t)d->num_tris));
-        s.allocs.push_back(bvh);
-        if (forest) {                                            // packed tight already: the nodes, then the triangles
-            HIP_CHECK(hipMemcpy(bvh, forest, node_bytes, hipMemcpyDeviceToDevice));
-            HIP_CHECK(hipMemcpy(bvh + tri_start, forest + forest_tris, sizeof(Tri1) * (size_t)d->num_tris, hipMemcpyDeviceToDevice));
-        }
-        for (int32_t o = 0; o < num_objects && !forest; o++) {
-            const size_t from_tris = sizeof(Node2) * (size_t)std::max(1, objects[o].num_tris - 1);
-            HIP_CHECK(hipMemcpy(bvh + sizeof(Node2) * (size_t)table[o].node_offset, built[o], sizeof(Node2) * (size_t)table[o].num_nodes,
-                                hipMemcpyDeviceToDevice));
-            HIP_CHECK(hipMemcpy(bvh + tri_start + sizeof(Tri1) * (size_t)table[o].tri_offset, built[o] + from_tris,
-                                sizeof(Tri1) * (size_t)table[o].num_tris, hipMemcpyDeviceToDevice));
-        }
-        HIP_CHECK(hipDeviceSynchronize());
-        free_built();
-        if (forest) HIP_CHECK(hipFree(forest));
-        s.dev.nodes = reinterpret_cast<const Node2*>(bvh);
-        s.dev.tris = reinterpret_cast<const Tri1*>(bvh + tri_start);
-    }
-    s.objects = upload(s, table.data(), table.size());
-    s.object_table = table;
-    s.object_ranges.assign(objects, objects + num_objects);
-    // descriptors (ids = indices), bases and light owners: fixed for the scene's life
-    std::vector<Desc> descs(instances, instances + num_instances);
-    std::vector<int2> bases((size_t)num_instances);
-    std::vector<int> owner((size_t)world_lights);
-    int32_t light_base = 0;
-    for (int32_t k = 0; k < num_instances; k++) {
-        descs[k].instance_id = k;
-        for (int32_t& word : descs[k].pad) word = 0;
-        const RodentObjectRange& o = objects[descs[k].object];
-        bases[k] = make_int2(o.first_tri, light_base - o.first_light);
-        for (int32_t j = 0; j < o.num_lights; j++) owner[(size_t)light_base + j] = k;
-        light_base += o.num_lights;
-    }
-    s.motion = kMotion;
-    if constexpr (kMotion) s.motion_descs = upload(s, descs.data(), descs.size());
-    else s.descs = upload(s, descs.data(), descs.size());
-    s.bases = upload(s, bases.data(), bases.size());
-    s.light_owner = upload(s, owner.data(), owner.size());
-    const auto device_block = [&](size_t bytes) { char* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
-        HIP_CHECK(hipMemset(p, 0, std::max<size_t>(bytes, 16))); s.allocs.push_back(p); return p; };
-    s.tlas_nodes = reinterpret_cast<Node2*>(device_block(sizeof(Node2) * (size_t)std::max(1, num_instances - 1)));
-    if constexpr (kMotion)
-        s.motion_instances = reinterpret_cast<RodentMotionInstance*>(device_block(sizeof(RodentMotionInstance) * (size_t)num_instances));
-    else s.instances = reinterpret_cast<RodentInstance*>(device_block(sizeof(RodentInstance) * (size_t)num_instances));
-    s.slot_of = reinterpret_cast<int*>(device_block(sizeof(int) * (size_t)num_instances));
-    s.world_lights = reinterpret_cast<RodentLight*>(device_block(sizeof(RodentLight) * (size_t)world_lights));
-    s.tlas_scratch = device_block((size_t)std::max<int64_t>(
-        kMotion ? rodent_hip_motion_tlas_scratch_bytes(num_instances) : rodent_hip_tlas_scratch_bytes(num_instances), 0));
-    s.tlas_info = reinterpret_cast<int32_t*>(device_block(4 * RODENT_BUILD_INFO_WORDS));
-    s.num_instances = num_instances; s.num_objects = num_objects; s.num_object_lights = d->num_lights;
-    s.dev.lights = s.world_lights;
-    s.dev.num_tris = d->num_tris; s.dev.num_materials = d->num_materials; s.dev.num_lights = (int32_t)world_lights;
-    s.dev.top_image = s.dev.top_image_large = nullptr;         // the instanced kernels stage no image; no other kernel is launched
-    HIP_CHECK(hipDeviceSynchronize());
-    const int32_t rc = derive_instanced(dev, s, nullptr);
-    int32_t info[RODENT_BUILD_INFO_WORDS] = {};
-    HIP_CHECK(hipDeviceSynchronize());
-    if (rc == RODENT_BUILD_OK) HIP_CHECK(hipMemcpy(info, s.tlas_info, sizeof(info), hipMemcpyDeviceToHost));
-    if (rc != RODENT_BUILD_OK || info[2]) return fail(rc != RODENT_BUILD_OK ? rc : info[2]);
-    upload_shading_records(s, d, textured);
-    s.inst.tlas = s.tlas_nodes; s.inst.instances = s.instances; s.inst.bases = s.bases;
-    s.num_nodes = (int)total_nodes; s.num_bvh_tris = d->num_tris; s.num_vertices = d->num_vertices; s.tri_delta = 0;
-    s.loaded = true; s.instanced = true;
-    ensure_ray_slots(r, 0);
-    r.mapping = resolve_mapping(r); r.trace_persistent = resolve_trace(r); resolve_refill(r);
-    return RODENT_SCENE_OK;
-}
-
-extern "C" {
-
-int32_t rodent_hip_scene_create_instanced(int32_t dev, const RodentSceneDesc* d, const RodentObjectRange* objects, int32_t num_objects,
-                                          const RodentInstanceDesc* instances, int32_t num_instances, const RodentBuildOptions* opt) {
-    return create_instanced_scene(dev, d, objects, num_objects, instances, num_instances, opt);
-}
-
-int32_t rodent_hip_scene_create_motion(int32_t dev, const RodentSceneDesc* d, const RodentObjectRange* objects, int32_t num_objects,
-                                       const RodentMotionInstanceDesc* instances, int32_t num_instances, const RodentBuildOptions* opt) {
-    return create_instanced_scene(dev, d, objects, num_objects, instances, num_instances, opt);
-}
-
-int32_t rodent_hip_scene_create_flags(int32_t dev) { return rdev(dev).create_flags; }
-
-void rodent_hip_scene_set_motion_transforms(int32_t dev, const float* m0_dev, const float* m1_dev, void* stream_) {
-    DevScene& s = motion_scene(dev, "rodent_hip_scene_set_motion_transforms");
-    RenderDevice& r = rdev(dev);
-    if (!m0_dev || !m1_dev) { fprintf(stderr, "rodent_hip: rodent_hip_scene_set_motion_transforms: NULL matrices\n"); abort(); }
-    HIP_CHECK(hipSetDevice(dev));
-    if (!r.ev_refit) HIP_CHECK(hipEventCreateWithFlags(&r.ev_refit, hipEventDisableTiming));
-    hipStream_t stream = (hipStream_t)stream_;
-    // behind the last move, whichever stream it took; frames need no wait (rodent_hip_scene_refit_device says why)
-    if (s.refit_enqueued) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_refit, 0));
-    hipLaunchKernelGGL(k_motion_instance_matrices, dim3((unsigned)((24 * s.num_instances + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                       m0_dev, m1_dev, s.num_instances, s.motion_descs);
-    const int32_t rc = derive_instanced(dev, s, stream);
-    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: top-level rebuild refused (%d)\n", rc); abort(); }
-    HIP_CHECK(hipEventRecord(r.ev_refit, stream));
-    s.refit_enqueued = true;
-}
-
-void rodent_hip_scene_motion_instances(int32_t dev, RodentSceneMotionInstances* out) {
-    DevScene& s = motion_scene(dev, "rodent_hip_scene_motion_instances");
-    if (!out) return;
-    ensure_ray_slots(rdev(dev), 0);
-    *out = RodentSceneMotionInstances{s.tlas_nodes, s.motion_instances, s.motion_descs, s.objects, s.slot_of,
-        reinterpret_cast<int32_t*>(s.bases), s.light_owner, s.world_lights, s.object_lights, s.inst.ray_slots, s.tlas_info, s.num_instances,
-        s.num_objects, std::max(1, s.num_instances - 1), s.dev.num_lights, s.num_object_lights, (int32_t)s.ray_slot_cap};
-}
 
 int32_t rodent_hip_render_shutter(int32_t dev, float open, float close) {
     RenderDevice& r = rdev(dev);
@@ -1591,183 +852,6 @@ int32_t rodent_hip_render_shutter(int32_t dev, float open, float close) {
 void rodent_hip_render_shutter_in_effect(int32_t dev, float out[2]) { const RenderDevice& r = rdev(dev);
     out[0] = r.shutter[0]; out[1] = r.shutter[1]; }
 int32_t rodent_hip_render_max_path_len_in_effect(int32_t dev) { return path_len_in_effect(rdev(dev)); }
-
-void rodent_hip_scene_set_transforms(int32_t dev, const float* object_to_world_dev, void* stream_) {
-    DevScene& s = instanced_scene(dev, "rodent_hip_scene_set_transforms");
-    RenderDevice& r = rdev(dev);
-    if (!object_to_world_dev) { fprintf(stderr, "rodent_hip: rodent_hip_scene_set_transforms: NULL matrices\n"); abort(); }
-    HIP_CHECK(hipSetDevice(dev));
-    if (!r.ev_refit) HIP_CHECK(hipEventCreateWithFlags(&r.ev_refit, hipEventDisableTiming));
-    hipStream_t stream = (hipStream_t)stream_;
-    // behind the last move, whichever stream it took; frames need no wait (rodent_hip_scene_refit_device says why)
-    if (s.refit_enqueued) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_refit, 0));
-    hipLaunchKernelGGL(k_instance_matrices, dim3((unsigned)((12 * s.num_instances + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                       object_to_world_dev, s.num_instances, s.descs);
-    const int32_t rc = derive_instanced(dev, s, stream);
-    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: top-level rebuild refused (%d)\n", rc); abort(); }
-    HIP_CHECK(hipEventRecord(r.ev_refit, stream));
-    s.refit_enqueued = true;
-}
-
-int32_t rodent_hip_scene_transforms_status(int32_t dev, int32_t* info) {
-    DevScene& s = loaded_scene(dev, "rodent_hip_scene_transforms_status");
-    if (!s.motion) instanced_scene(dev, "rodent_hip_scene_transforms_status");       // (it serves a moving scene's moves too)
-    int32_t words[RODENT_BUILD_INFO_WORDS] = {};
-    HIP_CHECK(hipSetDevice(dev));
-    if (s.refit_enqueued) HIP_CHECK(hipEventSynchronize(rdev(dev).ev_refit));
-    HIP_CHECK(hipMemcpy(words, s.tlas_info, sizeof(words), hipMemcpyDeviceToHost));
-    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
-    return words[2];
-}
-
-int32_t rodent_hip_scene_deform_prepare(int32_t dev, const int32_t* objects, int32_t num_objects, int32_t smooth_normals) {
-    RenderDevice& r = rdev(dev);
-    DevScene& s = r.scene;
-    // ---- the refusals: on the host, the scene and an earlier set stay as they are ----
-    if (!s.loaded || !s.instanced || s.motion) return RODENT_SCENE_ERR_NOT_INSTANCED;
-    if (!objects || num_objects < 1) return RODENT_SCENE_ERR_COUNTS;
-    std::vector<char> listed((size_t)s.num_objects, 0);
-    for (int32_t k = 0; k < num_objects; k++) {
-        if (objects[k] < 0 || objects[k] >= s.num_objects || listed[objects[k]]) return RODENT_SCENE_ERR_OBJECT;
-        listed[objects[k]] = 1;
-    }
-    std::vector<int32_t> first_tri((size_t)num_objects), num_tris((size_t)num_objects);
-    for (int32_t k = 0; k < num_objects; k++) {
-        first_tri[k] = s.object_ranges[objects[k]].first_tri; num_tris[k] = s.object_ranges[objects[k]].num_tris; }
-    std::vector<RodentRefitRange> ranges((size_t)num_objects);
-    int32_t totals[2] = {};
-    const int64_t scratch_bytes = rodent_hip_refit_objects_plan(s.object_table.data(), s.num_objects, objects, first_tri.data(),
-                                                                num_tris.data(), num_objects, ranges.data(), totals);
-    if (scratch_bytes < 0) return RODENT_SCENE_ERR_COUNTS;
-    // ---- from here on the set is the new one ----
-    HIP_CHECK(hipSetDevice(dev));
-    HIP_CHECK(hipDeviceSynchronize());                   // no update still works in the lists that are replaced
-    if (!r.ev_refit) HIP_CHECK(hipEventCreateWithFlags(&r.ev_refit, hipEventDisableTiming));
-    for (void* p : s.deform.allocs) HIP_CHECK(hipFree(p));
-    s.deform = DevScene::DeformSet();
-    DevScene::DeformSet& d = s.deform;
-    const auto put = [&](const auto* host, size_t count) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(host)>>;
-        T* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, std::max<size_t>(sizeof(T) * count, 16)));
-        if (count) HIP_CHECK(hipMemcpy(p, host, sizeof(T) * count, hipMemcpyHostToDevice));
-        d.allocs.push_back(p);
-        return p;
-    };
-    d.ranges = put(ranges.data(), ranges.size());
-    HIP_CHECK(hipMalloc(&d.scratch, (size_t)scratch_bytes + 4 * RODENT_BUILD_INFO_WORDS));
-    d.allocs.push_back(d.scratch);
-    d.info = reinterpret_cast<int32_t*>(d.scratch + scratch_bytes);
-    HIP_CHECK(hipMemset(d.info, 0, 4 * RODENT_BUILD_INFO_WORDS));
-    d.num_listed = num_objects; d.num_nodes = totals[0]; d.num_tris = totals[1]; d.smooth = smooth_normals != 0;
-    // The tables the lists are made from never change under an update: indices, light ids, materials.
-    const size_t nv = (size_t)s.num_vertices, nt = (size_t)s.dev.num_tris;
-    std::vector<int32_t> indices(4 * nt), light_ids(nt);
-    std::vector<RodentMaterial> materials((size_t)s.dev.num_materials);
-    HIP_CHECK(hipMemcpy(indices.data(), s.dev.indices, sizeof(int32_t) * indices.size(), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(light_ids.data(), s.dev.light_ids, sizeof(int32_t) * nt, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(materials.data(), s.dev.materials, sizeof(RodentMaterial) * materials.size(), hipMemcpyDeviceToHost));
-    // light k of D's light ranges: bound to the lowest emissive triangle that names it (one of its own object's: the creation checked)
-    std::vector<int2> bound;
-    for (int32_t o = 0; o < s.num_objects; o++) {
-        if (!listed[o]) continue;
-        const RodentObjectRange& g = s.object_ranges[o];
-        std::vector<int> tri((size_t)g.num_lights, -1);
-        for (int32_t t = g.first_tri; t < g.first_tri + g.num_tris; t++) {
-            const int32_t k = light_ids[t] - g.first_light;
-            if (materials[indices[4 * (size_t)t + 3]].emissive && k >= 0 && k < g.num_lights && tri[k] < 0) tri[k] = t;
-        }
-        for (int32_t k = 0; k < g.num_lights; k++) if (tri[k] >= 0) bound.push_back(make_int2(g.first_light + k, tri[k]));
-    }
-    d.lights = put(bound.data(), bound.size()); d.num_lights = (int)bound.size();
-    if (d.smooth) {
-        // the vertices D's triangles name, ascending, and for each the corners of ALL triangles that name it, ascending (triangle, corner)
-        std::vector<int> slot(nv, -1), verts;
-        for (int32_t o = 0; o < s.num_objects; o++) {
-            if (!listed[o]) continue;
-            const RodentObjectRange& g = s.object_ranges[o];
-            for (size_t c = 4 * (size_t)g.first_tri; c < 4 * (size_t)(g.first_tri + g.num_tris); c++) if (c % 4 != 3) slot[indices[c]] = 0;
-        }
-        for (size_t v = 0; v < nv; v++) if (slot[v] == 0) { slot[v] = (int)verts.size(); verts.push_back((int)v); }
-        std::vector<int> first(verts.size() + 1, 0);
-        for (size_t t = 0; t < nt; t++) for (int k = 0; k < 3; k++) { const int j = slot[indices[4 * t + k]]; if (j >= 0) first[(size_t)j + 1]++; }
-        for (size_t j = 0; j < verts.size(); j++) first[j + 1] += first[j];
-        std::vector<int> next(first.begin(), first.end() - 1), tri((size_t)first.back());
-        for (size_t t = 0; t < nt; t++) for (int k = 0; k < 3; k++) { const int j = slot[indices[4 * t + k]]; if (j >= 0) tri[next[j]++] = (int)t; }
-        d.verts = put(verts.data(), verts.size()); d.num_verts = (int)verts.size();
-        d.corner_first = put(first.data(), first.size());
-        d.corner_tri = put(tri.data(), tri.size());
-    }
-    return RODENT_SCENE_OK;
-}
-
-void rodent_hip_scene_deform_device(int32_t dev, const float* vertices_dev, const float* normals_dev, const float* object_to_world_dev,
-                                    void* stream_) {
-    DevScene& s = instanced_scene(dev, "rodent_hip_scene_deform_device");
-    RenderDevice& r = rdev(dev);
-    DevScene::DeformSet& d = s.deform;
-    if (!vertices_dev) { fprintf(stderr, "rodent_hip: rodent_hip_scene_deform_device: NULL vertices\n"); abort(); }
-    if (!d.ranges || (!normals_dev && !d.smooth)) {
-        fprintf(stderr, "rodent_hip: rodent_hip_scene_deform_device: no deforming set declared (rodent_hip_scene_deform_prepare%s)\n",
-                d.ranges ? " with smooth_normals, or pass normals" : ""); abort(); }
-    HIP_CHECK(hipSetDevice(dev));
-    hipStream_t stream = (hipStream_t)stream_;
-    // behind the last update or move, whichever stream it took; frames need no wait (rodent_hip_scene_refit_device says why)
-    if (s.refit_enqueued) HIP_CHECK(hipStreamWaitEvent(stream, r.ev_refit, 0));
-    const int nv = s.num_vertices;
-    float4* const vertices = reinterpret_cast<float4*>(const_cast<float*>(s.dev.vertices));
-    float4* const normals = reinterpret_cast<float4*>(const_cast<float*>(s.dev.normals));
-    float4* const face_normals = reinterpret_cast<float4*>(const_cast<float*>(s.dev.face_normals));
-    const int4* const indices = reinterpret_cast<const int4*>(s.dev.indices);
-    if (vertices_dev != s.dev.vertices)
-        HIP_CHECK(hipMemcpyAsync(vertices, vertices_dev, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToDevice, stream));
-    if (normals_dev && normals_dev != s.dev.normals)
-        HIP_CHECK(hipMemcpyAsync(normals, normals_dev, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToDevice, stream));
-    const auto blocks = [](int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
-    if (object_to_world_dev)
-        hipLaunchKernelGGL(k_instance_matrices, blocks(12 * s.num_instances), dim3(kBlock), 0, stream, object_to_world_dev,
-                           s.num_instances, s.descs);
-    const DeformTris tris{d.ranges, d.num_listed, d.num_tris};
-    hipLaunchKernelGGL(k_deform_face_normals, blocks(d.num_tris), dim3(kBlock), 0, stream, vertices, indices, tris, face_normals);
-    if (d.num_lights > 0) hipLaunchKernelGGL(k_deform_light_records, blocks(d.num_lights), dim3(kBlock), 0, stream, vertices, indices,
-                                             d.lights, d.num_lights, s.object_lights);
-    if (!normals_dev) hipLaunchKernelGGL(k_deform_smooth_normals, blocks(d.num_verts), dim3(kBlock), 0, stream, face_normals, d.verts,
-                                         d.corner_first, d.corner_tri, d.num_verts, normals);
-    // the listed objects' hierarchies, in the packed allocation: rodent_hip_scene_bvh's pointers stay valid
-    int32_t rc = rodent_hip_refit_objects(dev, s.dev.vertices, nv, s.dev.indices, s.dev.num_tris, const_cast<Node2*>(s.dev.nodes),
-                                          const_cast<Tri1*>(s.dev.tris), s.objects, s.num_objects, d.ranges, d.num_listed, d.num_nodes,
-                                          d.num_tris, d.scratch, d.info, stream);
-    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: refit of the deforming objects refused (%d)\n", rc); abort(); }
-    if (s.dev.tri_shade) hipLaunchKernelGGL(k_deform_tri_shade, blocks(d.num_tris), dim3(kBlock), 0, stream, face_normals, normals,
-                                            indices, tris, const_cast<float4*>(s.dev.tri_shade));
-    // the objects' boxes changed: the TLAS, slot_of and the world lights, as after a move
-    rc = derive_instanced(dev, s, stream);
-    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: top-level rebuild refused (%d)\n", rc); abort(); }
-    HIP_CHECK(hipEventRecord(r.ev_refit, stream));
-    s.refit_enqueued = true; d.enqueued = true;
-}
-
-int32_t rodent_hip_scene_deform_status(int32_t dev, int32_t* refit_info, int32_t* tlas_info) {
-    DevScene& s = instanced_scene(dev, "rodent_hip_scene_deform_status");
-    const DevScene::DeformSet& d = s.deform;
-    int32_t refit[RODENT_BUILD_INFO_WORDS] = {d.num_nodes, d.num_tris, 0, 0}, tlas[RODENT_BUILD_INFO_WORDS] = {};
-    HIP_CHECK(hipSetDevice(dev));
-    if (s.refit_enqueued) HIP_CHECK(hipEventSynchronize(rdev(dev).ev_refit));
-    if (d.enqueued) HIP_CHECK(hipMemcpy(refit, d.info, sizeof(refit), hipMemcpyDeviceToHost));    // before the first: a sound one's words
-    HIP_CHECK(hipMemcpy(tlas, s.tlas_info, sizeof(tlas), hipMemcpyDeviceToHost));
-    if (refit_info) std::copy(refit, refit + RODENT_BUILD_INFO_WORDS, refit_info);
-    if (tlas_info) std::copy(tlas, tlas + RODENT_BUILD_INFO_WORDS, tlas_info);
-    return refit[2] | tlas[2] | (refit[0] < d.num_nodes ? (int32_t)0x80000000u : 0);
-}
-
-void rodent_hip_scene_instances(int32_t dev, RodentSceneInstances* out) {
-    DevScene& s = instanced_scene(dev, "rodent_hip_scene_instances");
-    if (!out) return;
-    ensure_ray_slots(rdev(dev), 0);
-    *out = RodentSceneInstances{s.tlas_nodes, s.instances, s.descs, s.objects, s.slot_of, reinterpret_cast<int32_t*>(s.bases),
-        s.light_owner, s.world_lights, s.object_lights, s.inst.ray_slots, s.tlas_info, s.num_instances, s.num_objects,
-        std::max(1, s.num_instances - 1), s.dev.num_lights, s.num_object_lights, (int32_t)s.ray_slot_cap};
-}
 
 void rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len) {
     if (spp < 1 || max_path_len < 0) { fprintf(stderr, "rodent_hip: invalid render configuration\n"); abort(); }
@@ -1817,8 +901,7 @@ void rodent_hip_render_mapping(int32_t dev, int32_t mapping) {
     r.mapping = resolve_mapping(r);
 }
 int32_t rodent_hip_render_mapping_in_effect(int32_t dev) { return rdev(dev).mapping; }
-void rodent_hip_render_defaults(int32_t dev) { RenderDevice& r = rdev(dev); render_defaults(r); r.mapping = resolve_mapping(r);
-    r.trace_persistent = resolve_trace(r); resolve_refill(r); }
+void rodent_hip_render_defaults(int32_t dev) { RenderDevice& r = rdev(dev); render_defaults(r); resolve_options(r); }
 
 int32_t get_spp(void) { return rdev(g_current_dev).spp; }
 

@@ -357,6 +357,10 @@ def test_refusals_leave_the_loaded_scene_alone(R, parts, oracle, cam):
     quad = ranges[2, 0]
     stolen[quad] = 0                                                       # the quad's first triangle names the box's light
     far = scene.indices.copy(); far[3, 1] = len(scene.vertices)
+    assert 3 < quad < len(scene.indices) - 1
+    far_last = scene.indices.copy(); far_last[-1, 1] = len(scene.vertices)
+    no_material = scene.indices.copy(); no_material[3, 3] = len(scene.materials)
+    no_texture = scene.materials.copy(); no_texture["tex_kd"][0] = len(scene.textures) + 1
     with_bvh = changed(nodes=parts.hierarchy[0], tris=parts.hierarchy[1])
     bad_opt = abi.BuildOptions(9, 0, gpubuild.NODE_COST, gpubuild.TRI_COST)
     cases = [("a hierarchy in the description", R.SCENE_ERR_COUNTS, (with_bvh, ranges, t, ids), None),
@@ -371,7 +375,16 @@ def test_refusals_leave_the_loaded_scene_alone(R, parts, oracle, cam):
              ("a negative object index", R.SCENE_ERR_OBJECT, (scene, ranges, t, np.where(np.arange(7) == 2, -1, ids)), None),
              ("no light in any instance", R.SCENE_ERR_NO_LIGHT, (scene, ranges, t[1:5], ids[1:5]), None),
              ("max_leaf 9", R.SCENE_ERR_OPTIONS, (scene, ranges, t, ids), bad_opt),
-             ("a vertex index outside the table", R.SCENE_ERR_TABLE, (changed(indices=far), ranges, t, ids), None)]
+             ("a vertex index outside the table", R.SCENE_ERR_TABLE, (changed(indices=far), ranges, t, ids), None),
+             ("a material index outside the table", R.SCENE_ERR_TABLE, (changed(indices=no_material), ranges, t, ids), None),
+             ("a material that names a texture outside the table", R.SCENE_ERR_TABLE, (changed(materials=no_texture), ranges, t, ids), None),
+             # the order of the table checks: materials and textures, then triangle by triangle its indices and then its light
+             ("a missing texture before another object's light", R.SCENE_ERR_TABLE,
+              (changed(materials=no_texture, light_ids=stolen), ranges, t, ids), None),
+             ("an earlier triangle's index before a later one's light", R.SCENE_ERR_TABLE,
+              (changed(indices=far, light_ids=stolen), ranges, t, ids), None),
+             ("an earlier triangle's light before a later one's index", R.SCENE_ERR_LIGHT,
+              (changed(indices=far_last, light_ids=stolen), ranges, t, ids), None)]
     flat = R.Renderer(parts.cornell, W, H, SPP, MAXLEN)
     flat.render(cam, 0)
     film = flat.film()
