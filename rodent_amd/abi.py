@@ -58,6 +58,9 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "hip_occluded_motion_instanced_bvh2_tri1",
     "rodent_hip_refit_objects_plan", "rodent_hip_refit_objects",
     "rodent_hip_build_objects_plan", "rodent_hip_build_objects", "rodent_hip_build_objects_sync",
+    "rodent_hip_fuse_motion_bvh2_tri1", "rodent_hip_motion_bvh2_scratch_bytes", "rodent_hip_build_motion_bvh2_tri1",
+    "rodent_hip_build_motion_bvh2_tri1_sync",
+    "hip_traverse_motion_bvh2_tri1_async", "hip_intersect_motion_bvh2_tri1", "hip_occluded_motion_bvh2_tri1",
 ]
 BLOCK_OF_WIDTH = {2: F.BVH2_TRI1, 4: F.BVH4_TRI4, 8: F.BVH8_TRI4}
 
@@ -192,6 +195,18 @@ def lib():
         l.rodent_hip_build_objects.argtypes = [i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
         l.rodent_hip_build_objects_sync.restype = i32
         l.rodent_hip_build_objects_sync.argtypes = [i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp]
+        # deforming meshes under motion (include/rodent_motion.h)
+        l.rodent_hip_fuse_motion_bvh2_tri1.restype = i32
+        l.rodent_hip_fuse_motion_bvh2_tri1.argtypes = [i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+        l.rodent_hip_motion_bvh2_scratch_bytes.restype = C.c_int64; l.rodent_hip_motion_bvh2_scratch_bytes.argtypes = [i32, i32]
+        l.rodent_hip_build_motion_bvh2_tri1.restype = i32
+        l.rodent_hip_build_motion_bvh2_tri1.argtypes = [i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+        l.rodent_hip_build_motion_bvh2_tri1_sync.restype = i32
+        l.rodent_hip_build_motion_bvh2_tri1_sync.argtypes = [i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, C.POINTER(i32)]
+        l.hip_traverse_motion_bvh2_tri1_async.restype = None
+        l.hip_traverse_motion_bvh2_tri1_async.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, vp]
+        for name in ("hip_intersect_motion_bvh2_tri1", "hip_occluded_motion_bvh2_tri1"):
+            fn = getattr(l, name); fn.restype = None; fn.argtypes = [i32, vp, vp, vp, vp, vp, i32]
         _lib = l
     return _lib
 

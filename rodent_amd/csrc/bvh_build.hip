@@ -39,6 +39,8 @@
 // Node4 / Node8 + Tri4 (k_refit_wide_links, k_refit_tri4, k_refit_wide_climb; CPU model: tests/refit_wide_model.py).
 // rodent_hip_refit_objects (include/rodent_instances.h) refits a listed subset of the packed objects of an instanced scene in the same
 // three launches, whatever their number (k_forest_links, k_forest_tris, k_forest_climb).
+// rodent_hip_build_motion_bvh2_tri1 (include/rodent_motion.h; build_motion.h; CPU model: tests/motion_bvh_model.py): two copies of a
+// topology refitted to a mesh's two keys, then k_fuse_motion writes the two-key records a time per ray is traced through.
 // rodent_hip_build_objects (build_forest.h; CPU model: tests/forest_build_model.py) BUILDS a listed subset of the packed objects, or all
 // objects of a new set, in one launch list whatever their number: the LBVH's stages over the objects' triangles laid end to end
 // (k_bf_*), each object in its own frame, sorted by (list rank, code, row), every Karras position object-local.
@@ -57,6 +59,7 @@
 
 #include "rodent_build.h"
 #include "rodent_instances.h"
+#include "rodent_motion.h"
 
 namespace {
 #include "build_device.h"
@@ -144,6 +147,26 @@ RefitScratch carve_refit(char* base, int num_nodes, int num_bvh_tris) {
     RefitScratch s{};
     Carver c{base};
     c.take(s.parent, (size_t)num_nodes); c.take(s.arrivals, (size_t)num_nodes); c.take(s.tribox, 6 * (size_t)num_bvh_tris);
+    s.bytes = c.bytes;
+    return s;
+}
+
+// rodent_hip_build_motion_bvh2_tri1: the two copies of the topology, the two refits' info words (A's four, then B's), and ONE refit
+// scratch, which the two refits use one after the other on the call's stream.
+struct MotionScratch {
+    Node2* nodes[2];
+    Tri1* tris[2];
+    int32_t* refit_info;
+    char* refit;
+    size_t bytes;
+};
+
+MotionScratch carve_motion(char* base, int num_nodes, int num_bvh_tris) {
+    MotionScratch s{};
+    Carver c{base};
+    for (int k = 0; k < 2; k++) { c.take(s.nodes[k], (size_t)num_nodes); c.take(s.tris[k], (size_t)num_bvh_tris); }
+    c.take(s.refit_info, 2 * RODENT_BUILD_INFO_WORDS);
+    c.take(s.refit, carve_refit(nullptr, num_nodes, num_bvh_tris).bytes);
     s.bytes = c.bytes;
     return s;
 }
@@ -242,6 +265,7 @@ PlocScratch carve_ploc(char* base, int max_refs) {
 #include "build_split.h"
 #include "build_ploc.h"
 #include "build_refit.h"
+#include "build_motion.h"
 #include "build_forest.h"
 #include "build_collapse.h"
 
@@ -507,6 +531,39 @@ int32_t launch_refit(const float* vertices, int nv, const int32_t* indices, int 
     hipLaunchKernelGGL(k_refit_climb, dim3(blocks_for(num_nodes)), dim3(kBlock), 0, stream, nodes, num_nodes, tris, num_bvh_tris,
                        s.tribox, s.parent, s.arrivals, info_dev);
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
+// The fuse after its argument checks: info words zeroed (unless the build did), one launch.
+int32_t launch_fuse_motion(const Node2* nodes0, const Tri1* tris0, const Node2* nodes1, const Tri1* tris1, int num_nodes, int num_bvh_tris,
+                           RodentMotionNode2* motion_nodes, RodentMotionTri1* motion_tris, const int32_t* refit_info, int32_t* info_dev,
+                           void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (hipMemsetAsync(info_dev, 0, 4 * RODENT_BUILD_INFO_WORDS, stream) != hipSuccess) return RODENT_BUILD_ERR_LAUNCH;
+    hipLaunchKernelGGL(k_fuse_motion, dim3(blocks_for((long long)num_nodes + num_bvh_tris)), dim3(kBlock), 0, stream, nodes0, tris0, nodes1,
+                       tris1, num_nodes, num_bvh_tris, motion_nodes, motion_tris, refit_info, info_dev);
+    return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
+// The motion build after its argument checks: the fixed list of include/rodent_motion.h.
+int32_t launch_motion_build(const float* vertices0, const float* vertices1, int nv, const int32_t* indices, int n, const Node2* nodes,
+                            int num_nodes, const Tri1* tris, int num_bvh_tris, RodentMotionNode2* motion_nodes,
+                            RodentMotionTri1* motion_tris, void* scratch, int32_t* info_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const MotionScratch s = carve_motion(static_cast<char*>(scratch), num_nodes, num_bvh_tris);
+    for (int k = 0; k < 2; k++) {
+        // (the whole topology, copy B's too, before the first refit: what is refitted in place never feeds a copy)
+        if (hipMemcpyAsync(s.nodes[k], nodes, sizeof(Node2) * (size_t)num_nodes, hipMemcpyDeviceToDevice, stream) != hipSuccess
+            || hipMemcpyAsync(s.tris[k], tris, sizeof(Tri1) * (size_t)num_bvh_tris, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+            return RODENT_BUILD_ERR_LAUNCH;
+    }
+    const float* keys[2] = {vertices0, vertices1};
+    for (int k = 0; k < 2; k++) {
+        const int32_t rc = launch_refit(keys[k], nv, indices, n, s.nodes[k], num_nodes, s.tris[k], num_bvh_tris, s.refit,
+                                        s.refit_info + k * RODENT_BUILD_INFO_WORDS, stream_);
+        if (rc != RODENT_BUILD_OK) return rc;
+    }
+    return launch_fuse_motion(s.nodes[0], s.tris[0], s.nodes[1], s.tris[1], num_nodes, num_bvh_tris, motion_nodes, motion_tris,
+                              s.refit_info, info_dev, stream_);
 }
 
 // The refit of the listed objects of a packed set after its argument checks: launch_refit's list over the listed objects' nodes and
@@ -878,6 +935,50 @@ int32_t rodent_hip_refit_bvh2_tri1_sync(int32_t dev, const float* vertices, int3
         return rodent_hip_refit_bvh2_tri1(dev, vertices, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_bvh_tris, scratch,
                                           info_dev, nullptr);
     });
+}
+
+int32_t rodent_hip_fuse_motion_bvh2_tri1(int32_t dev, const struct Node2* nodes0, const struct Tri1* tris0, const struct Node2* nodes1,
+                                         const struct Tri1* tris1, int32_t num_nodes, int32_t num_bvh_tris,
+                                         struct RodentMotionNode2* motion_nodes, struct RodentMotionTri1* motion_tris, int32_t* info_dev,
+                                         void* stream) {
+    const int32_t rc = check_tree_args(dev, num_nodes, num_bvh_tris,
+                                       !nodes0 || !tris0 || !nodes1 || !tris1 || !motion_nodes || !motion_tris || !info_dev);
+    if (rc != RODENT_BUILD_OK) return rc;
+    return launch_fuse_motion(nodes0, tris0, nodes1, tris1, num_nodes, num_bvh_tris, motion_nodes, motion_tris, nullptr, info_dev, stream);
+}
+
+int64_t rodent_hip_motion_bvh2_scratch_bytes(int32_t num_nodes, int32_t num_bvh_tris) {
+    if (num_nodes < 1 || num_bvh_tris < 1) return -1;
+    return (int64_t)carve_motion(nullptr, num_nodes, num_bvh_tris).bytes;
+}
+
+int32_t rodent_hip_build_motion_bvh2_tri1(int32_t dev, const float* vertices0, const float* vertices1, int32_t num_vertices,
+                                          const int32_t* indices, int32_t num_tris, const struct Node2* nodes, int32_t num_nodes,
+                                          const struct Tri1* tris, int32_t num_bvh_tris, struct RodentMotionNode2* motion_nodes,
+                                          struct RodentMotionTri1* motion_tris, void* scratch, int32_t* info_dev, void* stream) {
+    // check_refit_args' order, with this entry's pointers
+    if (bad_num_tris(num_tris)) return RODENT_BUILD_ERR_NUM_TRIS;
+    if (num_vertices < 1) return RODENT_BUILD_ERR_NUM_VERTICES;
+    const int32_t rc = check_tree_args(dev, num_nodes, num_bvh_tris, !vertices0 || !vertices1 || !indices || !nodes || !tris || !motion_nodes
+                                                                         || !motion_tris || !scratch || !info_dev);
+    if (rc != RODENT_BUILD_OK) return rc;
+    return launch_motion_build(vertices0, vertices1, num_vertices, indices, num_tris, nodes, num_nodes, tris, num_bvh_tris, motion_nodes,
+                               motion_tris, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_build_motion_bvh2_tri1_sync(int32_t dev, const float* vertices0, const float* vertices1, int32_t num_vertices,
+                                               const int32_t* indices, int32_t num_tris, const struct Node2* nodes, int32_t num_nodes,
+                                               const struct Tri1* tris, int32_t num_bvh_tris, struct RodentMotionNode2* motion_nodes,
+                                               struct RodentMotionTri1* motion_tris, int32_t* info) {
+    int32_t words[RODENT_BUILD_INFO_WORDS] = {};
+    int32_t rc = refit_sync(dev, rodent_hip_motion_bvh2_scratch_bytes(num_nodes, num_bvh_tris), num_nodes, words,
+                            [&](void* scratch, int32_t* info_dev) {
+        return rodent_hip_build_motion_bvh2_tri1(dev, vertices0, vertices1, num_vertices, indices, num_tris, nodes, num_nodes, tris,
+                                                 num_bvh_tris, motion_nodes, motion_tris, scratch, info_dev, nullptr);
+    });
+    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
+    if (rc == RODENT_BUILD_OK && words[3] != num_nodes) rc = RODENT_BUILD_ERR_INPUT;      // key 1's count (refit_sync checked key 0's)
+    return rc;
 }
 
 int64_t rodent_hip_refit_wide_scratch_bytes(int32_t width, int32_t num_nodes, int32_t num_packets) {

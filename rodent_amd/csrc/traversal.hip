@@ -44,6 +44,7 @@
 #include "device_buffer.h"
 #include "rodent_traversal.h"
 #include "rodent_instances.h"
+#include "rodent_motion.h"
 #include "traversal_device.h"
 #include "traversal_steps.h"
 
@@ -1181,6 +1182,7 @@ template <bool ANY, int LDS_N, int CAPS, int LAST_RAYS = kWave> void L_phased(LA
 int wide_top_min_rays() { return g_top_min_rays; }
 #include "instance_inverse.h"        // the fp64 inverse the TLAS build stores and k_instanced_motion takes per ray
 #include "traversal_instanced.h"     // instanced scenes: a TLAS over objects' BVH2 / Tri1 (k_instanced, k_instanced_motion)
+#include "traversal_motion.h"        // deforming meshes: two-key records, a time per ray (k_bvh2_motion)
 #ifdef RODENT_HIP_LAB
 #include "lab/top_kernels.h"         // lab build only: superseded forms of the LDS-image kernels
 #include "lab/top_launchers.h"
@@ -1326,6 +1328,29 @@ void instanced_sync_call(int32_t dev, const Node2* tlas, const RodentInstance* i
     check_error_flag(s, nullptr);
 }
 
+// Deforming meshes (include/rodent_motion.h): one launch, one chunk per one-wave workgroup, as launch_instanced.
+void launch_motion_bvh2(DeviceState& s, const RodentMotionNode2* nodes, const RodentMotionTri1* tris, const Ray1* rays,
+    const float* times, Hit1* hits, int n, bool any_hit, hipStream_t stream) {
+    if (n <= 0) return;
+    if (any_hit)
+        hipLaunchKernelGGL((k_bvh2_motion<true>), dim3(blocks_for(n)), dim3(kWave), 0, stream, nodes, tris, rays, times, hits, n, s.ctl());
+    else
+        hipLaunchKernelGGL((k_bvh2_motion<false>), dim3(blocks_for(n)), dim3(kWave), 0, stream, nodes, tris, rays, times, hits, n, s.ctl());
+    HIP_CHECK(hipGetLastError());
+}
+
+void motion_bvh2_sync_call(int32_t dev, const RodentMotionNode2* nodes, const RodentMotionTri1* tris, const Ray1* rays,
+    const float* times, Hit1* hits, int32_t num_rays, bool any_hit) {
+    DeviceGuard on(dev);
+    DeviceState& s = device_state(dev, nullptr);
+    std::lock_guard<std::mutex> one_call(s.sync_mutex);
+    {
+        std::lock_guard<std::mutex> launching(s.mutex);
+        launch_motion_bvh2(s, nodes, tris, rays, times, hits, num_rays, any_hit, nullptr);
+    }
+    check_error_flag(s, nullptr);
+}
+
 int default_variant(int width) {
     const char* e = getenv(width == 2 ? "RODENT_HIP_BVH2_VARIANT" : (width == 4 ? "RODENT_HIP_BVH4_VARIANT" : "RODENT_HIP_BVH8_VARIANT"));
     return e ? atoi(e) : 0;
@@ -1399,6 +1424,25 @@ void hip_occluded_motion_instanced_bvh2_tri1(int32_t dev, const Node2* tlas_node
                                              const Node2* nodes, const Tri1* tris, const Ray1* rays, const float* times, Hit1* hits,
                                              int32_t* hit_instances, int32_t num_rays) {
     motion_instanced_sync_call(dev, tlas_nodes, motion_instances, nodes, tris, rays, times, hits, hit_instances, num_rays, true);
+}
+
+void hip_traverse_motion_bvh2_tri1_async(int32_t dev, const RodentMotionNode2* motion_nodes, const RodentMotionTri1* motion_tris,
+                                         const Ray1* rays, const float* times, Hit1* hits, int32_t num_rays, int32_t any_hit,
+                                         void* stream) {
+    DeviceGuard on(dev);
+    DeviceState& s = device_state(dev, (hipStream_t)stream);
+    std::lock_guard<std::mutex> launching(s.mutex);
+    launch_motion_bvh2(s, motion_nodes, motion_tris, rays, times, hits, num_rays, any_hit != 0, (hipStream_t)stream);
+}
+
+void hip_intersect_motion_bvh2_tri1(int32_t dev, const RodentMotionNode2* motion_nodes, const RodentMotionTri1* motion_tris,
+                                    const Ray1* rays, const float* times, Hit1* hits, int32_t num_rays) {
+    motion_bvh2_sync_call(dev, motion_nodes, motion_tris, rays, times, hits, num_rays, false);
+}
+
+void hip_occluded_motion_bvh2_tri1(int32_t dev, const RodentMotionNode2* motion_nodes, const RodentMotionTri1* motion_tris,
+                                   const Ray1* rays, const float* times, Hit1* hits, int32_t num_rays) {
+    motion_bvh2_sync_call(dev, motion_nodes, motion_tris, rays, times, hits, num_rays, true);
 }
 
 int32_t rodent_hip_check_errors(int32_t dev, void* stream) {

@@ -44,6 +44,10 @@ MOTION_INSTANCE_DESC = np.dtype([("object_to_world0", "<f4", (12,)), ("object_to
 MOTION_INSTANCE = np.dtype([("object_to_world0", "<f4", (12,)), ("object_to_world1", "<f4", (12,)), ("node_offset", "<i4"),
                             ("tri_offset", "<i4"), ("instance_id", "<i4"), ("pad", "<i4"), ("pad2", "<i4", (4,))])
 assert (MOTION_INSTANCE_DESC.itemsize, MOTION_INSTANCE.itemsize) == (128, 128)
+# deforming meshes (include/rodent_motion.h): a Node2 with its bounds at time 0 and at time 1, a Tri1 at time 0 and at time 1
+MOTION_NODE2 = np.dtype([("bounds0", "<f4", (12,)), ("bounds1", "<f4", (12,)), ("child", "<i4", (2,)), ("pad", "<i4", (6,))])
+MOTION_TRI1 = np.dtype([("key0", TRI1), ("key1", TRI1)])
+assert (MOTION_NODE2.itemsize, MOTION_TRI1.itemsize) == (128, 96)
 
 _BLOCK_DTYPES = {BVH2_TRI1: (NODE2, TRI1), BVH4_TRI4: (NODE4, TRI4), BVH8_TRI4: (NODE8, TRI4)}
 
