@@ -61,8 +61,9 @@
  * Motion instance: one object placed by TWO object_to_world matrices, M0 at time 0 and M1 at time 1.
  * Placement at time t: every ray carries a time t (a float, used as given: it is not clamped).  Entry by entry s = 1 - t; m = s*m0 + t*m1:
  *   two products and one sum, each rounded, no fused multiply-add.  So t = 0 gives M0 and t = 1 gives M1, bit for bit -- with one
- *   exception the three operations cannot avoid: an entry -0 whose partner is positive comes out as 1 * -0 + 0 * m1 = +0.  The value is
- *   the same, and the inverse differs at most in the sign of a zero of its own.
+ *   exception the three operations cannot avoid: an entry -0 whose partner is positive or +0 comes out as 1 * -0 + 0 * m1 = +0 (at
+ *   t = -0, where t * m1 is a zero of the opposite sign: an entry -0 whose partner is negative or -0).  The value is the same, and
+ *   the inverse differs at most in the sign of a zero of its own.
  * Per-ray inverse: the fp64 cofactor inverse above of the interpolated fp32 matrix, in the order above, each of the 12 entries rounded to
  *   fp32 once -- one function (csrc/instance_inverse.h) for the build stage and for the kernel.  At t = 0 it is bit-equal to what
  *   rodent_hip_build_tlas stores for M0 (but for the zeros just named).

@@ -17,8 +17,8 @@
  *   (rodent_instances.h): outside [0, 1] an interpolated bound can be NaN or infinite, and the precondition of the kernels and of the
  *   oracle is "no NaN bound".  -0 and 1 are traced.
  * Value at time t: for every bound and every one of the nine Tri1 floats  s = 1 - t;  x = s*x0 + t*x1  (a subtraction once per ray, two
- *   products and a sum per value).  t = 0 gives x0 and t = 1 gives x1 bit for bit, except for a -0 beside a positive partner, which comes
- *   out as +0.
+ *   products and a sum per value).  t = 0 gives x0 and t = 1 gives x1 bit for bit, except for a -0 beside a positive or +0 partner (at
+ *   t = -0: beside a negative or -0 partner), which comes out as +0.
  * Triangle at time t: the Tri1 {v0(t), e1(t), e2(t)} with key 0's w words goes unchanged into the triangle test with
  *   n = cross(e1(t), e2(t)), as a static Tri1 does.  e1 and e2 are linear in the corners, so in exact arithmetic the interpolated edges
  *   are the edges of the interpolated triangle.
