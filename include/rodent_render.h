@@ -25,6 +25,7 @@
 #include <stddef.h>
 #include "rodent_traversal.h"
 #include "rodent_instances.h"
+#include "rodent_motion.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -303,7 +304,8 @@ int32_t rodent_hip_scene_deform_status(int32_t dev, int32_t* refit_info, int32_t
  * fused_compact modes work.  The stage-level entries (hip_generate_rays, hip_traverse_primary / _secondary / _streams, hip_shade,
  * hip_shade_compact, hip_compact_primary) work on a moving scene through the same branches, on streams that hold these words.
  * rodent_hip_scene_set_transforms, _scene_instances, _scene_deform_* and _scene_refit* treat a moving scene
- * as they treat "no instanced scene" (abort, or RODENT_SCENE_ERR_NOT_INSTANCED): geometry that deforms under motion is not built.
+ * as they treat "no instanced scene" (abort, or RODENT_SCENE_ERR_NOT_INSTANCED): objects that deform under the motion TLAS are not built
+ * (a single mesh that deforms is: "deforming meshes in the renderer" below).
  *
  * rodent_hip_scene_create_motion: rodent_hip_scene_create_instanced with RodentMotionInstanceDesc records and rodent_hip_build_motion_tlas
  * (max_leaf 1): the same refusals in the same order, then RODENT_SCENE_ERR_MOVING_LIGHT, all on the host, leaving the loaded scene alone;
@@ -334,8 +336,78 @@ void    rodent_hip_scene_motion_instances(int32_t dev, struct RodentSceneMotionI
  * RODENT_SCENE_ERR_SHUTTER and changes nothing.  Without a moving scene it has no effect. */
 int32_t rodent_hip_render_shutter(int32_t dev, float open, float close);
 void    rodent_hip_render_shutter_in_effect(int32_t dev, float out[2]);
-/* The path length the next frame uses: min(requested, 255) with a moving scene loaded, else what rodent_hip_render_config was given. */
+/* The path length the next frame uses: min(requested, 255) with a moving or a deforming scene loaded, else what rodent_hip_render_config
+ * was given. */
 int32_t rodent_hip_render_max_path_len_in_effect(int32_t dev);
+/* ---- deforming meshes in the renderer: a time per path through the motion BVH of rodent_motion.h ----
+ * CPU model of everything below: tests/deforming_scene_model.py (over tests/motion_bvh_model.py, tests/scene_update_model.py,
+ * tests/motion_scene_model.py and the flat oracle).  A deforming scene is a flat scene that owns TWO keys, its vertex and normal tables at
+ * time 0 and at time 1; every path draws one time in the shutter interval and sees the mesh as that time puts it, vertex by vertex.
+ *
+ * The time travels as in a moving scene (above), word for word: PrimaryStream::depth[i] holds depth | ubits << 8,
+ * SecondaryStream::prim_id[i] a shadow ray's time as float bits, the shutter rule gives t, generation draws the third randf, the path
+ * length in effect is min(requested, RODENT_MOTION_DEPTH_MASK).
+ * Traversal (k_trace_deforming<false|true>): rodent_motion.h's records and rules over the stream I/O of an instanced scene's passes.  For
+ * a ray at time t: s = 1 - t once, every bound and every Tri1 float x = s*x0 + t*x1.  The hit record holds key 0's geom_id and prim_id
+ * words (prim_id indexes the scene's tables directly); a miss is {num_geometries, -1, tmax as given, 0, 0}.  rodent_motion.h's time rule
+ * holds for the stage-level entries, which let a caller write any word: a closest-hit ray with !(0 <= t && t <= 1) stores the miss
+ * record without traversal, a shadow ray outside is not occluded and adds its colour (inside the library's own loop t lies in the
+ * shutter interval, so the rule never acts there).  A stack overflow raises the flag a frame call aborts on.
+ * Shading a deforming hit: t from the depth word, s = 1 - t, lerp(x0, x1) = s*x0 + t*x1 with every operation rounded on its own:
+ *   corners       through the index row, v_k(t) = lerp of the two vertex tables' rows, three floats each;
+ *   face normal   the moved-geometry rule above on those corners: a = v1(t) - v0(t), b = v2(t) - v0(t), c = a x b,
+ *                 l = sqrt((c.x c.x + c.y c.y) + c.z c.z), fn = c * (1.0f / l).  NOT the interpolation of the keys' face normals: a
+ *                 triangle that turns over between the keys changes side at the time it is flat, as the traversal's own
+ *                 n = cross(e1(t), e2(t)) does;
+ *   corner normals n_k(t) = lerp of the two normal tables' rows, NOT normalised; the flat shader's lerp2 and normalize follow;
+ *   the rest      org, dir, t, u, v, the point, the material and the textures (prim indexes the tables directly) are the flat shader's;
+ *                 the emitter of a hit is lights[light_ids[prim]].
+ * This is, bit for bit, the flat shading of the scene baked at the hit's time by those rules.  The depth test uses word & 0xFF; the ray
+ * that goes on gets (depth + 1) | ubits << 8, the shadow ray the bits of t in prim_id.
+ * Lights stay static: an emissive triangle whose three corner rows (16 bytes each) differ in a byte between the keys is refused
+ * (RODENT_SCENE_ERR_MOVING_LIGHT).  The light table is key 0's.  The TRAVERSAL reaches such an emitter through s*x + t*x, which equals x
+ * only up to the rounding of that sum (at t = 0 and t = 1 exactly): an emitter's surface as rays hit it and its light record as
+ * next-event estimation samples it may differ in the last bits.  The model restates exactly this.
+ * Options in effect are those of a moving scene (streaming mapping, no persistent kernels, no refill, no sort); overlap and all three
+ * fused_compact modes work.  No LDS top images and no tri_shade / tri_tex records are built (rodent_hip_scene_tables returns NULL for
+ * them).  rodent_hip_scene_refit*, _scene_deform_*, _scene_set_transforms, _scene_set_motion_transforms, _scene_instances and
+ * _scene_motion_instances treat a deforming scene as they treat "no such scene" (abort, or RODENT_SCENE_ERR_NOT_INSTANCED).  Neither
+ * moving emitters, nor more than two keys, nor motion objects under the motion TLAS are built.
+ *
+ * rodent_hip_scene_create_deforming: `desc` as for rodent_hip_scene_create_device_bvh_opt (HOST tables, nodes / tris NULL, counts 0; its
+ * vertices / normals are the mesh at time 0), vertices1 / normals1 HOST tables of num_vertices float4 rows, the mesh at time 1; opt NULL =
+ * max_leaf 2, no passes.  Uploads the tables, builds the topology on the device from key 0 (rodent_hip_build_bvh2_tri1_opt) and the
+ * motion records over it (rodent_hip_build_motion_bvh2_tri1) into records and scratch the scene owns.  The static key-0 hierarchy stays
+ * in the scene as the read-only topology of later rebuilds (rodent_hip_scene_bvh returns it); no frame walks it.
+ * Returns RODENT_SCENE_OK or, decided on the host and leaving the loaded scene alone, in this order: RODENT_SCENE_ERR_COUNTS (a NULL
+ * table, a count < 1, a hierarchy in the description), RODENT_SCENE_ERR_OPTIONS, RODENT_SCENE_ERR_TABLE (a vertex, material, texture or
+ * light index outside its table) or RODENT_SCENE_ERR_LIGHT (an emissive triangle without an entry in the light table) for the first
+ * triangle that has either, RODENT_SCENE_ERR_MOVING_LIGHT.  A flag raised on the device, the builder's or the motion build's (a
+ * non-finite coordinate at either key: RODENT_BUILD_NON_FINITE), destroys what was half built -- no scene is loaded then -- and returns
+ * RODENT_SCENE_ERR_DEVICE, the flags through rodent_hip_scene_create_flags. */
+int32_t rodent_hip_scene_create_deforming(int32_t dev, const struct RodentSceneDesc* desc, const float* vertices1, const float* normals1,
+                                          const struct RodentBuildOptions* opt);
+/* Both keys moved; all pointers are DEVICE pointers on `dev`: num_vertices x 4 floats each.  A key may be the scene's own table of that
+ * key (rodent_hip_scene_motion_keys), written in place: then nothing is copied; the two keys may be one pointer.  normals0_dev /
+ * normals1_dev: both given, or both NULL: smooth normals are recomputed per key by rodent_hip_scene_refit_device's rule and kernels (face
+ * normals of the key, summed over each vertex's incidence list; the lists were prepared at creation).
+ * Enqueues on `stream`, in this order: the wait for the last update, the copies, the normals, rodent_hip_build_motion_bvh2_tri1 over the
+ * static topology into the scene's records with its scratch, the event.  After creation it allocates nothing, copies nothing to or from
+ * the host and does not wait; a frame started afterwards on any stream is ordered behind it.  The emitter rule cannot be checked without a
+ * host copy: the CALLER keeps the corner rows of every emissive triangle equal between the keys (and equal to the creation's: the light
+ * table is not rederived).  No deforming scene loaded, NULL vertices or one table of normals without the other aborts with a message. */
+void    rodent_hip_scene_set_motion_keys(int32_t dev, const float* vertices0_dev, const float* vertices1_dev, const float* normals0_dev,
+                                         const float* normals1_dev, void* stream);
+/* Waits for the last rodent_hip_scene_set_motion_keys (before the first: nothing to wait for, the creation's words) and copies the four
+ * info words of rodent_hip_build_motion_bvh2_tri1 (may be NULL).  Returns its flags, with bit 31 set when info[0] or info[3] differs from
+ * the node count (and for "no deforming scene loaded").  Never aborts; with a flag raised the records are undefined until a sound call. */
+int32_t rodent_hip_scene_motion_keys_status(int32_t dev, int32_t* info);
+/* DEVICE pointers and counts of a deforming scene's motion records, and of its key tables, for tests and tools.  No deforming scene
+ * aborts. */
+void    rodent_hip_scene_motion_bvh(int32_t dev, const struct RodentMotionNode2** nodes, const struct RodentMotionTri1** tris,
+                                    int32_t* num_nodes, int32_t* num_tris);
+struct RodentSceneMotionKeys { float *vertices0, *vertices1, *normals0, *normals1; int32_t* info; int32_t num_vertices; };
+void    rodent_hip_scene_motion_keys(int32_t dev, struct RodentSceneMotionKeys* out);
 void    rodent_hip_render_config(int32_t dev, int32_t spp, int32_t max_path_len);   /* defaults 4 / 64 (converter.cpp:1007-1012) */
 /* 0 = streaming wavefront loop (src/render/mapping_gpu.impala:308-369), 1 = persistent-threads megakernel
  * (mapping_gpu.impala:371-474; the reference selects it at configure time with the converter target

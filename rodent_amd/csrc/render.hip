@@ -34,6 +34,7 @@
 #include "shading.h"
 #include "traversal_device.h"
 #include "traversal_steps.h"
+#include "traversal_motion_steps.h"
 
 namespace {
 
@@ -139,6 +140,7 @@ __global__ void k_copy_int(const int* src, int* dst) { *dst = *src; }
 #include "render_update.h"
 #include "render_instanced.h"
 #include "render_motion.h"
+#include "render_deforming.h"
 
 // ---------------------------------------------------------------------------------------------
 // Host side: per-device state (interface.cpp:324-339), stream slabs, the streaming loop
@@ -173,6 +175,15 @@ struct DevScene {
     // `descs` / `instances`, which stay null, and the kernels take motion_dev() instead of `inst`.
     bool motion = false;
     RodentMotionInstanceDesc* motion_descs = nullptr; RodentMotionInstance* motion_instances = nullptr;
+    // A DEFORMING scene (rodent_hip_scene_create_deforming) is a flat one that owns two keys: dev.vertices / dev.normals are the mesh at
+    // time 0, `vertices1` / `normals1` the mesh at time 1, dev.nodes / dev.tris the static key-0 hierarchy -- the read-only topology of
+    // every rebuild, which no kernel walks -- and `motion_nodes` / `motion_tris` the two-key records the frame traces, rebuilt by every
+    // rodent_hip_scene_set_motion_keys with `motion_scratch` into `motion_info`.  `face_normals1`: key 1's face normals, scratch of the
+    // smooth normals (key 0's go to dev.face_normals).  Neither `instanced` nor `motion` is set; everything is in `allocs`.
+    bool deforming = false;
+    RodentMotionNode2* motion_nodes = nullptr; RodentMotionTri1* motion_tris = nullptr;
+    float *vertices1 = nullptr, *normals1 = nullptr, *face_normals1 = nullptr;
+    char* motion_scratch = nullptr; int32_t* motion_info = nullptr;
     // Host copies of the objects' ranges and of the RodentObject table, and the deforming set D of rodent_hip_scene_deform_prepare: its
     // range table, the forest refit's scratch with its info words behind it, the vertices D's triangles name with their incidence
     // lists (vertex verts[j]: corner_tri[corner_first[j] .. corner_first[j + 1])), its bound lights {object light, triangle}.  In
@@ -301,17 +312,26 @@ void render_defaults(RenderDevice& r) {
 }
 
 // what the next frame does about the sort by material: the per-ray slot array of an instanced scene is not moved by the sort
-int sort_in_effect(const RenderDevice& r) { return r.scene.instanced ? 0 : r.sort; }
-// ... and about the path length: a moving scene's depth word keeps eight bits for the depth
+// (nor is a deforming scene's time word, for which the sort is not built)
+int sort_in_effect(const RenderDevice& r) { return r.scene.instanced || r.scene.deforming ? 0 : r.sort; }
+// a scene whose paths carry a time: moving instances, or a deforming mesh
+bool timed_scene(const RenderDevice& r) { return r.scene.motion || r.scene.deforming; }
+// ... and about the path length: such a scene's depth word keeps eight bits for the depth
 int path_len_in_effect(const RenderDevice& r) {
-    return r.scene.motion ? std::min(r.max_path_len, RODENT_MOTION_DEPTH_MASK) : r.max_path_len;
+    return timed_scene(r) ? std::min(r.max_path_len, RODENT_MOTION_DEPTH_MASK) : r.max_path_len;
 }
 // the ray generation of the scene that is loaded
-decltype(&k_generate<false>) generate_kernel(const RenderDevice& r) { return r.scene.motion ? k_generate<true> : k_generate<false>; }
+decltype(&k_generate<false>) generate_kernel(const RenderDevice& r) { return timed_scene(r) ? k_generate<true> : k_generate<false>; }
 // what the kernels of a moving scene take beside SceneDev: the scene's tables and the shutter as it is now
 MotionDev motion_dev(const RenderDevice& r) {
     const DevScene& s = r.scene;
     return MotionDev{s.tlas_nodes, s.motion_instances, s.bases, s.inst.ray_slots, r.shutter[0], r.shutter[1]};
+}
+
+// ... of a deforming scene: the motion records, key 1's tables and the shutter as it is now
+DeformingDev deforming_dev(const RenderDevice& r) {
+    const DevScene& s = r.scene;
+    return DeformingDev{s.motion_nodes, s.motion_tris, s.vertices1, s.normals1, r.shutter[0], r.shutter[1]};
 }
 
 RenderDevice& rdev(int dev) {
@@ -453,9 +473,17 @@ template <typename Dev, typename... Args> void launch_k_shade_instanced(hipStrea
     else if (b == 512) hipLaunchKernelGGL((k_shade<512, true, Dev>), dim3(blocks), dim3(512), 0, stream, args..., inst);
     else hipLaunchKernelGGL((k_shade<1024, true, Dev>), dim3(blocks), dim3(1024), 0, stream, args..., inst);
 }
+// (a deforming scene: the flat shader's form with ONE trailing DeformingDev argument)
+template <typename... Args> void launch_k_shade_deforming(hipStream_t stream, int b, int rays, const DeformingDev& in, Args... args) {
+    const int blocks = (rays + b - 1) / b;
+    if (b == 256) hipLaunchKernelGGL((k_shade<256, false, DeformingDev>), dim3(blocks), dim3(256), 0, stream, args..., in);
+    else if (b == 512) hipLaunchKernelGGL((k_shade<512, false, DeformingDev>), dim3(blocks), dim3(512), 0, stream, args..., in);
+    else hipLaunchKernelGGL((k_shade<1024, false, DeformingDev>), dim3(blocks), dim3(1024), 0, stream, args..., in);
+}
 // the shader of the scene that is loaded
 template <typename... Args> void launch_shader(RenderDevice& r, hipStream_t stream, int b, int rays, Args... args) {
-    if (r.scene.motion) launch_k_shade_instanced(stream, b, rays, motion_dev(r), args...);
+    if (r.scene.deforming) launch_k_shade_deforming(stream, b, rays, deforming_dev(r), args...);
+    else if (r.scene.motion) launch_k_shade_instanced(stream, b, rays, motion_dev(r), args...);
     else if (r.scene.instanced) launch_k_shade_instanced(stream, b, rays, r.scene.inst, args...);
     else launch_k_shade(stream, b, rays, args...);
 }
@@ -516,7 +544,22 @@ void launch_trace_instanced(RenderDevice& r, hipStream_t stream, const ClosestPa
             PrimaryStream{}, *sh.s, sh.size_ptr, sh.max_n, r.film, sh.inv_spp, r.counters, r.ctl + 2, (int*)nullptr);
     }
 }
+// A deforming scene: one launch per pass over the motion records, no follow-up kernel (render_deforming.h).
+void launch_trace_deforming(RenderDevice& r, hipStream_t stream, const ClosestPass& c, const ShadowPass& sh) {
+    const DevScene& s = r.scene;
+    if (c.p) {
+        r.trace_kernel = "k_trace_deforming<false>";
+        hipLaunchKernelGGL(k_trace_deforming<false>, dim3((c.n + kWave - 1) / kWave), dim3(kWave), 0, stream, s.dev, deforming_dev(r),
+            *c.p, SecondaryStream{}, (const int*)nullptr, c.n, (float*)nullptr, 0.0f, r.counters, r.ctl + 2, r.ctl + 6);
+    }
+    if (sh.s) {
+        r.trace_kernel = "k_trace_deforming<true>";
+        hipLaunchKernelGGL(k_trace_deforming<true>, dim3((sh.max_n + kWave - 1) / kWave), dim3(kWave), 0, stream, s.dev,
+            deforming_dev(r), PrimaryStream{}, *sh.s, sh.size_ptr, sh.max_n, r.film, sh.inv_spp, r.counters, r.ctl + 2, (int*)nullptr);
+    }
+}
 void launch_trace(RenderDevice& r, hipStream_t stream, const ClosestPass& c, const ShadowPass& sh) {
+    if (r.scene.deforming) { launch_trace_deforming(r, stream, c, sh); return; }
     if (r.scene.instanced) { launch_trace_instanced(r, stream, c, sh); return; }
     const bool joint = c.p && sh.s;
     const int which = c.p ? 0 : 1;         // ticket array and spill block: [1] = a lone shadow pass (it may run beside a closest-hit one)
@@ -804,7 +847,7 @@ int auto_mega_max_nodes() {
     return v;
 }
 int resolve_mapping(const RenderDevice& r) {
-    if (r.scene.instanced) return 0;                   // the instanced kernels are stream kernels
+    if (r.scene.instanced || r.scene.deforming) return 0;      // the instanced and the deforming kernels are stream kernels
     if (r.mapping_request >= 0) return r.mapping_request;
     return r.scene.loaded && r.scene.num_nodes <= auto_mega_max_nodes() ? 1 : 0;
 }
@@ -812,7 +855,7 @@ int resolve_mapping(const RenderDevice& r) {
 // for every hierarchy above the megakernel's size class (+3 ... +9 % on the atrium at 306 ... 142 444 nodes, profiles/r03_joint_sweep.txt),
 // the 2-wave kernels with the shadow pass on a second stream for a tree of a few dozen nodes (Cornell box: joint -5 %).
 int resolve_trace(const RenderDevice& r) {
-    if (r.scene.instanced) return 0;
+    if (r.scene.instanced || r.scene.deforming) return 0;
     if (r.trace_persistent_request >= 0) return r.trace_persistent_request;
     return r.scene.loaded && r.scene.num_nodes > auto_mega_max_nodes() ? 2 : 0;
 }
@@ -823,7 +866,7 @@ int resolve_trace(const RenderDevice& r) {
 // -4 ... -11 % from 4 951 nodes down.
 constexpr int kRefillMinNodes = 16384, kRefillIdleLanes = 40;
 void resolve_refill(RenderDevice& r) {
-    if (r.scene.instanced) { r.trace_refill = r.trace_refill_shadow = 0; return; }
+    if (r.scene.instanced || r.scene.deforming) { r.trace_refill = r.trace_refill_shadow = 0; return; }
     if (r.trace_refill_request[0] >= 0) { r.trace_refill = r.trace_refill_request[0]; r.trace_refill_shadow = r.trace_refill_request[1];
         return; }
     r.trace_refill = r.trace_refill_shadow = r.scene.loaded && r.scene.num_nodes >= kRefillMinNodes ? kRefillIdleLanes : 0;

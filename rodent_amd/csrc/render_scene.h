@@ -1,7 +1,8 @@
 // render_scene.h -- the host code of a device's scene: everything that creates, checks, updates, reports on or destroys a DevScene
 // (included by render.hip at file scope, behind rdev, ensure_ray_slots and the resolve_* rules).  It launches only the small kernels of
-// render_update.h, render_instanced.h and render_motion.h; the frame loop and the launchers stay in render.hip.  One anonymous-namespace
-// part -- the steps the entries share, each stated once, then the creations -- and one extern "C" part, the ABI of rodent_render.h.
+// render_update.h, render_instanced.h and render_motion.h (a deforming scene: render_update.h's); the frame loop and the launchers stay in
+// render.hip.  One anonymous-namespace part -- the steps the entries share, each stated once, then the creations -- and one extern "C"
+// part, the ABI of rodent_render.h.
 #pragma once
 
 namespace {
@@ -356,6 +357,15 @@ DevScene& flat_scene(int32_t dev, const char* entry) {
     DevScene& s = loaded_scene(dev, entry);
     if (s.instanced) { fprintf(stderr, "rodent_hip: %s: the scene on device %d is instanced (move its instances with "
         "rodent_hip_scene_set_transforms)\n", entry, dev); abort(); }
+    // ... nor has a deforming scene one that a frame traces (its keys move with rodent_hip_scene_set_motion_keys)
+    if (s.deforming) { fprintf(stderr, "rodent_hip: %s: the scene on device %d is a deforming one (move its keys with "
+        "rodent_hip_scene_set_motion_keys)\n", entry, dev); abort(); }
+    return s;
+}
+DevScene& deforming_scene(int32_t dev, const char* entry) {
+    DevScene& s = loaded_scene(dev, entry);
+    if (!s.deforming) { fprintf(stderr, "rodent_hip: %s: the scene on device %d is no deforming one "
+        "(rodent_hip_scene_create_deforming)\n", entry, dev); abort(); }
     return s;
 }
 // (the static-instance entries: a moving scene is "no instanced scene" to them)
@@ -592,6 +602,92 @@ int32_t create_instanced_scene(int32_t dev, const RodentSceneDesc* d, const Rode
     s.num_nodes = (int)total_nodes; s.num_bvh_tris = d->num_tris; s.num_vertices = d->num_vertices; s.tri_delta = 0;
     s.loaded = true; s.instanced = true;
     ensure_ray_slots(r, 0);
+    resolve_options(r);
+    return RODENT_SCENE_OK;
+}
+
+// ---- The deforming scene ----
+// The motion records of the scene's two keys, enqueued on `stream`: rodent_hip_build_motion_bvh2_tri1 over the static key-0 topology
+// into the scene's records, with its scratch and info words (rodent_hip_scene_create_deforming, rodent_hip_scene_set_motion_keys).
+int32_t derive_deforming(int32_t dev, DevScene& s, hipStream_t stream) {
+    return rodent_hip_build_motion_bvh2_tri1(dev, s.dev.vertices, s.vertices1, s.num_vertices, s.dev.indices, s.dev.num_tris, s.dev.nodes,
+                                             s.num_nodes, s.dev.tris, s.num_bvh_tris, s.motion_nodes, s.motion_tris, s.motion_scratch,
+                                             s.motion_info, stream);
+}
+
+// rodent_hip_scene_create_deforming: the refusals on the host tables, then the flat creation's uploads, the topology from key 0 and the
+// motion records; a device flag destroys what was half built.
+int32_t create_deforming_scene(int32_t dev, const RodentSceneDesc* d, const float* vertices1, const float* normals1,
+                               const RodentBuildOptions* opt_) {
+    const RodentBuildOptions default_opt{2, 0, RODENT_BUILD_DEFAULT_NODE_COST, RODENT_BUILD_DEFAULT_TRI_COST};
+    const RodentBuildOptions* opt = opt_ ? opt_ : &default_opt;
+    // ---- the refusals: all on the host tables, before anything is enqueued or the current scene touched ----
+    if (!d || !vertices1 || !normals1) return RODENT_SCENE_ERR_COUNTS;
+    const bool textured = d->num_textures > 0;
+    if (d->nodes || d->tris || d->num_nodes || d->num_bvh_tris || !d->vertices || !d->normals || !d->face_normals || !d->indices
+        || !d->materials || !d->light_ids || d->num_vertices < 1 || d->num_tris < 1 || d->num_tris > RODENT_BUILD_MAX_TRIS
+        || d->num_materials < 1 || d->num_lights < 0 || (d->num_lights > 0 && !d->lights) || d->num_textures < 0
+        || (textured && (!d->texcoords || !d->textures || !d->texels))) return RODENT_SCENE_ERR_COUNTS;
+    if (rodent_hip_build_opt_scratch_bytes(1, opt) < 0) return RODENT_SCENE_ERR_OPTIONS;
+    for (int32_t k = 0; k < d->num_materials; k++) if (!textures_exist(d->materials[k], d->num_textures)) return RODENT_SCENE_ERR_TABLE;
+    for (int32_t k = 0; k < d->num_textures; k++) if (!texture_in_pool(d->textures[k], d->num_texels)) return RODENT_SCENE_ERR_TABLE;
+    for (int32_t t = 0; t < d->num_tris; t++) {
+        if (bad_index(d, (size_t)t)) return RODENT_SCENE_ERR_TABLE;
+        if (d->light_ids[t] < 0 || (d->light_ids[t] > 0 && d->light_ids[t] >= d->num_lights)) return RODENT_SCENE_ERR_TABLE;
+        if (emitter_without_light(d, (size_t)t, 0, d->num_lights)) return RODENT_SCENE_ERR_LIGHT;
+    }
+    for (int32_t t = 0; t < d->num_tris; t++) {             // lights stay static: an emitter's corner rows are equal byte for byte
+        if (!d->materials[d->indices[4 * (size_t)t + 3]].emissive) continue;
+        for (int k = 0; k < 3; k++) {
+            const size_t row = 4 * (size_t)d->indices[4 * (size_t)t + k];
+            if (std::memcmp(d->vertices + row, vertices1 + row, sizeof(float) * 4) != 0) return RODENT_SCENE_ERR_MOVING_LIGHT;
+        }
+    }
+
+    // ---- from here on the device's scene is the new one, or none ----
+    RenderDevice& r = rdev(dev);
+    rodent_hip_scene_destroy(dev);
+    HIP_CHECK(hipSetDevice(dev));
+    r.create_flags = 0;
+    DevScene& s = r.scene;
+    upload_tables(s, d);
+    const size_t nv = (size_t)d->num_vertices, nt = (size_t)d->num_tris;
+    s.vertices1 = upload(s.allocs, vertices1, 4 * nv);
+    s.normals1 = upload(s.allocs, normals1, 4 * nv);
+    s.face_normals1 = device_alloc<float>(s.allocs, 4 * nt, true);
+    s.dev.lights = upload(s.allocs, d->lights, (size_t)d->num_lights);          // key 0's: lights stay static
+    const auto fail = [&](int32_t flags) { rodent_hip_scene_destroy(dev); r.create_flags = flags; return RODENT_SCENE_ERR_DEVICE; };
+    // the topology from key 0: nodes (room for max(1, n - 1)) and triangles in one allocation, as the flat creation lays them out
+    const size_t node_bytes = sizeof(Node2) * std::max<size_t>(1, nt - 1);
+    char* const bvh = device_alloc<char>(s.allocs, node_bytes + sizeof(Tri1) * nt);
+    s.dev.nodes = reinterpret_cast<const Node2*>(bvh);
+    s.dev.tris = reinterpret_cast<const Tri1*>(bvh + node_bytes);
+    int32_t info[RODENT_BUILD_INFO_WORDS] = {};
+    {
+        BuildScratch work(rodent_hip_build_opt_scratch_bytes(d->num_tris, opt), RODENT_BUILD_INFO_WORDS);
+        const int32_t rc = rodent_hip_build_bvh2_tri1_opt(dev, s.dev.vertices, d->num_vertices, s.dev.indices, d->num_tris, opt,
+            reinterpret_cast<Node2*>(bvh), reinterpret_cast<Tri1*>(bvh + node_bytes), work.scratch, work.info_dev, nullptr);
+        if (const int32_t bad = work.finish(rc, info, 1, (int32_t)std::max<size_t>(1, nt - 1))) return fail(bad);
+    }
+    s.num_nodes = info[0]; s.num_bvh_tris = d->num_tris; s.num_vertices = d->num_vertices; s.tri_delta = 0;
+    s.dev.num_tris = d->num_tris; s.dev.num_materials = d->num_materials; s.dev.num_lights = d->num_lights;
+    // the motion records over it, with the scratch and the info words every later rebuild uses
+    s.motion_nodes = device_alloc<RodentMotionNode2>(s.allocs, (size_t)s.num_nodes, true);
+    s.motion_tris = device_alloc<RodentMotionTri1>(s.allocs, nt, true);
+    s.motion_scratch = alloc_scratch_info(s.allocs, rodent_hip_motion_bvh2_scratch_bytes(s.num_nodes, s.num_bvh_tris),
+                                          RODENT_BUILD_INFO_WORDS, s.motion_info);
+    HIP_CHECK(hipMemset(s.motion_info, 0, 4 * RODENT_BUILD_INFO_WORDS));
+    HIP_CHECK(hipDeviceSynchronize());
+    const int32_t rc = derive_deforming(dev, s, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (rc == RODENT_BUILD_OK) HIP_CHECK(hipMemcpy(info, s.motion_info, sizeof(info), hipMemcpyDeviceToHost));
+    if (rc != RODENT_BUILD_OK) return fail(rc);
+    if (info[2] || info[0] != s.num_nodes || info[3] != s.num_nodes) return fail(info[2] ? info[2] : (int32_t)0x80000000u);
+    // no LDS top images and no gathered shading records: the deforming kernels stage no image, the shader gathers both keys' rows
+    s.dev.top_image = s.dev.top_image_large = nullptr;
+    s.dev.tri_shade = nullptr; s.dev.tri_tex = nullptr;
+    s.loaded = true; s.deforming = true;
+    refit_prepare(r, true);                                 // the incidence lists a NULL-normals rodent_hip_scene_set_motion_keys needs
     resolve_options(r);
     return RODENT_SCENE_OK;
 }
@@ -887,6 +983,70 @@ int32_t rodent_hip_scene_deform_status(int32_t dev, int32_t* refit_info, int32_t
     if (refit_info) std::copy(refit, refit + RODENT_BUILD_INFO_WORDS, refit_info);
     if (tlas_info) std::copy(tlas, tlas + RODENT_BUILD_INFO_WORDS, tlas_info);
     return refit[2] | tlas[2] | (refit[0] < d.num_nodes ? (int32_t)0x80000000u : 0);
+}
+
+int32_t rodent_hip_scene_create_deforming(int32_t dev, const RodentSceneDesc* d, const float* vertices1, const float* normals1,
+                                          const RodentBuildOptions* opt) {
+    return create_deforming_scene(dev, d, vertices1, normals1, opt);
+}
+
+void rodent_hip_scene_set_motion_keys(int32_t dev, const float* vertices0_dev, const float* vertices1_dev, const float* normals0_dev,
+                                      const float* normals1_dev, void* stream_) {
+    DevScene& s = deforming_scene(dev, "rodent_hip_scene_set_motion_keys");
+    RenderDevice& r = rdev(dev);
+    if (!vertices0_dev || !vertices1_dev || !normals0_dev != !normals1_dev) {
+        fprintf(stderr, "rodent_hip: rodent_hip_scene_set_motion_keys: NULL vertices, or one table of normals without the other\n");
+        abort(); }
+    hipStream_t stream = begin_update(r, stream_);
+    const int nv = s.num_vertices, nt = s.dev.num_tris;
+    const size_t bytes = sizeof(float4) * (size_t)nv;
+    float* const own[4] = {const_cast<float*>(s.dev.vertices), s.vertices1, const_cast<float*>(s.dev.normals), s.normals1};
+    const float* const given[4] = {vertices0_dev, vertices1_dev, normals0_dev, normals1_dev};
+    for (int k = 0; k < 4; k++)                             // (a key that IS the scene's table was written in place: no copy)
+        if (given[k] && given[k] != own[k]) HIP_CHECK(hipMemcpyAsync(own[k], given[k], bytes, hipMemcpyDeviceToDevice, stream));
+    if (!normals0_dev) {                                    // smooth normals per key, by rodent_hip_scene_refit_device's rule and kernels
+        const int4* indices = reinterpret_cast<const int4*>(s.dev.indices);
+        float* const faces[2] = {const_cast<float*>(s.dev.face_normals), s.face_normals1};
+        for (int k = 0; k < 2; k++) {
+            hipLaunchKernelGGL(k_face_normals, blocks(nt), dim3(kBlock), 0, stream, reinterpret_cast<const float4*>(own[k]), indices, nt,
+                               reinterpret_cast<float4*>(faces[k]));
+            hipLaunchKernelGGL(k_smooth_normals, blocks(nv), dim3(kBlock), 0, stream, reinterpret_cast<const float4*>(faces[k]),
+                               s.corner_first, s.corner_tri, nv, reinterpret_cast<float4*>(own[2 + k]));
+        }
+    }
+    const int32_t rc = derive_deforming(dev, s, stream);
+    if (rc != RODENT_BUILD_OK) { fprintf(stderr, "rodent_hip: rebuild of the motion records refused (%d)\n", rc); abort(); }
+    HIP_CHECK(hipGetLastError());
+    end_update(r, stream);
+}
+
+int32_t rodent_hip_scene_motion_keys_status(int32_t dev, int32_t* info) {
+    RenderDevice& r = rdev(dev);
+    DevScene& s = r.scene;
+    int32_t words[RODENT_BUILD_INFO_WORDS] = {};
+    if (!s.loaded || !s.deforming) {                        // (never aborts: no such scene has completed nothing)
+        if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
+        return (int32_t)0x80000000u;
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    if (s.refit_enqueued) HIP_CHECK(hipEventSynchronize(r.ev_refit));
+    HIP_CHECK(hipMemcpy(words, s.motion_info, sizeof(words), hipMemcpyDeviceToHost));
+    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
+    return words[2] | (words[0] != s.num_nodes || words[3] != s.num_nodes ? (int32_t)0x80000000u : 0);
+}
+
+void rodent_hip_scene_motion_bvh(int32_t dev, const RodentMotionNode2** nodes, const RodentMotionTri1** tris, int32_t* num_nodes,
+                                 int32_t* num_tris) {
+    const DevScene& s = deforming_scene(dev, "rodent_hip_scene_motion_bvh");
+    *nodes = s.motion_nodes; *tris = s.motion_tris;
+    *num_nodes = s.num_nodes; *num_tris = s.num_bvh_tris;
+}
+
+void rodent_hip_scene_motion_keys(int32_t dev, RodentSceneMotionKeys* out) {
+    const DevScene& s = deforming_scene(dev, "rodent_hip_scene_motion_keys");
+    if (!out) return;
+    *out = RodentSceneMotionKeys{const_cast<float*>(s.dev.vertices), s.vertices1, const_cast<float*>(s.dev.normals), s.normals1,
+        s.motion_info, s.num_vertices};
 }
 
 void rodent_hip_scene_instances(int32_t dev, RodentSceneInstances* out) {

@@ -35,9 +35,11 @@ template <bool INST> __device__ __forceinline__ Surf hit_surface(const SceneDev&
     if constexpr (INST) return surface_element_instanced(&sc, frame, pv.org, pv.dir, pv.prim, pv.t, pv.u, pv.v);
     else return surface_element(&sc, pv.org, pv.dir, pv.prim, pv.t, pv.u, pv.v);
 }
-template <bool INST = false>
+// GIVEN (deforming meshes, k_shade<.., false, DeformingDev>): the caller computed the surface (surface_element_deforming) and passes it;
+// everything else is the flat shading.
+template <bool INST = false, bool GIVEN = false>
 __device__ __forceinline__ ShadeOut shade_vertex(const SceneDev& sc, const PathVertex& pv, int max_path_len,
-    const InstanceFrame* frame = nullptr) {
+    const InstanceFrame* frame = nullptr, const Surf* given = nullptr) {
     ShadeOut o;
     const float pdf_lightpick = 1.0f / (float)sc.num_lights;
     uint32_t rnd = pv.rnd;
@@ -58,7 +60,7 @@ __device__ __forceinline__ ShadeOut shade_vertex(const SceneDev& sc, const PathV
 #endif
     RodentMaterial textured;
     const RodentMaterial* m = resolve_material(&sc, sc.materials + pv.geom, &textured, pv.prim, pv.u, pv.v);
-    const Surf sf = hit_surface<INST>(sc, pv, frame);
+    const Surf sf = [&] { if constexpr (GIVEN) return *given; else return hit_surface<INST>(sc, pv, frame); }();
     const v3 out_dir = neg(pv.dir);
 
     // on_hit (renderer.impala:113-128)
@@ -197,13 +199,23 @@ __device__ __forceinline__ bool motion_frame(const RodentMotionInstance* instanc
     lerp_affine(m0, m1, t, m);
     return invert_affine(m, w) == 0;
 }
+// A DEFORMING scene (k_shade<kBlock, false, DeformingDev>): the depth word and the shadow ray's prim_id as for a moving scene; the hit is
+// shaded on the surface at its own time (surface_element_deforming: twelve gathers through the index row, the two keys' corners and
+// corner normals interpolated by the traversal's lerp rule, the face normal from the interpolated corners), the rest is the flat
+// shader's: pv.prim indexes the tables directly and the emitter of a hit is sc.lights[light_ids[prim]].  Its register budget:
+// kShadeDeformWaves.
 #ifndef RODENT_SHADE_MOTION_WAVES
 #define RODENT_SHADE_MOTION_WAVES 5      // (compile time) 7: 20 ... 26 spilled VGPRs, 6: 9 ... 13, 5: none beyond the flat shader's 68 bytes
 #endif
 constexpr int kShadeMotionWaves = RODENT_SHADE_MOTION_WAVES;
 template <bool INST, typename... Inst> constexpr bool shade_motion() { return (std::is_same<Inst, MotionDev>::value || ...); }
+#ifndef RODENT_SHADE_DEFORM_WAVES
+#define RODENT_SHADE_DEFORM_WAVES 5      // (compile time) 8: 34 ... 36 spilled VGPRs, 7: 24 ... 25, 6: 16, 5: none beyond the flat shader's 68 bytes
+#endif
+constexpr int kShadeDeformWaves = RODENT_SHADE_DEFORM_WAVES;
+template <bool INST, typename... Inst> constexpr bool shade_deforming() { return (std::is_same<Inst, DeformingDev>::value || ...); }
 template <bool INST, typename... Inst> constexpr int shade_waves() {
-    return shade_motion<INST, Inst...>() ? kShadeMotionWaves : INST ? 7 : 8;
+    return shade_deforming<INST, Inst...>() ? kShadeDeformWaves : shade_motion<INST, Inst...>() ? kShadeMotionWaves : INST ? 7 : 8;
 }
 template <int kBlock /* threads per workgroup = rays per compaction slot request (shade_block()) */, bool INST = false, typename... Inst>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(shade_waves<INST, Inst...>(), 8))) void k_shade(SceneDev sc,
@@ -211,9 +223,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(shade_wa
     PrimaryStream q, const int* __restrict__ perm, SecondaryStream s, const int* size_ptr, int n_value, float* film,
                                                    float inv_spp, int max_path_len, int unsorted, unsigned* scan, int* alive_total,
                                                    Inst... inst) {
-    static_assert(sizeof...(Inst) == (INST ? 1 : 0), "k_shade<.., true> takes one InstancedDev or MotionDev");
-    constexpr bool MOTION = shade_motion<INST, Inst...>();
-    int time_bits = 0;                                                  // MOTION: the depth word's bits above the depth
+    constexpr bool MOTION = shade_motion<INST, Inst...>(), DEFORM = shade_deforming<INST, Inst...>();
+    static_assert(sizeof...(Inst) == (INST || DEFORM ? 1 : 0) && !(INST && DEFORM),
+                  "k_shade<.., true> takes one InstancedDev or MotionDev, k_shade<.., false> nothing or one DeformingDev");
+    int time_bits = 0;                                                  // MOTION, DEFORM: the depth word's bits above the depth
     float time = 0.0f;
     __shared__ unsigned wave_total[kBlock / kWave + 1];
 #if RODENT_SHADE_HOIST_LIGHT == 2
@@ -264,6 +277,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(shade_wa
             const int2 base = in.bases[id.z & 0x7FFFFFFF];
             pv.prim += base.x; frame.light_offset = base.y;
             o = shade_vertex<true>(sc, pv, max_path_len, &frame);
+        } else if constexpr (DEFORM) {
+            const DeformingDev& in = (inst, ...);
+            time_bits = pv.depth & ~RODENT_MOTION_DEPTH_MASK; pv.depth &= RODENT_MOTION_DEPTH_MASK;
+            time = shutter_time((uint32_t)time_bits >> RODENT_MOTION_DEPTH_BITS, in.open, in.close);
+            const Surf sf = surface_element_deforming(&sc, &in, __fsub_rn(1.0f, time), time, pv.org, pv.dir, pv.prim, pv.t, pv.u, pv.v);
+            o = shade_vertex<false, true>(sc, pv, max_path_len, nullptr, &sf);
         } else if constexpr (INST) {
             const InstancedDev& in = (inst, ...);
             const float4* rec = reinterpret_cast<const float4*>(in.instances + in.ray_slots[src]);
@@ -284,7 +303,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(shade_wa
             s.rays.dir_x[i] = o.s_dir.x; s.rays.dir_y[i] = o.s_dir.y; s.rays.dir_z[i] = o.s_dir.z;
             s.rays.tmin[i] = kRayOffset; s.rays.tmax[i] = 1.0f - kRayOffset;
             s.color_r[i] = o.s_color.x; s.color_g[i] = o.s_color.y; s.color_b[i] = o.s_color.z;
-            if constexpr (MOTION) s.prim_id[i] = __float_as_int(time);
+            if constexpr (MOTION || DEFORM) s.prim_id[i] = __float_as_int(time);
         }
         s.rays.id[i] = o.shadow ? pv.pixel : -1;
     }
@@ -320,5 +339,5 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(shade_wa
     q.rays.tmin[d] = kRayOffset; q.rays.tmax[d] = FLT_MAX_REF;
     q.rnd[d] = o.rnd; q.mis[d] = o.mis;
     q.contrib_r[d] = o.contrib.x; q.contrib_g[d] = o.contrib.y; q.contrib_b[d] = o.contrib.z;
-    q.depth[d] = MOTION ? (pv.depth + 1) | time_bits : pv.depth + 1;
+    q.depth[d] = MOTION || DEFORM ? (pv.depth + 1) | time_bits : pv.depth + 1;
 }

@@ -277,6 +277,40 @@ RD_FN float shutter_time(uint32_t ubits, float open, float close) {
     return fminf(close, __fadd_rn(open, __fmul_rn(__fsub_rn(close, open), u)));
 }
 
+/* ---- deforming meshes (include/rodent_render.h, "deforming meshes in the renderer") ----
+ * What the kernels of a deforming scene take beside SceneDev (whose vertices / normals are key 0's and whose nodes / tris are the static
+ * key-0 hierarchy, which these kernels never walk): the two-key records, key 1's tables and the shutter. */
+struct DeformingDev {
+    const RodentMotionNode2* nodes; const RodentMotionTri1* tris;   /* the motion records (rodent_motion.h) */
+    const float* vertices1; const float* normals1;                  /* the mesh at time 1: num_vertices float4 rows each */
+    float open, close;                                              /* the shutter: 0 <= open <= close <= 1 */
+};
+/* One value at the hit's time: s * x0 + t * x1, two products and a sum, each rounded on its own (rodent_motion.h's rule). */
+RD_FN float key_lerp(float s, float t, float x0, float x1) { return __fadd_rn(__fmul_rn(s, x0), __fmul_rn(t, x1)); }
+RD_FN v3 key_lerp3(float s, float t, const float* k0, const float* k1) {
+    return V(key_lerp(s, t, k0[0], k1[0]), key_lerp(s, t, k0[1], k1[1]), key_lerp(s, t, k0[2], k1[2]));
+}
+/* surface_element for a hit on a deforming mesh at time t (s = 1 - t): the corners and the corner normals are the two keys' rows at t;
+ * the face normal is the moved-geometry rule on those corners, c = (v1 - v0) x (v2 - v0), fn = c * (1 / sqrt((c.x c.x + c.y c.y) +
+ * c.z c.z)) -- not the interpolation of the keys' face normals: a triangle that turns over between the keys changes side when it is
+ * flat, as the traversal's n = cross(e1(t), e2(t)) does.  The corner normals are not normalised; lerp2 and normalize follow as above. */
+RD_FN Surf surface_element_deforming(const SceneDev* sc, const DeformingDev* in, float s_, float t_, v3 org, v3 dir, int32_t prim,
+    float t, float u, float v) {
+    const int32_t* idx = sc->indices + 4 * prim;
+    const int32_t i0 = idx[0], i1 = idx[1], i2 = idx[2];
+    const v3 p0 = key_lerp3(s_, t_, sc->vertices + 4 * i0, in->vertices1 + 4 * i0);
+    const v3 p1 = key_lerp3(s_, t_, sc->vertices + 4 * i1, in->vertices1 + 4 * i1);
+    const v3 p2 = key_lerp3(s_, t_, sc->vertices + 4 * i2, in->vertices1 + 4 * i2);
+    const v3 n0 = key_lerp3(s_, t_, sc->normals + 4 * i0, in->normals1 + 4 * i0);
+    const v3 n1 = key_lerp3(s_, t_, sc->normals + 4 * i1, in->normals1 + 4 * i1);
+    const v3 n2 = key_lerp3(s_, t_, sc->normals + 4 * i2, in->normals1 + 4 * i2);
+    const v3 c = cross(sub(p1, p0), sub(p2, p0));
+    const v3 fn = mulf(c, 1.0f / sqrtf((c.x * c.x + c.y * c.y) + c.z * c.z));
+    const v3 nrm = normalize(V(lerp2(n0.x, n1.x, n2.x, u, v), lerp2(n0.y, n1.y, n2.y, u, v), lerp2(n0.z, n1.z, n2.z, u, v)));
+    Surf sf; sf.entering = dot(dir, fn) <= 0.0f; sf.point = add(org, mulf(dir, t));
+    sf.face_normal = sf.entering ? fn : neg(fn); sf.local = orthonormal(dot(dir, nrm) <= 0.0f ? nrm : neg(nrm)); return sf;
+}
+
 /* image.impala:24-38 (RGBA8 -> colour), :48-54 (repeat border), :64-86 (bilinear filter) */
 RD_FN v3 texel(const SceneDev* sc, const RodentTexture* t, int32_t x, int32_t y) {
     const uint32_t p = sc->texels[t->offset + (uint32_t)y * (uint32_t)t->width + (uint32_t)x];

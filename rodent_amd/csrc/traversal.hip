@@ -47,6 +47,7 @@
 #include "rodent_motion.h"
 #include "traversal_device.h"
 #include "traversal_steps.h"
+#include "traversal_motion_steps.h"
 
 namespace {
 

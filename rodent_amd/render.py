@@ -62,6 +62,16 @@ SCENE_ERRORS = {SCENE_ERR_COUNTS: "a missing table, a count below 1, more than 2
                 SCENE_ERR_TABLE: "a vertex, material or texture index outside its table",
                 SCENE_ERR_DEVICE: "the device raised a flag while building",
                 SCENE_ERR_MOVING_LIGHT: "an instance of an object with lights has two different placements (lights stay static)"}
+# rodent_hip_scene_create_deforming's refusals, where their wording differs
+DEFORMING_ERRORS = {SCENE_ERR_COUNTS: "a missing table, a count below 1, or a hierarchy in the description",
+                    SCENE_ERR_LIGHT: "an emissive triangle without an entry in the light table",
+                    SCENE_ERR_TABLE: "a vertex, material, texture or light index outside its table",
+                    SCENE_ERR_MOVING_LIGHT: "an emissive triangle's corners differ between the keys (lights stay static)"}
+
+
+class SceneMotionKeys(C.Structure):
+    """RodentSceneMotionKeys: device pointers of a deforming scene's key tables and of its motion build's info words."""
+    _fields_ = [(n, vp) for n in ("vertices0", "vertices1", "normals0", "normals1", "info")] + [("num_vertices", i32)]
 
 
 class SceneMotionInstances(C.Structure):
@@ -86,7 +96,9 @@ def unpack_depth_time(words):
     return (w & MOTION_DEPTH_MASK).astype(np.int32), (w >> MOTION_DEPTH_BITS).astype(np.int32)
 
 
-RENDER_EXPORTS = ["rodent_hip_scene_create_motion", "rodent_hip_scene_set_motion_transforms", "rodent_hip_scene_motion_instances",
+RENDER_EXPORTS = ["rodent_hip_scene_create_deforming", "rodent_hip_scene_set_motion_keys", "rodent_hip_scene_motion_keys_status",
+                  "rodent_hip_scene_motion_bvh", "rodent_hip_scene_motion_keys",
+                  "rodent_hip_scene_create_motion", "rodent_hip_scene_set_motion_transforms", "rodent_hip_scene_motion_instances",
                   "rodent_hip_render_shutter", "rodent_hip_render_shutter_in_effect", "rodent_hip_render_max_path_len_in_effect",
                   "rodent_hip_scene_create_instanced", "rodent_hip_scene_create_flags", "rodent_hip_scene_set_transforms",
                   "rodent_hip_scene_transforms_status", "rodent_hip_scene_instances", "rodent_hip_render_sort_in_effect",
@@ -156,6 +168,13 @@ def lib():
         l.rodent_hip_scene_set_motion_transforms.argtypes = [i32, vp, vp, vp]; l.rodent_hip_scene_set_motion_transforms.restype = None
         l.rodent_hip_scene_motion_instances.argtypes = [i32, C.POINTER(SceneMotionInstances)]
         l.rodent_hip_scene_motion_instances.restype = None
+        l.rodent_hip_scene_create_deforming.argtypes = [i32, C.POINTER(SceneDesc), vp, vp, C.POINTER(abi.BuildOptions)]
+        l.rodent_hip_scene_create_deforming.restype = i32
+        l.rodent_hip_scene_set_motion_keys.argtypes = [i32, vp, vp, vp, vp, vp]; l.rodent_hip_scene_set_motion_keys.restype = None
+        l.rodent_hip_scene_motion_keys_status.argtypes = [i32, C.POINTER(i32)]; l.rodent_hip_scene_motion_keys_status.restype = i32
+        l.rodent_hip_scene_motion_bvh.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
+        l.rodent_hip_scene_motion_bvh.restype = None
+        l.rodent_hip_scene_motion_keys.argtypes = [i32, C.POINTER(SceneMotionKeys)]; l.rodent_hip_scene_motion_keys.restype = None
         l.rodent_hip_render_shutter.argtypes = [i32, C.c_float, C.c_float]; l.rodent_hip_render_shutter.restype = i32
         l.rodent_hip_render_shutter_in_effect.argtypes = [i32, C.POINTER(C.c_float)]; l.rodent_hip_render_shutter_in_effect.restype = None
         l.rodent_hip_render_max_path_len_in_effect.argtypes = [i32]; l.rodent_hip_render_max_path_len_in_effect.restype = i32
@@ -246,6 +265,43 @@ def create_motion(dev, scene, ranges, transforms0, transforms1, object_ids, opt=
                                                 descs.ctypes.data_as(vp), len(t0), C.byref(opt) if opt is not None else None)
 
 
+def smooth_normals(vertices, indices):
+    """(num_vertices, 4) float32 smooth vertex normals by the loader's rule, as rodent_hip_scene_refit_device recomputes them: every
+    triangle's face normal c * (1 / |c|), c = (v1 - v0) x (v2 - v0); per vertex those of its corners summed in ascending (triangle,
+    corner) order, then normalised where the squared length exceeds FLT_EPSILON, (0, 1, 0) elsewhere.  float32, every operation
+    rounded on its own."""
+    f32 = np.float32
+    v = np.ascontiguousarray(vertices, f32).reshape(-1, 4)
+    ix = np.ascontiguousarray(indices, np.int32).reshape(-1, 4)
+    with np.errstate(all="ignore"):
+        v0, v1, v2 = (v[ix[:, k], :3] for k in range(3))
+        a, b = v1 - v0, v2 - v0
+        c = np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                      a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1).astype(f32)
+        fn = c * (f32(1.0) / np.sqrt((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]))[:, None]
+        total = np.zeros((len(v), 3), f32)
+        np.add.at(total, ix[:, :3].reshape(-1), np.repeat(fn, 3, axis=0))           # unbuffered: one float32 add per corner, in order
+        l2 = (total[:, 0] * total[:, 0] + total[:, 1] * total[:, 1]) + total[:, 2] * total[:, 2]
+        keep = l2 > np.finfo(f32).eps
+        out = np.zeros((len(v), 4), f32)
+        out[:, 1] = 1.0
+        out[keep, :3] = total[keep] * (f32(1.0) / np.sqrt(l2[keep]))[:, None]
+    return out
+
+
+def create_deforming(dev, scene, vertices1, normals1, opt=None):
+    """rodent_hip_scene_create_deforming as it stands: returns its status and raises nothing -- Renderer(deform=...) is the checked way
+    in.  vertices1 / normals1: (num_vertices, 4) float32 host tables, or None for a NULL pointer."""
+    desc, keep = scene_desc(scene)
+    if not len(scene.nodes):
+        desc.nodes = None
+    if not len(scene.tris):
+        desc.tris = None
+    tables = [None if t is None else np.ascontiguousarray(t, np.float32) for t in (vertices1, normals1)]
+    return lib().rodent_hip_scene_create_deforming(dev, C.byref(desc), *[None if t is None else t.ctypes.data_as(vp) for t in tables],
+                                                   C.byref(opt) if opt is not None else None)
+
+
 def make_settings(cam) -> Settings:
     v = lambda a: Vec3(float(a[0]), float(a[1]), float(a[2]))
     return Settings(v(cam["eye"]), v(cam["dir"]), v(cam["up"]), v(cam["right"]), float(cam["w"]), float(cam["h"]))
@@ -260,7 +316,7 @@ class Renderer:
         fused_sort=None, lds_image=None,
                  trace_persistent=None, fused_compact=None, mega_joint=None, trace_refill=None, hit_records_aos=None, gpu_bvh=None,
                  gpu_bvh_passes=0, gpu_bvh_split=0.0, gpu_bvh_max_pieces=64, gpu_bvh_ploc=0, persist_min_rays=None, instances=None,
-                 build=None, motion=None, shutter=(0.0, 1.0)):
+                 build=None, motion=None, shutter=(0.0, 1.0), deform=None):
         """Options left at None take the library's default, or what the option's RODENT_HIP_* environment variable says.
         gpu_bvh = max_leaf (1 ... 8): ignore the scene's hierarchy and build one on the device (rodent_hip_scene_create_device_bvh_opt);
         gpu_bvh_passes = 1 ... 3: treelet restructuring passes + SAH leaf collapse on it.
@@ -281,7 +337,19 @@ class Renderer:
         `instances`.  Instances of objects with lights must have equal placements.  Paths are at most 255 vertices long.
         set_motion_transforms() moves both placements, set_shutter() changes the interval.  `shutter` is checked whatever the scene
         (a pair outside 0 <= open <= close <= 1 raises ValueError) but only a moving scene uses it: without `motion` the device keeps
-        its default (0, 1)."""
+        its default (0, 1).
+        deform = (vertices1, normals1): a DEFORMING scene (rodent_hip_scene_create_deforming) -- `scene` is the mesh at time 0 (its
+        hierarchy is ignored: the topology is built on the device from key 0 with `build`), vertices1 / normals1 are (num_vertices, 4)
+        float32 tables, the mesh at time 1; normals1 = None: smooth normals of key 1 by the loader's rule (smooth_normals), computed
+        here on the host.  Every path draws a time in `shutter` and sees every vertex where that time puts it.  Excludes `instances`,
+        `motion` and `gpu_bvh`.  The corners of emissive triangles must be equal in both keys.  Paths are at most 255 vertices long.
+        set_motion_keys() moves both keys on the device, set_shutter() changes the interval.  A refusal raises gpubuild.BuildError."""
+        if deform is not None and instances is not None:
+            raise ValueError("deform: a deforming scene is one mesh with two keys (pass `deform` or `instances`, not both)")
+        if deform is not None and motion is not None:
+            raise ValueError("deform: a deforming scene is one mesh with two keys (pass `deform` or `motion`, not both)")
+        if deform is not None and gpu_bvh:
+            raise ValueError("deform: the hierarchy is built on the device anyway (pass `build`, not gpu_bvh)")
         if motion is not None and instances is not None:
             raise ValueError("motion: a moving scene carries its own placements (pass `motion` or `instances`, not both)")
         if not 0.0 <= float(shutter[0]) <= float(shutter[1]) <= 1.0:       # (with or without `motion`, before the device is touched)
@@ -314,7 +382,11 @@ class Renderer:
         l.rodent_hip_render_defaults(dev)                    # options of an earlier Renderer in this process do not leak into this one
         self.num_instances = 0
         self.moving = motion is not None
-        if self.moving:
+        self.deforming = deform is not None
+        if self.deforming:
+            self._create_deforming(desc, scene, deform, build)
+            self.set_shutter(*shutter)
+        elif self.moving:
             ranges, t0, t1, ids = motion
             self._create_instanced(desc, (ranges, t0, ids), build, transforms1=t1)
             self.set_shutter(*shutter)
@@ -391,10 +463,7 @@ class Renderer:
             descs = np.zeros(n, F.MOTION_INSTANCE_DESC)
             descs["object_to_world0"], descs["object_to_world1"] = t.reshape(n, 12), t1.reshape(n, 12)
         descs["object"] = np.clip(ids, -1, (1 << 31) - 1)                 # (an id past int32 is outside every table too)
-        if build is None or isinstance(build, abi.BuildOptions):
-            opt = build
-        else:
-            opt = gpubuild.options(*build) if isinstance(build, (tuple, list)) else gpubuild.options(int(build))
+        opt = self._build_options(build)
         desc.nodes = desc.tris = None
         desc.num_nodes = desc.num_bvh_tris = 0
         rc = getattr(lib(), entry)(self.dev, C.byref(desc), ranges.ctypes.data_as(C.POINTER(ObjectRange)), len(ranges),
@@ -407,6 +476,138 @@ class Renderer:
                 what += ": " + (", ".join(s for bit, s in _TLAS_FLAGS if flags > 0 and flags & bit) or f"flags {flags}")
             raise gpubuild.BuildError(f"{entry}: {what}")
         self.num_instances = n
+
+    @staticmethod
+    def _build_options(build):
+        from . import gpubuild
+        if build is None or isinstance(build, abi.BuildOptions):
+            return build
+        return gpubuild.options(*build) if isinstance(build, (tuple, list)) else gpubuild.options(int(build))
+
+    def _create_deforming(self, desc, scene, deform, build):
+        from . import gpubuild
+        vertices1, normals1 = deform
+        nv = len(scene.vertices)
+        v1 = np.ascontiguousarray(vertices1, np.float32)
+        if v1.shape != (nv, 4):
+            raise ValueError(f"deform: vertices1 must have shape ({nv}, 4), got {v1.shape}")
+        n1 = smooth_normals(v1, scene.indices) if normals1 is None else np.ascontiguousarray(normals1, np.float32)
+        if n1.shape != (nv, 4):
+            raise ValueError(f"deform: normals1 must have shape ({nv}, 4), got {n1.shape}")
+        opt = self._build_options(build)
+        desc.nodes = desc.tris = None
+        desc.num_nodes = desc.num_bvh_tris = 0
+        rc = lib().rodent_hip_scene_create_deforming(self.dev, C.byref(desc), v1.ctypes.data_as(vp), n1.ctypes.data_as(vp),
+                                                     C.byref(opt) if opt is not None else None)
+        if rc:
+            what = DEFORMING_ERRORS.get(rc) or SCENE_ERRORS.get(rc, f"status {rc}")
+            if rc == SCENE_ERR_DEVICE:
+                flags = lib().rodent_hip_scene_create_flags(self.dev)
+                what += ": " + self._build_flag_names(flags)
+            raise gpubuild.BuildError(f"rodent_hip_scene_create_deforming: {what}")
+
+    @staticmethod
+    def _build_flag_names(flags):
+        from . import gpubuild
+        names = [(gpubuild.NON_FINITE, "non-finite coordinate"), (gpubuild.BAD_INDEX, "vertex index out of range")]
+        return ", ".join(s for bit, s in names if flags > 0 and flags & bit) or f"flags {flags}"
+
+    def _no_deforming(self, entry):
+        """The entries that work on a flat or an instanced scene refuse a deforming one here: the library aborts on it."""
+        if self.deforming:
+            from . import gpubuild
+            raise gpubuild.BuildError(f"{entry}: the scene is a deforming one (move its keys with set_motion_keys)")
+
+    def set_motion_keys(self, vertices0, vertices1, normals0=None, normals1=None, stream=None, check=True):
+        """Both keys of a deforming scene moved (rodent_hip_scene_set_motion_keys): (num_vertices, 4) float32 tensors on the renderer's
+        device or integer device pointers; a key may be the scene's own table (motion_key_pointers()), written in place -- then nothing
+        is copied -- and the two keys may be one tensor.  normals0 / normals1: both given, or both None: smooth normals recomputed per
+        key on the device.  The copies, the normals and the rebuild of the motion records follow on `stream` (a torch stream; None: the
+        current one) with no host copy and no wait; the next frame, on any stream, sees the moved keys.  The caller keeps the corners
+        of emissive triangles as they were at creation: this call cannot check it.  check=True waits (motion_keys_status) and raises
+        gpubuild.BuildError on a flag.  The film is not cleared."""
+        import torch
+        if not self.deforming:
+            raise ValueError("set_motion_keys: the renderer was not made with `deform`")
+        if vertices0 is None or vertices1 is None or (normals0 is None) != (normals1 is None):
+            raise ValueError("set_motion_keys: both vertex tables are needed, and both tables of normals or neither")
+        stream = torch.cuda.current_stream(self.dev) if stream is None else stream
+        own = self.motion_key_pointers()
+        nv = own["num_vertices"]
+        given = (("vertices0", vertices0), ("vertices1", vertices1), ("normals0", normals0), ("normals1", normals1))
+        pointers = []
+        for name, t in given:
+            if t is None or isinstance(t, int):
+                pointers.append(t)
+                continue
+            if not (t.is_cuda and t.data_ptr() == own[name]) and (
+                    not t.is_cuda or t.device.index != self.dev or t.dtype != torch.float32 or tuple(t.shape) != (nv, 4)
+                    or not t.is_contiguous()):
+                raise ValueError(f"set_motion_keys: `{name}` must be a contiguous float32 tensor of shape ({nv}, 4) on cuda:{self.dev} "
+                                 "(or an integer device pointer)")
+            pointers.append(t.data_ptr())
+        tensors = [t for _, t in given if isinstance(t, torch.Tensor)]
+        if tensors:
+            stream.wait_stream(torch.cuda.current_stream(self.dev))          # the tensors may come from there
+        lib().rodent_hip_scene_set_motion_keys(self.dev, *pointers, C.c_void_p(stream.cuda_stream))
+        for t in tensors:
+            t.record_stream(stream)
+        if check:
+            self.motion_keys_status(raise_on_flag=True)
+
+    def motion_keys_status(self, raise_on_flag=False):
+        """(flags, info words) of the last set_motion_keys, once it has finished (before the first: the creation's); flags 0 = sound
+        (gpubuild.NON_FINITE, ...; bit 31: a key's refit completed another node count than the topology's)."""
+        words = (i32 * 4)()
+        flags = lib().rodent_hip_scene_motion_keys_status(self.dev, words)
+        if flags and raise_on_flag:
+            from . import gpubuild
+            raise gpubuild.BuildError("rodent_hip_scene_set_motion_keys: " + (self._build_flag_names(flags & 0x7FFFFFFF)
+                                      if flags & 0x7FFFFFFF else f"malformed hierarchy ({words[0]}, {words[3]} nodes completed)"))
+        return flags, list(words)
+
+    def motion_key_pointers(self):
+        """Device pointers (integers) of a deforming scene's key tables (rodent_hip_scene_motion_keys) and num_vertices."""
+        t = SceneMotionKeys()
+        lib().rodent_hip_scene_motion_keys(self.dev, C.byref(t))
+        return {n: (getattr(t, n) or 0) for n, _ in SceneMotionKeys._fields_}
+
+    def motion_key_tensor(self, name):
+        """One of the scene's own key tables ("vertices0", "vertices1", "normals0", "normals1") as a (num_vertices, 4) float32 torch
+        tensor that shares its memory: write it in place, then pass it to set_motion_keys (nothing is copied)."""
+        import torch
+        p = self.motion_key_pointers()
+
+        class Table:
+            __cuda_array_interface__ = {"shape": (p["num_vertices"], 4), "typestr": "<f4", "data": (p[name], False), "version": 2,
+                                        "strides": None}
+        return torch.as_tensor(Table(), device=f"cuda:{self.dev}")
+
+    def deforming_tables(self):
+        """Host copies (numpy) of what a deforming scene holds: vertices0, vertices1, normals0, normals1 ((num_vertices, 4) float32),
+        motion_nodes (MOTION_NODE2), motion_tris (MOTION_TRI1), lights (scene.LIGHT) and info (the last motion build's info words).
+        Waits for the device."""
+        import torch
+        from . import formats as F
+        from .scene import LIGHT
+        p = self.motion_key_pointers()
+        nodes, tris, nn, nt = vp(), vp(), i32(), i32()
+        lib().rodent_hip_scene_motion_bvh(self.dev, C.byref(nodes), C.byref(tris), C.byref(nn), C.byref(nt))
+        scene = self.scene_table_pointers()
+        torch.cuda.synchronize(self.dev)
+        hip = C.cdll.LoadLibrary("libamdhip64.so")
+
+        def fetch(ptr, dtype, count, shape=None):
+            nbytes = count * np.dtype(dtype).itemsize
+            t = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=f"cuda:{self.dev}")
+            hip.hipMemcpy(C.c_void_p(t.data_ptr()), C.c_void_p(ptr), C.c_size_t(nbytes), 3)
+            a = t.cpu().numpy()[:nbytes].view(dtype).copy()
+            return a.reshape(shape) if shape else a
+        nv = p["num_vertices"]
+        out = {n: fetch(p[n], "<f4", 4 * nv, (nv, 4)) for n in ("vertices0", "vertices1", "normals0", "normals1")}
+        out.update(motion_nodes=fetch(nodes.value, F.MOTION_NODE2, nn.value), motion_tris=fetch(tris.value, F.MOTION_TRI1, nt.value),
+                   lights=fetch(scene["lights"], LIGHT, scene["num_lights"]), info=fetch(p["info"], "<i4", 4))
+        return out
 
     def _matrices_pointer(self, t, what):
         """Device pointer of num_instances x 12 float32 entries given as a tensor on the renderer's device, or as an integer pointer."""
@@ -426,6 +627,7 @@ class Renderer:
         placements of every instance of an object with lights equal: this call cannot check it.  check=True waits
         (transforms_status) and raises gpubuild.BuildError on a flag (a singular or non-finite endpoint).  The film is not cleared."""
         import torch
+        self._no_deforming("set_motion_transforms")
         stream = torch.cuda.current_stream(self.dev) if stream is None else stream
         pointers = [self._matrices_pointer(t, "set_motion_transforms") for t in (transforms0, transforms1)]
         tensors = [t for t in (transforms0, transforms1) if not isinstance(t, int)]
@@ -471,6 +673,7 @@ class Renderer:
         (rodent_hip_scene_transforms_status) and raises gpubuild.BuildError on a flag (a singular or non-finite matrix): the scene must
         not be rendered before a sound rebuild.  The film is not cleared."""
         import torch
+        self._no_deforming("set_transforms")
         stream = torch.cuda.current_stream(self.dev) if stream is None else stream
         if isinstance(transforms, int):
             pointer = transforms
@@ -520,6 +723,7 @@ class Renderer:
         follow on `stream` (a torch stream; None: the current one) with no host copy and no wait; the next frame, on any stream, sees
         the deformed scene.  check=True waits (deform_status) and raises gpubuild.BuildError on a flag.  The film is not cleared."""
         import torch
+        self._no_deforming("deform_objects")
         stream = torch.cuda.current_stream(self.dev) if stream is None else stream
         tensors = [t for t in (vertices, normals, transforms) if isinstance(t, torch.Tensor)]
         pointers = [self._table_pointer(vertices, "vertices"), self._table_pointer(normals, "normals")]
@@ -590,13 +794,13 @@ class Renderer:
 
     def options_in_effect(self):
         """What the next frame uses for the scene that is loaded: mapping name, trace_persistent, (refill thresholds), sort.
-        The keys depend on how the renderer was made: one made with `motion=` ALSO returns max_path_len and shutter; every other
+        The keys depend on how the renderer was made: one made with `motion=` or `deform=` ALSO returns max_path_len and shutter; every other
         renderer returns exactly the four keys above (callers compare that dictionary for equality), and max_path_len() and
         shutter() read the two values for any renderer."""
         l = lib()
         out = {"mapping": self.mapping_name(), "trace_persistent": l.rodent_hip_render_trace_persistent_in_effect(self.dev),
                "trace_refill": self.trace_refill(), "sort": l.rodent_hip_render_sort_in_effect(self.dev)}
-        if self.moving:
+        if self.moving or self.deforming:
             out.update(max_path_len=self.max_path_len(), shutter=self.shutter())
         return out
 
@@ -669,6 +873,7 @@ class Renderer:
         """The scene's vertices moved: `scene` is a Scene with the same index table (and the same materials, light ids and textures)
         and new vertices, normals, face normals and lights.  Overwrites the device tables, refits the hierarchy in place and rebuilds
         what depends on positions (rodent_hip_scene_refit); synchronous.  The film is not cleared."""
+        self._no_deforming("update_geometry")
         if (len(scene.vertices), len(scene.lights), len(scene.texels)) != self._counts:
             raise ValueError("update_geometry: the scene's vertex, light or texel count differs from the one the renderer was created with")
         for n, mine in self._fixed.items():
@@ -681,6 +886,7 @@ class Renderer:
     def prepare_update(self, smooth_normals=True):
         """One-time allocations of update_geometry_device (rodent_hip_scene_refit_prepare), so that its first call allocates nothing
         either; smooth_normals: also the incidence lists a call without `normals` needs."""
+        self._no_deforming("prepare_update")
         lib().rodent_hip_scene_refit_prepare(self.dev, int(bool(smooth_normals)))
 
     def _table_pointer(self, t, what):
@@ -705,6 +911,7 @@ class Renderer:
         check=True waits for the refit (rodent_hip_scene_refit_status) and raises gpubuild.BuildError on a flag: a non-finite
         coordinate, a malformed hierarchy.  The film is not cleared."""
         import torch
+        self._no_deforming("update_geometry_device")
         stream = torch.cuda.current_stream(self.dev) if stream is None else stream
         tensors = [t for t in (vertices, normals) if isinstance(t, torch.Tensor)]
         pointers = (self._table_pointer(vertices, "vertices"), self._table_pointer(normals, "normals"))
