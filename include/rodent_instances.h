@@ -84,6 +84,33 @@
  * Sort point: lo + hi of the motion box; from there the LBVH stages as for rodent_hip_build_tlas.  RodentMotionInstance k is the k-th
  *   instance in that order: both matrices as given, the object's offsets, instance_id (bit 31: the last of its leaf), pads = 0.
  * Flags: RODENT_TLAS_BAD_TRANSFORM if either endpoint matrix fails the static checks; RODENT_TLAS_BAD_OBJECT as above.
+ *
+ * ---- deforming objects under moving instances: one time through both levels (tests/motion_objects_model.py restates this section) ----
+ * Motion object set: all objects' RodentMotionNode2 records (rodent_motion.h) lie in ONE array and all their RodentMotionTri1 records in
+ *   another; the RodentObject table indexes those arrays (node_offset / tri_offset count motion records); child ids and leaf starts stay
+ *   object-local, as in a static set.  An object that does not deform has equal keys.
+ * Time: one float per ray serves both levels, and rodent_motion.h's rule wins over "used as given" above: a ray with
+ *   !(0 <= t && t <= 1) stores the miss record {-1, tmax as given, 0, 0} and instance -1 without any traversal.  A NaN fails the test; -0
+ *   and 1 are traced.  Inside [0, 1] everything of "moving instances" holds unchanged: the entry-wise lerp of the placement, the fp64
+ *   cofactor inverse, the silent skip of an instance that is singular or non-finite at that time.
+ * Inside an object: rodent_motion.h unchanged, with the same s = 1 - t and t: the interpolated node goes into the unchanged slab test,
+ *   ordering and push, the interpolated Tri1 into the unchanged triangle test; a slot with child == 0 is never taken.
+ * Across instances: as for static objects: the <= acceptance rule, the shared tmax carried between instances, any-hit returning at the
+ *   first acceptance, hit = {prim_id & 0x7FFFFFFF, t, u, v}, hit_instance = instance_id.
+ * Stack: one stack of 64 entries serves both levels, in the slot order above.  P = the TLAS entries held on entering an instance + that
+ *   object's peak entries at the ray's own time (the interpolated boxes decide what is pushed): a ray whose P + 2 never exceeds 64 is
+ *   traced without a flag; any other ray raises the overflow word, stops where it stands and never pops a slot it did not push.
+ * Object box of a motion object: fminf of the lows and fmaxf of the highs over the root record's FOUR stored child boxes, two slots at
+ *   both keys; an empty slot's (+inf, -inf) drops out.  This is the union U over both keys, on purpose.  Mapping key 0's box by M0 and key
+ *   1's box by M1 would NOT bound the motion: a corner's world image is M(t) p(t), with both factors linear in t, so it is quadratic in t
+ *   and does not lie in the hull of its two endpoint images.  U contains every corner the kernel intersects at every t in [0, 1]: an
+ *   exact interpolation of a vertex lies between its keys, inside the unwidened boxes of both keys' hierarchies, and the stored bounds
+ *   were widened by 2^-19 M at fuse time (rodent_motion.h), which covers the three roundings of a corner's fp32 interpolation (and those
+ *   of v0 - e1 and v0 + e2).  The motion box of U under (M0, M1) by the rule above then contains the image of all of U under the
+ *   fp32-interpolated placement at every t in [0, 1], hence every such corner.  tests/test_motion_objects_model.py checks this in exact
+ *   rational arithmetic, and shows that key 0's root box alone fails it.
+ * Sort point, LBVH stages, leaf order and the RodentMotionInstance records: those of "moving instances", byte for byte.  The pad word of
+ *   an instance record stays 0: static and motion objects are not mixed under one TLAS.
  */
 #ifndef RODENT_INSTANCES_H
 #define RODENT_INSTANCES_H
@@ -277,6 +304,82 @@ void hip_occluded_motion_instanced_bvh2_tri1(int32_t dev, const struct Node2* tl
                                              const struct RodentMotionInstance* motion_instances, const struct Node2* nodes,
                                              const struct Tri1* tris, const struct Ray1* rays, const float* times, struct Hit1* hits,
                                              int32_t* hit_instances, int32_t num_rays);
+
+/* ---- deforming objects under moving instances (the section of that name at the top) ----
+ * Bytes of device scratch rodent_hip_build_motion_objects needs: num_nodes / num_recs are the record counts of the PACKED ARRAYS (every
+ * object's room; for a tight set listed whole they equal the plan's totals), refit_bytes what rodent_hip_refit_objects_plan returned for
+ * the list.  -1 for a count < 1 or refit_bytes < 0.  Any 256-byte aligned buffer of that size, its contents are ignored. */
+struct RodentMotionNode2;
+struct RodentMotionTri1;
+int64_t rodent_hip_motion_objects_scratch_bytes(int32_t num_nodes, int32_t num_recs, int64_t refit_bytes);
+
+/* The forest form of rodent_hip_build_motion_bvh2_tri1 (rodent_motion.h): the two-key records of ALL objects of a packed set, over
+ * vertices0 at time 0 and vertices1 at time 1.  DEVICE pointers: both vertex tables (num_vertices float4 rows each, the concatenated
+ * tables), indices (num_rows int4 rows), nodes / tris (the packed topology, num_nodes Node2 / num_recs Tri1: only read), objects, ranges
+ * (one RodentRefitRange per object, all objects in table order, from rodent_hip_refit_objects_plan, with its totals total_nodes /
+ * total_recs), motion_nodes / motion_tris (room for num_nodes / num_recs motion records: record k of the packed arrays becomes motion
+ * record k, so the object table serves both), scratch, info_dev (RODENT_BUILD_INFO_WORDS ints).  Asynchronous on `stream`: nothing is
+ * allocated, nothing waits for the device.  The launch list is fixed whatever the number of objects: four device-to-device copies (the
+ * packed arrays into scratch twice, copy A and copy B), rodent_hip_refit_objects' list on A with vertices0, the same on B with vertices1,
+ * a memset of the info words, k_fuse_motion over the packed arrays.
+ * info: [0] nodes completed at key 0 [1] records fused (num_nodes + num_recs) [2] the OR of all flags [3] nodes completed at key 1; a
+ * sound call leaves [0] == [3] == total_nodes.  Per object the output is byte for byte what rodent_hip_build_motion_bvh2_tri1 writes for
+ * that object alone; records outside every object (the unused room of a slotted set) are fused as they lie.  The flags are
+ * rodent_hip_refit_objects' at either key and the fuse's; a flagged object is left incomplete, the others come out complete.  Calling it
+ * again with moved keys is the refit.
+ * Checks: those of rodent_hip_refit_objects in its order, each enqueuing nothing when it fails: RODENT_BUILD_ERR_NUM_TRIS,
+ * RODENT_BUILD_ERR_NUM_VERTICES, RODENT_TLAS_ERR_NUM_OBJECTS, RODENT_BUILD_ERR_NUM_NODES (num_listed < 1, a negative total, num_nodes or
+ * num_recs < 1, a total beyond its array's count), RODENT_BUILD_ERR_NULL, RODENT_BUILD_ERR_DEVICE. */
+int32_t rodent_hip_build_motion_objects(int32_t dev, const float* vertices0, const float* vertices1, int32_t num_vertices,
+                                        const int32_t* indices, int32_t num_rows, const struct Node2* nodes, int32_t num_nodes,
+                                        const struct Tri1* tris, int32_t num_recs, const struct RodentObject* objects,
+                                        int32_t num_objects, const struct RodentRefitRange* ranges, int32_t num_listed,
+                                        int32_t total_nodes, int32_t total_recs, struct RodentMotionNode2* motion_nodes,
+                                        struct RodentMotionTri1* motion_tris, void* scratch, int32_t* info_dev, void* stream);
+
+/* Synchronous form on the null stream with its own scratch: copies the info words to `info` (host, may be NULL) and returns
+ * RODENT_BUILD_ERR_INPUT when the device raised a flag or a node stayed incomplete at either key.  It checks RODENT_BUILD_ERR_NUM_NODES
+ * and RODENT_BUILD_ERR_DEVICE first (it sizes and allocates the scratch), then as above. */
+int32_t rodent_hip_build_motion_objects_sync(int32_t dev, const float* vertices0, const float* vertices1, int32_t num_vertices,
+                                             const int32_t* indices, int32_t num_rows, const struct Node2* nodes, int32_t num_nodes,
+                                             const struct Tri1* tris, int32_t num_recs, const struct RodentObject* objects,
+                                             int32_t num_objects, const struct RodentRefitRange* ranges, int32_t num_listed,
+                                             int32_t total_nodes, int32_t total_recs, struct RodentMotionNode2* motion_nodes,
+                                             struct RodentMotionTri1* motion_tris, int32_t* info);
+
+/* rodent_hip_build_motion_tlas / _sync over a motion object set: `nodes` is the objects' RodentMotionNode2 array (only the root record of
+ * every object is read).  The same refusals in the same order, the same scratch (rodent_hip_motion_tlas_scratch_bytes), the same launch
+ * list; only the instance stage differs, which reads the object box by the rule "Object box of a motion object". */
+int32_t rodent_hip_build_motion_tlas_motion_objects(int32_t dev, const struct RodentMotionNode2* nodes,
+                                                    const struct RodentObject* objects, int32_t num_objects,
+                                                    const struct RodentMotionInstanceDesc* descs, int32_t num_instances,
+                                                    int32_t max_leaf, struct Node2* tlas_nodes, struct RodentMotionInstance* instances,
+                                                    void* scratch, int32_t* info_dev, void* stream);
+int32_t rodent_hip_build_motion_tlas_motion_objects_sync(int32_t dev, const struct RodentMotionNode2* nodes,
+                                                         const struct RodentObject* objects, int32_t num_objects,
+                                                         const struct RodentMotionInstanceDesc* descs, int32_t num_instances,
+                                                         int32_t max_leaf, struct Node2* tlas_nodes,
+                                                         struct RodentMotionInstance* instances, int32_t* info);
+
+/* The three motion traversal entries above through a motion TLAS over a motion object set: `times` is required and serves both levels; a
+ * ray whose time is not in [0, 1] is a miss without any traversal.  hit_instances may be NULL.  The overflow flag is reported by
+ * rodent_hip_check_errors; the synchronous forms abort() on it. */
+void hip_traverse_motion_instanced_motion_bvh2_tri1_async(int32_t dev, const struct Node2* tlas_nodes,
+                                                          const struct RodentMotionInstance* motion_instances,
+                                                          const struct RodentMotionNode2* motion_nodes,
+                                                          const struct RodentMotionTri1* motion_tris, const struct Ray1* rays,
+                                                          const float* times, struct Hit1* hits, int32_t* hit_instances,
+                                                          int32_t num_rays, int32_t any_hit, void* stream);
+void hip_intersect_motion_instanced_motion_bvh2_tri1(int32_t dev, const struct Node2* tlas_nodes,
+                                                     const struct RodentMotionInstance* motion_instances,
+                                                     const struct RodentMotionNode2* motion_nodes,
+                                                     const struct RodentMotionTri1* motion_tris, const struct Ray1* rays,
+                                                     const float* times, struct Hit1* hits, int32_t* hit_instances, int32_t num_rays);
+void hip_occluded_motion_instanced_motion_bvh2_tri1(int32_t dev, const struct Node2* tlas_nodes,
+                                                    const struct RodentMotionInstance* motion_instances,
+                                                    const struct RodentMotionNode2* motion_nodes,
+                                                    const struct RodentMotionTri1* motion_tris, const struct Ray1* rays,
+                                                    const float* times, struct Hit1* hits, int32_t* hit_instances, int32_t num_rays);
 
 #ifdef __cplusplus
 }

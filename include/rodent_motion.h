@@ -2,7 +2,7 @@
  * rodent_motion.h -- C ABI of deforming meshes under motion (librodent_hip.so): a BVH2 / Tri1 hierarchy with TWO keys per record, the
  * mesh at time 0 and at time 1, and a time per ray.  No reference counterpart; tests/motion_bvh_model.py restates everything below on
  * the CPU and predicts the bytes.  This is the traversal ABI; the renderer over these records is rodent_render.h's "deforming meshes
- * in the renderer".  Motion objects under the motion TLAS of rodent_instances.h are not built.
+ * in the renderer".  Motion objects under the motion TLAS: rodent_instances.h, "deforming objects under moving instances".
  *
  * Records: RodentMotionNode2 is a Node2 (rodent_traversal.h) with its 12 bounds twice -- bounds order, child encoding and leaf encoding
  *   unchanged --, RodentMotionTri1 a Tri1 twice; key 0 carries the pad / geom_id / prim_id words (bit 31 of prim_id = last in leaf), the

@@ -61,6 +61,10 @@ EXPORTS = SYNC_ENTRY_POINTS + ASYNC_ENTRY_POINTS + [
     "rodent_hip_fuse_motion_bvh2_tri1", "rodent_hip_motion_bvh2_scratch_bytes", "rodent_hip_build_motion_bvh2_tri1",
     "rodent_hip_build_motion_bvh2_tri1_sync",
     "hip_traverse_motion_bvh2_tri1_async", "hip_intersect_motion_bvh2_tri1", "hip_occluded_motion_bvh2_tri1",
+    "rodent_hip_motion_objects_scratch_bytes", "rodent_hip_build_motion_objects", "rodent_hip_build_motion_objects_sync",
+    "rodent_hip_build_motion_tlas_motion_objects", "rodent_hip_build_motion_tlas_motion_objects_sync",
+    "hip_traverse_motion_instanced_motion_bvh2_tri1_async", "hip_intersect_motion_instanced_motion_bvh2_tri1",
+    "hip_occluded_motion_instanced_motion_bvh2_tri1",
 ]
 BLOCK_OF_WIDTH = {2: F.BVH2_TRI1, 4: F.BVH4_TRI4, 8: F.BVH8_TRI4}
 
@@ -207,6 +211,23 @@ def lib():
         l.hip_traverse_motion_bvh2_tri1_async.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, vp]
         for name in ("hip_intersect_motion_bvh2_tri1", "hip_occluded_motion_bvh2_tri1"):
             fn = getattr(l, name); fn.restype = None; fn.argtypes = [i32, vp, vp, vp, vp, vp, i32]
+        # deforming objects under moving instances (include/rodent_instances.h)
+        l.rodent_hip_motion_objects_scratch_bytes.restype = C.c_int64
+        l.rodent_hip_motion_objects_scratch_bytes.argtypes = [i32, i32, C.c_int64]
+        l.rodent_hip_build_motion_objects.restype = i32
+        l.rodent_hip_build_motion_objects.argtypes = [i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp,
+                                                      vp, vp]
+        l.rodent_hip_build_motion_objects_sync.restype = i32
+        l.rodent_hip_build_motion_objects_sync.argtypes = [i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp,
+                                                           C.POINTER(i32)]
+        l.rodent_hip_build_motion_tlas_motion_objects.restype = i32
+        l.rodent_hip_build_motion_tlas_motion_objects.argtypes = l.rodent_hip_build_motion_tlas.argtypes
+        l.rodent_hip_build_motion_tlas_motion_objects_sync.restype = i32
+        l.rodent_hip_build_motion_tlas_motion_objects_sync.argtypes = l.rodent_hip_build_motion_tlas_sync.argtypes
+        l.hip_traverse_motion_instanced_motion_bvh2_tri1_async.restype = None
+        l.hip_traverse_motion_instanced_motion_bvh2_tri1_async.argtypes = l.hip_traverse_motion_instanced_bvh2_tri1_async.argtypes
+        for name in ("hip_intersect_motion_instanced_motion_bvh2_tri1", "hip_occluded_motion_instanced_motion_bvh2_tri1"):
+            fn = getattr(l, name); fn.restype = None; fn.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]
         _lib = l
     return _lib
 

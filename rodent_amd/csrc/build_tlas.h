@@ -1,6 +1,6 @@
 // build_tlas.h -- the top level of an instanced scene (include/rodent_instances.h; included by bvh_build.hip after build_lbvh.h): the
-// instance stage (k_instances; k_motion_instances for moving instances) in front of the LBVH's stages 2, 3, 5, 6 and 7 and the leaf stage
-// in the place of stage 4.  CPU models: tests/instance_model.py, tests/motion_instance_model.py.
+// instance stage (k_instances; k_motion_instances<ObjNode> for moving instances, over static or motion objects) in front of the LBVH's stages 2, 3, 5, 6 and 7 and the leaf stage
+// in the place of stage 4.  CPU models: tests/instance_model.py, tests/motion_instance_model.py, tests/motion_objects_model.py.
 #pragma once
 // invert_affine, the one inverse of the build stage and of k_instanced_motion: instance_inverse.h.
 
@@ -67,9 +67,28 @@ __device__ __forceinline__ void instance_widening(const float m[12], const float
     }
 }
 
+// The object box from an object's root record: the union of its two child boxes (an empty slot's (+inf, -inf) drops out) -- of a
+// two-key root the union over both keys too, the four stored child boxes (rodent_instances.h, "deforming objects under moving
+// instances": why it is the union and not key 0's box under M0 and key 1's under M1).
+struct ObjectBox { float lo[3], hi[3]; };
+__device__ __forceinline__ ObjectBox object_box(const Node2* root) {
+    const float4* np = reinterpret_cast<const float4*>(root);
+    const float4 b0 = np[0], b1 = np[1], b2 = np[2];                     // child 0: b0.x .. b1.y, child 1: b1.z .. b2.w
+    return {{fminf(b0.x, b1.z), fminf(b0.z, b2.x), fminf(b1.x, b2.z)}, {fmaxf(b0.y, b1.w), fmaxf(b0.w, b2.y), fmaxf(b1.y, b2.w)}};
+}
+__device__ __forceinline__ ObjectBox object_box(const RodentMotionNode2* root) {
+    const float4* np = reinterpret_cast<const float4*>(root);
+    const float4 b0 = np[0], b1 = np[1], b2 = np[2], c0 = np[3], c1 = np[4], c2 = np[5];     // key 0's rows, key 1's rows
+    return {{fminf(fminf(b0.x, b1.z), fminf(c0.x, c1.z)), fminf(fminf(b0.z, b2.x), fminf(c0.z, c2.x)),
+             fminf(fminf(b1.x, b2.z), fminf(c1.x, c2.z))},
+            {fmaxf(fmaxf(b0.y, b1.w), fmaxf(c0.y, c1.w)), fmaxf(fmaxf(b0.w, b2.y), fmaxf(c0.w, c2.y)),
+             fmaxf(fmaxf(b1.y, b2.w), fmaxf(c1.y, c2.w))}};
+}
+
 // staged[t]: the RodentMotionInstance record of descriptor t without its end-of-leaf bit; wbox[6 t]: its motion box; cent[t]: its sort
-// point.
-__global__ __launch_bounds__(kBlock) void k_motion_instances(const Node2* __restrict__ nodes, const RodentObject* __restrict__ objects,
+// point.  Stated once over the objects' record type, which decides only how the root is read (object_box).
+template <class ObjNode>
+__global__ __launch_bounds__(kBlock) void k_motion_instances(const ObjNode* __restrict__ nodes, const RodentObject* __restrict__ objects,
                                                              int num_objects, const RodentMotionInstanceDesc* __restrict__ descs, int n,
                                                              RodentMotionInstance* __restrict__ staged, float* __restrict__ wbox,
                                                              float4* __restrict__ cent, float* __restrict__ partial, int* info) {
@@ -87,10 +106,9 @@ __global__ __launch_bounds__(kBlock) void k_motion_instances(const Node2* __rest
         float w[12];                                                     // only the verdicts are kept: the kernel inverts per ray
         flags |= invert_affine(m0, w);
         flags |= invert_affine(m1, w);
-        const float4* np = reinterpret_cast<const float4*>(nodes + ob.x);
-        const float4 b0 = np[0], b1 = np[1], b2 = np[2];                 // child 0: b0.x .. b1.y, child 1: b1.z .. b2.w
-        const float olo[3] = {fminf(b0.x, b1.z), fminf(b0.z, b2.x), fminf(b1.x, b2.z)};
-        const float ohi[3] = {fmaxf(b0.y, b1.w), fmaxf(b0.w, b2.y), fmaxf(b1.y, b2.w)};
+        const ObjectBox ub = object_box(nodes + ob.x);
+        const float olo[3] = {ub.lo[0], ub.lo[1], ub.lo[2]};
+        const float ohi[3] = {ub.hi[0], ub.hi[1], ub.hi[2]};
         float box0[6], box1[6], e0[3], e1[3], box[6];
         instance_world_box(m0, olo, ohi, box0); instance_widening(m0, olo, ohi, e0);
         instance_world_box(m1, olo, ohi, box1); instance_widening(m1, olo, ohi, e1);
@@ -111,6 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_motion_instances(const Node2* __rest
     }
     block_bounds(lo, hi, partial + 6 * blockIdx.x);
 }
+
 
 // ---- the leaf stage: RodentInstance / RodentMotionInstance records and leaf boxes in sorted order (in the place of k_leaves) ---------
 template <class Rec>

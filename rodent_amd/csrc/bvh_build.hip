@@ -41,6 +41,9 @@
 // three launches, whatever their number (k_forest_links, k_forest_tris, k_forest_climb).
 // rodent_hip_build_motion_bvh2_tri1 (include/rodent_motion.h; build_motion.h; CPU model: tests/motion_bvh_model.py): two copies of a
 // topology refitted to a mesh's two keys, then k_fuse_motion writes the two-key records a time per ray is traced through.
+// rodent_hip_build_motion_objects (include/rodent_instances.h, "deforming objects under moving instances"; CPU model:
+// tests/motion_objects_model.py) is its forest form: the packed arrays copied twice, rodent_hip_refit_objects' launches at either key,
+// k_fuse_motion over the packed arrays; rodent_hip_build_motion_tlas_motion_objects is the motion TLAS over such a set.
 // rodent_hip_build_objects (build_forest.h; CPU model: tests/forest_build_model.py) BUILDS a listed subset of the packed objects, or all
 // objects of a new set, in one launch list whatever their number: the LBVH's stages over the objects' triangles laid end to end
 // (k_bf_*), each object in its own frame, sorted by (list rank, code, row), every Karras position object-local.
@@ -161,14 +164,19 @@ struct MotionScratch {
     size_t bytes;
 };
 
-MotionScratch carve_motion(char* base, int num_nodes, int num_bvh_tris) {
+// (rodent_hip_build_motion_objects carves the same way over the packed arrays, with the refit scratch of its plan: `refit_bytes`)
+MotionScratch carve_motion(char* base, int num_nodes, int num_bvh_tris, size_t refit_bytes) {
     MotionScratch s{};
     Carver c{base};
     for (int k = 0; k < 2; k++) { c.take(s.nodes[k], (size_t)num_nodes); c.take(s.tris[k], (size_t)num_bvh_tris); }
     c.take(s.refit_info, 2 * RODENT_BUILD_INFO_WORDS);
-    c.take(s.refit, carve_refit(nullptr, num_nodes, num_bvh_tris).bytes);
+    c.take(s.refit, refit_bytes);
     s.bytes = c.bytes;
     return s;
+}
+
+MotionScratch carve_motion(char* base, int num_nodes, int num_bvh_tris) {
+    return carve_motion(base, num_nodes, num_bvh_tris, carve_refit(nullptr, num_nodes, num_bvh_tris).bytes);
 }
 
 struct CollapseScratch {
@@ -493,11 +501,12 @@ int32_t launch_build(const float* vertices, int nv, const int32_t* indices, int 
 // The TLAS build after its argument checks: info words and arrival counters zeroed, the instance stage and the frame of its sort points,
 // the sort, the leaf stage, Karras and the LBVH tail over RodentInstance records -- or, with motion descriptors, the motion instance
 // stage and RodentMotionInstance records.
-inline auto instance_stage(const RodentInstanceDesc*) { return k_instances; }
-inline auto instance_stage(const RodentMotionInstanceDesc*) { return k_motion_instances; }
+inline auto instance_stage(const RodentInstanceDesc*, const Node2*) { return k_instances; }
+inline auto instance_stage(const RodentMotionInstanceDesc*, const Node2*) { return k_motion_instances<Node2>; }
+inline auto instance_stage(const RodentMotionInstanceDesc*, const RodentMotionNode2*) { return k_motion_instances<RodentMotionNode2>; }
 
-template <class Desc, class Rec>
-int32_t launch_tlas(const Node2* nodes, const RodentObject* objects, int num_objects, const Desc* descs, int n, int max_leaf,
+template <class ObjNode, class Desc, class Rec>
+int32_t launch_tlas(const ObjNode* nodes, const RodentObject* objects, int num_objects, const Desc* descs, int n, int max_leaf,
                     Node2* tlas_nodes, Rec* instances, void* scratch, int32_t* info_dev, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const Scratch s = carve(static_cast<char*>(scratch), n);
@@ -506,7 +515,7 @@ int32_t launch_tlas(const Node2* nodes, const RodentObject* objects, int num_obj
         || (n > 1 && hipMemsetAsync(s.arrivals, 0, 4 * (size_t)(n - 1), stream) != hipSuccess))
         return RODENT_BUILD_ERR_LAUNCH;
     const int cblocks = std::min(kBoundsBlocks, blocks_for(n));
-    hipLaunchKernelGGL(instance_stage(descs), dim3(cblocks), dim3(kBlock), 0, stream, nodes, objects, num_objects, descs, n, t.staged,
+    hipLaunchKernelGGL(instance_stage(descs, nodes), dim3(cblocks), dim3(kBlock), 0, stream, nodes, objects, num_objects, descs, n, t.staged,
                        t.wbox, s.cent, s.partial, info_dev);
     hipLaunchKernelGGL(k_bounds, dim3(1), dim3(kBlock), 0, stream, s.partial, cblocks, s.frame);
     launch_sort(s, n, nullptr, stream);
@@ -585,6 +594,28 @@ int32_t launch_refit_objects(const float* vertices, int nv, const int32_t* indic
         hipLaunchKernelGGL(k_forest_climb, dim3(blocks_for(a.total_nodes)), dim3(kBlock), 0, stream, nodes, tris, a, s.tribox, s.parent,
                            s.arrivals, info_dev);
     return hipGetLastError() == hipSuccess ? RODENT_BUILD_OK : RODENT_BUILD_ERR_LAUNCH;
+}
+
+// The motion build of a packed set after its argument checks: launch_motion_build's list with launch_refit_objects' in the place of
+// launch_refit's, over the whole packed arrays (num_nodes / num_recs records); `a` lists every object.
+int32_t launch_motion_objects(const float* vertices0, const float* vertices1, int nv, const int32_t* indices, const Node2* nodes,
+                              int num_nodes, const Tri1* tris, int num_recs, const ForestArgs& a, RodentMotionNode2* motion_nodes,
+                              RodentMotionTri1* motion_tris, void* scratch, int32_t* info_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const MotionScratch s = carve_motion(static_cast<char*>(scratch), num_nodes, num_recs, 0);      // (the refit scratch lies last)
+    for (int k = 0; k < 2; k++) {
+        if (hipMemcpyAsync(s.nodes[k], nodes, sizeof(Node2) * (size_t)num_nodes, hipMemcpyDeviceToDevice, stream) != hipSuccess
+            || hipMemcpyAsync(s.tris[k], tris, sizeof(Tri1) * (size_t)num_recs, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+            return RODENT_BUILD_ERR_LAUNCH;
+    }
+    const float* keys[2] = {vertices0, vertices1};
+    for (int k = 0; k < 2; k++) {
+        const int32_t rc = launch_refit_objects(keys[k], nv, indices, s.nodes[k], s.tris[k], a, s.refit,
+                                                s.refit_info + k * RODENT_BUILD_INFO_WORDS, stream_);
+        if (rc != RODENT_BUILD_OK) return rc;
+    }
+    return launch_fuse_motion(s.nodes[0], s.tris[0], s.nodes[1], s.tris[1], num_nodes, num_recs, motion_nodes, motion_tris, s.refit_info,
+                              info_dev, stream_);
 }
 
 // The build of the listed objects after its argument checks (build_forest.h): the info words and the arrival counters zeroed, then the
@@ -754,8 +785,8 @@ int32_t refit_sync(int32_t dev, int64_t scratch_bytes, int32_t num_nodes, int32_
 }
 
 // The TLAS entries, static and motion: the argument checks in the header's order, then the launch list.
-template <class Desc, class Rec>
-int32_t build_tlas(int32_t dev, const Node2* nodes, const RodentObject* objects, int32_t num_objects, const Desc* descs,
+template <class ObjNode, class Desc, class Rec>
+int32_t build_tlas(int32_t dev, const ObjNode* nodes, const RodentObject* objects, int32_t num_objects, const Desc* descs,
                    int32_t num_instances, int32_t max_leaf, Node2* tlas_nodes, Rec* instances, void* scratch, int32_t* info_dev,
                    void* stream) {
     if (num_instances < 1 || num_instances > RODENT_TLAS_MAX_INSTANCES) return RODENT_TLAS_ERR_NUM_INSTANCES;
@@ -766,8 +797,8 @@ int32_t build_tlas(int32_t dev, const Node2* nodes, const RodentObject* objects,
     return launch_tlas(nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch, info_dev, stream);
 }
 
-template <class Desc, class Rec>
-int32_t build_tlas_sync(int32_t dev, int64_t bytes, const Node2* nodes, const RodentObject* objects, int32_t num_objects,
+template <class ObjNode, class Desc, class Rec>
+int32_t build_tlas_sync(int32_t dev, int64_t bytes, const ObjNode* nodes, const RodentObject* objects, int32_t num_objects,
                         const Desc* descs, int32_t num_instances, int32_t max_leaf, Node2* tlas_nodes, Rec* instances, int32_t* info) {
     if (bytes < 0) return RODENT_TLAS_ERR_NUM_INSTANCES;
     if (max_leaf < 1 || max_leaf > RODENT_BUILD_MAX_LEAF) return RODENT_BUILD_ERR_MAX_LEAF;
@@ -1126,6 +1157,74 @@ int32_t rodent_hip_refit_objects(int32_t dev, const float* vertices, int32_t num
     if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
     const ForestArgs a{objects, ranges, num_objects, num_listed, total_nodes, total_recs, num_rows};
     return launch_refit_objects(vertices, num_vertices, indices, nodes, tris, a, scratch, info_dev, stream);
+}
+
+// RODENT_BUILD_ERR_NUM_NODES of rodent_hip_build_motion_objects: rodent_hip_refit_objects' class and the packed arrays' counts.
+static bool bad_motion_objects_counts(int32_t num_listed, int32_t total_nodes, int32_t total_recs, int32_t num_nodes, int32_t num_recs) {
+    return num_listed < 1 || total_nodes < 0 || total_recs < 0 || num_nodes < 1 || num_recs < 1 || total_nodes > num_nodes
+        || total_recs > num_recs;
+}
+
+int64_t rodent_hip_motion_objects_scratch_bytes(int32_t num_nodes, int32_t num_recs, int64_t refit_bytes) {
+    if (num_nodes < 1 || num_recs < 1 || refit_bytes < 0) return -1;
+    return (int64_t)carve_motion(nullptr, num_nodes, num_recs, (size_t)refit_bytes).bytes;
+}
+
+int32_t rodent_hip_build_motion_objects(int32_t dev, const float* vertices0, const float* vertices1, int32_t num_vertices,
+                                        const int32_t* indices, int32_t num_rows, const struct Node2* nodes, int32_t num_nodes,
+                                        const struct Tri1* tris, int32_t num_recs, const struct RodentObject* objects,
+                                        int32_t num_objects, const struct RodentRefitRange* ranges, int32_t num_listed,
+                                        int32_t total_nodes, int32_t total_recs, struct RodentMotionNode2* motion_nodes,
+                                        struct RodentMotionTri1* motion_tris, void* scratch, int32_t* info_dev, void* stream) {
+    // rodent_hip_refit_objects' order, with this entry's counts and pointers
+    if (bad_num_tris(num_rows)) return RODENT_BUILD_ERR_NUM_TRIS;
+    if (num_vertices < 1) return RODENT_BUILD_ERR_NUM_VERTICES;
+    if (num_objects < 1) return RODENT_TLAS_ERR_NUM_OBJECTS;
+    if (bad_motion_objects_counts(num_listed, total_nodes, total_recs, num_nodes, num_recs)) return RODENT_BUILD_ERR_NUM_NODES;
+    if (!vertices0 || !vertices1 || !indices || !nodes || !tris || !objects || !ranges || !motion_nodes || !motion_tris || !scratch
+        || !info_dev)
+        return RODENT_BUILD_ERR_NULL;
+    if (!set_device(dev)) return RODENT_BUILD_ERR_DEVICE;
+    const ForestArgs a{objects, ranges, num_objects, num_listed, total_nodes, total_recs, num_rows};
+    return launch_motion_objects(vertices0, vertices1, num_vertices, indices, nodes, num_nodes, tris, num_recs, a, motion_nodes,
+                                 motion_tris, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_build_motion_objects_sync(int32_t dev, const float* vertices0, const float* vertices1, int32_t num_vertices,
+                                             const int32_t* indices, int32_t num_rows, const struct Node2* nodes, int32_t num_nodes,
+                                             const struct Tri1* tris, int32_t num_recs, const struct RodentObject* objects,
+                                             int32_t num_objects, const struct RodentRefitRange* ranges, int32_t num_listed,
+                                             int32_t total_nodes, int32_t total_recs, struct RodentMotionNode2* motion_nodes,
+                                             struct RodentMotionTri1* motion_tris, int32_t* info) {
+    if (bad_motion_objects_counts(num_listed, total_nodes, total_recs, num_nodes, num_recs)) return RODENT_BUILD_ERR_NUM_NODES;
+    const int64_t refit_bytes = (int64_t)std::max<size_t>(carve_refit(nullptr, total_nodes, total_recs).bytes, 256);
+    int32_t words[RODENT_BUILD_INFO_WORDS] = {};
+    int32_t rc = refit_sync(dev, rodent_hip_motion_objects_scratch_bytes(num_nodes, num_recs, refit_bytes), total_nodes, words,
+                            [&](void* scratch, int32_t* info_dev) {
+        return rodent_hip_build_motion_objects(dev, vertices0, vertices1, num_vertices, indices, num_rows, nodes, num_nodes, tris,
+                                               num_recs, objects, num_objects, ranges, num_listed, total_nodes, total_recs, motion_nodes,
+                                               motion_tris, scratch, info_dev, nullptr);
+    });
+    if (info) std::copy(words, words + RODENT_BUILD_INFO_WORDS, info);
+    if (rc == RODENT_BUILD_OK && words[3] != total_nodes) rc = RODENT_BUILD_ERR_INPUT;    // key 1's count (refit_sync checked key 0's)
+    return rc;
+}
+
+int32_t rodent_hip_build_motion_tlas_motion_objects(int32_t dev, const struct RodentMotionNode2* nodes,
+                                                    const struct RodentObject* objects, int32_t num_objects,
+                                                    const struct RodentMotionInstanceDesc* descs, int32_t num_instances,
+                                                    int32_t max_leaf, struct Node2* tlas_nodes, struct RodentMotionInstance* instances,
+                                                    void* scratch, int32_t* info_dev, void* stream) {
+    return build_tlas(dev, nodes, objects, num_objects, descs, num_instances, max_leaf, tlas_nodes, instances, scratch, info_dev, stream);
+}
+
+int32_t rodent_hip_build_motion_tlas_motion_objects_sync(int32_t dev, const struct RodentMotionNode2* nodes,
+                                                         const struct RodentObject* objects, int32_t num_objects,
+                                                         const struct RodentMotionInstanceDesc* descs, int32_t num_instances,
+                                                         int32_t max_leaf, struct Node2* tlas_nodes,
+                                                         struct RodentMotionInstance* instances, int32_t* info) {
+    return build_tlas_sync(dev, rodent_hip_motion_tlas_scratch_bytes(num_instances), nodes, objects, num_objects, descs, num_instances,
+                           max_leaf, tlas_nodes, instances, info);
 }
 
 int64_t rodent_hip_build_objects_plan(const int32_t* listed, const int32_t* first_tri, const int32_t* num_tris, int32_t num_listed,

@@ -1182,7 +1182,7 @@ template <bool ANY, int LDS_N, int CAPS, int LAST_RAYS = kWave> void L_phased(LA
 #include "traversal_wide.h"          // BVH4 / BVH8 + Tri4: k_wide_single, k_wide_top_persist, k_wide_finish, L_wide_single, L_wide_top
 int wide_top_min_rays() { return g_top_min_rays; }
 #include "instance_inverse.h"        // the fp64 inverse the TLAS build stores and k_instanced_motion takes per ray
-#include "traversal_instanced.h"     // instanced scenes: a TLAS over objects' BVH2 / Tri1 (k_instanced, k_instanced_motion)
+#include "traversal_instanced.h"     // instanced scenes: a TLAS over objects' BVH2 / Tri1 (k_instanced, k_instanced_motion, k_instanced_motion_objects)
 #include "traversal_motion.h"        // deforming meshes: two-key records, a time per ray (k_bvh2_motion)
 #ifdef RODENT_HIP_LAB
 #include "lab/top_kernels.h"         // lab build only: superseded forms of the LDS-image kernels
@@ -1304,8 +1304,23 @@ void launch_motion_instanced(DeviceState& s, const Node2* tlas, const RodentMoti
     HIP_CHECK(hipGetLastError());
 }
 
-void motion_instanced_sync_call(int32_t dev, const Node2* tlas, const RodentMotionInstance* instances, const Node2* nodes,
-    const Tri1* tris, const Ray1* rays, const float* times, Hit1* hits, int32_t* hit_instances, int32_t num_rays, bool any_hit) {
+// ... over motion objects (the section "deforming objects under moving instances" of rodent_instances.h): the same launch.
+void launch_motion_instanced(DeviceState& s, const Node2* tlas, const RodentMotionInstance* instances, const RodentMotionNode2* nodes,
+    const RodentMotionTri1* tris, const Ray1* rays, const float* times, Hit1* hits, int32_t* hit_instances, int n, bool any_hit,
+    hipStream_t stream) {
+    if (n <= 0) return;
+    if (any_hit)
+        hipLaunchKernelGGL((k_instanced_motion_objects<true>), dim3(blocks_for(n)), dim3(kWave), 0, stream, tlas, instances, times, nodes,
+            tris, rays, hits, hit_instances, n, s.ctl());
+    else
+        hipLaunchKernelGGL((k_instanced_motion_objects<false>), dim3(blocks_for(n)), dim3(kWave), 0, stream, tlas, instances, times, nodes,
+            tris, rays, hits, hit_instances, n, s.ctl());
+    HIP_CHECK(hipGetLastError());
+}
+
+template <class ObjNode, class ObjTri>
+void motion_instanced_sync_call(int32_t dev, const Node2* tlas, const RodentMotionInstance* instances, const ObjNode* nodes,
+    const ObjTri* tris, const Ray1* rays, const float* times, Hit1* hits, int32_t* hit_instances, int32_t num_rays, bool any_hit) {
     DeviceGuard on(dev);
     DeviceState& s = device_state(dev, nullptr);
     std::lock_guard<std::mutex> one_call(s.sync_mutex);
@@ -1425,6 +1440,34 @@ void hip_occluded_motion_instanced_bvh2_tri1(int32_t dev, const Node2* tlas_node
                                              const Node2* nodes, const Tri1* tris, const Ray1* rays, const float* times, Hit1* hits,
                                              int32_t* hit_instances, int32_t num_rays) {
     motion_instanced_sync_call(dev, tlas_nodes, motion_instances, nodes, tris, rays, times, hits, hit_instances, num_rays, true);
+}
+
+void hip_traverse_motion_instanced_motion_bvh2_tri1_async(int32_t dev, const Node2* tlas_nodes,
+                                                          const RodentMotionInstance* motion_instances,
+                                                          const RodentMotionNode2* motion_nodes, const RodentMotionTri1* motion_tris,
+                                                          const Ray1* rays, const float* times, Hit1* hits, int32_t* hit_instances,
+                                                          int32_t num_rays, int32_t any_hit, void* stream) {
+    DeviceGuard on(dev);
+    DeviceState& s = device_state(dev, (hipStream_t)stream);
+    std::lock_guard<std::mutex> launching(s.mutex);
+    launch_motion_instanced(s, tlas_nodes, motion_instances, motion_nodes, motion_tris, rays, times, hits, hit_instances, num_rays,
+        any_hit != 0, (hipStream_t)stream);
+}
+
+void hip_intersect_motion_instanced_motion_bvh2_tri1(int32_t dev, const Node2* tlas_nodes, const RodentMotionInstance* motion_instances,
+                                                     const RodentMotionNode2* motion_nodes, const RodentMotionTri1* motion_tris,
+                                                     const Ray1* rays, const float* times, Hit1* hits, int32_t* hit_instances,
+                                                     int32_t num_rays) {
+    motion_instanced_sync_call(dev, tlas_nodes, motion_instances, motion_nodes, motion_tris, rays, times, hits, hit_instances, num_rays,
+        false);
+}
+
+void hip_occluded_motion_instanced_motion_bvh2_tri1(int32_t dev, const Node2* tlas_nodes, const RodentMotionInstance* motion_instances,
+                                                    const RodentMotionNode2* motion_nodes, const RodentMotionTri1* motion_tris,
+                                                    const Ray1* rays, const float* times, Hit1* hits, int32_t* hit_instances,
+                                                    int32_t num_rays) {
+    motion_instanced_sync_call(dev, tlas_nodes, motion_instances, motion_nodes, motion_tris, rays, times, hits, hit_instances, num_rays,
+        true);
 }
 
 void hip_traverse_motion_bvh2_tri1_async(int32_t dev, const RodentMotionNode2* motion_nodes, const RodentMotionTri1* motion_tris,

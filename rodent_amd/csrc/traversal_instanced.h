@@ -3,6 +3,9 @@
 // k_instanced_motion<ANY> is the same loop over RodentMotionInstance records (two placements each) with a time per ray: the loop is stated
 // once, instanced_loop, and the two kernels differ in how a record yields the object ray (StaticEnter, MotionEnter).  CPU model:
 // tests/motion_instance_model.py.
+// k_instanced_motion_objects<ANY> is that loop again over a motion TLAS whose objects hold two-key records (RodentMotionNode2 /
+// RodentMotionTri1): the loop's second policy says how the object level is walked (StaticObjects, MotionObjects), and one time per ray
+// serves both levels.  CPU model: tests/motion_objects_model.py.
 //
 // k_instanced<ANY>: one ray per lane, one 64-ray chunk per one-wave workgroup; the while-while loop of the follow-up kernel (finish_launch)
 // on both levels, built from node2_step and leaf_tri1 as they stand.  One stack of the reference's 64 entries serves both levels,
@@ -59,11 +62,46 @@ struct MotionEnter {
     }
 };
 
-// The loop of both kernels, stated once.
-template <bool ANY, class Enter>
-__device__ __forceinline__ void instanced_loop(const Node2* __restrict__ tlas, const Enter& in, const Node2* __restrict__ nodes,
-                                               const Tri1* __restrict__ tris, const Ray1* __restrict__ rays, Hit1* __restrict__ hits,
-                                               int* __restrict__ hit_instances, int n, Ctl* ctl, int* stack_lds) {
+// How the object level is walked: the second policy of the loop.  time(i) is what a ray keeps through the loop, traced() the time rule
+// (tested once, before the loop), step / leaf one node / one leaf of the entered object.  StaticObjects: Node2 / Tri1 with node2_step and
+// leaf_tri1 as they stand; a ray keeps nothing and is always traced.
+struct StaticObjects {
+    struct Time {};
+    __device__ __forceinline__ Time time(int) const { return {}; }
+    __device__ __forceinline__ static bool traced(const Time&) { return true; }
+    __device__ __forceinline__ static int step(const Node2* nodes, int top, const RayX& o, const Time&, InstanceStack& st, int& ptr) {
+        return node2_step(nodes, top, o, st, ptr);
+    }
+    template <bool ANY>
+    __device__ __forceinline__ static bool leaf(const Tri1* tris, int first, RayX& o, const Time&, HitAcc& h) {
+        return leaf_tri1<ANY>(tris, first, o, h);
+    }
+};
+
+// MotionObjects: RodentMotionNode2 / RodentMotionTri1 (the offsets of an instance record count these records) with motion_node2_step and
+// leaf_motion_tri1 at the ray's time.  s = 1 - t and t live in two registers through the loop, as in k_bvh2_motion; the time rule is
+// rodent_motion.h's: !(0 <= t && t <= 1), a NaN included, is a miss without any traversal.
+struct MotionObjects {
+    const float* times;
+    struct Time { float s, t; };
+    __device__ __forceinline__ Time time(int i) const { const float t = times[i]; return {__fsub_rn(1.0f, t), t}; }
+    __device__ __forceinline__ static bool traced(const Time& tm) { return 0.0f <= tm.t && tm.t <= 1.0f; }
+    __device__ __forceinline__ static int step(const RodentMotionNode2* nodes, int top, const RayX& o, const Time& tm, InstanceStack& st,
+                                               int& ptr) {
+        return motion_node2_step(nodes, top, o, tm.s, tm.t, st, ptr);
+    }
+    template <bool ANY>
+    __device__ __forceinline__ static bool leaf(const RodentMotionTri1* tris, int first, RayX& o, const Time& tm, HitAcc& h) {
+        return leaf_motion_tri1<ANY>(tris, first, o, tm.s, tm.t, h);
+    }
+};
+
+// The loop of all three kernels, stated once.
+template <bool ANY, class Objects = StaticObjects, class Enter, class ObjNode, class ObjTri>
+__device__ __forceinline__ void instanced_loop(const Node2* __restrict__ tlas, const Enter& in, const ObjNode* __restrict__ nodes,
+                                               const ObjTri* __restrict__ tris, const Ray1* __restrict__ rays, Hit1* __restrict__ hits,
+                                               int* __restrict__ hit_instances, int n, Ctl* ctl, int* stack_lds,
+                                               const Objects& objs = Objects{}) {
     const int i = blockIdx.x * kWave + threadIdx.x;
     if (i >= n) return;
     InstanceStack st{(lds_int*)stack_lds + threadIdx.x};
@@ -73,6 +111,8 @@ __device__ __forceinline__ void instanced_loop(const Node2* __restrict__ tlas, c
     int ptr = 0, top = 1; st.put(0, 0);
     int j = -1;                                                         // the instance to enter next, -1: a TLAS step is next
     bool overflow = false;
+    const typename Objects::Time tm = objs.time(i);
+    if (!Objects::traced(tm)) top = 0;                                  // a refused time: the lane sits out the loop, a miss as it stands
     // One loop for both levels: an iteration is one TLAS step (j < 0) or one whole instance (j >= 0).  The world ray is a local of the
     // iteration, loaded behind an opaque copy of the ray index, so no register holds it across an object's traversal.
     while (top != 0) {
@@ -89,18 +129,18 @@ __device__ __forceinline__ void instanced_loop(const Node2* __restrict__ tlas, c
         RayX o;
         int4 id;
         if (in.enter(j, again, ray, o, id)) {
-            const Node2* onodes = nodes + id.x;
-            const Tri1* otris = tris + id.y;
+            const ObjNode* onodes = nodes + id.x;
+            const ObjTri* otris = tris + id.y;
             HitAcc h{-1, 0.0f, 0.0f, 0.0f};
             bool done = false;
             int otop = 1; st.put(++ptr, 0);
             if (ptr >= kStackCap) { overflow = true; break; }
             while (otop != 0) {
-                otop = node2_step(onodes, otop, o, st, ptr);
+                otop = Objects::step(onodes, otop, o, tm, st, ptr);
                 if (ptr >= kStackCap) { overflow = true; break; }
                 while (otop < 0) {
                     const int first = ~otop; otop = st.get(ptr); ptr--;
-                    if (leaf_tri1<ANY>(otris, first, o, h)) { done = true; otop = 0; break; }
+                    if (Objects::template leaf<ANY>(otris, first, o, tm, h)) { done = true; otop = 0; break; }
                 }
             }
             if (h.id >= 0) { hit = h; hit_instance = id.z & 0x7FFFFFFF; }
@@ -135,4 +175,18 @@ __global__ __launch_bounds__(kWave) void k_instanced_motion(const Node2* __restr
                                                             Hit1* __restrict__ hits, int* __restrict__ hit_instances, int n, Ctl* ctl) {
     __shared__ int stack_lds[kStackCap * kWave];
     instanced_loop<ANY>(tlas, MotionEnter{instances, times}, nodes, tris, rays, hits, hit_instances, n, ctl, stack_lds);
+}
+
+// Deforming objects under moving instances: the motion TLAS over motion objects, one time per ray through both levels.
+template <bool ANY>
+__global__ __launch_bounds__(kWave) void k_instanced_motion_objects(const Node2* __restrict__ tlas,
+                                                                    const RodentMotionInstance* __restrict__ instances,
+                                                                    const float* __restrict__ times,
+                                                                    const RodentMotionNode2* __restrict__ nodes,
+                                                                    const RodentMotionTri1* __restrict__ tris,
+                                                                    const Ray1* __restrict__ rays, Hit1* __restrict__ hits,
+                                                                    int* __restrict__ hit_instances, int n, Ctl* ctl) {
+    __shared__ int stack_lds[kStackCap * kWave];
+    instanced_loop<ANY>(tlas, MotionEnter{instances, times}, nodes, tris, rays, hits, hit_instances, n, ctl, stack_lds,
+                        MotionObjects{times});
 }

@@ -12,6 +12,9 @@ include/rodent_instances.h; kernels: csrc/build_tlas.h, csrc/traversal_instanced
     rebuild_objects(slotted, [2, 0], moved_vertices, indices, rows[[2, 0]])   # rebuilds objects 2 and 0 where they lie (new topologies)
     moving = build_motion_tlas(objects, transforms0, transforms1, object_ids)     # every copy placed at time 0 and at time 1 ...
     hits, ids = trace_motion(objects, moving, rays, times)                        # ... and every ray traced at its own time
+    deforming = build_motion_objects(objects, vertices0, vertices1, indices, rows)    # every object at time 0 and at time 1 too:
+    moving = build_motion_tlas(deforming, transforms0, transforms1, object_ids)       # a MotionObjectSet goes where an ObjectSet goes,
+    hits, ids = trace_motion(deforming, moving, rays, times)                          # one time per ray through both levels
 
 The top-level hierarchy is a pure function of the objects' root boxes, the transforms and max_leaf, byte for byte.
 """
@@ -218,12 +221,13 @@ class MotionTlas(Tlas):
         return self.num_nodes * F.NODE2.itemsize + self.num_instances * F.MOTION_INSTANCE.itemsize
 
 
-def build_motion_tlas(objects: ObjectSet, transforms0, transforms1, object_ids, instance_ids=None, max_leaf=1, stream=None, scratch=None,
+def build_motion_tlas(objects, transforms0, transforms1, object_ids, instance_ids=None, max_leaf=1, stream=None, scratch=None,
                       out=None) -> MotionTlas:
     """build_tlas for instances that move: object_ids[k] is placed by transforms0[k] at time 0 and by transforms1[k] at time 1 (both
     object_to_world, 3 x 4 row-major; tensors on the device are taken without a host copy), and linearly between them, entry by entry.
     Raises BuildError on invalid arguments and on the device's flags (an object index outside the table, a singular or non-finite
-    transform at either end).  scratch / out: as in build_tlas; `out` (a MotionTlas) is rebuilt in place and returned."""
+    transform at either end).  scratch / out: as in build_tlas; `out` (a MotionTlas) is rebuilt in place and returned.
+    `objects`: an ObjectSet, or a MotionObjectSet (build_motion_objects): then every object's box is the union over its two keys."""
     _need_gpu()
     dev, cuda = objects.dev, f"cuda:{objects.dev}"
     if not 1 <= max_leaf <= MAX_LEAF:
@@ -252,7 +256,7 @@ def build_motion_tlas(objects: ObjectSet, transforms0, transforms1, object_ids, 
         if nodes.numel() < node_bytes or instances.numel() < inst_bytes:
             raise ValueError("build_motion_tlas: the buffers of `out` are too small for these instances")
     info = torch.empty(INFO_WORDS, dtype=torch.int32, device=cuda)
-    entry = "rodent_hip_build_motion_tlas"
+    entry = "rodent_hip_build_motion_tlas" + ("_motion_objects" if isinstance(objects, MotionObjectSet) else "")
     words = _enqueue(entry, dev, stream, info, (objects.buffer, objects.table_dev, desc, scratch, nodes, instances),
                      objects.nodes.data_ptr(), objects.table_dev.data_ptr(), objects.num_objects, desc.data_ptr(), n, int(max_leaf),
                      nodes.data_ptr(), instances.data_ptr(), scratch.data_ptr())
@@ -265,18 +269,22 @@ def build_motion_tlas(objects: ObjectSet, transforms0, transforms1, object_ids, 
     return out
 
 
-def trace_motion_async(objects: ObjectSet, tlas: MotionTlas, rays_dev, times_dev, hits_dev, instances_dev, num_rays, any_hit=False,
+def trace_motion_async(objects, tlas: MotionTlas, rays_dev, times_dev, hits_dev, instances_dev, num_rays, any_hit=False,
                        stream=None):
-    """trace_async through a MotionTlas: `times_dev` holds one float32 per ray, the time at which that ray sees every instance."""
+    """trace_async through a MotionTlas: `times_dev` holds one float32 per ray, the time at which that ray sees every instance -- and,
+    with a MotionObjectSet, every object; a ray whose time is not in [0, 1] is then a miss."""
     if stream is None:
         stream = torch.cuda.current_stream(objects.dev)
-    abi.lib().hip_traverse_motion_instanced_bvh2_tri1_async(
+    l = abi.lib()
+    fn = (l.hip_traverse_motion_instanced_motion_bvh2_tri1_async if isinstance(objects, MotionObjectSet)
+          else l.hip_traverse_motion_instanced_bvh2_tri1_async)
+    fn(
         objects.dev, tlas.nodes.data_ptr(), tlas.instances.data_ptr(), objects.nodes.data_ptr(), objects.tris.data_ptr(),
         rays_dev.data_ptr(), times_dev.data_ptr(), hits_dev.data_ptr(), None if instances_dev is None else instances_dev.data_ptr(),
         int(num_rays), int(any_hit), C.c_void_p(stream.cuda_stream))
 
 
-def trace_motion(objects: ObjectSet, tlas: MotionTlas, rays: np.ndarray, times, any_hit=False):
+def trace_motion(objects, tlas: MotionTlas, rays: np.ndarray, times, any_hit=False):
     """Synchronous convenience wrapper: host rays and their times (one float32 each) in, (Hit1 array, int32 instance ids) out."""
     _need_gpu()
     dev, n = objects.dev, len(rays)
@@ -288,7 +296,8 @@ def trace_motion(objects: ObjectSet, tlas: MotionTlas, rays: np.ndarray, times, 
     hits_dev = torch.zeros(max(n, 1) * F.HIT1.itemsize, dtype=torch.uint8, device=f"cuda:{dev}")
     ids_dev = torch.zeros(max(n, 1), dtype=torch.int32, device=f"cuda:{dev}")
     torch.cuda.synchronize(dev)
-    fn = abi.lib().hip_occluded_motion_instanced_bvh2_tri1 if any_hit else abi.lib().hip_intersect_motion_instanced_bvh2_tri1
+    kind = "motion_instanced_motion_bvh2_tri1" if isinstance(objects, MotionObjectSet) else "motion_instanced_bvh2_tri1"
+    fn = getattr(abi.lib(), ("hip_occluded_" if any_hit else "hip_intersect_") + kind)
     fn(dev, tlas.nodes.data_ptr(), tlas.instances.data_ptr(), objects.nodes.data_ptr(), objects.tris.data_ptr(), rays_dev.data_ptr(),
        times_dev.data_ptr(), hits_dev.data_ptr(), ids_dev.data_ptr(), n)
     return abi.from_device(hits_dev, F.HIT1)[:n], ids_dev.cpu().numpy()[:n]
@@ -355,6 +364,114 @@ def refit_objects(objects: ObjectSet, object_ids, vertices, indices, ranges, str
     if check and words[0] != plan.num_nodes:
         raise BuildError(f"{entry}: malformed hierarchy ({words[0]} of {plan.num_nodes} nodes completed)")
     return words
+
+
+# ---- deforming objects under moving instances: two-key records for every object of a set (rodent_hip_build_motion_objects) ----------
+class MotionObjectSet:
+    """The packed motion objects: every object's RodentMotionNode2 records in `nodes`, every object's RodentMotionTri1 records in `tris`
+    (uint8 views of ONE allocation, `buffer`), and the RodentObject table, whose offsets count motion records: it is the table of the
+    ObjectSet the records were built over.  `info`: the words of the build, `scratch` its scratch tensor."""
+
+    def __init__(self, buffer, nodes, tris, table, table_dev, dev, info=None, scratch=None):
+        self.buffer, self.nodes, self.tris, self.table, self.table_dev, self.dev = buffer, nodes, tris, table, table_dev, dev
+        self.num_objects, self.num_nodes, self.num_tris = len(table), int(table["num_nodes"].sum()), int(table["num_tris"].sum())
+        self.info, self.scratch = info, scratch
+
+    @property
+    def device_bytes(self):
+        return self.buffer.numel() + self.table_dev.numel() * self.table_dev.element_size()
+
+
+def _motion_room(num_nodes, num_recs, cuda):
+    node_bytes = num_nodes * F.MOTION_NODE2.itemsize
+    start = (node_bytes + 255) // 256 * 256
+    buffer = torch.zeros(start + num_recs * F.MOTION_TRI1.itemsize, dtype=torch.uint8, device=cuda)
+    return buffer, buffer[:node_bytes], buffer[start:]
+
+
+def build_motion_objects(objects: ObjectSet, vertices0, vertices1, indices, ranges, stream=None, scratch=None, out=None,
+                         check=True) -> MotionObjectSet:
+    """The two-key records of ALL objects of `objects` (the topologies; only read) over `vertices0` at time 0 and `vertices1` at time 1, in
+    one launch list whatever their number (rodent_hip_build_motion_objects).  `vertices*` and `indices` are the concatenated tables of
+    all objects ((n, 3) or (n, 4); tensors on the device are not copied); `ranges`: one (first_tri, num_tris) row per object, in table
+    order, or a RefitPlan of plan_refit over all objects.  Per object the records are those motion.build_motion_bvh2 writes for it alone.
+    scratch / out: reuse the scratch tensor / the record tensors of an earlier result: `out=` is the refit to moved keys, in place.
+    info: [0] nodes completed at key 0 [1] records fused [2] flags [3] nodes completed at key 1.  With `check` a flag or an incomplete
+    key raises BuildError."""
+    _need_gpu()
+    from .gpubuild import _columns4
+    dev, cuda = objects.dev, f"cuda:{objects.dev}"
+    plan = ranges if isinstance(ranges, RefitPlan) else plan_refit(objects, np.arange(objects.num_objects), ranges)
+    if plan.num_listed != objects.num_objects or not np.array_equal(plan.table["object"], np.arange(objects.num_objects)):
+        raise ValueError("build_motion_objects: one range per object, in table order, is needed")
+    v0, v1, ix = _columns4(vertices0, torch.float32, dev), _columns4(vertices1, torch.float32, dev), _columns4(indices, torch.int32, dev)
+    if v0.shape[0] != v1.shape[0]:
+        raise ValueError(f"build_motion_objects: {v0.shape[0]} vertices at time 0, {v1.shape[0]} at time 1")
+    num_nodes, num_recs = objects.nodes.numel() // F.NODE2.itemsize, objects.tris.numel() // F.TRI1.itemsize
+    if out is None:
+        buffer, nodes, tris = _motion_room(num_nodes, num_recs, cuda)
+    else:
+        buffer, nodes, tris = out.buffer, out.nodes, out.tris
+        if nodes.numel() < num_nodes * F.MOTION_NODE2.itemsize or tris.numel() < num_recs * F.MOTION_TRI1.itemsize:
+            raise ValueError("build_motion_objects: the buffers of `out` are too small for this set")
+    entry = "rodent_hip_build_motion_objects"
+    need = abi.lib().rodent_hip_motion_objects_scratch_bytes(num_nodes, num_recs, plan.scratch_bytes)
+    if need < 0:
+        raise BuildError(f"{entry}: an object set without nodes or records")
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    if scratch is None and out is not None:
+        scratch = out.scratch
+    if scratch is None or scratch.numel() * scratch.element_size() < need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=cuda)
+    info = torch.empty(INFO_WORDS, dtype=torch.int32, device=cuda)
+    words = _enqueue(entry, dev, stream, info, (v0, v1, ix, scratch, objects.buffer, objects.table_dev, plan.table_dev, buffer),
+                     v0.data_ptr(), v1.data_ptr(), v0.shape[0], ix.data_ptr(), ix.shape[0], objects.nodes.data_ptr(), num_nodes,
+                     objects.tris.data_ptr(), num_recs, objects.table_dev.data_ptr(), objects.num_objects, plan.table_dev.data_ptr(),
+                     plan.num_listed, plan.num_nodes, plan.num_recs, nodes.data_ptr(), tris.data_ptr(), scratch.data_ptr()).copy()
+    if out is None:
+        out = MotionObjectSet(buffer, nodes, tris, objects.table.copy(), objects.table_dev, dev)
+    out.info, out.scratch = words, scratch
+    if check and words[2]:
+        raise BuildError(f"{entry}: " + ", ".join(s for bit, s in _TLAS_FLAGS if words[2] & bit))
+    if check and (words[0] != plan.num_nodes or words[3] != plan.num_nodes):
+        raise BuildError(f"{entry}: malformed hierarchy ({words[0]} and {words[3]} of {plan.num_nodes} nodes completed)")
+    return out
+
+
+def pack_motion_objects(mbvhs, dev=0) -> MotionObjectSet:
+    """Packs motion.MotionBvh objects or (nodes MOTION_NODE2, tris MOTION_TRI1) numpy pairs into one MotionObjectSet: concatenation, no
+    id is rewritten."""
+    _need_gpu()
+    if not len(mbvhs):
+        raise ValueError("pack_motion_objects: at least one object is needed")
+    cuda = f"cuda:{dev}"
+    parts, table = [], np.zeros(len(mbvhs), F.OBJECT)
+    for k, b in enumerate(mbvhs):
+        if isinstance(b, tuple):
+            nodes, tris = (np.ascontiguousarray(a) for a in b)
+            if nodes.dtype != F.MOTION_NODE2 or tris.dtype != F.MOTION_TRI1:
+                raise ValueError("pack_motion_objects: (nodes MOTION_NODE2, tris MOTION_TRI1) arrays are needed")
+            nb, tb, count = abi.to_device(nodes, dev), abi.to_device(tris, dev), (len(nodes), len(tris))
+        else:
+            nb = b.nodes.view(torch.uint8).reshape(-1)[: b.num_nodes * F.MOTION_NODE2.itemsize].to(cuda)
+            tb = b.tris.view(torch.uint8).reshape(-1)[: b.num_tris * F.MOTION_TRI1.itemsize].to(cuda)
+            count = (b.num_nodes, b.num_tris)
+        if count[0] < 1 or count[1] < 1:
+            raise ValueError("pack_motion_objects: an object without nodes or triangles")
+        parts.append((nb, tb))
+        table[k]["num_nodes"], table[k]["num_tris"] = count
+    table["node_offset"] = np.cumsum(table["num_nodes"]) - table["num_nodes"]
+    table["tri_offset"] = np.cumsum(table["num_tris"]) - table["num_tris"]
+    buffer, nodes, tris = _motion_room(int(table["num_nodes"].sum()), int(table["num_tris"].sum()), cuda)
+    for row, (nb, tb) in zip(table, parts):
+        nodes[int(row["node_offset"]) * F.MOTION_NODE2.itemsize:][: nb.numel()] = nb
+        tris[int(row["tri_offset"]) * F.MOTION_TRI1.itemsize:][: tb.numel()] = tb
+    return MotionObjectSet(buffer, nodes, tris, table, abi.to_device(table, dev), dev)
+
+
+def download_motion_objects(objects: MotionObjectSet):
+    """(nodes MOTION_NODE2, tris MOTION_TRI1) host copies of the packed records, the whole arrays."""
+    return (objects.nodes.cpu().numpy().view(F.MOTION_NODE2).copy(), objects.tris.cpu().numpy().view(F.MOTION_TRI1).copy())
 
 
 # ---- the objects' hierarchies built in one launch list (rodent_hip_build_objects: csrc/build_forest.h) ----------------------------
